@@ -1,14 +1,14 @@
 #!/bin/bash
 # PMC passes for the bench workload (run on the GPU box). One counter group per rocprofv3
 # run, --kernel-trace only alongside (never sys/runtime traces with --pmc). Output:
-# gpurun_out/pmc/<pass>/... ; summarise with tools/pmc_summary.py.
+# $PMC_OUT (default bench_out/pmc)/<pass>/... ; summarise with tools/pmc_summary.py.
 set -e
 ROOT="${GRAFT_REPO_ROOT:-$(pwd)}"
-OUT="$ROOT/gpurun_out/pmc"
+OUT="${PMC_OUT:-$ROOT/bench_out/pmc}"
 mkdir -p "$OUT"
 cd /tmp
 export TMPDIR=/tmp
-ARGS="${BENCH_ARGS:---steps 4 --warmup 2 --no-cpu-baseline --iqn-steps 0}"
+ARGS="${BENCH_ARGS:---steps 4 --warmup 2 --full --no-cpu-baseline --iqn-steps 0}"
 run() {
   local name="$1"; shift
   timeout -k 10 400 rocprofv3 --pmc "$@" --kernel-trace -d "$OUT/$name" -o run --output-format csv -- \
