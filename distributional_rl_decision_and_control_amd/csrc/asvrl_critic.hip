@@ -77,8 +77,9 @@ __device__ __forceinline__ void critic_tile_b(const CriticArgs& a, const CriticL
   }
   const frag8* W1T = wimg(L.w1t, a.w.w1t_frag);
   const frag8* WCB = wimg(L.wc, a.w.wc_frag);
-  // NT = 32 (row_bcast segment sums) spills at 4 blocks per pass; 2 keeps it in registers
-  constexpr int BPP = ASVRL_TRAIN_B_BPP32 != 0 && NT == 32 ? ASVRL_TRAIN_B_BPP32 : 4;
+  // NT = 32 (row_bcast segment sums) spills at 4 blocks per pass; 2 keeps it in registers (a register-usage
+  // observation with no timing on record; the knob that allowed 4 at NT = 32 is removed)
+  constexpr int BPP = NT == 32 ? 2 : 4;
 #pragma unroll
   for (int half = 0; half < 8 / BPP; ++half) {  // BPP output blocks per pass: 2 * BPP accumulators live
     f32x16 acc0[BPP], acc4[BPP];

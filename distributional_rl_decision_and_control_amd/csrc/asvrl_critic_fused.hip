@@ -48,13 +48,9 @@
 // FMA contraction of this file's f32 epilogue arithmetic (the loss terms, the output layer's and the encoders'
 // gradient sums, the Bellman target): one v_fma_f32 where the source writes a * b + c (the library is built
 // with -ffp-contract=off for the env kernel's f64 parity). stage_fg's encoder dot products stay uncontracted,
-// op for op what oracle/learn_ref.critic_step_bf16 restates.
-#ifndef ASVRL_FUSED_CONTRACT
-#define ASVRL_FUSED_CONTRACT 1
-#endif
-#if ASVRL_FUSED_CONTRACT
+// op for op what oracle/learn_ref.critic_step_bf16 restates. Measured alternative, removed (this file uncontracted
+// too): 108.8 -> 111.0 us median per launch (profiles/r04e_fused_variants_ab.txt).
 #pragma clang fp contract(fast)
-#endif
 
 namespace asvrl {
 namespace {
@@ -64,25 +60,18 @@ constexpr int kC = 256, kH = 128, kNcos = 64, kNW = 4, kMaxA = ASVRL_IQN_MAX_ACT
 // a round issues the global loads of the next round's inputs behind the W2 fragment fetch in L1, so the
 // wait for the weight fragments fetched before it never includes these loads (127-129 vs 130 us per launch
 // against issuing them at the top of the round, stage phase 3.7k -> 3.1k cycles: profiles/r02_enc_ab.txt)
-// stage-ahead (1, default): round t + grid's F, G and cos images are staged in round t's last phase,
+// stage-ahead (AH in the kernel): round t + grid's F, G and cos images are staged in round t's last phase,
 // behind the dW1 MFMAs, into a second set of images (double-buffered), so a round starts with its first
-// layer instead of the staging phase and its barrier. Where the second set fits in LDS: AC-IQN, N = 32,
-// bf16 operands (the bench shape). Measured 129-133 -> 125-127 us per launch, round 34.2k -> 33.4k
-// cycles (profiles/r02_stage_ahead_ab.txt).
-#ifndef ASVRL_STAGE_AHEAD
-#define ASVRL_STAGE_AHEAD 1
-#endif
-// stage-ahead for IQN_Policy's update at N = 32 too (its second image set fits: no action features):
-// IQN loop 2852-2863 -> 2892-2896 learn-steps/s (profiles/r02_iqn_stage_ahead_ab.txt)
-#ifndef ASVRL_STAGE_AHEAD_IQN
-#define ASVRL_STAGE_AHEAD_IQN 1
-#endif
-// with stage-ahead: the cos layer's weight fragments of the wave's two blocks held in registers for the
-// kernel's life (L0 and L4 read the same 8 fragments every round) instead of fetched three times a round
-// (the VGPRs stage-ahead frees): 125-127 -> 121-126 us, round 32.8k cycles (profiles/r02_wc_resident_ab.txt)
-#ifndef ASVRL_WC_RESIDENT
-#define ASVRL_WC_RESIDENT 1
-#endif
+// layer instead of the staging phase and its barrier. Where the second set fits in LDS: N = 32, bf16
+// operands (the bench shape); N = 8 / 16 and the f32 build stage at the top of the round. Measured
+// alternative, removed (staging every round at its top): 129-133 -> 125-127 us per launch with stage-ahead,
+// round 34.2k -> 33.4k cycles (profiles/r02_stage_ahead_ab.txt).
+// IQN_Policy's update at N = 32 too (its second image set fits: no action features); measured alternative,
+// removed (IQN without it): IQN loop 2852-2863 -> 2892-2896 learn-steps/s (profiles/r02_iqn_stage_ahead_ab.txt)
+// with stage-ahead (WCR = AH): the cos layer's weight fragments of the wave's two blocks held in registers for
+// the kernel's life (L0 and L4 read the same 8 fragments every round) instead of fetched three times a round
+// (the VGPRs stage-ahead frees). Measured alternative, removed (stage-ahead with the per-round fetch):
+// 125-127 -> 121-126 us, round 32.8k cycles (profiles/r02_wc_resident_ab.txt)
 
 #if ASVRL_OPERAND_F32
 template <int NT> struct FusedNB { static constexpr int v = 1; };
@@ -204,12 +193,9 @@ struct InLayout {
 // Each lane's swizzled-image bases (RowA / TrA of the 64-, 128- and 256-position images), computed once per
 // launch into LDS: a phase reads the two or three it uses (ds_read) instead of recomputing them -- about 10
 // (RowA) / 25 (TrA) VALU instructions each, ~180 per round, where the round's vector issue, not its matrix work,
-// sets its length. Measured 110.2 -> 107.3 us median per launch, bit-identical, SQ_INSTS_VALU -6.3 %
-// (profiles/r05k_lane_table_ab.txt; r05_pmc_summary.json). Where the table would not fit beside the images the
-// bases are computed.
-#ifndef ASVRL_LANE_TABLE
-#define ASVRL_LANE_TABLE 1
-#endif
+// sets its length. Measured alternative, removed (every phase computing its bases): 110.2 -> 107.3 us median per
+// launch with the table, bit-identical, SQ_INSTS_VALU -6.3 % (profiles/r05k_lane_table_ab.txt;
+// r05_pmc_summary.json). Where the table would not fit beside the images (LT false) the bases are computed.
 // field-major [field][lane]: a phase's reads of one field are 64 consecutive dwords (conflict-free; a lane-major
 // table of 12-dword rows put four lanes on each bank)
 enum LaneField { kLbR64, kLbR128, kLbR256, kLbT64lo, kLbT64hi, kLbT128lo, kLbT128hi, kLbT256lo, kLbT256hi, kLbFields };
@@ -407,38 +393,29 @@ __device__ __forceinline__ int row_action(const float* in, int bl, int A) {
 // k-steps ahead: without the explicit read-ahead and a scheduling fence per k-step the compiler (at its
 // VGPR limit) issues each operand read right before its MFMA and waits for it (ds_read, s_waitcnt
 // lgkmcnt(0), v_mfma for every MFMA), exposing the LDS latency on every one. Same MFMA order (results
-// bit-identical); D = 0: the plain loop. D = 2 (default): round 32.8k -> 28.4k cycles, fused critic
-// 125 -> 110.5 us, AC-IQN step 0.316 -> 0.302 ms, IQN 2780 -> 2920 learn-steps/s; D = 3 spills
-// (profiles/r02_read_ahead_ab.txt).
-#ifndef ASVRL_READ_AHEAD
-#define ASVRL_READ_AHEAD 2
-#endif
+// bit-identical). Measured alternatives, removed: the plain loop (no read-ahead) against D = 2: round
+// 32.8k -> 28.4k cycles, fused critic 125 -> 110.5 us, AC-IQN step 0.316 -> 0.302 ms, IQN 2780 -> 2920
+// learn-steps/s; D = 3 spills (profiles/r02_read_ahead_ab.txt).
+constexpr int kReadAhead = 2;
 // (Measured in round 4 and removed, profiles/r04e_fused_variants_ab.txt: a deeper weight-gradient read-ahead,
 // dW2 + L3 and dW1 + L4 as interleaved MFMA streams, the cos layer's gradient loop a k-step ahead, and the dW2 /
 // dW1 partials stored during the last round -- all bit-identical, none faster.)
 template <int KS, int NB, int P, class WF>
 __device__ __forceinline__ void mfma_rows(f32x16 (&acc)[NB], const elem_t* img, const RowA<P>& RA, WF wf) {
-  constexpr int D = ASVRL_READ_AHEAD < KS ? ASVRL_READ_AHEAD : KS;
-  if constexpr (D == 0) {
+  constexpr int D = kReadAhead < KS ? kReadAhead : KS;
+  frag8 bq[D][NB];
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
+  for (int d = 0; d < D; ++d)
 #pragma unroll
-      for (int j = 0; j < NB; ++j) acc[j] = mfma(wf(ks), rowf(img, RA, j, ks), acc[j]);
-  } else {
-    frag8 bq[D][NB];
+    for (int j = 0; j < NB; ++j) bq[d][j] = rowf(img, RA, j, d);
 #pragma unroll
-    for (int d = 0; d < D; ++d)
+  for (int ks = 0; ks < KS; ++ks) {
 #pragma unroll
-      for (int j = 0; j < NB; ++j) bq[d][j] = rowf(img, RA, j, d);
+    for (int j = 0; j < NB; ++j) acc[j] = mfma(wf(ks), bq[ks % D][j], acc[j]);
+    if (ks + D < KS)
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-#pragma unroll
-      for (int j = 0; j < NB; ++j) acc[j] = mfma(wf(ks), bq[ks % D][j], acc[j]);
-      if (ks + D < KS)
-#pragma unroll
-        for (int j = 0; j < NB; ++j) bq[ks % D][j] = rowf(img, RA, j, ks + D);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+      for (int j = 0; j < NB; ++j) bq[ks % D][j] = rowf(img, RA, j, ks + D);
+    __builtin_amdgcn_sched_barrier(0);
   }
 }
 
@@ -447,28 +424,18 @@ __device__ __forceinline__ void mfma_rows(f32x16 (&acc)[NB], const elem_t* img, 
 // a whole kk ahead, one scheduling fence per step (see mfma_rows).
 template <int KK, int NN, class AF, class BF, class MF>
 __device__ __forceinline__ void mfma_grid(AF af, BF bf, MF mf) {
-  constexpr int T = KK * NN, D0 = ASVRL_READ_AHEAD < T ? ASVRL_READ_AHEAD : T;
-  if constexpr (D0 == 0) {
+  constexpr int T = KK * NN, D = kReadAhead < T ? kReadAhead : T;
+  frag8 bq[D], aq[2];
+  aq[0] = af(0);
 #pragma unroll
-    for (int kk = 0; kk < KK; ++kk) {
-      const frag8 A = af(kk);
+  for (int t = 0; t < D; ++t) bq[t] = bf(t / NN, t % NN);
 #pragma unroll
-      for (int n = 0; n < NN; ++n) mf(kk, n, A, bf(kk, n));
-    }
-  } else {
-    constexpr int D = D0;
-    frag8 bq[D], aq[2];
-    aq[0] = af(0);
-#pragma unroll
-    for (int t = 0; t < D; ++t) bq[t] = bf(t / NN, t % NN);
-#pragma unroll
-    for (int t = 0; t < T; ++t) {
-      const int kk = t / NN, n = t % NN;
-      if (n == 0 && kk + 1 < KK) aq[(kk + 1) % 2] = af(kk + 1);
-      mf(kk, n, aq[kk % 2], bq[t % D]);
-      if (t + D < T) bq[t % D] = bf((t + D) / NN, (t + D) % NN);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+  for (int t = 0; t < T; ++t) {
+    const int kk = t / NN, n = t % NN;
+    if (n == 0 && kk + 1 < KK) aq[(kk + 1) % 2] = af(kk + 1);
+    mf(kk, n, aq[kk % 2], bq[t % D]);
+    if (t + D < T) bq[t % D] = bf((t + D) / NN, (t + D) % NN);
+    __builtin_amdgcn_sched_barrier(0);
   }
 }
 
@@ -636,11 +603,11 @@ template <int NT, bool IQN, bool TQ = false>
 __global__ __launch_bounds__(kNW * 64) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void critic_fused_kernel(FusedArgs a) {
   constexpr int NB = FusedNB<NT>::v, G = 32 * NB, S = G / NT, NA = IQN ? 1 : 2;
-  constexpr bool AH = ASVRL_STAGE_AHEAD && (!IQN || ASVRL_STAGE_AHEAD_IQN) && NT == 32 && !ASVRL_OPERAND_F32;
+  constexpr bool AH = NT == 32 && !ASVRL_OPERAND_F32;
   constexpr int NSB = AH ? 2 : 1;
   __shared__ __attribute__((aligned(16))) FusedShared<NT, NB, S, IQN, NSB, TQ> U;
   static_assert(sizeof(U) <= 160 * 1024, "fused critic LDS image exceeds the CU's 160 KB");
-  constexpr bool LT = ASVRL_LANE_TABLE && sizeof(U) + sizeof(LaneBases) <= 160 * 1024;
+  constexpr bool LT = sizeof(U) + sizeof(LaneBases) <= 160 * 1024;
   __shared__ int LB[LT ? kLbFields : 1][64];   // each lane's image bases
   auto& L = U.f;
   if constexpr (TQ) target_phase<NT, NB, IQN>(a.tq, U.t, a.rounds);
@@ -761,7 +728,7 @@ void critic_fused_kernel(FusedArgs a) {
   f32x16 dWo = f32x16{};
 #pragma unroll
   for (int g = 0; g < (IQN ? 1 : 16); ++g) dwo[g] = 0.f;
-  constexpr bool WCR = AH && ASVRL_WC_RESIDENT;
+  constexpr bool WCR = AH;
   frag8 wcr0[WCR ? 4 : 1], wcr1[WCR ? 4 : 1];   // resident cos-layer fragments (blocks 2w, 2w + 1)
   if constexpr (WCR) {
 #pragma unroll
@@ -832,15 +799,13 @@ void critic_fused_kernel(FusedArgs a) {
       ASVRL_FRESH_LANE();
       const RowA<kNcos> RA_cos = row_base<kNcos, LT>(LB, lane, r, h);
       const RowA<kC> RA_x = row_base<kC, LT>(LB, lane, r, h);
-      // the cos rows' operand fragments are the same for both blocks: with read-ahead, all read first
-      frag8 cb[ASVRL_READ_AHEAD ? NB : 1][4];
-      if constexpr (ASVRL_READ_AHEAD != 0) {
+      // the cos rows' operand fragments are the same for both blocks: all read first
+      frag8 cb[NB][4];
 #pragma unroll
-        for (int j = 0; j < NB; ++j)
+      for (int j = 0; j < NB; ++j)
 #pragma unroll
-          for (int ks = 0; ks < 4; ++ks) cb[j][ks] = rowf(cosb, RA_cos, j, ks);
-        __builtin_amdgcn_sched_barrier(0);
-      }
+        for (int ks = 0; ks < 4; ++ks) cb[j][ks] = rowf(cosb, RA_cos, j, ks);
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int mq = 0; mq < 2; ++mq) {
         const int mb = 2 * w + mq;
@@ -853,9 +818,7 @@ void critic_fused_kernel(FusedArgs a) {
         for (int j = 0; j < NB; ++j) {
           f32x16 acc = acc_init(bcp, mb * 32, h);
 #pragma unroll
-          for (int ks = 0; ks < 4; ++ks)
-            acc = mfma(mq ? wc1[ks] : wc0[ks], ASVRL_READ_AHEAD ? cb[ASVRL_READ_AHEAD ? j : 0][ks]
-                                                                  : rowf(cosb, RA_cos, j, ks), acc);
+          for (int ks = 0; ks < 4; ++ks) acc = mfma(mq ? wc1[ks] : wc0[ks], cb[j][ks], acc);
           if constexpr (!kBiasFirst) acc += bias_init(bcp, mb * 32, h);
 #pragma unroll
           for (int s = 0; s < 2; ++s) {
@@ -1194,31 +1157,19 @@ void critic_fused_kernel(FusedArgs a) {
 #pragma unroll
         for (int s = 0; s < 2; ++s) lds8(Fb + ((32 * j + r) / NT) * kC + mb * 32 + 16 * s + 8 * h, fv[j][s]);
       float fsa[NB][16];
-      f32x16 dxs[ASVRL_READ_AHEAD ? NB : 1], ccs[ASVRL_READ_AHEAD ? NB : 1];
-      if constexpr (ASVRL_READ_AHEAD != 0) {
+      f32x16 dxs[NB], ccs[NB];
 #pragma unroll
-        for (int j = 0; j < NB; ++j) {
-          dxs[j] = f32x16{};
-          ccs[j] = acc_init(bcp, mb * 32, h);
-        }
-        mfma_rows<8, NB>(dxs, L.dz1, RA_d, [&](int ks) { return wt[ks]; });
-        mfma_rows<4, NB>(ccs, cosb, RA_cos, [&](int ks) { return wcc[ks]; });
+      for (int j = 0; j < NB; ++j) {
+        dxs[j] = f32x16{};
+        ccs[j] = acc_init(bcp, mb * 32, h);
       }
+      mfma_rows<8, NB>(dxs, L.dz1, RA_d, [&](int ks) { return wt[ks]; });
+      mfma_rows<4, NB>(ccs, cosb, RA_cos, [&](int ks) { return wcc[ks]; });
       ASVRL_STAMP(24 + 3 * mq);
 #pragma unroll
       for (int j = 0; j < NB; ++j) {
-        f32x16 dx, cc;
-        if constexpr (ASVRL_READ_AHEAD != 0) {
-          dx = dxs[ASVRL_READ_AHEAD ? j : 0];
-          cc = ccs[ASVRL_READ_AHEAD ? j : 0];
-        } else {
-          dx = f32x16{};
-#pragma unroll
-          for (int ks = 0; ks < 8; ++ks) dx = mfma(wt[ks], rowf(L.dz1, RA_d, j, ks), dx);
-          cc = acc_init(bcp, mb * 32, h);
-#pragma unroll
-          for (int ks = 0; ks < 4; ++ks) cc = mfma(wcc[ks], rowf(cosb, RA_cos, j, ks), cc);
-        }
+        const f32x16 dx = dxs[j];
+        f32x16 cc = ccs[j];
         if constexpr (!kBiasFirst) cc += bias_init(bcp, mb * 32, h);
 #pragma unroll
         for (int s = 0; s < 2; ++s) {

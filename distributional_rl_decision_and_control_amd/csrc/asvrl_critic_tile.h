@@ -18,9 +18,6 @@ template <int MODE> constexpr bool kIqn = MODE >= MODE_IQN_MAX;
 template <int MODE> constexpr bool kTrainMode = MODE == MODE_TRAIN || MODE == MODE_IQN_TRAIN;
 // the Wc image sits in LDS for the forward-only modes; the backward modes keep W2^T there
 template <int MODE> constexpr bool kFwdOnly = MODE == MODE_FWD || MODE == MODE_IQN_MAX || MODE == MODE_IQN_ACT;
-#ifndef ASVRL_TRAIN_B_BPP32
-#define ASVRL_TRAIN_B_BPP32 2
-#endif
 // Every wave stages its samples' feature rows in LDS in the prologue (F as bf16 for every mode,
 // G in f32 for the AC-IQN critic modes), computing them from the observation rows / actions when
 // given (the encoders fused into the trunk) or copying F / G. The per-feature reads that follow

@@ -105,12 +105,10 @@ constexpr int kC51Waves = 4;
 #ifndef ASVRL_C51_ROWS
 #define ASVRL_C51_ROWS 4
 #endif
-// the workgroup's long-run jobs pooled and walked by its first waves (1), or each wave its own (0): at
-// four rows per wave 16.8 -> 15.9 us at B = 65536; at two (B = 8192) 5.5 -> 5.9 us, so there each wave its own
+// the workgroup's long-run jobs pooled and walked by its first waves (kPool, at four rows per wave), or each
+// wave its own (below four). Measured alternative, removed (never pooled): at four rows per wave pooling is
+// 16.8 -> 15.9 us at B = 65536; at two (B = 8192) 5.5 -> 5.9 us, so there each wave its own
 // (profiles/r04aa_c51_pool_ab.txt)
-#ifndef ASVRL_C51_POOL
-#define ASVRL_C51_POOL 1
-#endif
 
 // acc + v[j0] + v[j0+1] + ... + v[j1-1], added in order; the LDS reads go out 8 at a time
 __device__ __forceinline__ float run_sum(const float* v, int j0, int j1, float acc) {
@@ -148,12 +146,12 @@ __global__ __launch_bounds__(kC51Waves * kWave) void c51_kernel(const float* __r
   // per wave and row: the lower / upper masses (a 65th slot for the second read of a run starting at lane
   // 63) and per target its runs' bounds as bytes {lower start, lower end, upper start, upper end}; the
   // workgroup's long-run jobs ((wave * ROWS + row) << 6 | target), walked by the first waves after a barrier
-  // (kPool: ASVRL_C51_POOL at four rows per wave; else each wave walks its own)
+  // (kPool: at four rows per wave; else each wave walks its own)
   __shared__ float s_lo[kC51Waves][ROWS][kWave + 1], s_up[kC51Waves][ROWS][kWave + 1];
   __shared__ uint32_t s_rb[kC51Waves][ROWS][kWave + 1];
   __shared__ uint16_t s_job[kC51Waves * ROWS * kWave];
   __shared__ int s_njob;
-  constexpr bool kPool = ASVRL_C51_POOL && ROWS >= 4;
+  constexpr bool kPool = ROWS >= 4;
   const int lane = threadIdx.x & (kWave - 1);
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int row0 = (blockIdx.x * kC51Waves + w) * ROWS;

@@ -27,34 +27,15 @@ namespace asvrl {
 namespace {
 
 // The split actor kernels run one wave per SIMD (4 waves per 32-row workgroup), so a weight fragment
-// fetched from L2 right before its MFMA exposes the whole L2 latency on every MFMA of a chain. With
-// ASVRL_MLP_WPRE a chain's fragments are all fetched first (A/B knob; same MFMA order, bit-identical).
-#ifndef ASVRL_MLP_WPRE
-#define ASVRL_MLP_WPRE 0
-#endif
+// fetched from L2 right before its MFMA exposes the whole L2 latency on every MFMA of a chain.
+// Measured alternatives, removed: a chain's fragments all fetched before its first MFMA, and the LDS
+// operands too (same MFMA order, bit-identical): AC-IQN step 0.304-0.305 ms against 0.302-0.304 and
+// 0.304-0.306, within noise (profiles/r02_mlp_prefetch_ab.txt); the plain loop stayed.
 template <int KS, int P>
 __device__ __forceinline__ f32x16 wchain(const frag8* W, int base, int lane, const elem_t* img, const RowA<P>& RA) {
   f32x16 acc = f32x16{};
-  if constexpr (ASVRL_MLP_WPRE != 0) {
-    frag8 q[KS];
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) q[ks] = W[(base + ks) * 64 + lane];
-    if constexpr (ASVRL_MLP_WPRE >= 2) {   // the LDS operands too
-      frag8 b[KS];
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) b[ks] = rowf(img, RA, 0, ks);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) acc = mfma(q[ks], b[ks], acc);
-    } else {
-      __builtin_amdgcn_sched_barrier(0);   // every fetch issued before the chain (not sunk to its MFMA)
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) acc = mfma(q[ks], rowf(img, RA, 0, ks), acc);
-    }
-  } else {
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) acc = mfma(W[(base + ks) * 64 + lane], rowf(img, RA, 0, ks), acc);
-  }
+  for (int ks = 0; ks < KS; ++ks) acc = mfma(W[(base + ks) * 64 + lane], rowf(img, RA, 0, ks), acc);
   return acc;
 }
 

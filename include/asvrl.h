@@ -366,10 +366,10 @@ int asvrl_critic_train_fused(const AsvCriticWeights* w, const AsvCriticIO* io, c
  * separate asvrl_critic_forward(target) of train_AC_IQN, agent.py:396-400): each workgroup first computes
  * q_next = Critic_target(tio->obs, tio->act, tio->taus) (AC_IQN_model.py:462-480) for exactly the samples
  * its rounds update into io->q_next, then runs the update reading them. tw: the target critic (with its
- * encoders); tio: B and N as io. With kernel variant 4 (asvrl_critic_fused_variant) the target pass is
- * asvrl_critic_forward's own tile: q_next bit for bit what asvrl_critic_forward(tw, tio) gives; with variant 8
- * (the default where it applies) it is the update kernel's own forward phases: the same rounding points, f32 sums
- * in another order. */
+ * encoders); tio: B and N as io. With kernel variant 4 (asvrl_critic_fused_variant; the default) the target
+ * pass is asvrl_critic_forward's own tile: q_next bit for bit what asvrl_critic_forward(tw, tio) gives; with
+ * variant 8 it is the update kernel's own forward phases: the same rounding points, f32 sums in another
+ * order. */
 int asvrl_critic_train_fused_tq(const AsvCriticWeights* w, const AsvCriticIO* io, const AsvCriticParts* parts,
                                 const AsvCriticWeights* tw, const AsvCriticIO* tio, void* stream);
 
