@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("ASVRL_LIB", os.path.join(HERE, "lib", "libasvrl.so"))
 # the same sources built with f32 learner operands (the parity build; asvrl_operand_bytes() == 4)
 LIB_PATH_F32 = os.path.join(HERE, "lib", "libasvrl_f32.so")
 OPERANDS = {"bf16": (LIB_PATH, 2), "f32": (LIB_PATH_F32, 4)}
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 SELF_DIM, OBJ_DIM, MAX_OBJ = 7, 5, 5
 OBS_DIM = 40   # self 7 | objects 25 | mask 5 | pad 3
@@ -85,6 +85,12 @@ class AsvEnvLaunch(C.Structure):
 
 
 ENV_LAYOUT_AUTO, ENV_LAYOUT_PAIRS, ENV_LAYOUT_SWEEP = 0, 1, 2
+
+
+class AsvRollout(C.Structure):
+    _fields_ = [("n_steps", C.c_int32), ("hold_done", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("actions", "noise", "reward", "done", "info", "env_done", "obs", "obj_cnt",
+                                          "rs", "steps_run")]
 
 
 class AsvCriticWeights(C.Structure):
@@ -243,6 +249,8 @@ EXPORTS = [
                                  C.POINTER(AsvStepOut), _VP]),
     ("asvrl_env_step_ex", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), _VP, _VP, C.POINTER(AsvStepCtl),
                                     C.POINTER(AsvStepOut), C.POINTER(AsvEnvLaunch), _VP]),
+    ("asvrl_env_rollout", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), C.POINTER(AsvStepCtl),
+                                    C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvEnvLaunch), _VP]),
     ("asvrl_env_reset", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), C.POINTER(AsvResetCfg), _VP, _U64,
                                   _U64, _VP, _VP]),
     ("asvrl_env_reset_observe", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), C.POINTER(AsvResetCfg), _VP,
@@ -332,6 +340,7 @@ EXPORTS = [
     ("asvrl_abi_version", C.c_int, []),
     ("asvrl_operand_bytes", C.c_int32, []),
     ("asvrl_struct_sizes", None, [C.c_void_p]),
+    ("asvrl_rollout_struct_size", _I64, []),
 ]
 
 _libs = {}

@@ -235,9 +235,12 @@ __device__ inline StepResult step_result(const AsvParams& p, const AsvStepCtl& c
 }
 
 // per-env end of the step (env.py:330, trainer.py:172): episode counter, episode end when the limit is
-// hit or no robot is left active, and the finished episode's totals
-__device__ inline void env_end(const AsvParams& p, const AsvEnvState& s, const AsvStepCtl& ctl,
-                               const AsvStepOut& out, int e, int ep_ts, int nrob, int alive, size_t NT) {
+// hit or no robot is left active, and the finished episode's totals. ret_of(j) / flags_of(j): robot j's
+// return and flags after the step (the single step reads them back from HBM, the K-step rollout from LDS)
+template <class RetOf, class FlagsOf>
+__device__ inline void env_end_from(const AsvParams& p, const AsvEnvState& s, const AsvStepCtl& ctl,
+                                    const AsvStepOut& out, int e, int ep_ts, int nrob, int alive, RetOf ret_of,
+                                    FlagsOf flags_of) {
   s.ep_ts[e] = ep_ts + 1;
   if (ctl.trainer_deactivate && out.env_done != nullptr) {
     const bool end = (ep_ts >= p.episode_limit) || alive == 0;
@@ -245,9 +248,8 @@ __device__ inline void env_end(const AsvParams& p, const AsvEnvState& s, const A
     if (end && out.stats != nullptr) {
       double sr = 0, sc = 0, sg = 0, sk = 0, st = 0;
       for (int j = 0; j < nrob; ++j) {
-        const size_t jd = static_cast<size_t>(e) * s.max_robots + j;
-        const uint8_t fj = s.rflags[jd];
-        sr += s.rs[ASVRL_F_RET * NT + jd];
+        const uint8_t fj = flags_of(j);
+        sr += ret_of(j);
         sc += 1;
         sg += (fj & ASVRL_FLAG_REACH_GOAL) ? 1 : 0;
         sk += (fj & ASVRL_FLAG_COLLISION) ? 1 : 0;
@@ -261,6 +263,12 @@ __device__ inline void env_end(const AsvParams& p, const AsvEnvState& s, const A
       atomicAdd(out.stats + 5, 1.0);
     }
   }
+}
+__device__ inline void env_end(const AsvParams& p, const AsvEnvState& s, const AsvStepCtl& ctl,
+                               const AsvStepOut& out, int e, int ep_ts, int nrob, int alive, size_t NT) {
+  const size_t e0 = static_cast<size_t>(e) * s.max_robots;
+  env_end_from(p, s, ctl, out, e, ep_ts, nrob, alive, [&](int j) { return s.rs[ASVRL_F_RET * NT + e0 + j]; },
+               [&](int j) { return s.rflags[e0 + j]; });
 }
 
 // check_apply_COLREGs (wamv.py:398-423) for one kept object. `ev` says whether the test got as far as
@@ -640,15 +648,21 @@ __global__ __launch_bounds__(BLOCK) void env_sweep_kernel(AsvParams p, AsvEnvSta
 #define ASVRL_ENV_PAIRS_WPE 4
 #endif
 // one workgroup's envs [bid * epb, (bid + 1) * epb) of the step (env_pairs_kernel loops over them)
-template <int BLOCK, int NM, bool DYN = true>   // DYN false: an observation pass only (do_dynamics = 0)
-__device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int bid, unsigned char* smem) {
+// ROLL (env_rollout_kernel): RO->n_steps open-loop steps in one launch. The robot lanes load their state, goal,
+// flags, return, phi and the env's step count once and keep them in registers over the steps; the buoys are
+// staged once; step t takes row t of A->actions (and of A->noise in mode 0) and draws at counter + t. The state
+// goes back to HBM after the env's last step; every step's outputs go to row t of the kept records, the last
+// step's to A->out. The phases are the single step's own code: without ROLL the loop below runs once.
+template <int BLOCK, int NM, bool DYN = true, bool ROLL = false>   // DYN false: an observation pass only (do_dynamics = 0)
+__device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int bid, unsigned char* smem,
+                                                KArg<AsvRollout> RO = nullptr) {
   const int R = A->s.max_robots;
   const int O = A->s.max_obs;
   const int S = O + R;               // candidate slots per robot (obstacles, then robots)
   const int nrb = epb * R;
   const int npairs = nrb * S;
   const int nslot = npairs > 5 * nrb ? npairs : 5 * nrb;
-  const int tid = threadIdx.x;
+  int tid = threadIdx.x;
 
   double* sx = reinterpret_cast<double*>(smem);   // [nrb] robots after the move
   double* sy = sx + nrb;
@@ -674,71 +688,127 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
   signed char* scnt = reinterpret_cast<signed char*>(sact + nrb);  // [nrb] kept count, -1 inactive
 
   const bool rlane = tid < nrb;
-  const int le = tid / R;
+  int le = tid / R;
   const int i = tid - le * R;
   const int e = bid * epb + le;
   const bool lane_env = rlane && e < A->s.n_envs;
-  const bool env_on = lane_env && (A->ctl.env_mask == nullptr || A->ctl.env_mask[e] != 0);
+  const bool env_on0 = lane_env && (A->ctl.env_mask == nullptr || A->ctl.env_mask[e] != 0);
   // a masked pass (the observation pass after a reset) touches few envs: workgroups with none leave
-  if (A->ctl.env_mask != nullptr && !__syncthreads_or(env_on ? 1 : 0)) return;
+  if (A->ctl.env_mask != nullptr && !__syncthreads_or(env_on0 ? 1 : 0)) return;
   const int nrob = lane_env ? A->s.n_robots[e] : 0;
-  const bool exists = env_on && i < nrob;
+  const bool exists0 = env_on0 && i < nrob;
   const size_t NT = static_cast<size_t>(A->s.n_envs) * R;
-  const size_t idx = static_cast<size_t>(e) * R + i;
-  const uint8_t fl = exists ? A->s.rflags[idx] : 0;
+  size_t idx = static_cast<size_t>(e) * R + i;
+  // what a rollout keeps over its steps (a single step: this step's values)
+  uint8_t flv = exists0 ? A->s.rflags[idx] : 0;
+  int ep_ts = env_on0 ? A->s.ep_ts[e] : 0;
+  Regs r{};
+  double gx = 0, gy = 0, phi = 0.0, ret = 0.0;
+  bool on = env_on0;   // hold_done: cleared after the env's end step
+  int taken = 0;       // steps the env took
+  const int n_steps = ROLL ? RO->n_steps : 1;
+  const bool hold = ROLL && RO->hold_done != 0;
+  auto load_state = [&] {
+    const double* rs = A->s.rs;
+    r.x = rs[ASVRL_F_X * NT + idx];
+    r.y = rs[ASVRL_F_Y * NT + idx];
+    r.th = rs[ASVRL_F_THETA * NT + idx];
+    r.vr0 = rs[ASVRL_F_VR0 * NT + idx];
+    r.vr1 = rs[ASVRL_F_VR1 * NT + idx];
+    r.vr2 = rs[ASVRL_F_VR2 * NT + idx];
+    r.v0 = rs[ASVRL_F_V0 * NT + idx];
+    r.v1 = rs[ASVRL_F_V1 * NT + idx];
+    r.v2 = rs[ASVRL_F_V2 * NT + idx];
+    r.tl = rs[ASVRL_F_TL * NT + idx];
+    r.tr = rs[ASVRL_F_TR * NT + idx];
+    r.lp = rs[ASVRL_F_LP * NT + idx];
+    r.rp = rs[ASVRL_F_RP * NT + idx];
+    gx = rs[ASVRL_F_GX * NT + idx];
+    gy = rs[ASVRL_F_GY * NT + idx];
+  };
+  auto store_state = [&] {   // what the dynamics change
+    double* rs = A->s.rs;
+    rs[ASVRL_F_X * NT + idx] = r.x;
+    rs[ASVRL_F_Y * NT + idx] = r.y;
+    rs[ASVRL_F_THETA * NT + idx] = r.th;
+    rs[ASVRL_F_VR0 * NT + idx] = r.vr0;
+    rs[ASVRL_F_VR1 * NT + idx] = r.vr1;
+    rs[ASVRL_F_VR2 * NT + idx] = r.vr2;
+    rs[ASVRL_F_V0 * NT + idx] = r.v0;
+    rs[ASVRL_F_V1 * NT + idx] = r.v1;
+    rs[ASVRL_F_V2 * NT + idx] = r.v2;
+    rs[ASVRL_F_TL * NT + idx] = r.tl;
+    rs[ASVRL_F_TR * NT + idx] = r.tr;
+  };
+  if constexpr (ROLL) {
+    if (exists0) {
+      load_state();
+      phi = A->s.rs[ASVRL_F_PHI * NT + idx];
+      ret = A->s.rs[ASVRL_F_RET * NT + idx];
+    }
+  }
+
+  // the step loop (its body keeps the single step's indentation; closed at "step t" below)
+  for (int t = 0; t < n_steps; ++t) {
+  if constexpr (ROLL) {
+    // the lane's indices, opaque per step: the addresses built on them (17 state fields, records, outputs, LDS
+    // rows) are then computed where they are used, as in the single step, not hoisted out of the step loop and
+    // held in registers over all of it
+    asm volatile("" : "+v"(tid), "+v"(le), "+v"(idx));
+    // every env of the workgroup is held: nothing left to do
+    if (hold && !__syncthreads_or(on ? 1 : 0)) break;
+  }
+  const bool env_on = ROLL ? on : env_on0;
+  const bool exists = ROLL ? (exists0 && on) : exists0;
+  const uint8_t fl = flv;
   const bool deact = (fl & ASVRL_FLAG_DEACTIVATED) != 0;
   const bool active = exists && !deact;
-  const int ep_ts = env_on ? A->s.ep_ts[e] : 0;
   bool coll = (fl & ASVRL_FLAG_COLLISION) != 0;
   bool reach = (fl & ASVRL_FLAG_REACH_GOAL) != 0;
   double reward = 0.0;
+  // the step's outputs: A->out (a single step; a rollout's last step, and every step of a held rollout, whose
+  // envs end on different steps) and row t of the rollout's kept records, whose members may be null
+  const bool wlast = !ROLL || hold || t == n_steps - 1;
+  auto rec_row = [&] {
+    AsvStepOut o{};
+    if constexpr (ROLL) {
+      const KArg<AsvRollout> Q = kfresh(RO);   // read where used, not held over the step
+      const size_t t0 = static_cast<size_t>(t) * NT;
+      o.obs = Q->obs != nullptr ? Q->obs + t0 * ASVRL_OBS_DIM : nullptr;
+      o.obj_cnt = Q->obj_cnt != nullptr ? Q->obj_cnt + t0 : nullptr;
+      o.reward = Q->reward != nullptr ? Q->reward + t0 : nullptr;
+      o.done = Q->done != nullptr ? Q->done + t0 : nullptr;
+      o.info = Q->info != nullptr ? Q->info + t0 : nullptr;
+    }
+    return o;
+  };
+  auto each_out = [&](KArg<PairsArgs> Ak, auto&& f) {
+    if (wlast) f(kref(Ak).out, std::false_type{});
+    if constexpr (ROLL) f(rec_row(), std::true_type{});
+  };
 
   // ---------------- phase 1: dynamics (env.py:247-277), the observation's self part
   {
-    Regs r{};
-    double gx = 0, gy = 0;
-    if (exists) {
-      const double* rs = A->s.rs;
-      r.x = rs[ASVRL_F_X * NT + idx];
-      r.y = rs[ASVRL_F_Y * NT + idx];
-      r.th = rs[ASVRL_F_THETA * NT + idx];
-      r.vr0 = rs[ASVRL_F_VR0 * NT + idx];
-      r.vr1 = rs[ASVRL_F_VR1 * NT + idx];
-      r.vr2 = rs[ASVRL_F_VR2 * NT + idx];
-      r.v0 = rs[ASVRL_F_V0 * NT + idx];
-      r.v1 = rs[ASVRL_F_V1 * NT + idx];
-      r.v2 = rs[ASVRL_F_V2 * NT + idx];
-      r.tl = rs[ASVRL_F_TL * NT + idx];
-      r.tr = rs[ASVRL_F_TR * NT + idx];
-      r.lp = rs[ASVRL_F_LP * NT + idx];
-      r.rp = rs[ASVRL_F_RP * NT + idx];
-      gx = rs[ASVRL_F_GX * NT + idx];
-      gy = rs[ASVRL_F_GY * NT + idx];
+    if constexpr (!ROLL) {
+      r = Regs{};
+      gx = 0;
+      gy = 0;
+      if (exists) load_state();
     }
     if (active && (DYN && A->ctl.do_dynamics)) {
       const double d_before = sqrt((gx - r.x) * (gx - r.x) + (gy - r.y) * (gy - r.y));
       const int nc = A->s.n_cores[e];
       const double* cores = A->s.cores + static_cast<size_t>(e) * A->s.max_cores * 4;
-      robot_act(ParamsKArg{&A->p}, r, A->actions[2 * idx], A->actions[2 * idx + 1], A->ctl.is_continuous, cores,
+      const double* act = A->actions + (ROLL ? static_cast<size_t>(t) * 2 * NT : 0);
+      robot_act(ParamsKArg{&A->p}, r, act[2 * idx], act[2 * idx + 1], A->ctl.is_continuous, cores,
                 nc < A->s.max_cores ? nc : A->s.max_cores);
       const double d_after = sqrt((gx - r.x) * (gx - r.x) + (gy - r.y) * (gy - r.y));
       reward = 0.0;
       reward += A->p.timestep_penalty;
       reward += d_before - d_after;
     }
-    if (exists && (DYN && A->ctl.do_dynamics)) {
-      double* rs = A->s.rs;
-      rs[ASVRL_F_X * NT + idx] = r.x;
-      rs[ASVRL_F_Y * NT + idx] = r.y;
-      rs[ASVRL_F_THETA * NT + idx] = r.th;
-      rs[ASVRL_F_VR0 * NT + idx] = r.vr0;
-      rs[ASVRL_F_VR1 * NT + idx] = r.vr1;
-      rs[ASVRL_F_VR2 * NT + idx] = r.vr2;
-      rs[ASVRL_F_V0 * NT + idx] = r.v0;
-      rs[ASVRL_F_V1 * NT + idx] = r.v1;
-      rs[ASVRL_F_V2 * NT + idx] = r.v2;
-      rs[ASVRL_F_TL * NT + idx] = r.tl;
-      rs[ASVRL_F_TR * NT + idx] = r.tr;
+    if constexpr (!ROLL) {
+      if (exists && (DYN && A->ctl.do_dynamics)) store_state();
     }
     double so0 = 0, so1 = 0, so2 = 0, so3 = 0, so4 = 0;
     if (rlane) {
@@ -766,42 +836,48 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
       if (sqrt((gx - r.x) * (gx - r.x) + (gy - r.y) * (gy - r.y)) <= A->p.goal_dis) reach = true;
     }
     if (env_on) {   // packed f32 obs row, self part (replay_buffer.py:51-69 + the .float() of agent.py:363-366)
-      float* of = A->out.obs + idx * ASVRL_OBS_DIM;
       const bool a = active;
-      *reinterpret_cast<float4*>(of) = a ? make_float4(static_cast<float>(so0), static_cast<float>(so1),
-                                                        static_cast<float>(so2), static_cast<float>(so3))
-                                         : make_float4(0.f, 0.f, 0.f, 0.f);
-      of[4] = a ? static_cast<float>(so4) : 0.f;
-      of[5] = a ? static_cast<float>(r.tl) : 0.f;
-      of[6] = a ? static_cast<float>(r.tr) : 0.f;
-      if (A->out.obs64 != nullptr) {
-        double* o = A->out.obs64 + idx * 32;
-        o[0] = a ? so0 : 0.0;
-        o[1] = a ? so1 : 0.0;
-        o[2] = a ? so2 : 0.0;
-        o[3] = a ? so3 : 0.0;
-        o[4] = a ? so4 : 0.0;
-        o[5] = a ? r.tl : 0.0;
-        o[6] = a ? r.tr : 0.0;
-      }
+      each_out(A, [&](const AsvStepOut& o, auto opt) {
+        if (!opt || o.obs != nullptr) {
+          float* of = o.obs + idx * ASVRL_OBS_DIM;
+          *reinterpret_cast<float4*>(of) = a ? make_float4(static_cast<float>(so0), static_cast<float>(so1),
+                                                            static_cast<float>(so2), static_cast<float>(so3))
+                                             : make_float4(0.f, 0.f, 0.f, 0.f);
+          of[4] = a ? static_cast<float>(so4) : 0.f;
+          of[5] = a ? static_cast<float>(r.tl) : 0.f;
+          of[6] = a ? static_cast<float>(r.tr) : 0.f;
+        }
+        if (o.obs64 != nullptr) {
+          double* ob = o.obs64 + idx * 32;
+          ob[0] = a ? so0 : 0.0;
+          ob[1] = a ? so1 : 0.0;
+          ob[2] = a ? so2 : 0.0;
+          ob[3] = a ? so3 : 0.0;
+          ob[4] = a ? so4 : 0.0;
+          ob[5] = a ? r.tl : 0.0;
+          ob[6] = a ? r.tr : 0.0;
+        }
+      });
     }
   }
   if (env_on) {
-    const int no = A->s.n_obs[e];
-    for (int k = i; k < O; k += R) {
-      const double* ob = A->s.obstacles + (static_cast<size_t>(e) * O + k) * 3;
-      double* dst = sob + (static_cast<size_t>(le) * O + k) * 3;
-      if (k < no) {
-        dst[0] = ob[0];
-        dst[1] = ob[1];
-        dst[2] = ob[2];
+    if (!ROLL || t == 0) {   // the buoys and the counts do not change over a rollout
+      const int no = A->s.n_obs[e];
+      for (int k = i; k < O; k += R) {
+        const double* ob = A->s.obstacles + (static_cast<size_t>(e) * O + k) * 3;
+        double* dst = sob + (static_cast<size_t>(le) * O + k) * 3;
+        if (k < no) {
+          dst[0] = ob[0];
+          dst[1] = ob[1];
+          dst[2] = ob[2];
+        }
+      }
+      if (i == 0) {
+        sno[le] = no;
+        snr[le] = nrob;
       }
     }
-    if (i == 0) {
-      salive[le] = 0;
-      sno[le] = no;
-      snr[le] = nrob;
-    }
+    if (i == 0) salive[le] = 0;
   }
   __syncthreads();
   A = kfresh(A);
@@ -828,7 +904,10 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
     vy0 = sv1[qe * R + j];
     return true;
   };
-  const uint64_t ctr = A->ctl.counter + (A->ctl.counter_dev != nullptr ? *A->ctl.counter_dev : 0ull);
+  const uint64_t ctr = A->ctl.counter + (A->ctl.counter_dev != nullptr ? *A->ctl.counter_dev : 0ull) +
+                       (ROLL ? static_cast<uint64_t>(t) : 0ull);
+  // row t of the injected draws
+  const size_t noise_t = (ROLL && NM == 0) ? static_cast<size_t>(t) * NT * S * 5 : 0;
   const bool full_circle = 0.5 * A->p.angle >= kPi;
 
   // ---------------- phase 2: one (robot, candidate) pair per lane (wamv.py:478-511)
@@ -845,7 +924,7 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
     if (sact[qr] && candidate(qe, qi, c, ox, oy, orad, vx0, vy0)) {
       const size_t qidx = static_cast<size_t>(bid * epb + qe) * R + qi;
       double n0, n1, n2, n3, n4;
-      draw_noise<NM>(kref(A).p, kref(A).ctl, ctr, A->noise, qidx, c, S, n0, n1, n2, n3, n4);
+      draw_noise<NM>(kref(A).p, kref(A).ctl, ctr, A->noise + noise_t, qidx, c, S, n0, n1, n2, n3, n4);
       pvm[q] = static_cast<VmT>(n4);
       const double cs = scs[qr], sn = ssn[qr], tx = stx[qr], ty = sty[qr];
       const double pxn = ox + n0, pyn = oy + n1;  // Perception (wamv.py:27-40)
@@ -956,7 +1035,7 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
         double ox = 0, oy = 0, orad = 0, vx0 = 0, vy0 = 0;
         candidate(qe, qi, c, ox, oy, orad, vx0, vy0);
         double n0, n1, n2, n3, n4 = static_cast<double>(pvm[qr * S + c]);
-        draw_noise<NM, false>(kref(A).p, kref(A).ctl, ctr, A->noise, qidx, c, S, n0, n1, n2, n3, n4);
+        draw_noise<NM, false>(kref(A).p, kref(A).ctl, ctr, A->noise + noise_t, qidx, c, S, n0, n1, n2, n3, n4);
         const double cs = scs[qr], sn = ssn[qr], tx = stx[qr], ty = sty[qr];
         const double pxn = ox + n0, pyn = oy + n1;  // as phase 2
         const double vxn = vx0 + n2, vyn = vy0 + n3;
@@ -972,20 +1051,24 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
           cf = static_cast<unsigned char>((ev ? 1 : 0) | (hit ? 2 : 0));
         }
       }
-      float* of = A->out.obs + qidx * ASVRL_OBS_DIM + 7 + 5 * k;
-      of[0] = static_cast<float>(ra);
-      of[1] = static_cast<float>(rb);
-      of[2] = static_cast<float>(rc);
-      of[3] = static_cast<float>(rd);
-      of[4] = static_cast<float>(re);
-      if (A->out.obs64 != nullptr) {
-        double* o = A->out.obs64 + qidx * 32 + 7 + 5 * k;
-        o[0] = ra;
-        o[1] = rb;
-        o[2] = rc;
-        o[3] = rd;
-        o[4] = re;
-      }
+      each_out(A, [&](const AsvStepOut& o, auto opt) {
+        if (!opt || o.obs != nullptr) {
+          float* of = o.obs + qidx * ASVRL_OBS_DIM + 7 + 5 * k;
+          of[0] = static_cast<float>(ra);
+          of[1] = static_cast<float>(rb);
+          of[2] = static_cast<float>(rc);
+          of[3] = static_cast<float>(rd);
+          of[4] = static_cast<float>(re);
+        }
+        if (o.obs64 != nullptr) {
+          double* ob = o.obs64 + qidx * 32 + 7 + 5 * k;
+          ob[0] = ra;
+          ob[1] = rb;
+          ob[2] = rc;
+          ob[3] = rd;
+          ob[4] = re;
+        }
+      });
     }
     pfl[kq] = cf;
     pk[kq] = ph;
@@ -995,7 +1078,7 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
 
   // ---------------- phase 5: COLREGs in order (wamv.py:517-521), reward / done / info, bookkeeping
   bool apply = false;
-  double phi = exists ? A->s.rs[ASVRL_F_PHI * NT + idx] : 0.0;
+  if constexpr (!ROLL) phi = exists ? A->s.rs[ASVRL_F_PHI * NT + idx] : 0.0;
   for (int k = 0; k < cnt; ++k) {   // the serial chain: phi of every evaluated object up to the first hit
     const unsigned char f = pfl[5 * tid + k];
     if (f & 1) phi = pk[5 * tid + k];
@@ -1004,45 +1087,97 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
       break;
     }
   }
+  if constexpr (!ROLL) ret = exists ? A->s.rs[ASVRL_F_RET * NT + idx] : 0.0;
   const StepResult res = step_result(kref(A).p, kref(A).ctl, exists, deact, active, ep_ts, fl, coll, reach, apply, phi, reward,
-                                     exists ? A->s.rs[ASVRL_F_RET * NT + idx] : 0.0);
+                                     ret);
   if (A->ctl.trainer_deactivate && (DYN && A->ctl.do_dynamics) && exists && !(res.nfl & ASVRL_FLAG_DEACTIVATED))
     atomicAdd(&salive[le], 1);
   if (exists) {
-    if ((DYN && A->ctl.do_dynamics)) A->s.rs[ASVRL_F_RET * NT + idx] = res.ret;
-    A->s.rs[ASVRL_F_PHI * NT + idx] = phi;
-    A->s.rflags[idx] = res.nfl;
+    if constexpr (!ROLL) {
+      if ((DYN && A->ctl.do_dynamics)) A->s.rs[ASVRL_F_RET * NT + idx] = res.ret;
+      A->s.rs[ASVRL_F_PHI * NT + idx] = phi;
+      A->s.rflags[idx] = res.nfl;
+    } else {
+      // kept for the next step, and where the env's lane 0 sums an ended episode (env_end_from): this lane's
+      // first (robot, k) slot, whose phase 4 values the chain above has read
+      ret = res.ret;
+      flv = res.nfl;
+      pk[5 * tid] = res.ret;
+      pfl[5 * tid] = res.nfl;
+    }
   }
   if (env_on) {
-    float4* o4 = reinterpret_cast<float4*>(A->out.obs + idx * ASVRL_OBS_DIM);
     const bool a = active;
-    for (int k = cnt > 0 ? cnt : 0; k < 5; ++k) {   // the object rows phase 4 did not write
-      float* of = A->out.obs + idx * ASVRL_OBS_DIM + 7 + 5 * k;
-      of[0] = 0.f;
-      of[1] = 0.f;
-      of[2] = 0.f;
-      of[3] = 0.f;
-      of[4] = 0.f;
-      if (A->out.obs64 != nullptr) {
-        double* o = A->out.obs64 + idx * 32 + 7 + 5 * k;
-        o[0] = 0.0;
-        o[1] = 0.0;
-        o[2] = 0.0;
-        o[3] = 0.0;
-        o[4] = 0.0;
+    each_out(A, [&](const AsvStepOut& o, auto opt) {
+      if (!opt || o.obs != nullptr) {
+        float4* o4 = reinterpret_cast<float4*>(o.obs + idx * ASVRL_OBS_DIM);
+        for (int k = cnt > 0 ? cnt : 0; k < 5; ++k) {   // the object rows phase 4 did not write
+          float* of = o.obs + idx * ASVRL_OBS_DIM + 7 + 5 * k;
+          of[0] = 0.f;
+          of[1] = 0.f;
+          of[2] = 0.f;
+          of[3] = 0.f;
+          of[4] = 0.f;
+        }
+        o4[8] = make_float4((a && cnt > 0) ? 1.f : 0.f, (a && cnt > 1) ? 1.f : 0.f, (a && cnt > 2) ? 1.f : 0.f,
+                            (a && cnt > 3) ? 1.f : 0.f);
+        o4[9] = make_float4((a && cnt > 4) ? 1.f : 0.f, 0.f, 0.f, 0.f);
       }
-    }
-    o4[8] = make_float4((a && cnt > 0) ? 1.f : 0.f, (a && cnt > 1) ? 1.f : 0.f, (a && cnt > 2) ? 1.f : 0.f,
-                        (a && cnt > 3) ? 1.f : 0.f);
-    o4[9] = make_float4((a && cnt > 4) ? 1.f : 0.f, 0.f, 0.f, 0.f);
-    A->out.obj_cnt[idx] = static_cast<int8_t>(exists ? cnt : -1);
-    A->out.reward[idx] = res.reward;
-    A->out.done[idx] = res.done;
-    A->out.info[idx] = res.info;
+      if (o.obs64 != nullptr) {
+        for (int k = cnt > 0 ? cnt : 0; k < 5; ++k) {
+          double* ob = o.obs64 + idx * 32 + 7 + 5 * k;
+          ob[0] = 0.0;
+          ob[1] = 0.0;
+          ob[2] = 0.0;
+          ob[3] = 0.0;
+          ob[4] = 0.0;
+        }
+      }
+      if (!opt || o.obj_cnt != nullptr) o.obj_cnt[idx] = static_cast<int8_t>(exists ? cnt : -1);
+      if (!opt || o.reward != nullptr) o.reward[idx] = res.reward;
+      if (!opt || o.done != nullptr) o.done[idx] = res.done;
+      if (!opt || o.info != nullptr) o.info[idx] = res.info;
+    });
   }
   __syncthreads();
   A = kfresh(A);
-  if (env_on && i == 0 && (DYN && A->ctl.do_dynamics)) env_end(kref(A).p, kref(A).s, kref(A).ctl, kref(A).out, e, ep_ts, nrob, salive[le], NT);
+  if constexpr (!ROLL) {
+    if (env_on && i == 0 && (DYN && A->ctl.do_dynamics)) env_end(kref(A).p, kref(A).s, kref(A).ctl, kref(A).out, e, ep_ts, nrob, salive[le], NT);
+  } else {
+    // the env's end (trainer.py:172), by its lane 0 for the totals and by every lane of a held rollout
+    const KArg<AsvRollout> Q = kfresh(RO);
+    bool end = false;
+    if (env_on && A->ctl.trainer_deactivate && (hold || i == 0))
+      end = (ep_ts >= A->p.episode_limit) || salive[le] == 0;
+    if (env_on && i == 0) {
+      env_end_from(kref(A).p, kref(A).s, kref(A).ctl, kref(A).out, e, ep_ts, nrob, salive[le],
+                   [&](int j) { return pk[5 * (le * R + j)]; }, [&](int j) { return pfl[5 * (le * R + j)]; });
+      if (Q->env_done != nullptr) Q->env_done[static_cast<size_t>(t) * A->s.n_envs + e] = end ? 1 : 0;
+    }
+    // the state goes back to HBM after the env's last step
+    if (exists && (t == n_steps - 1 || (hold && end))) {
+      store_state();
+      A->s.rs[ASVRL_F_RET * NT + idx] = ret;
+      A->s.rs[ASVRL_F_PHI * NT + idx] = phi;
+      A->s.rflags[idx] = flv;
+    }
+    if (exists && Q->rs != nullptr) {
+      double* q = Q->rs + static_cast<size_t>(t) * ASVRL_NUM_FIELDS * NT + idx;
+      const double v[ASVRL_NUM_FIELDS] = {r.x, r.y, r.th, r.vr0, r.vr1, r.vr2, r.v0, r.v1, r.v2, r.tl, r.tr,
+                                          r.lp, r.rp, gx, gy, phi, ret};
+#pragma unroll
+      for (int f = 0; f < ASVRL_NUM_FIELDS; ++f) q[f * NT] = v[f];
+    }
+    if (env_on) {
+      ++ep_ts;
+      ++taken;
+    }
+    if (hold && end) on = false;
+  }
+  }   // step t
+  if constexpr (ROLL) {
+    if (lane_env && i == 0 && RO->steps_run != nullptr) RO->steps_run[e] = taken;
+  }
 }
 
 
@@ -1065,6 +1200,55 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(NM == 1 ?
   const KArg<PairsArgs> A = kargs<PairsArgs>();
   env_pairs_block<BLOCK, NM>(A, A->epb,
                              A->group0 + xcd_group(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x)), smem);
+}
+
+// K open-loop steps in one launch (asvrl_env_rollout): env_pairs_kernel's workgroup-to-group mapping and LDS
+// carve, the step loop inside the workgroup (env_pairs_block<ROLL>). An env group needs nothing from another
+// group, so no step waits on the rest of the grid. Two waves per SIMD by registers: the resident state rides
+// through the pair phases, and the training shape (4096 envs x 5 robots: 512 workgroups of 4 waves on 1024
+// SIMDs) has no more than two waves per SIMD to place.
+#ifndef ASVRL_ENV_ROLLOUT_WPE
+#define ASVRL_ENV_ROLLOUT_WPE 2
+#endif
+struct RolloutArgs {
+  PairsArgs k;   // actions / noise: row 0 of the rollout's
+  AsvRollout ro;
+};
+template <int BLOCK, int NM>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(NM == 1 ? 1 : ASVRL_ENV_ROLLOUT_WPE))) void env_rollout_kernel(RolloutArgs) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const KArg<RolloutArgs> RA = kargs<RolloutArgs>();
+  env_pairs_block<BLOCK, NM, true, true>(
+      &RA->k, RA->k.epb, RA->k.group0 + xcd_group(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x)), smem,
+      &RA->ro);
+}
+
+// The sweep layout's rollout is K single launches (asvrl_env_rollout); after step t this kernel, one lane per
+// env, copies the step's outputs and state into row t of the kept records, counts the env's steps and, for
+// hold_done, clears the mask of an env whose episode ended.
+__global__ __launch_bounds__(kBlock) void rollout_record_kernel(AsvEnvState s, AsvStepOut out, AsvRollout ro, int t,
+                                                                const uint8_t* mask, uint8_t* hold_mask) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= s.n_envs) return;
+  if (mask != nullptr && mask[e] == 0) return;
+  const int R = s.max_robots;
+  const size_t NT = static_cast<size_t>(s.n_envs) * R;
+  const size_t t0 = static_cast<size_t>(t) * NT;
+  const int nrob = s.n_robots[e];
+  for (int i = 0; i < R; ++i) {
+    const size_t idx = static_cast<size_t>(e) * R + i;
+    if (ro.reward != nullptr) ro.reward[t0 + idx] = out.reward[idx];
+    if (ro.done != nullptr) ro.done[t0 + idx] = out.done[idx];
+    if (ro.info != nullptr) ro.info[t0 + idx] = out.info[idx];
+    if (ro.obj_cnt != nullptr) ro.obj_cnt[t0 + idx] = out.obj_cnt[idx];
+    if (ro.obs != nullptr)
+      for (int k = 0; k < ASVRL_OBS_DIM; ++k) ro.obs[(t0 + idx) * ASVRL_OBS_DIM + k] = out.obs[idx * ASVRL_OBS_DIM + k];
+    if (ro.rs != nullptr && i < nrob)
+      for (int f = 0; f < ASVRL_NUM_FIELDS; ++f) ro.rs[(static_cast<size_t>(t) * ASVRL_NUM_FIELDS + f) * NT + idx] = s.rs[f * NT + idx];
+  }
+  if (ro.env_done != nullptr) ro.env_done[static_cast<size_t>(t) * s.n_envs + e] = out.env_done[e];
+  if (ro.steps_run != nullptr) ro.steps_run[e] += 1;
+  if (hold_mask != nullptr && out.env_done[e] != 0) hold_mask[e] = 0;
 }
 
 // ------------------------------------------------------------------ reset (env.py:72-164)
@@ -1446,6 +1630,89 @@ extern "C" int asvrl_env_step_ex(const AsvParams* params, const AsvEnvState* sta
 extern "C" int asvrl_env_step(const AsvParams* params, const AsvEnvState* state, const double* actions,
                               const double* noise, const AsvStepCtl* ctl, const AsvStepOut* out, void* stream) {
   return asvrl_env_step_ex(params, state, actions, noise, ctl, out, nullptr, stream);
+}
+
+extern "C" int asvrl_env_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                                 const AsvStepOut* out, const AsvRollout* ro, const AsvEnvLaunch* launch,
+                                 void* stream) {
+  ASVRL_REQUIRE(params && state && ctl && out && ro, "asvrl_env_rollout: null argument");
+  ASVRL_REQUIRE(ro->n_steps >= 1, "asvrl_env_rollout: n_steps must be >= 1");
+  ASVRL_REQUIRE(ro->actions != nullptr, "asvrl_env_rollout: null actions");
+  ASVRL_REQUIRE(ctl->do_dynamics, "asvrl_env_rollout: do_dynamics must be 1");
+  ASVRL_REQUIRE(!ro->hold_done || ctl->trainer_deactivate, "asvrl_env_rollout: hold_done needs trainer_deactivate");
+  ASVRL_REQUIRE(ctl->noise_mode != 0 || ro->noise != nullptr, "asvrl_env_rollout: noise_mode 0 needs injected noise");
+  ASVRL_REQUIRE(!(ro->hold_done || ro->env_done) || (ctl->trainer_deactivate && out->env_done),
+                "asvrl_env_rollout: hold_done and the env_done record need trainer_deactivate and out->env_done");
+  ASVRL_REQUIRE(state->max_robots >= 1 && state->max_robots <= kBlock, "asvrl_env_rollout: max_robots must be in [1, 256]");
+  ASVRL_REQUIRE(state->max_obs >= 0 && state->max_cores >= 0 && state->max_cores <= kMaxCoresStep,
+                "asvrl_env_rollout: bad max_obs/max_cores");
+  ASVRL_REQUIRE(params->max_obj_num >= 0 && params->max_obj_num <= ASVRL_MAX_OBJ, "asvrl_env_rollout: max_obj_num > 5");
+  ASVRL_REQUIRE(params->N >= 1, "asvrl_env_rollout: N < 1");
+  ASVRL_REQUIRE(out->obs && out->obj_cnt && out->reward && out->done && out->info, "asvrl_env_rollout: null output");
+  ASVRL_REQUIRE(state->rs && state->rflags && state->n_robots && state->n_obs && state->n_cores && state->ep_ts,
+                "asvrl_env_rollout: null state array");
+  if (state->n_envs == 0) return 0;
+  const AsvEnvLaunch lz{};
+  const AsvEnvLaunch& lc = launch != nullptr ? *launch : lz;
+  ASVRL_REQUIRE(lc.layout >= 0 && lc.layout <= 2, "asvrl_env_rollout: layout must be 0 (auto), 1 (pairs) or 2 (sweep)");
+  ASVRL_REQUIRE(lc.block == 0 || lc.block == 64 || lc.block == 128 || lc.block == 256,
+                "asvrl_env_rollout: block must be 0, 64, 128 or 256");
+  ASVRL_REQUIRE(lc.envs_per_block >= 0 && lc.max_groups >= 0, "asvrl_env_rollout: negative envs_per_block / max_groups");
+  const int nm = ctl->noise_mode == 0 ? 0 : (ctl->noise_mode == 1 ? 1 : 2);
+  const PairLaunch pl = pair_launch(state->max_robots, state->max_obs, state->n_envs, lc.block, lc.envs_per_block,
+                                    nm == 2 ? 4 : 8);
+  const bool per_robot = state->robot_params != nullptr;
+  ASVRL_REQUIRE(lc.layout != 1 || pl.smem <= 150 * 1024, "asvrl_env_rollout: the pair layout's LDS does not fit");
+  ASVRL_REQUIRE(lc.layout != 1 || !per_robot, "asvrl_env_rollout: per-robot parameters take the sweep layout (2)");
+  hipStream_t st = as_stream(stream);
+  if (ro->steps_run != nullptr && hipMemsetAsync(ro->steps_run, 0, sizeof(int32_t) * state->n_envs, st) != hipSuccess)
+    return check_launch("asvrl_env_rollout");
+  if (lc.layout != 2 && !per_robot && pl.smem <= 150 * 1024) {
+    const int groups = (state->n_envs + pl.epb - 1) / pl.epb;
+    const int chunk = lc.max_groups > 0 && lc.max_groups < groups ? lc.max_groups : groups;
+    auto go = [&](auto kern) {
+      RolloutArgs a{PairsArgs{*params, *state, *ctl, *out, ro->actions, ro->noise, pl.epb, 0}, *ro};
+      for (int g0 = 0; g0 < groups; g0 += chunk) {
+        a.k.group0 = g0;
+        hipLaunchKernelGGL(kern, dim3(groups - g0 < chunk ? groups - g0 : chunk), dim3(pl.blk), pl.smem, st, a);
+      }
+    };
+    if (pl.blk == 64)
+      nm == 0 ? go(env_rollout_kernel<64, 0>) : nm == 1 ? go(env_rollout_kernel<64, 1>) : go(env_rollout_kernel<64, 2>);
+    else if (pl.blk == 128)
+      nm == 0 ? go(env_rollout_kernel<128, 0>) : nm == 1 ? go(env_rollout_kernel<128, 1>) : go(env_rollout_kernel<128, 2>);
+    else
+      nm == 0 ? go(env_rollout_kernel<256, 0>) : nm == 1 ? go(env_rollout_kernel<256, 1>) : go(env_rollout_kernel<256, 2>);
+    return check_launch("asvrl_env_rollout");
+  }
+  // the sweep layout: K single launches; hold_done's mask lives in a stream-ordered scratch of n_envs bytes
+  const size_t NT = static_cast<size_t>(state->n_envs) * state->max_robots;
+  const size_t noise_row = NT * (static_cast<size_t>(state->max_obs) + state->max_robots) * 5;
+  uint8_t* hold_mask = nullptr;
+  if (ro->hold_done) {
+    if (hipMallocAsync(reinterpret_cast<void**>(&hold_mask), state->n_envs, st) != hipSuccess)
+      return check_launch("asvrl_env_rollout");
+    if (ctl->env_mask != nullptr)
+      (void)hipMemcpyAsync(hold_mask, ctl->env_mask, state->n_envs, hipMemcpyDeviceToDevice, st);
+    else
+      (void)hipMemsetAsync(hold_mask, 1, state->n_envs, st);
+  }
+  int rc = 0;
+  for (int t = 0; t < ro->n_steps && rc == 0; ++t) {
+    AsvStepCtl c = *ctl;
+    c.counter = ctl->counter + static_cast<uint64_t>(t);
+    if (hold_mask != nullptr) c.env_mask = hold_mask;
+    rc = asvrl_env_step_ex(params, state, ro->actions + static_cast<size_t>(t) * 2 * NT,
+                           ro->noise != nullptr ? ro->noise + static_cast<size_t>(t) * noise_row : nullptr, &c, out,
+                           launch, stream);
+    if (rc == 0) {
+      hipLaunchKernelGGL(rollout_record_kernel, dim3((state->n_envs + kBlock - 1) / kBlock), dim3(kBlock), 0, st,
+                         *state, *out, *ro, t, c.env_mask, hold_mask);
+      rc = check_launch("asvrl_env_rollout");
+    }
+  }
+  if (hold_mask != nullptr) (void)hipFreeAsync(hold_mask, st);
+  return rc;
 }
 
 extern "C" int asvrl_env_reset(const AsvParams* params, const AsvEnvState* state, const AsvResetCfg* cfg,

@@ -430,6 +430,7 @@ extern "C" void asvrl_struct_sizes(int64_t* out5) {
   out5[3] = sizeof(AsvStepOut);
   out5[4] = sizeof(AsvResetCfg);
 }
+extern "C" int64_t asvrl_rollout_struct_size(void) { return sizeof(AsvRollout); }
 
 extern "C" int asvrl_quantile_huber(const float* qt, const float* qe, const float* tau, int32_t B, int32_t N,
                                     int32_t Np, float kappa, float grad_scale, float* row_loss, float* loss,

@@ -122,6 +122,78 @@ class DeviceEnvBatch:
                                               C.byref(ctl), C.byref(out), C.byref(ln), _abi.stream_ptr(stream))
         _abi.check(rc, "asvrl_env_step")
 
+    # per-step records of rollout(): name -> (row shape, dtype, pre-fill of rows the env did not take)
+    def _record_specs(self):
+        NT, E = self.n_envs * self.max_robots, self.n_envs
+        return {"reward": ((NT,), torch.float64, 0), "done": ((NT,), torch.uint8, 1),
+                "info": ((NT,), torch.uint8, _abi.INFO_ABSENT), "env_done": ((E,), torch.uint8, 0),
+                "obs": ((NT, OBS_DIM), torch.float32, 0), "obj_cnt": ((NT,), torch.int8, 0),
+                "rs": ((NUM_FIELDS, NT), torch.float64, 0)}
+
+    def rollout(self, actions, noise=None, *, keep=("reward", "done", "info"), hold_done=False, is_continuous=True,
+                trainer_deactivate=False, seed=0, counter=0, counter_dev=None, gamma=0.0, env_mask=None, obs=None,
+                obj_cnt=None, fast_noise=False, launch=None, stream=None):
+        """asvrl_env_rollout: K = actions.shape[0] open-loop steps in one launch, bit for bit the K calls
+        step(actions[t], noise[t], counter=counter + t). actions: f64 [K, E*R, 2]; noise: f64 [K, E*R, O+R, 5]
+        or None (Philox). keep: the per-step records to return, names out of reward, done, info, env_done, obs,
+        obj_cnt, rs (allocated here, [K, ...] each; rows of steps an env did not take -- masked, or after a
+        hold -- stay at done = 1, info = INFO_ABSENT, zero elsewhere), or a dict name -> the caller's own
+        pre-filled tensor (also "steps_run": nothing is allocated then and the call can be graph-captured).
+        hold_done (needs trainer_deactivate): an env stops after the step that sets its env_done. The last
+        step's outputs land where step() writes them (obs / obj_cnt, self.reward, ...). Returns a namespace of
+        the kept records (None where not kept) and steps_run [E] i32. No host sync."""
+        import types
+        assert actions.dtype == torch.float64 and actions.is_contiguous() and actions.dim() == 3
+        K, NT = int(actions.shape[0]), self.n_envs * self.max_robots
+        assert tuple(actions.shape[1:]) == (NT, 2)
+        if noise is not None:
+            assert noise.dtype == torch.float64 and noise.is_contiguous()
+            assert noise.numel() == K * NT * (self.max_obs + self.max_robots) * 5
+        specs = self._record_specs()
+        given = dict(keep) if isinstance(keep, dict) else {}
+        rec = {}
+        for name in keep:
+            if name == "steps_run":
+                continue
+            if name not in specs:
+                raise ValueError(f"rollout: unknown record {name!r}; choose from {sorted(specs)}")
+            if name == "env_done" and not trainer_deactivate:
+                raise ValueError("rollout: the env_done record needs trainer_deactivate")
+            shape, dtype, fill = specs[name]
+            t = given.get(name)
+            if t is None:
+                t = torch.full((K,) + shape, fill, dtype=dtype, device=self.device)
+            assert t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == (K,) + shape, name
+            rec[name] = t
+        steps_run = given.get("steps_run")
+        if steps_run is None:
+            steps_run = torch.zeros(self.n_envs, dtype=torch.int32, device=self.device)
+        assert steps_run.dtype == torch.int32 and steps_run.numel() == self.n_envs
+        ctl = _abi.AsvStepCtl()
+        ctl.is_continuous = int(bool(is_continuous))
+        ctl.do_dynamics = 1
+        ctl.trainer_deactivate = int(bool(trainer_deactivate))
+        ctl.noise_mode = 0 if noise is not None else (2 if fast_noise else 1)
+        ctl.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        ctl.counter = int(counter) & 0xFFFFFFFFFFFFFFFF
+        ctl.counter_dev = counter_dev.data_ptr() if counter_dev is not None else None
+        ctl.gamma = float(gamma)
+        ctl.env_mask = env_mask.data_ptr() if env_mask is not None else None
+        ro = _abi.AsvRollout()
+        ro.n_steps, ro.hold_done = K, int(bool(hold_done))
+        ro.actions = actions.data_ptr()
+        ro.noise = noise.data_ptr() if noise is not None else None
+        for name, t in rec.items():
+            setattr(ro, name, t.data_ptr())
+        ro.steps_run = steps_run.data_ptr()
+        st = self.state_struct()
+        out = self.out_struct(obs, obj_cnt, with_env_done=trainer_deactivate)
+        ln = C.byref(_abi.AsvEnvLaunch(*(int(v) for v in launch))) if launch is not None else None
+        rc = _abi.lib().asvrl_env_rollout(C.byref(self.params), C.byref(st), C.byref(ctl), C.byref(out), C.byref(ro),
+                                          ln, _abi.stream_ptr(stream))
+        _abi.check(rc, "asvrl_env_rollout")
+        return types.SimpleNamespace(steps_run=steps_run, **{n: rec.get(n) for n in specs})
+
     def reset(self, cfg, env_mask=None, seed=0, counter=0, counter_dev=None, stream=None):
         st = self.state_struct()
         rc = _abi.lib().asvrl_env_reset(C.byref(self.params), C.byref(st), C.byref(cfg), _abi.ptr(env_mask),

@@ -90,6 +90,19 @@ class VecMarineNavEnv:
                         obj_cnt=self.cnt_next, fast_noise=True,   # f32 Philox draws (noise_mode 2)
                         launch=self._launch())
 
+    def rollout(self, actions, hold_done=True, keep=("reward", "done", "info")):
+        """K = actions.shape[0] open-loop steps in one launch (DeviceEnvBatch.rollout): the values of K rounds of
+        step(actions[t]); advance_device(), with the last step's observation in obs_next / cnt_next and the step
+        counter advanced by K on the device (so follow with auto_reset(counted=True) and
+        advance_device(counted=True)). hold_done: an env stops after the step that ends its episode, so
+        auto_reset after the call resets exactly the envs that ended. Returns the kept per-step records."""
+        rec = self.batch.rollout(actions, keep=keep, hold_done=hold_done, is_continuous=self.is_continuous,
+                                 trainer_deactivate=True, seed=self.seed, counter=0, counter_dev=self.counter,
+                                 gamma=self.gamma, obs=self.obs_next, obj_cnt=self.cnt_next, fast_noise=True,
+                                 launch=self._launch())
+        self.counter += int(actions.shape[0])
+        return rec
+
     def _launch(self):
         """The step kernel's shape: automatic, or launches of at most `max_groups` workgroups one after another
         (the rollout's share of the chip beside a concurrent learner; results do not depend on it)."""

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define ASVRL_ABI_VERSION 26
+#define ASVRL_ABI_VERSION 27
 
 #define ASVRL_SELF_DIM 7   /* wamv.py:443-453 self observation */
 #define ASVRL_OBJ_DIM 5    /* wamv.py:481,508 [px, py, vx, vy, r] */
@@ -182,6 +182,39 @@ typedef struct AsvEnvLaunch {
 int asvrl_env_step_ex(const AsvParams* params, const AsvEnvState* state, const double* actions,
                       const double* noise, const AsvStepCtl* ctl, const AsvStepOut* out,
                       const AsvEnvLaunch* launch, void* stream);
+
+/* ABI 27: K open-loop env steps in one launch (asvrl_env_rollout). */
+typedef struct AsvRollout {
+  int32_t n_steps;        /* K >= 1 */
+  int32_t hold_done;      /* 1 (needs trainer_deactivate): an env stops after the step that sets its env_done */
+  const double* actions;  /* [K][n_envs*max_robots][2] */
+  const double* noise;    /* noise_mode 0: [K][n_envs*max_robots][max_obs+max_robots][5] */
+  /* per-step records, every member optional (NULL: not kept) */
+  double*  reward;        /* [K][NT], NT = n_envs*max_robots */
+  uint8_t* done;          /* [K][NT] */
+  uint8_t* info;          /* [K][NT] */
+  uint8_t* env_done;      /* [K][n_envs] (trainer_deactivate) */
+  float*   obs;           /* [K][NT][ASVRL_OBS_DIM] */
+  int8_t*  obj_cnt;       /* [K][NT] */
+  double*  rs;            /* [K][ASVRL_NUM_FIELDS][NT] state after each step (placed robots only) */
+  int32_t* steps_run;     /* [n_envs] steps this env took (K unless held or masked: 0) */
+} AsvRollout;
+
+/* n_steps calls of asvrl_env_step_ex in one launch: step t takes row t of ro->actions (and of ro->noise in
+ * noise_mode 0) and draws Philox noise at ctl->counter + t (+ *ctl->counter_dev) -- the values, bit for bit, that
+ * n_steps single calls with counter + t compute (replaying a recorded trace, teacher-forced evaluation, action
+ * repeat, scoring candidate action sequences). An env group lives inside one workgroup of the pair layout, so
+ * the workgroup loops over the steps with the robot state, goals, flags and returns resident in registers and
+ * LDS and the buoys staged once; the state returns to HBM after the env's last step. `last` receives the last
+ * step's outputs as a single step writes them (with hold_done: each env's end step); stats accumulate as over
+ * the single calls. ctl->do_dynamics must be 1; ctl->env_mask is honoured. Record rows of steps an env did not
+ * take (masked, or after a hold) are not written: pre-fill them. hold_done is the chain of single steps whose
+ * env_mask drops an env after its env_done. launch->max_groups splits the rollout into launches over groups.
+ * The sweep layout (robot_params, layout 2, pair LDS too large) runs n_steps single launches instead, each
+ * followed by a small record launch (hold_done: with a stream-ordered scratch mask of n_envs bytes). */
+int asvrl_env_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                      const AsvStepOut* last, const AsvRollout* ro, const AsvEnvLaunch* launch /* NULL: automatic */,
+                      void* stream);
 
 /* MarineNavEnv3.reset (env.py:72-164) for envs with env_mask != 0, sampled on the device
  * with Philox (same rejection rules and iteration caps; not the reference's RandomState
@@ -982,6 +1015,8 @@ int32_t asvrl_operand_bytes(void);
 /* sizeof(AsvParams, AsvEnvState, AsvStepCtl, AsvStepOut, AsvResetCfg) as compiled, for
  * binding checks (host pointer to 5 int64). */
 void asvrl_struct_sizes(int64_t* out5);
+/* ABI 27: sizeof(AsvRollout) as compiled (asvrl_struct_sizes keeps its five: its callers pass five slots). */
+int64_t asvrl_rollout_struct_size(void);
 
 #ifdef __cplusplus
 }

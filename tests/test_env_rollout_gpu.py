@@ -1,0 +1,376 @@
+"""GPU: the fused K-step env rollout (asvrl_env_rollout, env_rollout_kernel) against
+
+  * the K-call loop of single steps it replaces, bit for bit (records of every step, final state and outputs),
+    over shapes with partial groups, 1 / 12 / 30 robots and vortex cores, both Philox precisions, three launch
+    shapes; with episode ends inside the window, with and without hold_done; through the sweep fallback; and
+    through VecMarineNavEnv.rollout,
+  * the reference's own episodes: every golden trace free-running from its first state through all of its
+    recorded actions and perception noise in ONE launch (nothing re-seeded from the reference on the way), masks
+    exact and values within 1e-12 at every step.
+"""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import env_oracle as eo
+
+pytestmark = pytest.mark.gpu
+
+TOL = 1e-12
+E = 37           # not a multiple of any envs-per-workgroup in use: the last group is partial
+GAMMA = 0.99
+RECORDS = ("reward", "done", "info", "env_done", "obs", "obj_cnt", "rs")
+FINALS = ("rs", "rflags", "ep_ts", "obs", "obs64", "obj_cnt", "reward", "done", "info", "env_done")   # + stats
+
+
+def _close(a, b, tol=TOL):   # tests/test_env_kernel_gpu.py's
+    a = np.asarray(a, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    scale = np.maximum(1.0, np.abs(b))
+    return np.all(np.abs(a - b) <= tol * scale), float(np.max(np.abs(a - b) / scale)) if a.size else 0.0
+
+
+def _same(got, ref, what):
+    # exact, NaN = NaN: phi is NaN, in the single step and in the reference too, when COLREGs evaluates an object
+    # closer than its radius + 1 (asin of a ratio > 1, wamv.py:388); it never enters a reward
+    torch.testing.assert_close(got, ref, rtol=0, atol=0, equal_nan=True, msg=lambda m: f"{what}: {m}")
+
+
+def _fresh(R, O, C, fast, params=None, robot_params=False):
+    """A device-reset batch with its reset observation; the same call gives the same batch."""
+    from distributional_rl_decision_and_control_amd.device_env import DeviceEnvBatch, reset_cfg
+    W = 55.0 if R <= 5 else 110.0
+    b = DeviceEnvBatch(E, R, O, C, obs64=True, params=params)
+    if robot_params:
+        b.set_robot_params([b.params] * (E * R))
+    b.reset(reset_cfg(R, O, C, 20.0, width=W, height=W), seed=11)
+    b.step(None, do_dynamics=False, seed=11, counter=0, fast_noise=fast)
+    return b
+
+
+def _actions(K, R):
+    g = torch.Generator(device="cuda").manual_seed(3)
+    return torch.stack([(torch.rand((E * R, 2), generator=g, device="cuda", dtype=torch.float64) * 2 - 1)
+                        for _ in range(K)]).contiguous()
+
+
+def _finals(b):
+    return {k: getattr(b, k).clone() for k in FINALS + ("stats",)}
+
+
+def _loop(b, acts, hold=False, launch=None, env_mask=None, counter=1, **kw):
+    """The reference: K calls of b.step(..., counter=counter + t); with hold, env_mask drops an env after its
+    env_done. Returns the records as rollout() lays them out (rows of steps an env did not take at the pre-fill),
+    the steps every env took, and the finals after each step."""
+    K = acts.shape[0]
+    spec = b._record_specs()
+    rec = {n: torch.full((K,) + spec[n][0], spec[n][2], dtype=spec[n][1], device="cuda") for n in RECORDS}
+    mask = env_mask.clone() if env_mask is not None else (torch.ones(E, dtype=torch.uint8, device="cuda") if hold else None)
+    steps_run = torch.zeros(E, dtype=torch.int32, device="cuda")
+    finals = []
+    R = b.max_robots
+    for t in range(K):
+        b.step(acts[t], seed=11, counter=counter + t, trainer_deactivate=True, gamma=GAMMA, env_mask=mask,
+               launch=launch, **kw)
+        on_e = (mask != 0) if mask is not None else torch.ones(E, dtype=torch.bool, device="cuda")
+        on_r = on_e.repeat_interleave(R)
+        for n in RECORDS:
+            src = getattr(b, n)
+            if n == "rs":
+                rec[n][t][:, on_r] = src[:, on_r]
+            else:
+                sel = on_e if n == "env_done" else on_r
+                rec[n][t][sel] = src[sel]
+        steps_run += on_e.int()
+        if hold:
+            mask = mask * (b.env_done == 0).to(torch.uint8)
+        finals.append(_finals(b))
+    return rec, steps_run, finals
+
+
+def _check(b, got, ref_rec, ref_steps, ref_final, K, what):
+    for n in RECORDS:
+        _same(getattr(got, n), ref_rec[n][:K], f"{what}: record {n}")
+    _same(got.steps_run, ref_steps, f"{what}: steps_run")
+    for n in FINALS:
+        _same(getattr(b, n), ref_final[n], f"{what}: final {n}")
+    s, r = b.stats.cpu().numpy(), ref_final["stats"].cpu().numpy()
+    assert np.array_equal(s[1:], r[1:]), f"{what}: stats counts {s} vs {r}"
+    # the return sum is a sum of f64 atomics in no fixed order
+    assert abs(s[0] - r[0]) <= 1e-12 * max(1.0, abs(r[0])), f"{what}: stats return sum {s[0]} vs {r[0]}"
+
+
+SHAPES = [(1, 0, 0), (5, 4, 2), (12, 8, 0), (30, 2, 0)]
+KMAX = 13
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(R, O, C, fast):
+    """One 13-call loop per (shape, precision): its first K steps are the reference of the K-step rollout."""
+    recs, _, finals = _loop(_fresh(R, O, C, fast), _actions(KMAX, R), fast_noise=fast)
+    return recs, finals
+
+
+@pytest.mark.parametrize("fast", [True, False])
+@pytest.mark.parametrize("R,O,C", SHAPES)
+def test_rollout_matches_single_launches(R, O, C, fast):
+    """Bit-identity to K single launches: every kept record at every step, the final state, flags, step counts
+    and outputs; K = 1, 2, 13; the automatic launch shape, a forced one-wave shape and the automatic shape as
+    launches of at most 3 workgroups."""
+    from distributional_rl_decision_and_control_amd import _abi
+    ref_rec, ref_finals = _reference(R, O, C, fast)
+    acts = _actions(KMAX, R)
+    for K in (1, 2, 13):
+        for launch in (None, (_abi.ENV_LAYOUT_PAIRS, 64, max(1, 64 // R)), (0, 0, 0, 3)):
+            b = _fresh(R, O, C, fast)
+            got = b.rollout(acts[:K].contiguous(), keep=RECORDS, trainer_deactivate=True, seed=11, counter=1,
+                            gamma=GAMMA, fast_noise=fast, launch=launch)
+            _check(b, got, ref_rec, torch.full((E,), K, dtype=torch.int32, device="cuda"), ref_finals[K - 1],
+                   K, f"R={R} O={O} K={K} launch={launch}")
+
+
+def _ending_batch(fast=True, **kw):
+    """Every env ends inside a 13-step window, at a step that depends on the env: episode_limit 5 and ep_ts
+    preset to e % 9 (the end step is the first with ep_ts >= 5)."""
+    from distributional_rl_decision_and_control_amd import _abi
+    b = _fresh(5, 4, 0, fast, params=_abi.params_from(episode_limit=5), **kw)
+    b.ep_ts.copy_(torch.arange(E, dtype=torch.int32, device="cuda") % 9)
+    return b
+
+
+def test_rollout_episode_ends_without_hold():
+    acts = _actions(KMAX, 5)
+    ref_rec, ref_steps, ref_finals = _loop(_ending_batch(), acts, fast_noise=True)
+    assert bool((ref_rec["env_done"].sum(0) > 0).all()), "every env must end inside the window"
+    b = _ending_batch()
+    got = b.rollout(acts, keep=RECORDS, trainer_deactivate=True, seed=11, counter=1, gamma=GAMMA, fast_noise=True)
+    _check(b, got, ref_rec, ref_steps, ref_finals[-1], KMAX, "no hold")
+
+
+@pytest.mark.parametrize("masked", [False, True])
+def test_rollout_hold_done(masked):
+    """hold_done is the chain of single steps whose env_mask drops an env after its env_done; `masked`: on top of
+    a caller's mask that leaves every fourth env (and one whole workgroup's envs) out."""
+    acts = _actions(KMAX, 5)
+    mask = None
+    if masked:
+        mask = torch.ones(E, dtype=torch.uint8, device="cuda")
+        mask[::4] = 0
+        mask[8:16] = 0
+    ref_rec, ref_steps, ref_finals = _loop(_ending_batch(), acts, hold=True, env_mask=mask, fast_noise=True)
+    b = _ending_batch()
+    before = _finals(b)
+    got = b.rollout(acts, keep=RECORDS, hold_done=True, trainer_deactivate=True, seed=11, counter=1, gamma=GAMMA,
+                    fast_noise=True, env_mask=mask)
+    _check(b, got, ref_rec, ref_steps, ref_finals[-1], KMAX, f"hold masked={masked}")
+    steps = ref_steps.cpu().numpy()
+    on = np.ones(E, bool) if mask is None else mask.cpu().numpy() != 0
+    # the end step is known: the index of the first step with ep_ts >= 5, plus one
+    expect = np.where(on, np.maximum(1, 5 - np.arange(E) % 9 + 1), 0)
+    assert np.array_equal(steps, expect)
+    assert np.array_equal(got.steps_run.cpu().numpy(), expect)
+    assert int(b.stats[5].item()) == int(on.sum()), "every ended env enters the totals once"
+    # rows of steps an env did not take keep their pre-fill; an env that took none is untouched
+    R = 5
+    t_idx = np.arange(KMAX)[:, None]
+    idle_e = t_idx >= expect[None, :]
+    idle_r = np.repeat(idle_e, R, axis=1)
+    assert (got.done.cpu().numpy()[idle_r] == 1).all() and (got.info.cpu().numpy()[idle_r] == 255).all()
+    assert (got.reward.cpu().numpy()[idle_r] == 0).all() and (got.env_done.cpu().numpy()[idle_e] == 0).all()
+    assert not got.obs.cpu().numpy()[idle_r].any() and not got.rs.cpu().numpy().transpose(0, 2, 1)[idle_r].any()
+    off_r = torch.from_numpy(np.repeat(~on, R)).cuda()
+    for n in ("obs", "reward", "done", "info", "obj_cnt"):
+        _same(getattr(b, n)[off_r], before[n][off_r], f"masked env's {n}")
+    _same(b.rs[:, off_r], before["rs"][:, off_r], "masked env's state")
+
+
+@pytest.mark.parametrize("case", ["robot_params", "layout2", "layout2_hold"])
+def test_rollout_sweep_fallback(case):
+    """Per-robot parameters and an explicit layout 2 take K single launches of the sweep kernel inside the call:
+    the same records and finals as the K-call loop."""
+    from distributional_rl_decision_and_control_amd import _abi
+    K = 3
+    acts = _actions(K, 5)
+    hold = case == "layout2_hold"
+    launch = None if case == "robot_params" else (_abi.ENV_LAYOUT_SWEEP, 0, 0)
+    mk = (lambda: _ending_batch(robot_params=case == "robot_params")) if hold else (
+        lambda: _fresh(5, 4, 2, True, robot_params=case == "robot_params"))
+    ref_rec, ref_steps, ref_finals = _loop(mk(), acts, hold=hold, launch=launch, fast_noise=True)
+    b = mk()
+    got = b.rollout(acts, keep=RECORDS, hold_done=hold, trainer_deactivate=True, seed=11, counter=1, gamma=GAMMA,
+                    fast_noise=True, launch=launch)
+    _check(b, got, ref_rec, ref_steps, ref_finals[-1], K, case)
+    if hold:
+        assert int((ref_steps < K).sum()) > 0, "some env must be held inside the window"
+
+
+# ------------------------------------------------------------------ free-running through the reference's episodes
+def _trace_groups():
+    """Traces of one (robots, buoys, action kind, length) share a batch, one env each."""
+    groups = {}
+    for name, tr in eo.load_traces().items():
+        key = (int(tr["n_robots"]), int(tr["O"]), not name.startswith("disc"), len(tr["reward"]))
+        groups.setdefault(key, []).append(name)
+    return groups
+
+
+def _gid(k):
+    return f"r{k[0]}o{k[1]}{'' if k[2] else 'disc'}_T{k[3]}"
+
+
+def _trace_batch(key):
+    """The group's envs loaded with each trace's FIRST state only (as tests/test_env_kernel_gpu.py's _run_rows loads
+    a step), and the whole recorded actions [T] and perception noise [T]."""
+    from distributional_rl_decision_and_control_amd import _abi
+    from distributional_rl_decision_and_control_amd.device_env import DeviceEnvBatch
+    n, O, continuous, T = key
+    traces = eo.load_traces()
+    names = _trace_groups()[key]
+    Eg, Cm = len(names), 8
+    b = DeviceEnvBatch(Eg, n, O, Cm, params=_abi.params_from())
+    rs = np.zeros((_abi.NUM_FIELDS, Eg * n))
+    fl = np.zeros(Eg * n, np.uint8)
+    acts = np.zeros((T, Eg * n, 2))
+    noise = np.zeros((T, Eg * n, O + n, 5))
+    for e, nm in enumerate(names):
+        tr = traces[nm]
+        inp = eo.trace_step_inputs(tr, 0)
+        assert inp["state_before"].shape[0] == n and inp["O"] == O
+        sl = slice(e * n, (e + 1) * n)
+        rs[:13, sl] = inp["state_before"].T
+        rs[_abi.F_GX, sl], rs[_abi.F_GY, sl] = inp["goals"][:, 0], inp["goals"][:, 1]
+        fl[sl] = (inp["deact"] * _abi.FLAG_DEACTIVATED) | (inp["coll"] * _abi.FLAG_COLLISION) | (
+            inp["reach"] * _abi.FLAG_REACH_GOAL)
+        b.n_robots[e], b.n_obs[e], b.n_cores[e], b.ep_ts[e] = n, inp["n_obs"], inp["n_cores"], inp["ep_ts"]
+        b.obstacles[e, :O] = torch.from_numpy(inp["obstacles"])
+        if inp["n_cores"]:
+            b.cores[e, :inp["n_cores"]] = torch.from_numpy(inp["cores"][:inp["n_cores"]].astype(np.float64))
+        for t in range(T):
+            it = eo.trace_step_inputs(tr, t)
+            acts[t, sl], noise[t, sl] = it["actions"], it["noise"]
+    b.rs.copy_(torch.from_numpy(rs))
+    b.rflags.copy_(torch.from_numpy(fl))
+    return b, torch.from_numpy(acts).cuda(), torch.from_numpy(noise).cuda(), names, traces
+
+
+def _check_flags(b, names, traces, n, t, what):
+    from distributional_rl_decision_and_control_amd import _abi
+    fl = b.rflags.cpu().numpy()
+    ts = b.ep_ts.cpu().numpy()
+    for e, nm in enumerate(names):
+        tr, f = traces[nm], fl[e * n:(e + 1) * n]
+        assert np.array_equal((f & _abi.FLAG_COLLISION) > 0, tr["collision"][t][:n] > 0), f"{nm} {what}: collision"
+        assert np.array_equal((f & _abi.FLAG_REACH_GOAL) > 0, tr["reach"][t][:n] > 0), f"{nm} {what}: reach"
+        assert np.array_equal((f & _abi.FLAG_DEACTIVATED) > 0, tr["deact_after"][t][:n] > 0), f"{nm} {what}: deactivated"
+        assert int(ts[e]) == int(tr["ep_ts"][t]) + 1, f"{nm} {what}: ep_ts"
+
+
+@pytest.mark.parametrize("key", sorted(_trace_groups()), ids=_gid)
+def test_rollout_free_runs_reference_episodes(key):
+    """Every golden trace, free-running: ONE launch runs all T recorded actions with the perception noise the
+    reference drew (noise mode 0) from the trace's first state, the kernel's own state feeding every next step;
+    nothing is re-seeded from the reference on the way (the existing single-step test re-seeds every step; the
+    chained-returns test holds 1e-9). At every step done / info / object counts / env_done equal the trace
+    exactly -- info carries the collision / reach flag of every deactivated robot and of the step an active one
+    sets it, obj_cnt = -1 the deactivated flag before the step -- and the flags themselves after the last step
+    (test_rollout_windows_flags: after windows on the way). State, reward, the packed observation (against the
+    trace's f64 rows cast to f32, as the single-step test casts them) at every step and the final discounted
+    return within 1e-12, the project's bar for env values."""
+    from distributional_rl_decision_and_control_amd import _abi
+    n, O, continuous, T = key
+    b, acts, noise, names, traces = _trace_batch(key)
+    got = b.rollout(acts, noise, keep=RECORDS, is_continuous=continuous, trainer_deactivate=True, gamma=GAMMA)
+    torch.cuda.synchronize()
+    g = {k: getattr(got, k).cpu().numpy() for k in RECORDS}
+    assert (got.steps_run.cpu().numpy() == T).all()
+    _check_flags(b, names, traces, n, T - 1, "after the last step")
+    for e, nm in enumerate(names):
+        tr = traces[nm]
+        sl = slice(e * n, (e + 1) * n)
+        assert np.array_equal(g["done"][:, sl], tr["done"][:, :n]), f"{nm}: done"
+        assert np.array_equal(g["info"][:, sl], tr["info"][:, :n]), f"{nm}: info"
+        assert np.array_equal(g["env_done"][:, e], tr["end_episode"]), f"{nm}: env_done"
+        valid = tr["obs_valid"][:, :n]
+        ref_cnt = np.where(valid == 1, tr["obj_cnt"][:, :n], -1)
+        assert np.array_equal(g["obj_cnt"][:, sl].astype(int), ref_cnt.astype(int)), f"{nm}: object counts"
+        obs = g["obs"][:, sl]
+        mask = np.arange(5)[None, None, :] < ref_cnt[:, :, None]
+        so = np.where(valid[:, :, None] == 1, tr["self_obs"][:, :n], 0.0).astype(np.float32)
+        oo = np.where(mask[:, :, :, None], tr["obj_obs"][:, :n], 0.0).astype(np.float32).reshape(T, n, 25)
+        assert np.array_equal(obs[:, :, 32:37], mask.astype(np.float32)), f"{nm}: object mask"
+        checks = {"state": (g["rs"][:, :13, sl].transpose(0, 2, 1), tr["state_after"][:, :n]),
+                  "reward": (g["reward"][:, sl], tr["reward"][:, :n]),
+                  "self_obs": (obs[:, :, :7], so),
+                  "obj_obs": (obs[:, :, 7:32], oo),
+                  "return": (g["rs"][T - 1, _abi.F_RET, sl], tr["ep_return"][T - 1, :n])}
+        for k, (a, r) in checks.items():
+            ok, err = _close(a, r)
+            print(f"{nm}: {k} within {err:.3e} over {T} free-running steps")
+            assert ok, f"{nm}: {k} off by {err}"
+
+
+@pytest.mark.parametrize("key", sorted(_trace_groups()), ids=_gid)
+def test_rollout_windows_flags(key):
+    """The same episodes as windows of 1, 2, 3, ... steps back to back (the state goes through HBM between
+    windows): collision / reach / deactivated flags and the step count after every window equal the trace."""
+    n, O, continuous, T = key
+    b, acts, noise, names, traces = _trace_batch(key)
+    t, w = 0, 1
+    while t < T:
+        w = min(w, T - t)
+        b.rollout(acts[t:t + w].contiguous(), noise[t:t + w].contiguous(), keep=(), is_continuous=continuous,
+                  trainer_deactivate=True, gamma=GAMMA)
+        t += w
+        w += 1
+        _check_flags(b, names, traces, n, t - 1, f"after {t} steps")
+
+
+# ------------------------------------------------------------------ VecMarineNavEnv.rollout
+def _vec(seed=5):
+    from distributional_rl_decision_and_control_amd.vec_env import VecMarineNavEnv
+    env = VecMarineNavEnv(E, num_robots=5, num_obs=4, min_start_goal_dis=20.0, seed=seed)
+    env.reset()
+    return env
+
+
+def test_vec_env_rollout_matches_steps():
+    K = 4
+    acts = _actions(K, 5)
+    twin = _vec()
+    for t in range(K):
+        twin.step(acts[t])
+        twin.advance_device()
+    env = _vec()
+    rec = env.rollout(acts, hold_done=False)
+    assert rec.reward.shape == (K, E * 5)
+    _same(env.obs_next, twin.obs_next, "obs_next")
+    _same(env.cnt_next, twin.cnt_next, "cnt_next")
+    _same(env.counter, twin.counter, "counter")
+    for n in ("rs", "rflags", "ep_ts", "reward", "done", "info", "env_done"):
+        _same(getattr(env.batch, n), getattr(twin.batch, n), n)
+    _same(rec.reward[-1], twin.batch.reward, "last reward record")
+
+
+def test_vec_env_rollout_hold_then_auto_reset():
+    """hold_done + auto_reset: the envs that ended are reset (step count 0, fresh robots), the others untouched."""
+    K = 4
+    env = _vec()
+    env.batch.params.episode_limit = 2          # ep_ts e % 4: an env ends on the first step with ep_ts >= 2 ...
+    env.batch.ep_ts.copy_(torch.arange(E, dtype=torch.int32, device="cuda") % 4 - 2)   # ... or not at all (ep_ts -2)
+    rec = env.rollout(_actions(K, 5), hold_done=True, keep=("reward", "env_done"))
+    ended = env.batch.env_done.clone() != 0
+    assert 0 < int(ended.sum()) < E
+    _same(ended, rec.env_done.sum(0) > 0, "env_done of the held envs")
+    before = {n: getattr(env.batch, n).clone() for n in ("rs", "rflags", "ep_ts")}
+    obs_before = env.obs_next.clone()
+    env.auto_reset(counted=True)
+    torch.cuda.synchronize()
+    er = ended.repeat_interleave(5)
+    assert bool((env.batch.ep_ts[ended] == 0).all())
+    assert not torch.equal(env.batch.rs[:, er], before["rs"][:, er])
+    _same(env.batch.rs[:, ~er], before["rs"][:, ~er], "running envs' state")
+    _same(env.batch.rflags[~er], before["rflags"][~er], "running envs' flags")
+    _same(env.batch.ep_ts[~ended], before["ep_ts"][~ended], "running envs' step counts")
+    _same(env.obs_next[~er], obs_before[~er], "running envs' observation")
