@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("ASVRL_LIB", os.path.join(HERE, "lib", "libasvrl.so"))
 # the same sources built with f32 learner operands (the parity build; asvrl_operand_bytes() == 4)
 LIB_PATH_F32 = os.path.join(HERE, "lib", "libasvrl_f32.so")
 OPERANDS = {"bf16": (LIB_PATH, 2), "f32": (LIB_PATH_F32, 4)}
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 SELF_DIM, OBJ_DIM, MAX_OBJ = 7, 5, 5
 OBS_DIM = 40   # self 7 | objects 25 | mask 5 | pad 3
@@ -186,6 +186,12 @@ class AsvMlpIO(C.Structure):
                 ("eps_initial", _D), ("eps_final", _D), ("seed", _U64)]
 
 
+class AsvPolicy(C.Structure):
+    _fields_ = [("w", AsvMlpWeights), ("obs_in", _VP), ("step_dev", _VP), ("eps_steps_per_count", _D),
+                ("eps_total", _D), ("eps_fraction", _D), ("eps_initial", _D), ("eps_final", _D), ("seed", _U64),
+                ("actions", _VP)]
+
+
 class AsvSampleArgs(C.Structure):
     _fields_ = [("ring", _VP), ("capacity", _I64), ("ring_state", _VP), ("seed", _U64), ("counter", _U64),
                 ("counter_dev", _VP), ("guard", _I64), ("B", _I32), ("tau_sets", _I32), ("tau_n", _I32),
@@ -341,6 +347,10 @@ EXPORTS = [
     ("asvrl_operand_bytes", C.c_int32, []),
     ("asvrl_struct_sizes", None, [C.c_void_p]),
     ("asvrl_rollout_struct_size", _I64, []),
+    ("asvrl_policy_rollout", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), C.POINTER(AsvStepCtl),
+                                       C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvPolicy),
+                                       C.POINTER(AsvEnvLaunch), _VP]),
+    ("asvrl_policy_struct_size", _I64, []),
 ]
 
 _libs = {}

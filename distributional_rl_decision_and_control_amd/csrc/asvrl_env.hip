@@ -21,6 +21,7 @@
 
 #include "asvrl_common.h"
 #include "asvrl_vonmises_k1.h"
+#include "asvrl_actor_tile.h"
 
 namespace asvrl {
 namespace {
@@ -29,6 +30,8 @@ constexpr int kBlock = 256;
 // env-step workgroup: one wave of whole envs when they fit (R <= 64), spreading a 4096-env batch
 // over every CU instead of packing 51 envs per 256-lane group onto a third of them
 __host__ __device__ constexpr int step_block(int R) { return R <= 64 ? 64 : 256; }
+// the policy rollout's LDS rows (observations, actions) start at the first 16-byte boundary behind the pair carve
+__host__ __device__ constexpr size_t policy_rows_offset(size_t carve_bytes) { return (carve_bytes + 15) & ~size_t{15}; }
 constexpr int kMaxCores = 16;        // the device reset sampler's LDS table (env_reset_kernel)
 constexpr int kMaxCoresStep = 4096;  // the step and the current field read the cores from HBM
 
@@ -653,9 +656,16 @@ __global__ __launch_bounds__(BLOCK) void env_sweep_kernel(AsvParams p, AsvEnvSta
 // staged once; step t takes row t of A->actions (and of A->noise in mode 0) and draws at counter + t. The state
 // goes back to HBM after the env's last step; every step's outputs go to row t of the kept records, the last
 // step's to A->out. The phases are the single step's own code: without ROLL the loop below runs once.
-template <int BLOCK, int NM, bool DYN = true, bool ROLL = false>   // DYN false: an observation pass only (do_dynamics = 0)
+// POL (env_policy_rollout_kernel, with ROLL): closed loop. The AC-IQN Actor (asvrl_actor_tile.h, its weights
+// staged once into AL) runs in front of phase 1 of every step on the workgroup's nrb robot rows, wave w on the
+// 32-row tiles w, w + waves, ...; it reads the rows of an LDS copy of the observation (PI->obs_in before step 0,
+// then what the phases of the step before wrote: they write it beside their global outputs) and leaves the f64
+// action pairs in LDS, where phase 1 takes the lane's action instead of from A->actions.
+template <int BLOCK, int NM, bool DYN = true, bool ROLL = false, bool POL = false>   // DYN false: an observation pass only (do_dynamics = 0)
 __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int bid, unsigned char* smem,
-                                                KArg<AsvRollout> RO = nullptr) {
+                                                KArg<AsvRollout> RO = nullptr, KArg<AsvPolicy> PI = nullptr,
+                                                atile::ActorLds* AL = nullptr) {
+  static_assert(!POL || ROLL, "the policy runs inside the rollout's step loop");
   const int R = A->s.max_robots;
   const int O = A->s.max_obs;
   const int S = O + R;               // candidate slots per robot (obstacles, then robots)
@@ -686,6 +696,10 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
   unsigned char* soff = pfl + nslot;   // [nrb] not a candidate (absent / deactivated before the step)
   unsigned char* sact = soff + nrb;    // [nrb] active
   signed char* scnt = reinterpret_cast<signed char*>(sact + nrb);  // [nrb] kept count, -1 inactive
+  // POL: the robots' observation rows [nrb][ASVRL_OBS_DIM] f32 and action pairs [nrb][2] f64, 16-byte aligned
+  float* sobs = reinterpret_cast<float*>(smem + policy_rows_offset(reinterpret_cast<unsigned char*>(scnt + nrb) - smem));
+  double* sa64 = reinterpret_cast<double*>(sobs + static_cast<size_t>(nrb) * ASVRL_OBS_DIM);
+  const size_t row0 = POL ? static_cast<size_t>(bid) * nrb : 0;   // the workgroup's first global robot row
 
   const bool rlane = tid < nrb;
   int le = tid / R;
@@ -747,6 +761,17 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
       ret = A->s.rs[ASVRL_F_RET * NT + idx];
     }
   }
+  if constexpr (POL) {
+    // the weights once per workgroup; the rows step 0 acts on (rows past the batch: zeros, never consumed)
+    atile::stage_actor<BLOCK>(*AL, kref(PI).w, tid);
+    constexpr int kRowV = ASVRL_OBS_DIM / 4;
+    const float4* src = reinterpret_cast<const float4*>(PI->obs_in);
+    for (int k = tid; k < nrb * kRowV; k += BLOCK) {
+      const size_t g = row0 + k / kRowV;
+      reinterpret_cast<float4*>(sobs)[k] = g < NT ? src[g * kRowV + k % kRowV] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    __syncthreads();
+  }
 
   // the step loop (its body keeps the single step's indentation; closed at "step t" below)
   for (int t = 0; t < n_steps; ++t) {
@@ -782,10 +807,45 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
     }
     return o;
   };
+  // f(o, opt, base): the outputs o (opt: members may be null); o.obs's rows are numbered from global row `base`
   auto each_out = [&](KArg<PairsArgs> Ak, auto&& f) {
-    if (wlast) f(kref(Ak).out, std::false_type{});
-    if constexpr (ROLL) f(rec_row(), std::true_type{});
+    if (wlast) f(kref(Ak).out, std::false_type{}, size_t{0});
+    if constexpr (ROLL) f(rec_row(), std::true_type{}, size_t{0});
+    if constexpr (POL) {   // the rows the Actor reads at the next step
+      AsvStepOut o{};
+      o.obs = sobs;
+      f(o, std::true_type{}, row0);
+    }
   };
+
+  // ---------------- act: the Actor on the workgroup's rows, epsilon-greedy at step *step_dev + t
+  if constexpr (POL) {
+    const KArg<AsvPolicy> P = kfresh(PI);
+    const uint64_t step = (P->step_dev != nullptr ? static_cast<uint64_t>(*P->step_dev) : 0ull) + static_cast<uint64_t>(t);
+    const int ln = tid & (kWave - 1), wv = __builtin_amdgcn_readfirstlane(tid / kWave);
+    for (int tile = wv; tile * 32 < nrb; tile += BLOCK / kWave) {   // wave-uniform: the MFMAs run with every lane on
+      // the tile's LDS reads stay inside the loop: its only stores are the f64 action pairs, so the f32 bias and
+      // output-layer reads (384 values per lane) would otherwise be hoisted in front of it and spilled
+      asm volatile("" ::: "memory");
+      const int lr = tile * 32 + (ln & 31);
+      const bool valid = lr < nrb;
+      frag8 bx[2];
+      float mk[atile::kObjN];
+      atile::load_obs(sobs, ASVRL_OBS_DIM, valid ? lr : nrb - 1, ln >> 5, bx, mk);
+      float z0, z1, a0, a1;
+      atile::actor_chain<atile::MLP_ACT>(kref(P).w, AsvMlpIO{}, *AL, 0, false, ln, bx, mk, z0, z1, a0, a1);
+      if (valid && ln < 32)
+        atile::explore(step, atile::EpsSchedule{P->eps_steps_per_count, P->eps_total, P->eps_fraction, P->eps_initial,
+                                                P->eps_final},
+                       P->seed, static_cast<int>(row0 + lr), a0, a1, sa64[2 * lr], sa64[2 * lr + 1]);
+    }
+    __syncthreads();
+    if (env_on && P->actions != nullptr) {   // the action every robot slot of a stepping env was given
+      double* rec = P->actions + (static_cast<size_t>(t) * NT + idx) * 2;
+      rec[0] = sa64[2 * tid];
+      rec[1] = sa64[2 * tid + 1];
+    }
+  }
 
   // ---------------- phase 1: dynamics (env.py:247-277), the observation's self part
   {
@@ -799,8 +859,9 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
       const double d_before = sqrt((gx - r.x) * (gx - r.x) + (gy - r.y) * (gy - r.y));
       const int nc = A->s.n_cores[e];
       const double* cores = A->s.cores + static_cast<size_t>(e) * A->s.max_cores * 4;
-      const double* act = A->actions + (ROLL ? static_cast<size_t>(t) * 2 * NT : 0);
-      robot_act(ParamsKArg{&A->p}, r, act[2 * idx], act[2 * idx + 1], A->ctl.is_continuous, cores,
+      // the lane's action: the Actor's (LDS), or row t of the caller's
+      const double* act = POL ? sa64 + 2 * tid : A->actions + (ROLL ? static_cast<size_t>(t) * 2 * NT : 0) + 2 * idx;
+      robot_act(ParamsKArg{&A->p}, r, act[0], act[1], A->ctl.is_continuous, cores,
                 nc < A->s.max_cores ? nc : A->s.max_cores);
       const double d_after = sqrt((gx - r.x) * (gx - r.x) + (gy - r.y) * (gy - r.y));
       reward = 0.0;
@@ -837,9 +898,9 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
     }
     if (env_on) {   // packed f32 obs row, self part (replay_buffer.py:51-69 + the .float() of agent.py:363-366)
       const bool a = active;
-      each_out(A, [&](const AsvStepOut& o, auto opt) {
+      each_out(A, [&](const AsvStepOut& o, auto opt, size_t base) {
         if (!opt || o.obs != nullptr) {
-          float* of = o.obs + idx * ASVRL_OBS_DIM;
+          float* of = o.obs + (idx - base) * ASVRL_OBS_DIM;
           *reinterpret_cast<float4*>(of) = a ? make_float4(static_cast<float>(so0), static_cast<float>(so1),
                                                             static_cast<float>(so2), static_cast<float>(so3))
                                              : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1051,9 +1112,9 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
           cf = static_cast<unsigned char>((ev ? 1 : 0) | (hit ? 2 : 0));
         }
       }
-      each_out(A, [&](const AsvStepOut& o, auto opt) {
+      each_out(A, [&](const AsvStepOut& o, auto opt, size_t base) {
         if (!opt || o.obs != nullptr) {
-          float* of = o.obs + qidx * ASVRL_OBS_DIM + 7 + 5 * k;
+          float* of = o.obs + (qidx - base) * ASVRL_OBS_DIM + 7 + 5 * k;
           of[0] = static_cast<float>(ra);
           of[1] = static_cast<float>(rb);
           of[2] = static_cast<float>(rc);
@@ -1108,11 +1169,11 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
   }
   if (env_on) {
     const bool a = active;
-    each_out(A, [&](const AsvStepOut& o, auto opt) {
+    each_out(A, [&](const AsvStepOut& o, auto opt, size_t base) {
       if (!opt || o.obs != nullptr) {
-        float4* o4 = reinterpret_cast<float4*>(o.obs + idx * ASVRL_OBS_DIM);
+        float4* o4 = reinterpret_cast<float4*>(o.obs + (idx - base) * ASVRL_OBS_DIM);
         for (int k = cnt > 0 ? cnt : 0; k < 5; ++k) {   // the object rows phase 4 did not write
-          float* of = o.obs + idx * ASVRL_OBS_DIM + 7 + 5 * k;
+          float* of = o.obs + (idx - base) * ASVRL_OBS_DIM + 7 + 5 * k;
           of[0] = 0.f;
           of[1] = 0.f;
           of[2] = 0.f;
@@ -1221,6 +1282,43 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(NM == 1 ?
   env_pairs_block<BLOCK, NM, true, true>(
       &RA->k, RA->k.epb, RA->k.group0 + xcd_group(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x)), smem,
       &RA->ro);
+}
+
+// K closed-loop steps in one launch (asvrl_policy_rollout): env_rollout_kernel with the AC-IQN Actor in front of
+// every step (env_pairs_block<POL>). The Actor's weight images (bf16: 112 KB, 115 KB with the f32 biases and the
+// output layer) sit in LDS beside the pair carve, the workgroup's observation rows (160 B per robot) and action
+// pairs (16 B per robot), so one workgroup owns a CU: one wave per SIMD and the whole register file.
+#ifndef ASVRL_ENV_POLICY_WPE
+#define ASVRL_ENV_POLICY_WPE 1, 1
+#endif
+struct PolicyArgs {
+  PairsArgs k;   // actions null; noise: row 0 of the rollout's
+  AsvRollout ro;
+  AsvPolicy pi;
+};
+template <int BLOCK, int NM>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(ASVRL_ENV_POLICY_WPE))) void env_policy_rollout_kernel(PolicyArgs) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ __attribute__((aligned(16))) atile::ActorLds AL;
+  const KArg<PolicyArgs> PA = kargs<PolicyArgs>();
+  env_pairs_block<BLOCK, NM, true, true, true>(
+      &PA->k, PA->k.epb, PA->k.group0 + xcd_group(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x)), smem,
+      &PA->ro, &PA->pi, &AL);
+}
+
+// The sweep fallback of asvrl_policy_rollout: the step count of its t-th act launch, *src + t, into the call's
+// scratch (the caller's counter is never written) ...
+__global__ void policy_step_count_kernel(const int64_t* src, int64_t* dst, int t) {
+  *dst = (src != nullptr ? *src : 0) + t;
+}
+// ... and the actions of the envs that take step t into row t of the record
+__global__ __launch_bounds__(kBlock) void policy_actions_kernel(const double* __restrict__ act, double* __restrict__ row,
+                                                                const uint8_t* __restrict__ mask, int n_envs, int R) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n_envs * R) return;
+  if (mask != nullptr && mask[k / R] == 0) return;
+  row[2 * k] = act[2 * k];
+  row[2 * k + 1] = act[2 * k + 1];
 }
 
 // The sweep layout's rollout is K single launches (asvrl_env_rollout); after step t this kernel, one lane per
@@ -1632,32 +1730,43 @@ extern "C" int asvrl_env_step(const AsvParams* params, const AsvEnvState* state,
   return asvrl_env_step_ex(params, state, actions, noise, ctl, out, nullptr, stream);
 }
 
+// the argument checks asvrl_env_rollout and asvrl_policy_rollout share (`who` names the call in the error text)
+static int rollout_checks(const std::string& who, const AsvParams* params, const AsvEnvState* state,
+                          const AsvStepCtl* ctl, const AsvStepOut* out, const AsvRollout* ro,
+                          const AsvEnvLaunch* launch) {
+  ASVRL_REQUIRE(ctl->do_dynamics, who + ": do_dynamics must be 1");
+  ASVRL_REQUIRE(!ro->hold_done || ctl->trainer_deactivate, who + ": hold_done needs trainer_deactivate");
+  ASVRL_REQUIRE(ctl->noise_mode != 0 || ro->noise != nullptr, who + ": noise_mode 0 needs injected noise");
+  ASVRL_REQUIRE(!(ro->hold_done || ro->env_done) || (ctl->trainer_deactivate && out->env_done),
+                who + ": hold_done and the env_done record need trainer_deactivate and out->env_done");
+  ASVRL_REQUIRE(state->max_robots >= 1 && state->max_robots <= kBlock, who + ": max_robots must be in [1, 256]");
+  ASVRL_REQUIRE(state->max_obs >= 0 && state->max_cores >= 0 && state->max_cores <= kMaxCoresStep,
+                who + ": bad max_obs/max_cores");
+  ASVRL_REQUIRE(params->max_obj_num >= 0 && params->max_obj_num <= ASVRL_MAX_OBJ, who + ": max_obj_num > 5");
+  ASVRL_REQUIRE(params->N >= 1, who + ": N < 1");
+  ASVRL_REQUIRE(out->obs && out->obj_cnt && out->reward && out->done && out->info, who + ": null output");
+  ASVRL_REQUIRE(state->rs && state->rflags && state->n_robots && state->n_obs && state->n_cores && state->ep_ts,
+                who + ": null state array");
+  if (launch != nullptr && state->n_envs != 0) {
+    ASVRL_REQUIRE(launch->layout >= 0 && launch->layout <= 2, who + ": layout must be 0 (auto), 1 (pairs) or 2 (sweep)");
+    ASVRL_REQUIRE(launch->block == 0 || launch->block == 64 || launch->block == 128 || launch->block == 256,
+                  who + ": block must be 0, 64, 128 or 256");
+    ASVRL_REQUIRE(launch->envs_per_block >= 0 && launch->max_groups >= 0,
+                  who + ": negative envs_per_block / max_groups");
+  }
+  return 0;
+}
+
 extern "C" int asvrl_env_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                  const AsvStepOut* out, const AsvRollout* ro, const AsvEnvLaunch* launch,
                                  void* stream) {
   ASVRL_REQUIRE(params && state && ctl && out && ro, "asvrl_env_rollout: null argument");
   ASVRL_REQUIRE(ro->n_steps >= 1, "asvrl_env_rollout: n_steps must be >= 1");
   ASVRL_REQUIRE(ro->actions != nullptr, "asvrl_env_rollout: null actions");
-  ASVRL_REQUIRE(ctl->do_dynamics, "asvrl_env_rollout: do_dynamics must be 1");
-  ASVRL_REQUIRE(!ro->hold_done || ctl->trainer_deactivate, "asvrl_env_rollout: hold_done needs trainer_deactivate");
-  ASVRL_REQUIRE(ctl->noise_mode != 0 || ro->noise != nullptr, "asvrl_env_rollout: noise_mode 0 needs injected noise");
-  ASVRL_REQUIRE(!(ro->hold_done || ro->env_done) || (ctl->trainer_deactivate && out->env_done),
-                "asvrl_env_rollout: hold_done and the env_done record need trainer_deactivate and out->env_done");
-  ASVRL_REQUIRE(state->max_robots >= 1 && state->max_robots <= kBlock, "asvrl_env_rollout: max_robots must be in [1, 256]");
-  ASVRL_REQUIRE(state->max_obs >= 0 && state->max_cores >= 0 && state->max_cores <= kMaxCoresStep,
-                "asvrl_env_rollout: bad max_obs/max_cores");
-  ASVRL_REQUIRE(params->max_obj_num >= 0 && params->max_obj_num <= ASVRL_MAX_OBJ, "asvrl_env_rollout: max_obj_num > 5");
-  ASVRL_REQUIRE(params->N >= 1, "asvrl_env_rollout: N < 1");
-  ASVRL_REQUIRE(out->obs && out->obj_cnt && out->reward && out->done && out->info, "asvrl_env_rollout: null output");
-  ASVRL_REQUIRE(state->rs && state->rflags && state->n_robots && state->n_obs && state->n_cores && state->ep_ts,
-                "asvrl_env_rollout: null state array");
+  if (int rc = rollout_checks("asvrl_env_rollout", params, state, ctl, out, ro, launch)) return rc;
   if (state->n_envs == 0) return 0;
   const AsvEnvLaunch lz{};
   const AsvEnvLaunch& lc = launch != nullptr ? *launch : lz;
-  ASVRL_REQUIRE(lc.layout >= 0 && lc.layout <= 2, "asvrl_env_rollout: layout must be 0 (auto), 1 (pairs) or 2 (sweep)");
-  ASVRL_REQUIRE(lc.block == 0 || lc.block == 64 || lc.block == 128 || lc.block == 256,
-                "asvrl_env_rollout: block must be 0, 64, 128 or 256");
-  ASVRL_REQUIRE(lc.envs_per_block >= 0 && lc.max_groups >= 0, "asvrl_env_rollout: negative envs_per_block / max_groups");
   const int nm = ctl->noise_mode == 0 ? 0 : (ctl->noise_mode == 1 ? 1 : 2);
   const PairLaunch pl = pair_launch(state->max_robots, state->max_obs, state->n_envs, lc.block, lc.envs_per_block,
                                     nm == 2 ? 4 : 8);
@@ -1714,6 +1823,141 @@ extern "C" int asvrl_env_rollout(const AsvParams* params, const AsvEnvState* sta
   if (hold_mask != nullptr) (void)hipFreeAsync(hold_mask, st);
   return rc;
 }
+
+// The closed-loop launch's shape: 256-lane workgroups, one per CU (the Actor's weights fill most of its LDS), so
+// enough envs per workgroup that the batch makes about one workgroup per CU (4096 envs x 5 robots: 16 envs, 256
+// workgroups), never fewer than the open-loop shape's, and as many as the LDS left beside the weights holds.
+// AsvEnvLaunch overrides block and envs_per_block. fits = false: the sweep fallback.
+struct PolicyLaunch {
+  PairLaunch pl;
+  size_t smem;   // dynamic: the pair carve + the observation rows and action pairs
+  bool fits;
+};
+static PolicyLaunch policy_launch(int R, int O, int n_envs, int blk_req, int epb_req, int vm_bytes) {
+  constexpr size_t kLdsBytes = 160 * 1024;
+  constexpr size_t kLdsStatic = 1024;   // room for the workgroup-vote scratch (__syncthreads_or) and alignment
+  constexpr int kCus = 256;
+  auto total = [&](const PairLaunch& l) {
+    return policy_rows_offset(l.smem) + static_cast<size_t>(l.epb) * R * (ASVRL_OBS_DIM * sizeof(float) + 2 * sizeof(double));
+  };
+  PolicyLaunch L;
+  int blk = (blk_req == 64 || blk_req == 128) ? blk_req : 256;
+  if (R > blk) blk = 256;
+  int epb = epb_req;
+  if (epb <= 0) {
+    const int base = pair_launch(R, O, n_envs, blk, 0, vm_bytes).epb, per_cu = (n_envs + kCus - 1) / kCus;
+    epb = per_cu > base ? per_cu : base;
+  }
+  for (;;) {
+    L.pl = pair_launch(R, O, n_envs, blk, epb, vm_bytes);   // (at most blk / R envs)
+    L.smem = total(L.pl);
+    L.fits = sizeof(atile::ActorLds) + kLdsStatic + L.smem <= kLdsBytes;
+    if (L.fits || epb_req > 0 || L.pl.epb <= 1) break;
+    epb = L.pl.epb - 1;
+  }
+  return L;
+}
+
+extern "C" int asvrl_policy_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                                    const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi,
+                                    const AsvEnvLaunch* launch, void* stream) {
+  ASVRL_REQUIRE(params && state && ctl && out && ro, "asvrl_policy_rollout: null argument");
+  ASVRL_REQUIRE(ro->n_steps >= 1, "asvrl_policy_rollout: n_steps must be >= 1");
+  ASVRL_REQUIRE(ro->actions == nullptr, "asvrl_policy_rollout: ro->actions must be null (the policy supplies the actions)");
+  ASVRL_REQUIRE(pi != nullptr, "asvrl_policy_rollout: null policy");
+  ASVRL_REQUIRE(pi->obs_in != nullptr, "asvrl_policy_rollout: null obs_in");
+  ASVRL_REQUIRE(ctl->is_continuous, "asvrl_policy_rollout: is_continuous must be 1 (the Actor is the continuous agent)");
+  const AsvMlpWeights& w = pi->w;
+  ASVRL_REQUIRE(w.enc_frag && w.b_enc && w.w1_frag && w.w2_frag && w.b1 && w.b2 && w.wout && w.bout,
+                "asvrl_policy_rollout: null actor image");
+  if (int rc = rollout_checks("asvrl_policy_rollout", params, state, ctl, out, ro, launch)) return rc;
+  ASVRL_REQUIRE(reinterpret_cast<uintptr_t>(pi->obs_in) % 16 == 0 && reinterpret_cast<uintptr_t>(out->obs) % 16 == 0,
+                "asvrl_policy_rollout: observation rows must be 16-byte aligned");
+  if (state->n_envs == 0) return 0;
+  const AsvEnvLaunch lz{};
+  const AsvEnvLaunch& lc = launch != nullptr ? *launch : lz;
+  const int nm = ctl->noise_mode == 0 ? 0 : (ctl->noise_mode == 1 ? 1 : 2);
+  const bool per_robot = state->robot_params != nullptr;
+  hipStream_t st = as_stream(stream);
+  const size_t NT = static_cast<size_t>(state->n_envs) * state->max_robots;
+  if (ro->steps_run != nullptr && hipMemsetAsync(ro->steps_run, 0, sizeof(int32_t) * state->n_envs, st) != hipSuccess)
+    return check_launch("asvrl_policy_rollout");
+  if (lc.layout != 2 && !per_robot) {
+    const PolicyLaunch L = policy_launch(state->max_robots, state->max_obs, state->n_envs, lc.block, lc.envs_per_block,
+                                         nm == 2 ? 4 : 8);
+    if (L.fits) {
+      const PairLaunch& pl = L.pl;
+      const int groups = (state->n_envs + pl.epb - 1) / pl.epb;
+      const int chunk = lc.max_groups > 0 && lc.max_groups < groups ? lc.max_groups : groups;
+      auto go = [&](auto kern) {
+        PolicyArgs a{PairsArgs{*params, *state, *ctl, *out, nullptr, ro->noise, pl.epb, 0}, *ro, *pi};
+        for (int g0 = 0; g0 < groups; g0 += chunk) {
+          a.k.group0 = g0;
+          hipLaunchKernelGGL(kern, dim3(groups - g0 < chunk ? groups - g0 : chunk), dim3(pl.blk), L.smem, st, a);
+        }
+      };
+      if (pl.blk == 64)
+        nm == 0 ? go(env_policy_rollout_kernel<64, 0>) : nm == 1 ? go(env_policy_rollout_kernel<64, 1>) : go(env_policy_rollout_kernel<64, 2>);
+      else if (pl.blk == 128)
+        nm == 0 ? go(env_policy_rollout_kernel<128, 0>) : nm == 1 ? go(env_policy_rollout_kernel<128, 1>) : go(env_policy_rollout_kernel<128, 2>);
+      else
+        nm == 0 ? go(env_policy_rollout_kernel<256, 0>) : nm == 1 ? go(env_policy_rollout_kernel<256, 1>) : go(env_policy_rollout_kernel<256, 2>);
+      return check_launch("asvrl_policy_rollout");
+    }
+  }
+  // the fallback: K x (the act launch into a stream-ordered scratch, the single step, the record launches)
+  const size_t noise_row = NT * (static_cast<size_t>(state->max_obs) + state->max_robots) * 5;
+  double* act = nullptr;       // [NT][2] f64, then the act launch's step count (i64)
+  uint8_t* hold_mask = nullptr;
+  if (hipMallocAsync(reinterpret_cast<void**>(&act), sizeof(double) * 2 * NT + sizeof(int64_t), st) != hipSuccess)
+    return check_launch("asvrl_policy_rollout");
+  int64_t* step = reinterpret_cast<int64_t*>(act + 2 * NT);
+  int rc = 0;
+  if (ro->hold_done) {
+    if (hipMallocAsync(reinterpret_cast<void**>(&hold_mask), state->n_envs, st) != hipSuccess)
+      rc = check_launch("asvrl_policy_rollout");
+    else if (ctl->env_mask != nullptr)
+      (void)hipMemcpyAsync(hold_mask, ctl->env_mask, state->n_envs, hipMemcpyDeviceToDevice, st);
+    else
+      (void)hipMemsetAsync(hold_mask, 1, state->n_envs, st);
+  }
+  for (int t = 0; t < ro->n_steps && rc == 0; ++t) {
+    AsvStepCtl c = *ctl;
+    c.counter = ctl->counter + static_cast<uint64_t>(t);
+    if (hold_mask != nullptr) c.env_mask = hold_mask;
+    hipLaunchKernelGGL(policy_step_count_kernel, dim3(1), dim3(1), 0, st, pi->step_dev, step, t);
+    AsvMlpIO io{};
+    io.x = t == 0 ? pi->obs_in : out->obs;   // the observation the step before wrote
+    io.ldx = ASVRL_OBS_DIM;
+    io.n = static_cast<int32_t>(NT);
+    io.a_out64 = act;
+    io.step_dev = step;
+    io.eps_steps_per_count = pi->eps_steps_per_count;
+    io.eps_total = pi->eps_total;
+    io.eps_fraction = pi->eps_fraction;
+    io.eps_initial = pi->eps_initial;
+    io.eps_final = pi->eps_final;
+    io.seed = pi->seed;
+    rc = asvrl_actor_forward(&pi->w, &io, atile::MLP_ACT, stream);
+    if (rc == 0 && pi->actions != nullptr)
+      hipLaunchKernelGGL(policy_actions_kernel, dim3((static_cast<unsigned>(NT) + kBlock - 1) / kBlock), dim3(kBlock), 0, st,
+                         act, pi->actions + static_cast<size_t>(t) * 2 * NT, c.env_mask, state->n_envs,
+                         state->max_robots);
+    if (rc == 0)
+      rc = asvrl_env_step_ex(params, state, act, ro->noise != nullptr ? ro->noise + static_cast<size_t>(t) * noise_row : nullptr,
+                             &c, out, launch, stream);
+    if (rc == 0) {
+      hipLaunchKernelGGL(rollout_record_kernel, dim3((state->n_envs + kBlock - 1) / kBlock), dim3(kBlock), 0, st,
+                         *state, *out, *ro, t, c.env_mask, hold_mask);
+      rc = check_launch("asvrl_policy_rollout");
+    }
+  }
+  if (hold_mask != nullptr) (void)hipFreeAsync(hold_mask, st);
+  (void)hipFreeAsync(act, st);
+  return rc;
+}
+
+extern "C" int64_t asvrl_policy_struct_size(void) { return sizeof(AsvPolicy); }
 
 extern "C" int asvrl_env_reset(const AsvParams* params, const AsvEnvState* state, const AsvResetCfg* cfg,
                                const uint8_t* env_mask, uint64_t seed, uint64_t counter,

@@ -14,7 +14,8 @@
 //                          bf16 copy of obs columns 0..31 (operand of the encoder wgrad)
 //   actor_kernel<ACT>      Actor on every robot row with epsilon-greedy exploration (agent.py:207-225,
 //                          trainer.py:257-264): f64 actions for the env kernel; one wave per 32-row
-//                          tile, weights staged in LDS
+//                          tile, weights staged in LDS (the tile's code: asvrl_actor_tile.h, shared with
+//                          the env kernel's closed-loop rollout)
 //   actor_split_kernel     the learner's B rows, 4 waves per tile splitting each layer's features:
 //     <FWD>                f32 actions (target actor, agent.py:398)
 //     <TRAIN>              saving bf16 activations for the backward (agent.py:419-426)
@@ -22,9 +23,11 @@
 #include "asvrl_common.h"
 #include "asvrl_mfma.h"
 #include "asvrl_lds.h"
+#include "asvrl_actor_tile.h"
 
 namespace asvrl {
 namespace {
+using namespace atile;   // the one-wave Actor tile, shared with asvrl_env.hip
 
 // The split actor kernels run one wave per SIMD (4 waves per 32-row workgroup), so a weight fragment
 // fetched from L2 right before its MFMA exposes the whole L2 latency on every MFMA of a chain.
@@ -39,82 +42,7 @@ __device__ __forceinline__ f32x16 wchain(const frag8* W, int base, int lane, con
   return acc;
 }
 
-constexpr int kEnc = 256, kObsK = 32, kHid = 128, kNa = 2;
-constexpr int kSelfF = 56, kObjF = 40, kSelfIn = 7, kObjIn = 5, kObjN = 5;
-constexpr int kFragEnc = kEnc * kObsK / 8;   // 1024 fragments
-constexpr int kFragAe = kHid * 16 / 8;       // 256 (action encoder, K padded 2 -> 16)
-constexpr int kFragH1 = kHid * kEnc / 8;     // 4096
-constexpr int kFragH2 = kHid * kHid / 8;     // 2048
 constexpr int kMlpWaves = 4;
-
-enum { MLP_ENCODE = 0, MLP_ACT = 1, MLP_FWD = 2, MLP_TRAIN = 3 };
-
-struct MlpArgs {
-  AsvMlpWeights w;
-  AsvMlpIO io;
-};
-
-struct ActorLds {
-  frag8 enc[lds_frags(kFragEnc)];
-  frag8 w1[lds_frags(kFragH1)];
-  frag8 w2[lds_frags(kFragH2)];
-  float benc[kEnc], b1[kHid], b2[kHid], wout[kNa * kHid], bout[kNa];
-};
-
-// object index of encoder feature m (>= 56)
-__host__ __device__ constexpr int obj_of(int m) { return (m - kSelfF) / kObjF; }
-
-// Encoder output of one 32-row tile: B operand from obs columns 0..31, 8 blocks in 2 halves;
-// epilogue bias + relu + mask. Hands each finished (block, s) group of 8 features to `emit`.
-template <typename Emit>
-__device__ __forceinline__ void encode_tile(const frag8* ENC, const float* benc, const frag8 (&bx)[2],
-                                            const float (&mk)[kObjN], int lane, Emit emit) {
-  const int h = lane >> 5;
-#pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    f32x16 acc[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) acc[q] = f32x16{};
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) acc[q] = mfma(ENC[((half * 4 + q) * 2 + ks) * 64 + lane], bx[ks], acc[q]);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int mb = half * 4 + q;
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int g = 8 * s + j;
-          const int m0 = mb * 32 + (g & 3) + 8 * (g >> 2);   // feature for h = 0; h = 1 adds 4
-          const float mk0 = m0 < kSelfF ? 1.f : (mk[obj_of(m0)] < 0.5f ? 0.f : 1.f);
-          const float mk1 = m0 + 4 < kSelfF ? 1.f : (mk[obj_of(m0 + 4)] < 0.5f ? 0.f : 1.f);
-          float x = acc[q][g] + benc[m0 + 4 * h];
-          x = relu(x);
-          v[j] = x * (h ? mk1 : mk0);
-        }
-        emit(mb, s, v);
-      }
-    }
-  }
-}
-
-// bf16 B operand of the encoder (obs columns 0..31) + the object mask, for row `row`
-__device__ __forceinline__ void load_obs(const float* __restrict__ x, int64_t ldx, int row, int h, frag8 (&bx)[2],
-                                         float (&mk)[kObjN]) {
-  const float* xr = x + static_cast<int64_t>(row) * ldx;
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) {
-    const float4 u = *reinterpret_cast<const float4*>(xr + ks * 16 + 8 * h);
-    const float4 v = *reinterpret_cast<const float4*>(xr + ks * 16 + 8 * h + 4);
-    const float e[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
-    bx[ks] = pack8(e);
-  }
-#pragma unroll
-  for (int o = 0; o < kObjN; ++o) mk[o] = xr[32 + o];
-}
 
 // ------------------------------------------------------------------ ENCODE (critic F, G)
 __global__ __launch_bounds__(kMlpWaves * 64) void encode_kernel(MlpArgs a) {
@@ -184,88 +112,14 @@ __device__ __forceinline__ void actor_tile(const MlpArgs& a, const ActorLds& L, 
     for (int ks = 0; ks < 2; ++ks)
       *reinterpret_cast<frag8*>(bp(io.xb) + static_cast<int64_t>(row) * kObsK + ks * 16 + 8 * h) = bx[ks];
   }
-  // encoders -> h0 (chained B operand of hidden_layer)
-  frag8 fpk[16];
-  encode_tile(wimg(L.enc, a.w.enc_frag), L.benc, bx, mk, lane, [&](int mb, int s, const float* v) {
-    fpk[mb * 2 + s] = pack8(*reinterpret_cast<const float (*)[8]>(v));
-    if (MODE == MLP_TRAIN)
-      store16(valid ? bp(io.h0) + static_cast<int64_t>(row) * kEnc + mb * 32 + 16 * s : nullptr, v, h);
-  });
-  // hidden_layer 256 -> 128, relu
-  const frag8* W1 = wimg(L.w1, a.w.w1_frag);
-  const frag8* W2 = wimg(L.w2, a.w.w2_frag);
-  f32x16 acc1[4];
-#pragma unroll
-  for (int mb = 0; mb < 4; ++mb) acc1[mb] = f32x16{};
-#pragma unroll
-  for (int ks = 0; ks < kEnc / 16; ++ks)
-#pragma unroll
-    for (int mb = 0; mb < 4; ++mb) acc1[mb] = mfma(W1[(mb * 16 + ks) * 64 + lane], fpk[ks], acc1[mb]);
-  frag8 h1pk[8];
-#pragma unroll
-  for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float x = acc1[mb][8 * s + j] + L.b1[feat(mb, 8 * s + j, h)];
-        v[j] = relu(x);
-      }
-      h1pk[mb * 2 + s] = pack8(v);
-      if (MODE == MLP_TRAIN)
-      store16(valid ? bp(io.h1) + static_cast<int64_t>(row) * kHid + mb * 32 + 16 * s : nullptr, v, h);
-    }
-  // hidden_layer_2 128 -> 128, relu; output_layer 128 -> 2
-  f32x16 acc2[4];
-#pragma unroll
-  for (int mb = 0; mb < 4; ++mb) acc2[mb] = f32x16{};
-#pragma unroll
-  for (int ks = 0; ks < kHid / 16; ++ks)
-#pragma unroll
-    for (int mb = 0; mb < 4; ++mb) acc2[mb] = mfma(W2[(mb * 8 + ks) * 64 + lane], h1pk[ks], acc2[mb]);
-  float p0 = 0.f, p1 = 0.f;
-#pragma unroll
-  for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int m = feat(mb, 8 * s + j, h);
-        const float x = acc2[mb][8 * s + j] + L.b2[m];
-        v[j] = relu(x);
-        p0 += L.wout[m] * v[j];
-        p1 += L.wout[kHid + m] * v[j];
-      }
-      if (MODE == MLP_TRAIN)
-      store16(valid ? bp(io.h2) + static_cast<int64_t>(row) * kHid + mb * 32 + 16 * s : nullptr, v, h);
-    }
-  const float z0 = p0 + __shfl_xor(p0, 32, 64) + L.bout[0];
-  const float z1 = p1 + __shfl_xor(p1, 32, 64) + L.bout[1];
-  const float a0 = a.w.out_scale * atanf(z0);   // atan_scale * torch.atan(actions)
-  const float a1 = a.w.out_scale * atanf(z1);
+  float z0, z1, a0, a1;
+  actor_chain<MODE>(a.w, io, L, row, valid, lane, bx, mk, z0, z1, a0, a1);
   if (!valid || h != 0) return;
   if (MODE == MLP_ACT) {
-    // epsilon-greedy (agent.py:207-225): greedy iff random() > eps, else uniform(-1, 1) per dim;
-    // eps: linear schedule of the device step counter (trainer.py:257-264)
     const uint64_t step = io.step_dev != nullptr ? static_cast<uint64_t>(*io.step_dev) : 0ull;
-    const double progress = static_cast<double>(step) * io.eps_steps_per_count / io.eps_total;
-    const double eps = progress < io.eps_fraction
-                           ? io.eps_initial + (progress / io.eps_fraction) * (io.eps_final - io.eps_initial)
-                           : io.eps_final;
-    const U4 u = philox4x32_10(U4{static_cast<uint32_t>(row), static_cast<uint32_t>(step),
-                                  static_cast<uint32_t>(step >> 32), 0xAC7u},
-                               static_cast<uint32_t>(io.seed), static_cast<uint32_t>(io.seed >> 32));
-    const double c = (static_cast<double>(u.x >> 8) + 1.0) * (1.0 / 16777216.0);   // (0, 1]
     double* o = io.a_out64 + static_cast<int64_t>(row) * 2;
-    if (c > eps) {
-      o[0] = a0;
-      o[1] = a1;
-    } else {
-      o[0] = 2.0 * (static_cast<double>(u.y >> 8) * (1.0 / 16777216.0)) - 1.0;
-      o[1] = 2.0 * (static_cast<double>(u.z >> 8) * (1.0 / 16777216.0)) - 1.0;
-    }
+    explore(step, EpsSchedule{io.eps_steps_per_count, io.eps_total, io.eps_fraction, io.eps_initial, io.eps_final},
+            io.seed, row, a0, a1, o[0], o[1]);
   } else {
     float* o = io.a_out + static_cast<int64_t>(row) * io.ld_aout;
     o[0] = a0;
@@ -289,25 +143,7 @@ __global__ __launch_bounds__(kMlpWaves * 64) void actor_kernel(MlpArgs a) {
     const int row = tile * 32 + (lane & 31);
     load_obs(a.io.x, a.io.ldx, row < a.io.n ? row : a.io.n - 1, lane >> 5, bx, mk);
   }
-  {
-    const frag8* ge = reinterpret_cast<const frag8*>(a.w.enc_frag);
-    const frag8* g1 = reinterpret_cast<const frag8*>(a.w.w1_frag);
-    const frag8* g2 = reinterpret_cast<const frag8*>(a.w.w2_frag);
-    if constexpr (kWeightsInLds) {
-      constexpr int CH = kElemBytes == 2 ? 16 : 8;   // fragments in flight per thread
-      copy_frags<kMlpWaves * 64, kFragEnc, CH>(L.enc, ge, threadIdx.x);
-      copy_frags<kMlpWaves * 64, kFragH1, CH>(L.w1, g1, threadIdx.x);
-      copy_frags<kMlpWaves * 64, kFragH2, CH>(L.w2, g2, threadIdx.x);
-    }
-    for (int i = threadIdx.x; i < kEnc; i += kMlpWaves * 64) L.benc[i] = a.w.b_enc[i];
-    for (int i = threadIdx.x; i < kHid; i += kMlpWaves * 64) {
-      L.b1[i] = a.w.b1[i];
-      L.b2[i] = a.w.b2[i];
-      L.wout[i] = a.w.wout[i];
-      L.wout[kHid + i] = a.w.wout[kHid + i];
-    }
-    if (threadIdx.x < kNa) L.bout[threadIdx.x] = a.w.bout[threadIdx.x];
-  }
+  stage_actor<kMlpWaves * 64>(L, a.w, threadIdx.x);
   __syncthreads();
   if (active) actor_tile<MODE>(a, L, tile, lane, bx, mk);
 }

@@ -130,6 +130,30 @@ class DeviceEnvBatch:
                 "obs": ((NT, OBS_DIM), torch.float32, 0), "obj_cnt": ((NT,), torch.int8, 0),
                 "rs": ((NUM_FIELDS, NT), torch.float64, 0)}
 
+    def _records(self, who, keep, K, specs, trainer_deactivate):
+        """The kept records of a K-step rollout: allocated at their pre-fill, or the caller's own tensors (keep a
+        dict name -> tensor). Returns (name -> tensor, steps_run)."""
+        given = dict(keep) if isinstance(keep, dict) else {}
+        rec = {}
+        for name in keep:
+            if name == "steps_run":
+                continue
+            if name not in specs:
+                raise ValueError(f"{who}: unknown record {name!r}; choose from {sorted(specs)}")
+            if name == "env_done" and not trainer_deactivate:
+                raise ValueError(f"{who}: the env_done record needs trainer_deactivate")
+            shape, dtype, fill = specs[name]
+            t = given.get(name)
+            if t is None:
+                t = torch.full((K,) + shape, fill, dtype=dtype, device=self.device)
+            assert t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == (K,) + shape, name
+            rec[name] = t
+        steps_run = given.get("steps_run")
+        if steps_run is None:
+            steps_run = torch.zeros(self.n_envs, dtype=torch.int32, device=self.device)
+        assert steps_run.dtype == torch.int32 and steps_run.numel() == self.n_envs
+        return rec, steps_run
+
     def rollout(self, actions, noise=None, *, keep=("reward", "done", "info"), hold_done=False, is_continuous=True,
                 trainer_deactivate=False, seed=0, counter=0, counter_dev=None, gamma=0.0, env_mask=None, obs=None,
                 obj_cnt=None, fast_noise=False, launch=None, stream=None):
@@ -150,25 +174,7 @@ class DeviceEnvBatch:
             assert noise.dtype == torch.float64 and noise.is_contiguous()
             assert noise.numel() == K * NT * (self.max_obs + self.max_robots) * 5
         specs = self._record_specs()
-        given = dict(keep) if isinstance(keep, dict) else {}
-        rec = {}
-        for name in keep:
-            if name == "steps_run":
-                continue
-            if name not in specs:
-                raise ValueError(f"rollout: unknown record {name!r}; choose from {sorted(specs)}")
-            if name == "env_done" and not trainer_deactivate:
-                raise ValueError("rollout: the env_done record needs trainer_deactivate")
-            shape, dtype, fill = specs[name]
-            t = given.get(name)
-            if t is None:
-                t = torch.full((K,) + shape, fill, dtype=dtype, device=self.device)
-            assert t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == (K,) + shape, name
-            rec[name] = t
-        steps_run = given.get("steps_run")
-        if steps_run is None:
-            steps_run = torch.zeros(self.n_envs, dtype=torch.int32, device=self.device)
-        assert steps_run.dtype == torch.int32 and steps_run.numel() == self.n_envs
+        rec, steps_run = self._records("rollout", keep, K, specs, trainer_deactivate)
         ctl = _abi.AsvStepCtl()
         ctl.is_continuous = int(bool(is_continuous))
         ctl.do_dynamics = 1
@@ -192,6 +198,65 @@ class DeviceEnvBatch:
         rc = _abi.lib().asvrl_env_rollout(C.byref(self.params), C.byref(st), C.byref(ctl), C.byref(out), C.byref(ro),
                                           ln, _abi.stream_ptr(stream))
         _abi.check(rc, "asvrl_env_rollout")
+        return types.SimpleNamespace(steps_run=steps_run, **{n: rec.get(n) for n in specs})
+
+    def policy_rollout(self, pack, K, obs_in, *, noise=None, keep=("reward", "done", "info"), hold_done=False,
+                       step_dev=None, eps=(1.0, 1.0, 1.0, 0.0, 0.0), policy_seed=0, trainer_deactivate=False, seed=0,
+                       counter=0, counter_dev=None, gamma=0.0, env_mask=None, obs=None, obj_cnt=None,
+                       fast_noise=False, launch=None, stream=None):
+        """asvrl_policy_rollout: K closed-loop steps in one launch -- the AC-IQN Actor of `pack` (an MlpPack of
+        kind "actor") acts on every robot row and the env steps on its actions, bit for bit the K rounds of
+        fused_mlp.actor_act(pack, obs, act64, step, *eps, policy_seed) at step = step_dev + t followed by
+        step(act64, counter=counter + t), where round 0 acts on obs_in (f32 [E*R, 40]; may be the tensor the step
+        writes) and round t > 0 on the observation of round t - 1. eps: (steps_per_count, total, fraction, initial,
+        final) of the linear epsilon schedule (the default is greedy); step_dev: i64 device step counter (None: 0),
+        only read. keep, noise, hold_done and the remaining arguments are rollout()'s; keep also takes "actions":
+        f64 [K, E*R, 2], the action every robot slot of a stepping env was given (rows of steps an env did not
+        take stay 0). The call goes to pack.L, so an f32 pack runs the f32-operand build. No host sync; with every
+        record passed in by the caller (and steps_run) the call can be graph-captured."""
+        import types
+        K, NT = int(K), self.n_envs * self.max_robots
+        assert pack.kind == "actor"
+        assert obs_in.dtype == torch.float32 and obs_in.is_contiguous() and tuple(obs_in.shape) == (NT, OBS_DIM)
+        if noise is not None:
+            assert noise.dtype == torch.float64 and noise.is_contiguous()
+            assert noise.numel() == K * NT * (self.max_obs + self.max_robots) * 5
+        if step_dev is not None:
+            assert step_dev.dtype == torch.int64 and step_dev.numel() >= 1
+        specs = self._record_specs()
+        specs["actions"] = ((NT, 2), torch.float64, 0)
+        rec, steps_run = self._records("policy_rollout", keep, K, specs, trainer_deactivate)
+        ctl = _abi.AsvStepCtl()
+        ctl.is_continuous = 1
+        ctl.do_dynamics = 1
+        ctl.trainer_deactivate = int(bool(trainer_deactivate))
+        ctl.noise_mode = 0 if noise is not None else (2 if fast_noise else 1)
+        ctl.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        ctl.counter = int(counter) & 0xFFFFFFFFFFFFFFFF
+        ctl.counter_dev = counter_dev.data_ptr() if counter_dev is not None else None
+        ctl.gamma = float(gamma)
+        ctl.env_mask = env_mask.data_ptr() if env_mask is not None else None
+        ro = _abi.AsvRollout()
+        ro.n_steps, ro.hold_done = K, int(bool(hold_done))
+        ro.noise = noise.data_ptr() if noise is not None else None
+        for name, t in rec.items():
+            if name != "actions":
+                setattr(ro, name, t.data_ptr())
+        ro.steps_run = steps_run.data_ptr()
+        pi = _abi.AsvPolicy()
+        pi.w = pack.w
+        pi.obs_in = obs_in.data_ptr()
+        pi.step_dev = step_dev.data_ptr() if step_dev is not None else None
+        (pi.eps_steps_per_count, pi.eps_total, pi.eps_fraction, pi.eps_initial,
+         pi.eps_final) = (float(v) for v in eps)
+        pi.seed = int(policy_seed) & 0xFFFFFFFFFFFFFFFF
+        pi.actions = rec["actions"].data_ptr() if "actions" in rec else None
+        st = self.state_struct()
+        out = self.out_struct(obs, obj_cnt, with_env_done=trainer_deactivate)
+        ln = C.byref(_abi.AsvEnvLaunch(*(int(v) for v in launch))) if launch is not None else None
+        rc = pack.L.asvrl_policy_rollout(C.byref(self.params), C.byref(st), C.byref(ctl), C.byref(out), C.byref(ro),
+                                         C.byref(pi), ln, _abi.stream_ptr(stream))
+        _abi.check(rc, "asvrl_policy_rollout", pack.L)
         return types.SimpleNamespace(steps_run=steps_run, **{n: rec.get(n) for n in specs})
 
     def reset(self, cfg, env_mask=None, seed=0, counter=0, counter_dev=None, stream=None):

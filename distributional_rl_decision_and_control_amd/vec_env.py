@@ -103,6 +103,24 @@ class VecMarineNavEnv:
         self.counter += int(actions.shape[0])
         return rec
 
+    def policy_rollout(self, pack, K, hold_done=True, keep=("reward", "done", "info"), eps=(1.0, 1.0, 1.0, 0.0, 0.0),
+                       policy_seed=0, env_mask=None):
+        """K closed-loop steps in one launch (DeviceEnvBatch.policy_rollout): the AC-IQN Actor of `pack` acts on
+        obs_cur and every next observation -- the values of K rounds of fused_mlp.actor_act(pack, obs_cur, actions,
+        counter, *eps, policy_seed); step(actions); advance_device(), with the last step's observation in obs_next /
+        cnt_next and the step counter advanced by K on the device. eps: the linear epsilon schedule over the step
+        counter (the default is greedy). The contract is otherwise rollout()'s. Returns the kept per-step records
+        (keep also takes "actions")."""
+        if not self.is_continuous:
+            raise ValueError("policy_rollout: the Actor drives continuous-action envs")
+        rec = self.batch.policy_rollout(pack, K, self.obs_cur, keep=keep, hold_done=hold_done, step_dev=self.counter,
+                                        eps=eps, policy_seed=policy_seed, trainer_deactivate=True, seed=self.seed,
+                                        counter=0, counter_dev=self.counter, gamma=self.gamma, env_mask=env_mask,
+                                        obs=self.obs_next, obj_cnt=self.cnt_next, fast_noise=True,
+                                        launch=self._launch())
+        self.counter += int(K)
+        return rec
+
     def _launch(self):
         """The step kernel's shape: automatic, or launches of at most `max_groups` workgroups one after another
         (the rollout's share of the chip beside a concurrent learner; results do not depend on it)."""

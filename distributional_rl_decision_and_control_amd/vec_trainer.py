@@ -200,6 +200,44 @@ class VecTrainer:
         else:   # actor on every robot row, explore
             self.fused2.act(*args)
 
+    def _eval_env(self):
+        """A fresh env batch of the training env's shape, parameters and current curriculum stage, with its own
+        seed, reset and observed (greedy_episodes)."""
+        from . import _abi
+        src = self.env
+        c = src.cfg
+        env = VecMarineNavEnv(self.E, c.num_robots, c.num_obs, c.num_cores, c.min_start_goal_dis, c.width, c.height,
+                              seed=self.seed + 7919, device=self.device, is_continuous=True, gamma=self.gamma,
+                              max_robots=src.max_robots, max_obs=src.batch.max_obs, max_cores=src.batch.max_cores)
+        env.batch.params = _abi.AsvParams.from_buffer_copy(src.batch.params)
+        env.reset()
+        return env
+
+    @torch.no_grad()
+    def greedy_episodes(self, max_steps=1000, chunk=64):
+        """Greedy evaluation of the current local actor: one episode per env of a fresh batch (_eval_env), run in
+        closed-loop windows of `chunk` steps, one launch each (VecMarineNavEnv.policy_rollout with epsilon 0 and
+        hold_done; an env that ended stays out of the later windows), until every env has ended or after
+        max_steps. Returns that batch's episode_stats() plus steps_run, the steps every env took. The training
+        env, the replay and the step counter are not touched. AC-IQN only."""
+        if self.fused2 is None:
+            raise NotImplementedError("greedy_episodes runs the AC-IQN actor; IQN and Rainbow act inside their own "
+                                      "kernels")
+        env = self._eval_env()
+        alive = torch.ones(self.E, dtype=torch.uint8, device=self.device)
+        steps_run = torch.zeros(self.E, dtype=torch.int32, device=self.device)
+        done = 0
+        while done < max_steps:
+            k = min(int(chunk), max_steps - done)
+            rec = env.policy_rollout(self.fused2.actor, k, hold_done=True, keep=("env_done",), env_mask=alive)
+            env.advance_device(counted=True)   # the next window acts on this one's last observation
+            steps_run += rec.steps_run
+            alive *= (rec.env_done.sum(0) == 0).to(torch.uint8)
+            done += k
+            if not bool(alive.any().item()):   # one host sync per window
+                break
+        return dict(env.episode_stats(), steps_run=steps_run.cpu().numpy())
+
     def _push(self, snap=None):
         """The replay push of every robot that acted; for the uniform ring it is one launch that also
         increments the env step counter (and writes the new ring state to `snap` when given). Returns

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define ASVRL_ABI_VERSION 27
+#define ASVRL_ABI_VERSION 28
 
 #define ASVRL_SELF_DIM 7   /* wamv.py:443-453 self observation */
 #define ASVRL_OBJ_DIM 5    /* wamv.py:481,508 [px, py, vx, vy, r] */
@@ -1003,6 +1003,36 @@ int asvrl_small_wgrad(const float* dz, int64_t ldz, const float* x, int64_t ldx,
 int asvrl_small_wgrad_partial(const float* dz, int64_t ldz, const float* x, int64_t ldx, int32_t R,
                               int32_t M, int32_t K, float* partial, int64_t partial_floats,
                               int32_t* groups_out, void* stream);
+
+/* ---------------------------------------------------------------- closed-loop policy rollout (ABI 28) */
+
+/* The AC-IQN Actor driving asvrl_policy_rollout. */
+typedef struct AsvPolicy {
+  AsvMlpWeights w;                /* the actor's packed images (asvrl_mlp_pack) */
+  const float* obs_in;            /* [NT][ASVRL_OBS_DIM] the observation step 0 acts on (16-byte aligned) */
+  const int64_t* step_dev;        /* epsilon schedule / exploration key: step = *step_dev + t (NULL: 0 + t) */
+  double eps_steps_per_count, eps_total, eps_fraction, eps_initial, eps_final;   /* as AsvMlpIO's */
+  uint64_t seed;                  /* Philox key of the exploration draws */
+  double* actions;                /* optional record [K][NT][2]: the action every robot slot was given */
+} AsvPolicy;
+
+/* K closed-loop steps in one launch: for t < ro->n_steps, the Actor's epsilon-greedy act on every robot row
+ * (asvrl_actor_forward mode 1 with step = *step_dev + t: the same MFMA chain, the same Philox draw keyed by the
+ * global row and that step) and then the env step of asvrl_env_rollout on those actions. Step 0 acts on
+ * pi->obs_in, step t > 0 on the observation step t - 1 produced -- bit for bit the 2 K launches of act and
+ * asvrl_env_step_ex it replaces. The Actor's weight images are staged once into the LDS of the workgroup that
+ * owns an env group, beside its env-step arrays, its robots' observation rows and action pairs; one workgroup
+ * per CU. ro->actions must be NULL (the policy supplies the actions); every other AsvRollout member, ctl, `last`
+ * and launch mean what they mean to asvrl_env_rollout (ro->noise with noise_mode 0: recorded perception noise
+ * under a live policy). ctl->is_continuous must be 1. An env that is masked or held takes no action and its rows
+ * of pi->actions are not written: pre-fill them. pi->obs_in may be last->obs. The caller's step counter is only
+ * read. Per-robot parameters, layout 2 and an env group whose arrays do not fit the LDS beside the weights run
+ * K x (the act launch into a stream-ordered scratch, the single step, the record launches) instead. */
+int asvrl_policy_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                         const AsvStepOut* last, const AsvRollout* ro, const AsvPolicy* pi,
+                         const AsvEnvLaunch* launch /* NULL: automatic */, void* stream);
+/* sizeof(AsvPolicy) as compiled. */
+int64_t asvrl_policy_struct_size(void);
 
 /* ---------------------------------------------------------------- misc */
 const char* asvrl_last_error(void);
