@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("ASVRL_LIB", os.path.join(HERE, "lib", "libasvrl.so"))
 # the same sources built with f32 learner operands (the parity build; asvrl_operand_bytes() == 4)
 LIB_PATH_F32 = os.path.join(HERE, "lib", "libasvrl_f32.so")
 OPERANDS = {"bf16": (LIB_PATH, 2), "f32": (LIB_PATH_F32, 4)}
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 SELF_DIM, OBJ_DIM, MAX_OBJ = 7, 5, 5
 OBS_DIM = 40   # self 7 | objects 25 | mask 5 | pad 3
@@ -192,6 +192,11 @@ class AsvPolicy(C.Structure):
                 ("actions", _VP)]
 
 
+class AsvAutoReset(C.Structure):
+    _fields_ = [("cfg", AsvResetCfg), ("reset_counter", _U64), ("obs_counter", _U64), ("obs_in", _VP),
+                ("obs_prev", _VP), ("pushed", _VP), ("resets", _VP)]
+
+
 class AsvSampleArgs(C.Structure):
     _fields_ = [("ring", _VP), ("capacity", _I64), ("ring_state", _VP), ("seed", _U64), ("counter", _U64),
                 ("counter_dev", _VP), ("guard", _I64), ("B", _I32), ("tau_sets", _I32), ("tau_n", _I32),
@@ -351,6 +356,15 @@ EXPORTS = [
                                        C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvPolicy),
                                        C.POINTER(AsvEnvLaunch), _VP]),
     ("asvrl_policy_struct_size", _I64, []),
+    ("asvrl_env_rollout_ar", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), C.POINTER(AsvStepCtl),
+                                       C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvAutoReset),
+                                       C.POINTER(AsvEnvLaunch), _VP]),
+    ("asvrl_policy_rollout_ar", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), C.POINTER(AsvStepCtl),
+                                          C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvPolicy),
+                                          C.POINTER(AsvAutoReset), C.POINTER(AsvEnvLaunch), _VP]),
+    ("asvrl_autoreset_struct_size", _I64, []),
+    ("asvrl_replay_push_window", C.c_int, [_VP, _VP, _VP, _VP, _I32, _I64, _VP, _VP, _I32, _I32, _VP, _VP, _I64, _VP,
+                                           _VP, _VP, _VP, _I64, _VP]),
 ]
 
 _libs = {}

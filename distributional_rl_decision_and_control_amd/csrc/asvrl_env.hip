@@ -650,6 +650,22 @@ __global__ __launch_bounds__(BLOCK) void env_sweep_kernel(AsvParams p, AsvEnvSta
 #ifndef ASVRL_ENV_PAIRS_WPE
 #define ASVRL_ENV_PAIRS_WPE 4
 #endif
+// the device reset sampler (below, "reset"), which the auto-resetting rollout calls from its step loop
+constexpr int kResetWaves = 4;
+constexpr int kResetMaxR = 32;
+constexpr int kResetMaxO = 32;
+// The accepted sets of one env's reset, in the resetting wave's LDS
+struct ResetLds {
+  double rob[4][kResetMaxR];      // x, y, gx, gy of accepted robots
+  double core[kMaxCores][4];      // x, y, clockwise, Gamma
+  double obs[kResetMaxO][3];      // x, y, r
+};
+__device__ __forceinline__ void reset_env(const AsvParams& p, const AsvEnvState& s, const AsvResetCfg& cfg, int e,
+                                          uint64_t seed, uint64_t ctr, int lane, ResetLds& W);
+// the auto-resetting rollout's LDS behind the carve (and the policy rows): a ResetLds per wave, a flag per env
+__host__ __device__ constexpr size_t autoreset_lds(int blk, int epb) {
+  return static_cast<size_t>(blk / 64) * sizeof(ResetLds) + sizeof(int) * static_cast<size_t>(epb);
+}
 // one workgroup's envs [bid * epb, (bid + 1) * epb) of the step (env_pairs_kernel loops over them)
 // ROLL (env_rollout_kernel): RO->n_steps open-loop steps in one launch. The robot lanes load their state, goal,
 // flags, return, phi and the env's step count once and keep them in registers over the steps; the buoys are
@@ -661,11 +677,29 @@ __global__ __launch_bounds__(BLOCK) void env_sweep_kernel(AsvParams p, AsvEnvSta
 // 32-row tiles w, w + waves, ...; it reads the rows of an LDS copy of the observation (PI->obs_in before step 0,
 // then what the phases of the step before wrote: they write it beside their global outputs) and leaves the f64
 // action pairs in LDS, where phase 1 takes the lane's action instead of from A->actions.
-template <int BLOCK, int NM, bool DYN = true, bool ROLL = false, bool POL = false>   // DYN false: an observation pass only (do_dynamics = 0)
+// AR (asvrl_env_rollout_ar / asvrl_policy_rollout_ar, with ROLL): episodes restart inside the window. After the
+// phases of step t the workgroup votes on "an env of mine ended in this step"; if so its waves reset the ended envs
+// (reset_env, one wave per env, the waves taking them in turn, each in its own ResetLds behind the carve and the
+// policy rows), the robot lanes of those envs reload what the rollout keeps over the steps (state, goal, phi, ret,
+// flags, ep_ts, n_robots and with it `exists`, the staged buoys and counts), and the step's own phases run once
+// more as the masked observation pass (obsp: no act, no dynamics, no bookkeeping, the draws at obs_counter + t),
+// writing A->out, the policy's LDS rows and row t + 1 of the obs_prev record -- never row t of the step's records.
+// The second pass is a jump back to the top of the phases, not a loop around them, so the instantiations without AR
+// keep their control flow (and their code: compared instruction for instruction). Barriers: the vote, the barriers
+// around the reset and the phases' own are reached by every lane of the workgroup: the vote's result is
+// workgroup-uniform, the reset loop's trip count depends on the wave index and epb only and its condition (an LDS
+// flag per env, through readfirstlane) is wave-uniform, reset_env has wave barriers only, the reload is plain
+// lane-predicated code in front of the observation pass's first barrier, and that pass runs the same barrier
+// sequence as the step (the act and the env-end sections, which it skips, are skipped by all lanes alike). No lane
+// leaves the step loop early (hold_done is refused with AR), and since every lane of an env reads the env's alive
+// count for `end`, the vote is also the barrier between those reads and the next step's reset of the count.
+template <int BLOCK, int NM, bool DYN = true, bool ROLL = false, bool POL = false, bool AR = false>   // DYN false: an observation pass only (do_dynamics = 0)
 __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int bid, unsigned char* smem,
                                                 KArg<AsvRollout> RO = nullptr, KArg<AsvPolicy> PI = nullptr,
-                                                atile::ActorLds* AL = nullptr) {
+                                                atile::ActorLds* AL = nullptr, KArg<AsvAutoReset> RS = nullptr,
+                                                unsigned char* ar_lds = nullptr) {
   static_assert(!POL || ROLL, "the policy runs inside the rollout's step loop");
+  static_assert(!AR || ROLL, "the auto-reset runs inside the rollout's step loop");
   const int R = A->s.max_robots;
   const int O = A->s.max_obs;
   const int S = O + R;               // candidate slots per robot (obstacles, then robots)
@@ -709,8 +743,8 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
   const bool env_on0 = lane_env && (A->ctl.env_mask == nullptr || A->ctl.env_mask[e] != 0);
   // a masked pass (the observation pass after a reset) touches few envs: workgroups with none leave
   if (A->ctl.env_mask != nullptr && !__syncthreads_or(env_on0 ? 1 : 0)) return;
-  const int nrob = lane_env ? A->s.n_robots[e] : 0;
-  const bool exists0 = env_on0 && i < nrob;
+  int nrob = lane_env ? A->s.n_robots[e] : 0;   // (AR: reloaded after the env's reset, which may place fewer robots)
+  bool exists0 = env_on0 && i < nrob;
   const size_t NT = static_cast<size_t>(A->s.n_envs) * R;
   size_t idx = static_cast<size_t>(e) * R + i;
   // what a rollout keeps over its steps (a single step: this step's values)
@@ -720,6 +754,8 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
   double gx = 0, gy = 0, phi = 0.0, ret = 0.0;
   bool on = env_on0;   // hold_done: cleared after the env's end step
   int taken = 0;       // steps the env took
+  int nreset = 0;      // AR: resets of the env
+  bool rstl = false;   // AR: the lane's env was reset after this step's phases (the lanes of the observation pass)
   const int n_steps = ROLL ? RO->n_steps : 1;
   const bool hold = ROLL && RO->hold_done != 0;
   auto load_state = [&] {
@@ -772,6 +808,16 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
     }
     __syncthreads();
   }
+  if constexpr (AR) {   // row 0 of the acted-on observations: the caller's rows in front of step 0
+    const KArg<AsvAutoReset> Q = kfresh(RS);
+    const float* src0 = POL ? PI->obs_in : Q->obs_in;
+    if (env_on0 && Q->obs_prev != nullptr) {
+      const float4* src = reinterpret_cast<const float4*>(src0 + idx * ASVRL_OBS_DIM);
+      float4* dst = reinterpret_cast<float4*>(Q->obs_prev + idx * ASVRL_OBS_DIM);
+#pragma unroll
+      for (int k = 0; k < ASVRL_OBS_DIM / 4; ++k) dst[k] = src[k];
+    }
+  }
 
   // the step loop (its body keeps the single step's indentation; closed at "step t" below)
   for (int t = 0; t < n_steps; ++t) {
@@ -783,8 +829,13 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
     // every env of the workgroup is held: nothing left to do
     if (hold && !__syncthreads_or(on ? 1 : 0)) break;
   }
-  const bool env_on = ROLL ? on : env_on0;
-  const bool exists = ROLL ? (exists0 && on) : exists0;
+  // AR: the phases run as the step and then, only behind a reset in this workgroup, once more as the reset envs'
+  // observation pass (obsp; the jump back to `phases` is at the end of the step, its only writer)
+  bool obsp = false;
+  [[maybe_unused]] phases:
+  if constexpr (AR) asm volatile("" : "+v"(tid), "+v"(le), "+v"(idx));   // (opaque per pass as per step)
+  const bool env_on = ROLL ? (on && (!obsp || rstl)) : env_on0;
+  const bool exists = ROLL ? (exists0 && env_on) : exists0;
   const uint8_t fl = flv;
   const bool deact = (fl & ASVRL_FLAG_DEACTIVATED) != 0;
   const bool active = exists && !deact;
@@ -810,15 +861,29 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
   // f(o, opt, base): the outputs o (opt: members may be null); o.obs's rows are numbered from global row `base`
   auto each_out = [&](KArg<PairsArgs> Ak, auto&& f) {
     if (wlast) f(kref(Ak).out, std::false_type{}, size_t{0});
-    if constexpr (ROLL) f(rec_row(), std::true_type{}, size_t{0});
+    if constexpr (AR) {   // the records of row t keep the step's values, not the reset pass's
+      if (!obsp) f(rec_row(), std::true_type{}, size_t{0});
+    } else if constexpr (ROLL) {
+      f(rec_row(), std::true_type{}, size_t{0});
+    }
     if constexpr (POL) {   // the rows the Actor reads at the next step
       AsvStepOut o{};
       o.obs = sobs;
       f(o, std::true_type{}, row0);
     }
+    if constexpr (AR) {   // the acted-on observation of step t + 1: what this step, or the reset pass behind it, leaves
+      const KArg<AsvAutoReset> Q = kfresh(RS);
+      AsvStepOut o{};
+      if (Q->obs_prev != nullptr && t + 1 < n_steps)
+        o.obs = Q->obs_prev + static_cast<size_t>(t + 1) * NT * ASVRL_OBS_DIM;
+      f(o, std::true_type{}, size_t{0});
+    }
   };
 
   // ---------------- act: the Actor on the workgroup's rows, epsilon-greedy at step *step_dev + t
+  if constexpr (AR) {
+    if (obsp) goto acted;   // (workgroup-uniform) the observation pass acts on nothing
+  }
   if constexpr (POL) {
     const KArg<AsvPolicy> P = kfresh(PI);
     const uint64_t step = (P->step_dev != nullptr ? static_cast<uint64_t>(*P->step_dev) : 0ull) + static_cast<uint64_t>(t);
@@ -846,6 +911,7 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
       rec[1] = sa64[2 * tid + 1];
     }
   }
+  [[maybe_unused]] acted:
 
   // ---------------- phase 1: dynamics (env.py:247-277), the observation's self part
   {
@@ -855,7 +921,7 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
       gy = 0;
       if (exists) load_state();
     }
-    if (active && (DYN && A->ctl.do_dynamics)) {
+    if (active && (DYN && A->ctl.do_dynamics) && !obsp) {
       const double d_before = sqrt((gx - r.x) * (gx - r.x) + (gy - r.y) * (gy - r.y));
       const int nc = A->s.n_cores[e];
       const double* cores = A->s.cores + static_cast<size_t>(e) * A->s.max_cores * 4;
@@ -922,7 +988,7 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
     }
   }
   if (env_on) {
-    if (!ROLL || t == 0) {   // the buoys and the counts do not change over a rollout
+    if (!ROLL || t == 0 || obsp) {   // the buoys and the counts do not change over a rollout, but for a reset
       const int no = A->s.n_obs[e];
       for (int k = i; k < O; k += R) {
         const double* ob = A->s.obstacles + (static_cast<size_t>(e) * O + k) * 3;
@@ -965,8 +1031,11 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
     vy0 = sv1[qe * R + j];
     return true;
   };
-  const uint64_t ctr = A->ctl.counter + (A->ctl.counter_dev != nullptr ? *A->ctl.counter_dev : 0ull) +
-                       (ROLL ? static_cast<uint64_t>(t) : 0ull);
+  uint64_t ctr = A->ctl.counter + (A->ctl.counter_dev != nullptr ? *A->ctl.counter_dev : 0ull) +
+                 (ROLL ? static_cast<uint64_t>(t) : 0ull);
+  if constexpr (AR) {
+    if (obsp) ctr = ctr - A->ctl.counter + RS->obs_counter;
+  }
   // row t of the injected draws
   const size_t noise_t = (ROLL && NM == 0) ? static_cast<size_t>(t) * NT * S * 5 : 0;
   const bool full_circle = 0.5 * A->p.angle >= kPi;
@@ -1149,10 +1218,24 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
     }
   }
   if constexpr (!ROLL) ret = exists ? A->s.rs[ASVRL_F_RET * NT + idx] : 0.0;
-  const StepResult res = step_result(kref(A).p, kref(A).ctl, exists, deact, active, ep_ts, fl, coll, reach, apply, phi, reward,
+  AsvStepCtl cobs{};   // AR: the observation pass's control (do_dynamics, trainer_deactivate, gamma: 0)
+  if constexpr (AR) {
+    if (!obsp) {
+      cobs.do_dynamics = A->ctl.do_dynamics;
+      cobs.trainer_deactivate = A->ctl.trainer_deactivate;
+      cobs.gamma = A->ctl.gamma;
+    }
+  }
+  const StepResult res = step_result(kref(A).p, AR ? cobs : kref(A).ctl, exists, deact, active, ep_ts, fl, coll, reach, apply, phi, reward,
                                      ret);
-  if (A->ctl.trainer_deactivate && (DYN && A->ctl.do_dynamics) && exists && !(res.nfl & ASVRL_FLAG_DEACTIVATED))
+  if (A->ctl.trainer_deactivate && (DYN && A->ctl.do_dynamics) && !obsp && exists && !(res.nfl & ASVRL_FLAG_DEACTIVATED))
     atomicAdd(&salive[le], 1);
+  if constexpr (AR) {   // the step's rows a replay push takes (obj_cnt >= 0), a wave's count in one atomic
+    if (!obsp && RS->pushed != nullptr) {
+      const unsigned long long bal = __ballot(exists && cnt >= 0);
+      if ((tid & (kWave - 1)) == 0 && bal != 0) atomicAdd(RS->pushed + t, static_cast<int32_t>(__popcll(bal)));
+    }
+  }
   if (exists) {
     if constexpr (!ROLL) {
       if ((DYN && A->ctl.do_dynamics)) A->s.rs[ASVRL_F_RET * NT + idx] = res.ret;
@@ -1202,13 +1285,25 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
   }
   __syncthreads();
   A = kfresh(A);
+  if constexpr (AR) {
+    if (obsp) {
+      // the observation pass's own state writes (phi of its COLREGs chain, the flags), kept in registers until the
+      // window's last step
+      if (exists && t == n_steps - 1) {
+        A->s.rs[ASVRL_F_PHI * NT + idx] = phi;
+        A->s.rflags[idx] = flv;
+      }
+      continue;   // the next step
+    }
+  }
   if constexpr (!ROLL) {
     if (env_on && i == 0 && (DYN && A->ctl.do_dynamics)) env_end(kref(A).p, kref(A).s, kref(A).ctl, kref(A).out, e, ep_ts, nrob, salive[le], NT);
   } else {
-    // the env's end (trainer.py:172), by its lane 0 for the totals and by every lane of a held rollout
+    // the env's end (trainer.py:172), by its lane 0 for the totals and by every lane of a held or auto-resetting
+    // rollout
     const KArg<AsvRollout> Q = kfresh(RO);
     bool end = false;
-    if (env_on && A->ctl.trainer_deactivate && (hold || i == 0))
+    if (env_on && A->ctl.trainer_deactivate && (hold || AR || i == 0))
       end = (ep_ts >= A->p.episode_limit) || salive[le] == 0;
     if (env_on && i == 0) {
       env_end_from(kref(A).p, kref(A).s, kref(A).ctl, kref(A).out, e, ep_ts, nrob, salive[le],
@@ -1216,7 +1311,8 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
       if (Q->env_done != nullptr) Q->env_done[static_cast<size_t>(t) * A->s.n_envs + e] = end ? 1 : 0;
     }
     // the state goes back to HBM after the env's last step
-    if (exists && (t == n_steps - 1 || (hold && end))) {
+    // (AR: and in front of the env's reset, whose sampler leaves the rows of robot slots it does not fill as they are)
+    if (exists && (t == n_steps - 1 || ((hold || AR) && end))) {
       store_state();
       A->s.rs[ASVRL_F_RET * NT + idx] = ret;
       A->s.rs[ASVRL_F_PHI * NT + idx] = phi;
@@ -1234,10 +1330,56 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
       ++taken;
     }
     if (hold && end) on = false;
+    if constexpr (AR) {
+      // ---------------- the ended envs restart (see the comment in front of this function for the barriers)
+      rstl = env_on && end;
+      int* srst = reinterpret_cast<int*>(ar_lds + (BLOCK / kWave) * sizeof(ResetLds));   // [epb] env le was reset
+      if (rlane && i == 0) srst[le] = rstl ? 1 : 0;
+      if (!__syncthreads_or(rstl ? 1 : 0)) continue;   // workgroup-uniform: no env of the group ended in this step
+      // the ended envs' state stores above (and the flags in LDS) before the resetting waves' reads and stores
+      __syncthreads();
+      {
+        const KArg<AsvAutoReset> Z = kfresh(RS);
+        const uint64_t rctr = Z->reset_counter + (A->ctl.counter_dev != nullptr ? *A->ctl.counter_dev : 0ull) +
+                              static_cast<uint64_t>(t);
+        const int wv = __builtin_amdgcn_readfirstlane(tid / kWave);
+        ResetLds* W = reinterpret_cast<ResetLds*>(ar_lds);
+        // one wave per env, the waves taking the group's envs in turn (qe and the flag are wave-uniform)
+        for (int qe = wv; qe < epb; qe += BLOCK / kWave)
+          if (__builtin_amdgcn_readfirstlane(srst[qe]) != 0)
+            reset_env(kref(A).p, kref(A).s, kref(Z).cfg, bid * epb + qe, A->ctl.seed, rctr, tid & (kWave - 1), W[wv]);
+      }
+      __syncthreads();   // the resets' global writes (workgroup-scope release / acquire) before the reloads below
+      A = kfresh(A);
+      if (rstl) {   // what the rollout keeps over the steps, from the reset state
+        nrob = A->s.n_robots[e];
+        exists0 = i < nrob;
+        r = Regs{};
+        gx = 0;
+        gy = 0;
+        phi = 0.0;
+        ret = 0.0;
+        flv = 0;
+        if (exists0) {
+          load_state();
+          phi = A->s.rs[ASVRL_F_PHI * NT + idx];
+          ret = A->s.rs[ASVRL_F_RET * NT + idx];
+          flv = A->s.rflags[idx];
+        }
+        ep_ts = 0;
+        if (i == 0) ++nreset;
+      }
+      // the observation pass of the reset envs (it restages their buoys and counts)
+      obsp = true;
+      goto phases;
+    }
   }
   }   // step t
   if constexpr (ROLL) {
     if (lane_env && i == 0 && RO->steps_run != nullptr) RO->steps_run[e] = taken;
+  }
+  if constexpr (AR) {
+    if (lane_env && i == 0 && RS->resets != nullptr) RS->resets[e] = nreset;
   }
 }
 
@@ -1306,6 +1448,70 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(ASVRL_ENV
       &PA->ro, &PA->pi, &AL);
 }
 
+// The two rollouts with the auto-reset in the step loop (asvrl_env_rollout_ar / asvrl_policy_rollout_ar): new
+// instantiations (env_pairs_block<AR>) with the waves' ResetLds and the per-env reset flags at ar_off of the dynamic
+// LDS, behind everything the plain kernels carve. Philox noise only.
+struct RolloutArArgs {
+  PairsArgs k;
+  AsvRollout ro;
+  AsvAutoReset ar;
+  int ar_off;
+};
+template <int BLOCK, int NM>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(NM == 1 ? 1 : ASVRL_ENV_ROLLOUT_WPE))) void env_rollout_ar_kernel(RolloutArArgs) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const KArg<RolloutArArgs> RA = kargs<RolloutArArgs>();
+  env_pairs_block<BLOCK, NM, true, true, false, true>(
+      &RA->k, RA->k.epb, RA->k.group0 + xcd_group(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x)), smem,
+      &RA->ro, nullptr, nullptr, &RA->ar, smem + RA->ar_off);
+}
+struct PolicyArArgs {
+  PairsArgs k;
+  AsvRollout ro;
+  AsvPolicy pi;
+  AsvAutoReset ar;
+  int ar_off;
+};
+template <int BLOCK, int NM>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(ASVRL_ENV_POLICY_WPE))) void env_policy_rollout_ar_kernel(PolicyArArgs) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ __attribute__((aligned(16))) atile::ActorLds AL;
+  const KArg<PolicyArArgs> PA = kargs<PolicyArArgs>();
+  env_pairs_block<BLOCK, NM, true, true, true, true>(
+      &PA->k, PA->k.epb, PA->k.group0 + xcd_group(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x)), smem,
+      &PA->ro, &PA->pi, &AL, &PA->ar, smem + PA->ar_off);
+}
+
+// The K-launch fallback of the two calls. In front of step t: row t of obs_prev, the observation (src) the stepping
+// envs' rows hold ...
+__global__ __launch_bounds__(kBlock) void autoreset_obs_prev_kernel(const float* __restrict__ src, float* __restrict__ row,
+                                                                    const uint8_t* __restrict__ mask, int n_envs, int R) {
+  constexpr int kQ = ASVRL_OBS_DIM / 4;
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= n_envs * R * kQ) return;
+  if (mask != nullptr && mask[q / (R * kQ)] == 0) return;
+  reinterpret_cast<float4*>(row)[q] = reinterpret_cast<const float4*>(src)[q];
+}
+// ... and behind it, one lane per env: the reset mask (the env stepped and its episode ended), formed on the
+// device, and the window's counts
+__global__ __launch_bounds__(kBlock) void autoreset_mask_kernel(const uint8_t* __restrict__ env_done,
+                                                                const uint8_t* __restrict__ mask,
+                                                                const int8_t* __restrict__ obj_cnt, int n_envs, int R,
+                                                                uint8_t* __restrict__ reset_mask, int32_t* resets,
+                                                                int32_t* pushed_t) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_envs) return;
+  const bool on = mask == nullptr || mask[e] != 0;
+  const bool rst = on && env_done[e] != 0;
+  reset_mask[e] = rst ? 1 : 0;
+  if (rst && resets != nullptr) resets[e] += 1;
+  if (on && pushed_t != nullptr) {
+    int c = 0;
+    for (int i = 0; i < R; ++i) c += obj_cnt[static_cast<size_t>(e) * R + i] >= 0 ? 1 : 0;
+    if (c != 0) atomicAdd(pushed_t, c);
+  }
+}
+
 // The sweep fallback of asvrl_policy_rollout: the step count of its t-th act launch, *src + t, into the call's
 // scratch (the caller's counter is never written) ...
 __global__ void policy_step_count_kernel(const int64_t* src, int64_t* dst, int t) {
@@ -1369,10 +1575,6 @@ __device__ inline bool far_enough(double ax, double ay, double bx, double by, do
 // retesting up to 63 candidates each time). The accepted set of the phase lives in LDS for the phases
 // after it. Restated one candidate at a time by oracle/asv_oracle.c or_device_reset (bit-identical:
 // tests/test_env_kernel_gpu.py).
-constexpr int kResetWaves = 4;
-constexpr int kResetMaxR = 32;
-constexpr int kResetMaxO = 32;
-
 struct CandDraw {
   uint32_t k0, k1, e, ctr;
   __device__ double u(int phase, int cand, int j) const {   // j-th double of candidate cand
@@ -1415,13 +1617,6 @@ __device__ __forceinline__ bool core_conflict(const AsvResetCfg& cfg, double cor
   const double v2 = gs / (2 * kPi * core_r);
   return v1 > cfg.p_rel * v2;
 }
-
-// The accepted sets of one env's reset, in the resetting wave's LDS
-struct ResetLds {
-  double rob[4][kResetMaxR];      // x, y, gx, gy of accepted robots
-  double core[kMaxCores][4];      // x, y, clockwise, Gamma
-  double obs[kResetMaxO][3];      // x, y, r
-};
 
 // env e's reset by one wave (lane = its lane index)
 __device__ __forceinline__ void reset_env(const AsvParams& p, const AsvEnvState& s, const AsvResetCfg& cfg, int e,
@@ -1833,12 +2028,13 @@ struct PolicyLaunch {
   size_t smem;   // dynamic: the pair carve + the observation rows and action pairs
   bool fits;
 };
-static PolicyLaunch policy_launch(int R, int O, int n_envs, int blk_req, int epb_req, int vm_bytes) {
+static PolicyLaunch policy_launch(int R, int O, int n_envs, int blk_req, int epb_req, int vm_bytes, bool ar = false) {
   constexpr size_t kLdsBytes = 160 * 1024;
   constexpr size_t kLdsStatic = 1024;   // room for the workgroup-vote scratch (__syncthreads_or) and alignment
   constexpr int kCus = 256;
   auto total = [&](const PairLaunch& l) {
-    return policy_rows_offset(l.smem) + static_cast<size_t>(l.epb) * R * (ASVRL_OBS_DIM * sizeof(float) + 2 * sizeof(double));
+    const size_t rows = policy_rows_offset(l.smem) + static_cast<size_t>(l.epb) * R * (ASVRL_OBS_DIM * sizeof(float) + 2 * sizeof(double));
+    return ar ? policy_rows_offset(rows) + autoreset_lds(l.blk, l.epb) : rows;   // (the auto-reset's LDS behind the rows)
   };
   PolicyLaunch L;
   int blk = (blk_req == 64 || blk_req == 128) ? blk_req : 256;
@@ -1958,6 +2154,217 @@ extern "C" int asvrl_policy_rollout(const AsvParams* params, const AsvEnvState* 
 }
 
 extern "C" int64_t asvrl_policy_struct_size(void) { return sizeof(AsvPolicy); }
+
+// ------------------------------------------------------------------ auto-reset inside the rollout windows
+// what the two _ar calls refuse beyond their plain calls' checks (`who` names the call)
+static int autoreset_checks(const std::string& who, const AsvEnvState* state, const AsvStepCtl* ctl,
+                            const AsvStepOut* out, const AsvRollout* ro, const AsvAutoReset* ar, bool open_loop) {
+  ASVRL_REQUIRE(ar != nullptr, who + ": null ar (the auto-reset description)");
+  ASVRL_REQUIRE(!ro->hold_done, who + ": ro->hold_done cannot be combined with the auto-reset");
+  ASVRL_REQUIRE(ctl->trainer_deactivate && out->env_done != nullptr,
+                who + ": the auto-reset needs ctl->trainer_deactivate and last->env_done");
+  ASVRL_REQUIRE(ctl->noise_mode == 1 || ctl->noise_mode == 2,
+                who + ": noise_mode 0 (recorded noise) cannot cover a sampled reset; Philox noise only (mode 1 or 2)");
+  ASVRL_REQUIRE(!open_loop || ar->obs_prev == nullptr || ar->obs_in != nullptr,
+                who + ": ar->obs_prev needs ar->obs_in (the rows in front of step 0)");
+  ASVRL_REQUIRE(ar->cfg.num_robots >= 0 && ar->cfg.num_robots <= kResetMaxR && state->max_robots <= kResetMaxR,
+                who + ": ar->cfg.num_robots / max_robots beyond the reset sampler's 32");
+  ASVRL_REQUIRE(ar->cfg.num_obs >= 0 && ar->cfg.num_obs <= kResetMaxO && state->max_obs <= kResetMaxO,
+                who + ": ar->cfg.num_obs / max_obs beyond the reset sampler's 32");
+  ASVRL_REQUIRE(ar->cfg.num_cores >= 0 && ar->cfg.num_cores <= kMaxCores && state->max_cores <= kMaxCores,
+                who + ": ar->cfg.num_cores / max_cores beyond the reset sampler's 16");
+  ASVRL_REQUIRE(ar->cfg.width > 4.0 && ar->cfg.height > 4.0, who + ": ar->cfg map too small");
+  return 0;
+}
+
+// The K-launch form of both calls (per-robot parameters, layout 2, a carve that does not fit): per step the act
+// launch (closed loop), the obs_prev row, the single step, its record launch, the reset mask and counts, and the
+// reset of the ended envs with their observation (asvrl_env_reset_observe, or the two launches where that call does
+// not apply). pi null: the open loop.
+static int autoreset_fallback(const char* who, const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                              const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi, const AsvAutoReset* ar,
+                              const AsvEnvLaunch* launch, void* stream) {
+  hipStream_t st = as_stream(stream);
+  const int E = state->n_envs, R = state->max_robots;
+  const size_t NT = static_cast<size_t>(E) * R;
+  const unsigned egrid = (static_cast<unsigned>(E) + kBlock - 1) / kBlock;
+  const unsigned qgrid = (static_cast<unsigned>(NT) * (ASVRL_OBS_DIM / 4) + kBlock - 1) / kBlock;
+  // scratch: the actions [NT][2] f64 and the act launch's step count (closed loop), then the reset mask [E]
+  unsigned char* scratch = nullptr;
+  const size_t act_bytes = pi != nullptr ? sizeof(double) * 2 * NT + sizeof(int64_t) : 0;
+  if (hipMallocAsync(reinterpret_cast<void**>(&scratch), act_bytes + E, st) != hipSuccess) return check_launch(who);
+  double* act = reinterpret_cast<double*>(scratch);
+  int64_t* step = reinterpret_cast<int64_t*>(scratch + sizeof(double) * 2 * NT);
+  uint8_t* rmask = scratch + act_bytes;
+  const PairLaunch one = pair_launch(R, state->max_obs, E, kWave, 1, ctl->noise_mode == 2 ? 4 : 8);
+  const bool one_launch = state->robot_params == nullptr && one.blk == kWave && one.epb == 1 && one.smem <= 60 * 1024;
+  AsvStepOut oo = *out;   // the observation pass's outputs: no episode bookkeeping
+  oo.env_done = nullptr;
+  oo.stats = nullptr;
+  const float* obs_first = pi != nullptr ? pi->obs_in : ar->obs_in;
+  int rc = 0;
+  for (int t = 0; t < ro->n_steps && rc == 0; ++t) {
+    AsvStepCtl c = *ctl;
+    c.counter = ctl->counter + static_cast<uint64_t>(t);
+    const float* obs_t = t == 0 ? obs_first : out->obs;   // the observation the step before (or its reset) wrote
+    const double* actions = nullptr;
+    if (pi != nullptr) {
+      hipLaunchKernelGGL(policy_step_count_kernel, dim3(1), dim3(1), 0, st, pi->step_dev, step, t);
+      AsvMlpIO io{};
+      io.x = obs_t;
+      io.ldx = ASVRL_OBS_DIM;
+      io.n = static_cast<int32_t>(NT);
+      io.a_out64 = act;
+      io.step_dev = step;
+      io.eps_steps_per_count = pi->eps_steps_per_count;
+      io.eps_total = pi->eps_total;
+      io.eps_fraction = pi->eps_fraction;
+      io.eps_initial = pi->eps_initial;
+      io.eps_final = pi->eps_final;
+      io.seed = pi->seed;
+      rc = asvrl_actor_forward(&pi->w, &io, atile::MLP_ACT, stream);
+      if (rc == 0 && pi->actions != nullptr)
+        hipLaunchKernelGGL(policy_actions_kernel, dim3((static_cast<unsigned>(NT) + kBlock - 1) / kBlock), dim3(kBlock), 0, st,
+                           act, pi->actions + static_cast<size_t>(t) * 2 * NT, c.env_mask, E, R);
+      actions = act;
+    } else {
+      actions = ro->actions + static_cast<size_t>(t) * 2 * NT;
+    }
+    if (rc == 0 && ar->obs_prev != nullptr)
+      hipLaunchKernelGGL(autoreset_obs_prev_kernel, dim3(qgrid), dim3(kBlock), 0, st, obs_t,
+                         ar->obs_prev + static_cast<size_t>(t) * NT * ASVRL_OBS_DIM, c.env_mask, E, R);
+    if (rc == 0) rc = asvrl_env_step_ex(params, state, actions, nullptr, &c, out, launch, stream);
+    if (rc != 0) break;
+    hipLaunchKernelGGL(rollout_record_kernel, dim3(egrid), dim3(kBlock), 0, st, *state, *out, *ro, t, c.env_mask,
+                       static_cast<uint8_t*>(nullptr));
+    hipLaunchKernelGGL(autoreset_mask_kernel, dim3(egrid), dim3(kBlock), 0, st, out->env_done, c.env_mask, out->obj_cnt,
+                       E, R, rmask, ar->resets, ar->pushed != nullptr ? ar->pushed + t : nullptr);
+    rc = check_launch(who);
+    if (rc != 0) break;
+    AsvStepCtl co{};
+    co.is_continuous = ctl->is_continuous;
+    co.noise_mode = ctl->noise_mode;
+    co.seed = ctl->seed;
+    co.counter = ar->obs_counter + static_cast<uint64_t>(t);
+    co.counter_dev = ctl->counter_dev;
+    co.env_mask = rmask;
+    const uint64_t rctr = ar->reset_counter + static_cast<uint64_t>(t);
+    if (one_launch) {
+      rc = asvrl_env_reset_observe(params, state, &ar->cfg, rmask, ctl->seed, rctr, ctl->counter_dev, &co, &oo, stream);
+    } else {
+      rc = asvrl_env_reset(params, state, &ar->cfg, rmask, ctl->seed, rctr, ctl->counter_dev, stream);
+      if (rc == 0) rc = asvrl_env_step_ex(params, state, nullptr, nullptr, &co, &oo, launch, stream);
+    }
+  }
+  (void)hipFreeAsync(scratch, st);
+  return rc;
+}
+
+extern "C" int asvrl_env_rollout_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                                    const AsvStepOut* out, const AsvRollout* ro, const AsvAutoReset* ar,
+                                    const AsvEnvLaunch* launch, void* stream) {
+  const char* who = "asvrl_env_rollout_ar";
+  ASVRL_REQUIRE(params && state && ctl && out && ro, "asvrl_env_rollout_ar: null argument");
+  if (int rc = autoreset_checks(who, state, ctl, out, ro, ar, true)) return rc;
+  ASVRL_REQUIRE(ro->n_steps >= 1, "asvrl_env_rollout_ar: n_steps must be >= 1");
+  ASVRL_REQUIRE(ro->actions != nullptr, "asvrl_env_rollout_ar: null actions");
+  if (int rc = rollout_checks(who, params, state, ctl, out, ro, launch)) return rc;
+  ASVRL_REQUIRE(ar->obs_prev == nullptr || (reinterpret_cast<uintptr_t>(ar->obs_in) % 16 == 0 &&
+                                            reinterpret_cast<uintptr_t>(ar->obs_prev) % 16 == 0),
+                "asvrl_env_rollout_ar: ar->obs_in / ar->obs_prev rows must be 16-byte aligned");
+  if (state->n_envs == 0) return 0;
+  const AsvEnvLaunch lz{};
+  const AsvEnvLaunch& lc = launch != nullptr ? *launch : lz;
+  const int nm = ctl->noise_mode == 1 ? 1 : 2;
+  const PairLaunch pl = pair_launch(state->max_robots, state->max_obs, state->n_envs, lc.block, lc.envs_per_block,
+                                    nm == 2 ? 4 : 8);
+  const bool per_robot = state->robot_params != nullptr;
+  const size_t ar_off = policy_rows_offset(pl.smem), smem = ar_off + autoreset_lds(pl.blk, pl.epb);
+  ASVRL_REQUIRE(lc.layout != 1 || smem <= 150 * 1024, "asvrl_env_rollout_ar: the pair layout's LDS does not fit");
+  ASVRL_REQUIRE(lc.layout != 1 || !per_robot, "asvrl_env_rollout_ar: per-robot parameters take the sweep layout (2)");
+  hipStream_t st = as_stream(stream);
+  if (ro->steps_run != nullptr && hipMemsetAsync(ro->steps_run, 0, sizeof(int32_t) * state->n_envs, st) != hipSuccess)
+    return check_launch(who);
+  if (ar->resets != nullptr && hipMemsetAsync(ar->resets, 0, sizeof(int32_t) * state->n_envs, st) != hipSuccess)
+    return check_launch(who);
+  if (lc.layout != 2 && !per_robot && smem <= 150 * 1024) {
+    const int groups = (state->n_envs + pl.epb - 1) / pl.epb;
+    const int chunk = lc.max_groups > 0 && lc.max_groups < groups ? lc.max_groups : groups;
+    auto go = [&](auto kern) {
+      RolloutArArgs a{PairsArgs{*params, *state, *ctl, *out, ro->actions, nullptr, pl.epb, 0}, *ro, *ar,
+                      static_cast<int>(ar_off)};
+      for (int g0 = 0; g0 < groups; g0 += chunk) {
+        a.k.group0 = g0;
+        hipLaunchKernelGGL(kern, dim3(groups - g0 < chunk ? groups - g0 : chunk), dim3(pl.blk), smem, st, a);
+      }
+    };
+    if (pl.blk == 64)
+      nm == 1 ? go(env_rollout_ar_kernel<64, 1>) : go(env_rollout_ar_kernel<64, 2>);
+    else if (pl.blk == 128)
+      nm == 1 ? go(env_rollout_ar_kernel<128, 1>) : go(env_rollout_ar_kernel<128, 2>);
+    else
+      nm == 1 ? go(env_rollout_ar_kernel<256, 1>) : go(env_rollout_ar_kernel<256, 2>);
+    return check_launch(who);
+  }
+  return autoreset_fallback(who, params, state, ctl, out, ro, nullptr, ar, launch, stream);
+}
+
+extern "C" int asvrl_policy_rollout_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                                       const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi,
+                                       const AsvAutoReset* ar, const AsvEnvLaunch* launch, void* stream) {
+  const char* who = "asvrl_policy_rollout_ar";
+  ASVRL_REQUIRE(params && state && ctl && out && ro, "asvrl_policy_rollout_ar: null argument");
+  if (int rc = autoreset_checks(who, state, ctl, out, ro, ar, false)) return rc;
+  ASVRL_REQUIRE(ro->n_steps >= 1, "asvrl_policy_rollout_ar: n_steps must be >= 1");
+  ASVRL_REQUIRE(ro->actions == nullptr, "asvrl_policy_rollout_ar: ro->actions must be null (the policy supplies the actions)");
+  ASVRL_REQUIRE(pi != nullptr, "asvrl_policy_rollout_ar: null policy");
+  ASVRL_REQUIRE(pi->obs_in != nullptr, "asvrl_policy_rollout_ar: null obs_in");
+  ASVRL_REQUIRE(ctl->is_continuous, "asvrl_policy_rollout_ar: is_continuous must be 1 (the Actor is the continuous agent)");
+  const AsvMlpWeights& w = pi->w;
+  ASVRL_REQUIRE(w.enc_frag && w.b_enc && w.w1_frag && w.w2_frag && w.b1 && w.b2 && w.wout && w.bout,
+                "asvrl_policy_rollout_ar: null actor image");
+  if (int rc = rollout_checks(who, params, state, ctl, out, ro, launch)) return rc;
+  ASVRL_REQUIRE(reinterpret_cast<uintptr_t>(pi->obs_in) % 16 == 0 && reinterpret_cast<uintptr_t>(out->obs) % 16 == 0 &&
+                    reinterpret_cast<uintptr_t>(ar->obs_prev) % 16 == 0,
+                "asvrl_policy_rollout_ar: observation rows must be 16-byte aligned");
+  if (state->n_envs == 0) return 0;
+  const AsvEnvLaunch lz{};
+  const AsvEnvLaunch& lc = launch != nullptr ? *launch : lz;
+  const int nm = ctl->noise_mode == 1 ? 1 : 2;
+  const bool per_robot = state->robot_params != nullptr;
+  hipStream_t st = as_stream(stream);
+  if (ro->steps_run != nullptr && hipMemsetAsync(ro->steps_run, 0, sizeof(int32_t) * state->n_envs, st) != hipSuccess)
+    return check_launch(who);
+  if (ar->resets != nullptr && hipMemsetAsync(ar->resets, 0, sizeof(int32_t) * state->n_envs, st) != hipSuccess)
+    return check_launch(who);
+  if (lc.layout != 2 && !per_robot) {
+    const PolicyLaunch L = policy_launch(state->max_robots, state->max_obs, state->n_envs, lc.block, lc.envs_per_block,
+                                         nm == 2 ? 4 : 8, true);
+    if (L.fits) {
+      const PairLaunch& pl = L.pl;
+      const int groups = (state->n_envs + pl.epb - 1) / pl.epb;
+      const int chunk = lc.max_groups > 0 && lc.max_groups < groups ? lc.max_groups : groups;
+      auto go = [&](auto kern) {
+        PolicyArArgs a{PairsArgs{*params, *state, *ctl, *out, nullptr, nullptr, pl.epb, 0}, *ro, *pi, *ar,
+                       static_cast<int>(L.smem - autoreset_lds(pl.blk, pl.epb))};
+        for (int g0 = 0; g0 < groups; g0 += chunk) {
+          a.k.group0 = g0;
+          hipLaunchKernelGGL(kern, dim3(groups - g0 < chunk ? groups - g0 : chunk), dim3(pl.blk), L.smem, st, a);
+        }
+      };
+      if (pl.blk == 64)
+        nm == 1 ? go(env_policy_rollout_ar_kernel<64, 1>) : go(env_policy_rollout_ar_kernel<64, 2>);
+      else if (pl.blk == 128)
+        nm == 1 ? go(env_policy_rollout_ar_kernel<128, 1>) : go(env_policy_rollout_ar_kernel<128, 2>);
+      else
+        nm == 1 ? go(env_policy_rollout_ar_kernel<256, 1>) : go(env_policy_rollout_ar_kernel<256, 2>);
+      return check_launch(who);
+    }
+  }
+  return autoreset_fallback(who, params, state, ctl, out, ro, pi, ar, launch, stream);
+}
+
+extern "C" int64_t asvrl_autoreset_struct_size(void) { return sizeof(AsvAutoReset); }
 
 extern "C" int asvrl_env_reset(const AsvParams* params, const AsvEnvState* state, const AsvResetCfg* cfg,
                                const uint8_t* env_mask, uint64_t seed, uint64_t counter,

@@ -381,6 +381,97 @@ __global__ __launch_bounds__(kPushBlock) void replay_push_kernel(
   }
 }
 
+// The push of a whole K-step window (asvrl_replay_push_window). Block (b, t) owns rows [256 b, 256 b + 256) of step
+// t. Its first slot follows the rows of steps 0..t-1 (the K per-step counts: counts[]) and the rows of step t in
+// front of it (counted by the block inside its own step only): step-major, then row order, what K pushes leave,
+// at a cost linear in K (replay_push_kernel over the K n flattened rows would recount every earlier step in every
+// block). The last block to arrive advances {head, size} as the single push does.
+__global__ __launch_bounds__(kPushBlock) void replay_window_count_kernel(const int8_t* __restrict__ cnt, int n, int* counts) {
+  __shared__ int sh[kPushBlock / kWave];
+  const int c = count_pushed(cnt + static_cast<size_t>(blockIdx.x) * n, n, sh);
+  if (threadIdx.x == 0) counts[blockIdx.x] = c;
+}
+__global__ __launch_bounds__(kPushBlock) void replay_push_window_kernel(
+    const float* __restrict__ obs_prev, const float* __restrict__ obs_next, const int8_t* __restrict__ cnt_all,
+    const double* __restrict__ actions, int adim, int64_t ald, const double* __restrict__ reward,
+    const uint8_t* __restrict__ done, int n, const int* __restrict__ counts, float* __restrict__ ring, int64_t cap,
+    int64_t* ring_state, int* arrive, int nblocks, int64_t* snap, int64_t* counter_inc, int64_t counter_by) {
+  __shared__ int sh[kPushBlock / kWave], shw[kPushBlock / kWave];
+  __shared__ int s_last;
+  __shared__ int64_t s_slot[kPushBlock];   // the ring slot of each of the block's rows, -1: not pushed
+  const int t = blockIdx.y;
+  const size_t t0 = static_cast<size_t>(t) * n;   // the step's first row
+  const int8_t* cnt = cnt_all + t0;
+  int cb = 0;
+  for (int k = threadIdx.x; k < t; k += kPushBlock) cb += counts[k];
+  const int base = block_sum(cb, sh);
+  const int before = base + count_pushed(cnt, static_cast<int>(blockIdx.x) * kPushBlock, sh);
+  const int k = blockIdx.x * kPushBlock + threadIdx.x;
+  const bool v = k < n && cnt[k] >= 0;
+  const unsigned long long bal = __ballot(v);
+  const int lane = threadIdx.x & 63;
+  const int rank_in_wave = __popcll(bal & ((1ull << lane) - 1ull));
+  if (lane == 0) shw[threadIdx.x >> 6] = __popcll(bal);
+  __syncthreads();
+  const int64_t head_in = ring_state[0];
+  if (v) {
+    int wave_off = 0;
+    for (int w = 0; w < (threadIdx.x >> 6); ++w) wave_off += shw[w];
+    const int64_t slot = (head_in + before + wave_off + rank_in_wave) % cap;
+    float4* dst = reinterpret_cast<float4*>(ring + slot * ASVRL_TR_DIM);
+    s_slot[threadIdx.x] = slot;
+    const size_t g = t0 + k;
+    const float a0 = static_cast<float>(actions[g * ald]);
+    const float a1 = adim > 1 ? static_cast<float>(actions[g * ald + 1]) : 0.f;
+    dst[2 * ASVRL_OBS_DIM / 4] = make_float4(a0, a1, static_cast<float>(reward[g]), done[g] ? 1.f : 0.f);
+    dst[2 * ASVRL_OBS_DIM / 4 + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
+  } else {
+    s_slot[threadIdx.x] = -1;
+  }
+  __syncthreads();
+  {   // the block's observation rows, copied cooperatively as in replay_push_kernel
+    constexpr int kQ = ASVRL_OBS_DIM / 4;
+    const int k0 = blockIdx.x * kPushBlock;
+    const int nr = n - k0 < kPushBlock ? n - k0 : kPushBlock;
+    const float4* a4 = reinterpret_cast<const float4*>(obs_prev) + (t0 + k0) * kQ;
+    const float4* b4 = reinterpret_cast<const float4*>(obs_next) + (t0 + k0) * kQ;
+#pragma unroll 10
+    for (int q = threadIdx.x; q < nr * kQ; q += kPushBlock) {
+      const int r = q / kQ;
+      const float4 x = a4[q], y = b4[q];   // in bounds for every row of the block: loads ahead of the test
+      const int64_t slot = s_slot[r];
+      if (slot >= 0) {
+        float4* dst = reinterpret_cast<float4*>(ring + slot * ASVRL_TR_DIM) + (q - r * kQ);
+        dst[0] = x;
+        dst[kQ] = y;
+      }
+    }
+  }
+  __syncthreads();   // every lane's read of ring_state is done before the block arrives
+  if (threadIdx.x == 0) {
+    int c = 0;
+    for (int w = 0; w < kPushBlock / kWave; ++w) c += shw[w];
+    atomicAdd(arrive + 1, c);
+    __threadfence();
+    s_last = atomicAdd(arrive, 1) == nblocks - 1;
+  }
+  __syncthreads();
+  if (!s_last) return;
+  if (threadIdx.x == 0) {
+    const int tot = atomicExch(arrive + 1, 0);
+    const int64_t nh = (head_in + tot) % cap, ns0 = ring_state[1] + tot;
+    const int64_t ns = ns0 < cap ? ns0 : cap;
+    ring_state[0] = nh;
+    ring_state[1] = ns;
+    if (snap != nullptr) {
+      snap[0] = nh;
+      snap[1] = ns;
+    }
+    if (counter_inc != nullptr) *counter_inc += counter_by;
+    *arrive = 0;
+  }
+}
+
 // one wave per sampled row, 22 lanes x float4
 __global__ __launch_bounds__(4 * kWave) void replay_sample_kernel(const float* __restrict__ ring, int64_t cap,
                                                                   const int64_t* __restrict__ ring_state,
@@ -505,6 +596,31 @@ extern "C" int asvrl_replay_push(const float* obs_prev, const float* obs_next, c
                                  int64_t* ring_state, int32_t* work, void* stream) {
   return asvrl_replay_push_ex(obs_prev, obs_next, obj_cnt_next, actions, action_dim, action_dim, reward, done, n, ring, capacity,
                               ring_state, work, nullptr, nullptr, stream);
+}
+
+extern "C" int asvrl_replay_push_window(const float* obs_prev, const float* obs_next, const int8_t* obj_cnt_next,
+                                        const double* actions, int32_t action_dim, int64_t action_ld,
+                                        const double* reward, const uint8_t* done, int32_t n, int32_t K,
+                                        const int32_t* pushed, float* ring, int64_t capacity, int64_t* ring_state,
+                                        int32_t* work, int64_t* snap, int64_t* counter_inc, int64_t counter_by,
+                                        void* stream) {
+  ASVRL_REQUIRE(obs_prev && obs_next && obj_cnt_next && actions && reward && done && ring && ring_state && work,
+                "asvrl_replay_push_window: null argument");
+  ASVRL_REQUIRE(n >= 0 && K >= 1, "asvrl_replay_push_window: n must be >= 0 and K >= 1");
+  ASVRL_REQUIRE(capacity > 0 && static_cast<int64_t>(K) * n <= capacity,
+                "asvrl_replay_push_window: K * n rows exceed the ring's capacity");
+  ASVRL_REQUIRE(action_dim == 1 || action_dim == 2, "asvrl_replay_push_window: action_dim must be 1 or 2");
+  ASVRL_REQUIRE(action_ld >= action_dim, "asvrl_replay_push_window: action row stride below action_dim");
+  if (n <= 0) return 0;
+  const int nb = (n + kPushBlock - 1) / kPushBlock;
+  if (pushed == nullptr)
+    hipLaunchKernelGGL(replay_window_count_kernel, dim3(K), dim3(kPushBlock), 0, as_stream(stream), obj_cnt_next, n,
+                       work + 2);
+  hipLaunchKernelGGL(replay_push_window_kernel, dim3(nb, K), dim3(kPushBlock), 0, as_stream(stream), obs_prev,
+                     obs_next, obj_cnt_next, actions, action_dim, action_ld, reward, done, n,
+                     pushed != nullptr ? pushed : work + 2, ring, capacity, ring_state, work, nb * K, snap, counter_inc,
+                     counter_by);
+  return check_launch("asvrl_replay_push_window");
 }
 
 extern "C" int asvrl_replay_sample(const float* ring, int64_t capacity, const int64_t* ring_state,

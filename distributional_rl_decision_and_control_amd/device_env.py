@@ -154,9 +154,40 @@ class DeviceEnvBatch:
         assert steps_run.dtype == torch.int32 and steps_run.numel() == self.n_envs
         return rec, steps_run
 
+    def _auto_reset(self, who, auto_reset, K, specs):
+        """The AsvAutoReset of rollout(auto_reset=...) / policy_rollout(auto_reset=...): a dict or namespace with
+        cfg (AsvResetCfg), reset_counter, obs_counter and, for the open loop's obs_prev record, obs_in; optionally
+        the caller's own pushed [K] / resets [E] i32 tensors (graph capture). Adds the obs_prev record to specs.
+        Returns (struct, pushed, resets); pushed is zeroed here."""
+        get = auto_reset.get if isinstance(auto_reset, dict) else (lambda k, d=None: getattr(auto_reset, k, d))
+        NT = self.n_envs * self.max_robots
+        specs["obs_prev"] = ((NT, OBS_DIM), torch.float32, 0)
+        ar = _abi.AsvAutoReset()
+        cfg = get("cfg")
+        if cfg is None:
+            raise ValueError(f"{who}: auto_reset needs cfg (an AsvResetCfg)")
+        ar.cfg = cfg
+        ar.reset_counter = int(get("reset_counter", 0)) & 0xFFFFFFFFFFFFFFFF
+        ar.obs_counter = int(get("obs_counter", 0)) & 0xFFFFFFFFFFFFFFFF
+        obs_in = get("obs_in")
+        if obs_in is not None:
+            assert obs_in.dtype == torch.float32 and obs_in.is_contiguous() and tuple(obs_in.shape) == (NT, OBS_DIM)
+            ar.obs_in = obs_in.data_ptr()
+        pushed, resets = get("pushed"), get("resets")
+        if pushed is None:
+            pushed = torch.zeros(K, dtype=torch.int32, device=self.device)
+        else:
+            assert pushed.dtype == torch.int32 and pushed.numel() == K and pushed.is_contiguous()
+            pushed.zero_()
+        if resets is None:
+            resets = torch.zeros(self.n_envs, dtype=torch.int32, device=self.device)
+        assert resets.dtype == torch.int32 and resets.numel() == self.n_envs and resets.is_contiguous()
+        ar.pushed, ar.resets = pushed.data_ptr(), resets.data_ptr()
+        return ar, pushed, resets
+
     def rollout(self, actions, noise=None, *, keep=("reward", "done", "info"), hold_done=False, is_continuous=True,
                 trainer_deactivate=False, seed=0, counter=0, counter_dev=None, gamma=0.0, env_mask=None, obs=None,
-                obj_cnt=None, fast_noise=False, launch=None, stream=None):
+                obj_cnt=None, fast_noise=False, launch=None, stream=None, auto_reset=None):
         """asvrl_env_rollout: K = actions.shape[0] open-loop steps in one launch, bit for bit the K calls
         step(actions[t], noise[t], counter=counter + t). actions: f64 [K, E*R, 2]; noise: f64 [K, E*R, O+R, 5]
         or None (Philox). keep: the per-step records to return, names out of reward, done, info, env_done, obs,
@@ -165,7 +196,13 @@ class DeviceEnvBatch:
         pre-filled tensor (also "steps_run": nothing is allocated then and the call can be graph-captured).
         hold_done (needs trainer_deactivate): an env stops after the step that sets its env_done. The last
         step's outputs land where step() writes them (obs / obj_cnt, self.reward, ...). Returns a namespace of
-        the kept records (None where not kept) and steps_run [E] i32. No host sync."""
+        the kept records (None where not kept) and steps_run [E] i32. No host sync.
+        auto_reset (asvrl_env_rollout_ar; see _auto_reset): an env whose episode ends in step t is reset inside the
+        window (cfg at reset_counter + t) and observed (obs_counter + t) before step t + 1 -- the values of
+        reset_observe(cfg, env_done & env_mask, counter=reset_counter + t, obs_counter=obs_counter + t) behind every
+        step. Needs trainer_deactivate and Philox noise, not hold_done. keep then also takes "obs_prev"
+        (f32 [K, E*R, 40]: the observation every robot row of a stepping env had in front of step t; needs
+        auto_reset's obs_in), and the namespace gains resets [E] i32 and pushed [K] i32 (rows with obj_cnt >= 0)."""
         import types
         assert actions.dtype == torch.float64 and actions.is_contiguous() and actions.dim() == 3
         K, NT = int(actions.shape[0]), self.n_envs * self.max_robots
@@ -174,6 +211,9 @@ class DeviceEnvBatch:
             assert noise.dtype == torch.float64 and noise.is_contiguous()
             assert noise.numel() == K * NT * (self.max_obs + self.max_robots) * 5
         specs = self._record_specs()
+        ar = pushed = resets = None
+        if auto_reset is not None:
+            ar, pushed, resets = self._auto_reset("rollout", auto_reset, K, specs)
         rec, steps_run = self._records("rollout", keep, K, specs, trainer_deactivate)
         ctl = _abi.AsvStepCtl()
         ctl.is_continuous = int(bool(is_continuous))
@@ -190,11 +230,19 @@ class DeviceEnvBatch:
         ro.actions = actions.data_ptr()
         ro.noise = noise.data_ptr() if noise is not None else None
         for name, t in rec.items():
-            setattr(ro, name, t.data_ptr())
+            if name != "obs_prev":
+                setattr(ro, name, t.data_ptr())
         ro.steps_run = steps_run.data_ptr()
         st = self.state_struct()
         out = self.out_struct(obs, obj_cnt, with_env_done=trainer_deactivate)
         ln = C.byref(_abi.AsvEnvLaunch(*(int(v) for v in launch))) if launch is not None else None
+        if ar is not None:
+            ar.obs_prev = rec["obs_prev"].data_ptr() if "obs_prev" in rec else None
+            rc = _abi.lib().asvrl_env_rollout_ar(C.byref(self.params), C.byref(st), C.byref(ctl), C.byref(out),
+                                                 C.byref(ro), C.byref(ar), ln, _abi.stream_ptr(stream))
+            _abi.check(rc, "asvrl_env_rollout_ar")
+            return types.SimpleNamespace(steps_run=steps_run, resets=resets, pushed=pushed,
+                                         **{n: rec.get(n) for n in specs})
         rc = _abi.lib().asvrl_env_rollout(C.byref(self.params), C.byref(st), C.byref(ctl), C.byref(out), C.byref(ro),
                                           ln, _abi.stream_ptr(stream))
         _abi.check(rc, "asvrl_env_rollout")
@@ -203,7 +251,7 @@ class DeviceEnvBatch:
     def policy_rollout(self, pack, K, obs_in, *, noise=None, keep=("reward", "done", "info"), hold_done=False,
                        step_dev=None, eps=(1.0, 1.0, 1.0, 0.0, 0.0), policy_seed=0, trainer_deactivate=False, seed=0,
                        counter=0, counter_dev=None, gamma=0.0, env_mask=None, obs=None, obj_cnt=None,
-                       fast_noise=False, launch=None, stream=None):
+                       fast_noise=False, launch=None, stream=None, auto_reset=None):
         """asvrl_policy_rollout: K closed-loop steps in one launch -- the AC-IQN Actor of `pack` (an MlpPack of
         kind "actor") acts on every robot row and the env steps on its actions, bit for bit the K rounds of
         fused_mlp.actor_act(pack, obs, act64, step, *eps, policy_seed) at step = step_dev + t followed by
@@ -213,7 +261,9 @@ class DeviceEnvBatch:
         only read. keep, noise, hold_done and the remaining arguments are rollout()'s; keep also takes "actions":
         f64 [K, E*R, 2], the action every robot slot of a stepping env was given (rows of steps an env did not
         take stay 0). The call goes to pack.L, so an f32 pack runs the f32-operand build. No host sync; with every
-        record passed in by the caller (and steps_run) the call can be graph-captured."""
+        record passed in by the caller (and steps_run) the call can be graph-captured.
+        auto_reset (asvrl_policy_rollout_ar): as rollout()'s; the Actor acts on a reset env's reset observation at the
+        next step, and "obs_prev" records the rows it acted on at every step (obs_in comes from this call's own)."""
         import types
         K, NT = int(K), self.n_envs * self.max_robots
         assert pack.kind == "actor"
@@ -225,6 +275,10 @@ class DeviceEnvBatch:
             assert step_dev.dtype == torch.int64 and step_dev.numel() >= 1
         specs = self._record_specs()
         specs["actions"] = ((NT, 2), torch.float64, 0)
+        ar = pushed = resets = None
+        if auto_reset is not None:
+            ar, pushed, resets = self._auto_reset("policy_rollout", auto_reset, K, specs)
+            ar.obs_in = None
         rec, steps_run = self._records("policy_rollout", keep, K, specs, trainer_deactivate)
         ctl = _abi.AsvStepCtl()
         ctl.is_continuous = 1
@@ -240,7 +294,7 @@ class DeviceEnvBatch:
         ro.n_steps, ro.hold_done = K, int(bool(hold_done))
         ro.noise = noise.data_ptr() if noise is not None else None
         for name, t in rec.items():
-            if name != "actions":
+            if name not in ("actions", "obs_prev"):
                 setattr(ro, name, t.data_ptr())
         ro.steps_run = steps_run.data_ptr()
         pi = _abi.AsvPolicy()
@@ -254,6 +308,13 @@ class DeviceEnvBatch:
         st = self.state_struct()
         out = self.out_struct(obs, obj_cnt, with_env_done=trainer_deactivate)
         ln = C.byref(_abi.AsvEnvLaunch(*(int(v) for v in launch))) if launch is not None else None
+        if ar is not None:
+            ar.obs_prev = rec["obs_prev"].data_ptr() if "obs_prev" in rec else None
+            rc = pack.L.asvrl_policy_rollout_ar(C.byref(self.params), C.byref(st), C.byref(ctl), C.byref(out),
+                                                C.byref(ro), C.byref(pi), C.byref(ar), ln, _abi.stream_ptr(stream))
+            _abi.check(rc, "asvrl_policy_rollout_ar", pack.L)
+            return types.SimpleNamespace(steps_run=steps_run, resets=resets, pushed=pushed,
+                                         **{n: rec.get(n) for n in specs})
         rc = pack.L.asvrl_policy_rollout(C.byref(self.params), C.byref(st), C.byref(ctl), C.byref(out), C.byref(ro),
                                          C.byref(pi), ln, _abi.stream_ptr(stream))
         _abi.check(rc, "asvrl_policy_rollout", pack.L)

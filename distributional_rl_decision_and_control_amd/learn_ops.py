@@ -88,6 +88,7 @@ class DeviceReplay:
         self.ring = torch.zeros((self.capacity, TR_DIM), dtype=torch.float32, device=self.device)
         self.state = torch.zeros(2, dtype=torch.int64, device=self.device)  # head, size
         self._work = None
+        self._work_w = None   # push_window's scratch
         self._n_host = 0  # host mirror for the compat path (exact when fed by add())
 
     def push(self, obs_prev, obs_next, obj_cnt_next, actions, reward, done, stream=None, snap=None,
@@ -110,6 +111,37 @@ class DeviceReplay:
                                              _abi.ptr(self._work), _abi.ptr(snap), _abi.ptr(counter_inc),
                                              _abi.stream_ptr(stream))
         _abi.check(rc, "asvrl_replay_push")
+
+    def push_window(self, records, K, pushed=None, stream=None, snap=None, counter_inc=None, counter_by=None):
+        """The push of a whole K-step window in one call (asvrl_replay_push_window): the ring and {head, size} of K
+        push() calls on rows t = 0..K-1. records: a dict or namespace of the window's [K, n, ...] records obs_prev,
+        obs (the next observation), obj_cnt, actions ([K, n, 1 or 2] f64), reward, done, as a rollout with
+        auto_reset keeps them. pushed: i32 [K], the rows of every step with obj_cnt >= 0 (the rollout's own count),
+        or None (a pre-pass of K blocks counts them). counter_inc is advanced by counter_by (default K)."""
+        get = records.get if isinstance(records, dict) else (lambda k: getattr(records, k))
+        obs_prev, obs_next, cnt, actions, reward, done = (get(k) for k in ("obs_prev", "obs", "obj_cnt", "actions",
+                                                                            "reward", "done"))
+        K = int(K)
+        n = obs_prev.shape[1]
+        for t in (obs_prev, obs_next, cnt, actions, reward, done):
+            assert t.is_contiguous() and t.shape[0] == K and t.shape[1] == n
+        assert obs_prev.dtype == torch.float32 and obs_next.dtype == torch.float32 and cnt.dtype == torch.int8
+        assert actions.dtype == torch.float64 and reward.dtype == torch.float64 and done.dtype == torch.uint8
+        if K * n > self.capacity:
+            raise ValueError(f"push_window: {K} x {n} rows exceed the ring's capacity {self.capacity}")
+        adim = 1 if actions.dim() == 2 else min(actions.shape[2], 2)
+        ald = 1 if actions.dim() == 2 else actions.shape[2]
+        if pushed is not None:
+            assert pushed.dtype == torch.int32 and pushed.numel() == K and pushed.is_contiguous()
+        if self._work_w is None or self._work_w.numel() < K + 2:
+            self._work_w = torch.zeros(K + 2, dtype=torch.int32, device=self.device)
+        rc = _abi.lib().asvrl_replay_push_window(_abi.ptr(obs_prev), _abi.ptr(obs_next), _abi.ptr(cnt),
+                                                 _abi.ptr(actions), adim, ald, _abi.ptr(reward), _abi.ptr(done), n, K,
+                                                 _abi.ptr(pushed), _abi.ptr(self.ring), self.capacity,
+                                                 _abi.ptr(self.state), _abi.ptr(self._work_w), _abi.ptr(snap),
+                                                 _abi.ptr(counter_inc), int(K if counter_by is None else counter_by),
+                                                 _abi.stream_ptr(stream))
+        _abi.check(rc, "asvrl_replay_push_window")
 
     def write_rows(self, rows, slots, stream=None):
         rc = _abi.lib().asvrl_replay_write_rows(_abi.ptr(rows), _abi.ptr(slots), rows.shape[0], _abi.ptr(self.ring),

@@ -90,35 +90,60 @@ class VecMarineNavEnv:
                         obj_cnt=self.cnt_next, fast_noise=True,   # f32 Philox draws (noise_mode 2)
                         launch=self._launch())
 
-    def rollout(self, actions, hold_done=True, keep=("reward", "done", "info")):
+    def _auto_reset(self, auto_reset, open_loop):
+        """DeviceEnvBatch's auto_reset description from this env's own: cfg, and the keys auto_reset() uses -- with
+        the device counter at c at the window's start the reset after step t is keyed at 0x40000000 + c + t and its
+        observation at 0x80000000 + c + t, what step; push (+1); auto_reset(counted=True) key them at. auto_reset:
+        False / None, True, or a dict of the caller's own pushed / resets tensors (graph capture)."""
+        if not auto_reset:
+            return None
+        ar = dict(auto_reset) if isinstance(auto_reset, dict) else {}
+        ar.update(cfg=self.cfg, reset_counter=0x40000000, obs_counter=0x80000000)
+        if open_loop:
+            ar["obs_in"] = self.obs_cur
+        return ar
+
+    def rollout(self, actions, hold_done=True, keep=("reward", "done", "info"), auto_reset=False, count=True):
         """K = actions.shape[0] open-loop steps in one launch (DeviceEnvBatch.rollout): the values of K rounds of
         step(actions[t]); advance_device(), with the last step's observation in obs_next / cnt_next and the step
         counter advanced by K on the device (so follow with auto_reset(counted=True) and
         advance_device(counted=True)). hold_done: an env stops after the step that ends its episode, so
-        auto_reset after the call resets exactly the envs that ended. Returns the kept per-step records."""
-        rec = self.batch.rollout(actions, keep=keep, hold_done=hold_done, is_continuous=self.is_continuous,
+        auto_reset after the call resets exactly the envs that ended. Returns the kept per-step records.
+        auto_reset (see _auto_reset): ended envs restart inside the window with this env's cfg and the keys of
+        auto_reset(), so the call is K rounds of step(actions[t]); auto_reset(); advance_device() (nothing is held:
+        hold_done is ignored; follow with advance_device(counted=True) only). keep then also takes "obs_prev" and the
+        records gain resets and pushed. count=False leaves the step counter to the caller (a window push that
+        advances it by K)."""
+        ar = self._auto_reset(auto_reset, True)
+        rec = self.batch.rollout(actions, keep=keep, hold_done=hold_done and ar is None,
+                                 is_continuous=self.is_continuous,
                                  trainer_deactivate=True, seed=self.seed, counter=0, counter_dev=self.counter,
                                  gamma=self.gamma, obs=self.obs_next, obj_cnt=self.cnt_next, fast_noise=True,
-                                 launch=self._launch())
-        self.counter += int(actions.shape[0])
+                                 launch=self._launch(), auto_reset=ar)
+        if count:
+            self.counter += int(actions.shape[0])
         return rec
 
     def policy_rollout(self, pack, K, hold_done=True, keep=("reward", "done", "info"), eps=(1.0, 1.0, 1.0, 0.0, 0.0),
-                       policy_seed=0, env_mask=None):
+                       policy_seed=0, env_mask=None, auto_reset=False, count=True):
         """K closed-loop steps in one launch (DeviceEnvBatch.policy_rollout): the AC-IQN Actor of `pack` acts on
         obs_cur and every next observation -- the values of K rounds of fused_mlp.actor_act(pack, obs_cur, actions,
         counter, *eps, policy_seed); step(actions); advance_device(), with the last step's observation in obs_next /
         cnt_next and the step counter advanced by K on the device. eps: the linear epsilon schedule over the step
         counter (the default is greedy). The contract is otherwise rollout()'s. Returns the kept per-step records
-        (keep also takes "actions")."""
+        (keep also takes "actions"). auto_reset, count: as rollout()'s (the Actor acts on a reset env's reset
+        observation at the next step)."""
         if not self.is_continuous:
             raise ValueError("policy_rollout: the Actor drives continuous-action envs")
-        rec = self.batch.policy_rollout(pack, K, self.obs_cur, keep=keep, hold_done=hold_done, step_dev=self.counter,
+        ar = self._auto_reset(auto_reset, False)
+        rec = self.batch.policy_rollout(pack, K, self.obs_cur, keep=keep, hold_done=hold_done and ar is None,
+                                        step_dev=self.counter,
                                         eps=eps, policy_seed=policy_seed, trainer_deactivate=True, seed=self.seed,
                                         counter=0, counter_dev=self.counter, gamma=self.gamma, env_mask=env_mask,
                                         obs=self.obs_next, obj_cnt=self.cnt_next, fast_noise=True,
-                                        launch=self._launch())
-        self.counter += int(K)
+                                        launch=self._launch(), auto_reset=ar)
+        if count:
+            self.counter += int(K)
         return rec
 
     def _launch(self):

@@ -260,6 +260,49 @@ class VecTrainer:
         self.env.auto_reset(counted)
         self.env.advance_device(counted)
 
+    def _collect_buffers(self, K):
+        """collect(K)'s records, allocated once per window length."""
+        bufs = getattr(self, "_collect_bufs", None)
+        if bufs is None:
+            bufs = self._collect_bufs = {}
+        if K not in bufs:
+            NT, dev = self.E * self.R, self.device
+            bufs[K] = dict(
+                obs=torch.zeros((K, NT, 40), dtype=torch.float32, device=dev),
+                obs_prev=torch.zeros((K, NT, 40), dtype=torch.float32, device=dev),
+                obj_cnt=torch.full((K, NT), -1, dtype=torch.int8, device=dev),
+                reward=torch.zeros((K, NT), dtype=torch.float64, device=dev),
+                done=torch.ones((K, NT), dtype=torch.uint8, device=dev),
+                actions=torch.zeros((K, NT, 2), dtype=torch.float64, device=dev),
+                steps_run=torch.zeros(self.E, dtype=torch.int32, device=dev),
+                pushed=torch.zeros(K, dtype=torch.int32, device=dev),
+                resets=torch.zeros(self.E, dtype=torch.int32, device=dev))
+        return bufs[K]
+
+    @torch.no_grad()
+    def collect(self, K, snap=None):
+        """K calls of rollout() in two launches, bit for bit: one closed-loop window of K steps with the training
+        epsilon schedule and seed of act(), ended envs restarting inside it (VecMarineNavEnv.policy_rollout with
+        auto_reset), recorded into persistent buffers, then one push of the whole window into the uniform ring
+        (DeviceReplay.push_window), which also advances the step counter by K. No host sync: the call can be
+        graph-captured. Returns the window's records (views of the persistent buffers: obs, obs_prev, obj_cnt,
+        reward, done, actions, steps_run, pushed, resets). AC-IQN with the uniform ring only; the caller accounts for
+        the host-side step count (env.advance_host() per step) as iteration() does."""
+        if self.fused2 is None or self.per is not None:
+            raise NotImplementedError("collect runs the AC-IQN actor and pushes into the uniform ring; IQN and Rainbow "
+                                      "act inside their own kernels")
+        K = int(K)
+        buf = self._collect_buffers(K)
+        buf["obj_cnt"].fill_(-1)   # a row no env took is never pushed
+        keep = {k: buf[k] for k in ("obs", "obs_prev", "obj_cnt", "reward", "done", "actions", "steps_run")}
+        rec = self.env.policy_rollout(self.fused2.actor, K, hold_done=False, keep=keep,
+                                      eps=(self.E, self.total_timesteps, self.exploration_fraction, self.initial_eps,
+                                           self.final_eps), policy_seed=self.seed + 4242,
+                                      auto_reset=dict(pushed=buf["pushed"], resets=buf["resets"]), count=False)
+        self.replay.push_window(buf, K, pushed=buf["pushed"], snap=snap, counter_inc=self.env.counter, counter_by=K)
+        self.env.advance_device(True)
+        return rec
+
     def learn(self, state=None, guard=0, actor_wait=None, target_wait=None, actor_done=None):
         """One learn step of batch B: sample (uniform ring, or the prioritised tree for Rainbow) and the
         agent's fused update. state / guard: the ring snapshot to sample against and the newest entries to

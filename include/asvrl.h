@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define ASVRL_ABI_VERSION 28
+#define ASVRL_ABI_VERSION 29
 
 #define ASVRL_SELF_DIM 7   /* wamv.py:443-453 self observation */
 #define ASVRL_OBJ_DIM 5    /* wamv.py:481,508 [px, py, vx, vy, r] */
@@ -1033,6 +1033,55 @@ int asvrl_policy_rollout(const AsvParams* params, const AsvEnvState* state, cons
                          const AsvEnvLaunch* launch /* NULL: automatic */, void* stream);
 /* sizeof(AsvPolicy) as compiled. */
 int64_t asvrl_policy_struct_size(void);
+
+/* ---------------------------------------------------------------- auto-reset inside rollout windows (ABI 29) */
+
+/* Episodes restart inside a K-step window. After step t has written its outputs and records, every stepping env
+ * whose env_done the step set is reset by asvrl_env_reset's sampler (cfg, ctl->seed, the draws keyed at
+ * reset_counter + t + *ctl->counter_dev) and observed by the masked do_dynamics = 0 pass (ctl's noise_mode and
+ * seed, gamma 0, keyed at obs_counter + t + *ctl->counter_dev), which writes `last` (obs, obs64, obj_cnt, reward,
+ * done, info: what asvrl_env_reset_observe writes) and, in the closed loop, the row the Actor reads at step t + 1.
+ * The records of row t keep the step's values. Bit for bit the composed loop: per step the act (closed loop),
+ * asvrl_env_step_ex at counter + t, then asvrl_env_reset_observe on last->env_done AND ctl->env_mask. */
+typedef struct AsvAutoReset {
+  AsvResetCfg cfg;
+  uint64_t reset_counter, obs_counter;   /* + t (+ *ctl->counter_dev) */
+  const float* obs_in;   /* open loop: [NT][ASVRL_OBS_DIM] the rows in front of step 0 (needed for obs_prev);
+                            closed loop: NULL (pi->obs_in is used) */
+  float* obs_prev;       /* optional record [K][NT][ASVRL_OBS_DIM]: row t is the observation every robot row of a
+                            stepping env had in front of step t (row 0: obs_in; row t > 0: what step t - 1, or its
+                            reset, left); rows of envs that do not step are not written */
+  int32_t* pushed;       /* optional [K]: per step, the rows of stepping envs with obj_cnt >= 0 are ADDED (integer
+                            atomics): the caller zeroes it */
+  int32_t* resets;       /* optional [n_envs]: resets of every env in the window (zeroed by the call) */
+} AsvAutoReset;
+
+/* asvrl_env_rollout / asvrl_policy_rollout with the auto-reset above in the step loop (one launch; per-robot
+ * parameters, layout 2 and a carve that does not fit run K x the single launches, the reset launches and a small
+ * record launch, with the same results). Needs ctl->trainer_deactivate, last->env_done, Philox noise (noise_mode 1
+ * or 2: recorded noise cannot cover a sampled reset) and no ro->hold_done; cfg's counts and the batch's max_robots /
+ * max_obs / max_cores within asvrl_env_reset's tables (32 robots, 32 obstacles, 16 cores). Everything else is the
+ * two calls' own contract. */
+int asvrl_env_rollout_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                         const AsvStepOut* last, const AsvRollout* ro, const AsvAutoReset* ar,
+                         const AsvEnvLaunch* launch /* NULL: automatic */, void* stream);
+int asvrl_policy_rollout_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                            const AsvStepOut* last, const AsvRollout* ro, const AsvPolicy* pi,
+                            const AsvAutoReset* ar, const AsvEnvLaunch* launch /* NULL: automatic */, void* stream);
+/* sizeof(AsvAutoReset) as compiled. */
+int64_t asvrl_autoreset_struct_size(void);
+
+/* The replay push of a whole window in one call: the rows of K steps (row t * n + k of every array; actions
+ * [K * n][action_ld] f64) go into the ring in step-major, then row order, rows with obj_cnt_next < 0 skipped --
+ * the ring bytes and {head, size} of K calls of asvrl_replay_push_ex on rows t = 0..K-1. A block counts only inside
+ * its own step and takes the step's base from the K per-step counts: `pushed` ([K], e.g. AsvAutoReset.pushed), or,
+ * when it is NULL, a pre-pass of K blocks that counts them into `work`. work: zeroed int32[2 + K], left zeroed in
+ * its first two. snap as asvrl_replay_push_ex; *counter_inc += counter_by. K * n <= capacity. */
+int asvrl_replay_push_window(const float* obs_prev, const float* obs_next, const int8_t* obj_cnt_next,
+                             const double* actions, int32_t action_dim, int64_t action_ld, const double* reward,
+                             const uint8_t* done, int32_t n, int32_t K, const int32_t* pushed, float* ring,
+                             int64_t capacity, int64_t* ring_state, int32_t* work, int64_t* snap,
+                             int64_t* counter_inc, int64_t counter_by, void* stream);
 
 /* ---------------------------------------------------------------- misc */
 const char* asvrl_last_error(void);
