@@ -197,6 +197,12 @@ class AsvAutoReset(C.Structure):
                 ("obs_prev", _VP), ("pushed", _VP), ("resets", _VP)]
 
 
+class AsvEvalMetrics(C.Structure):
+    _fields_ = [("n_steps", _I32), ("n_envs", _I32), ("max_robots", _I32), ("episode_limit", _I32), ("gamma", _D)] + \
+               [(n, _VP) for n in ("reward", "info", "rs", "steps_run", "n_robots", "dt", "N", "pc", "length", "ended",
+                                   "alive", "deact", "outcome", "ret", "time", "energy")]
+
+
 class AsvSampleArgs(C.Structure):
     _fields_ = [("ring", _VP), ("capacity", _I64), ("ring_state", _VP), ("seed", _U64), ("counter", _U64),
                 ("counter_dev", _VP), ("guard", _I64), ("B", _I32), ("tau_sets", _I32), ("tau_n", _I32),
@@ -365,6 +371,8 @@ EXPORTS = [
     ("asvrl_autoreset_struct_size", _I64, []),
     ("asvrl_replay_push_window", C.c_int, [_VP, _VP, _VP, _VP, _I32, _I64, _VP, _VP, _I32, _I32, _VP, _VP, _I64, _VP,
                                            _VP, _VP, _VP, _I64, _VP]),
+    ("asvrl_eval_metrics", C.c_int, [C.POINTER(AsvEvalMetrics), _VP]),
+    ("asvrl_eval_metrics_struct_size", _I64, []),
 ]
 
 _libs = {}

@@ -1,0 +1,281 @@
+"""Trainer.evaluation (trainer.py:266-392) resident on the device.
+
+policy/batched_eval.evaluate_configs advances every eval config together, but through the Python MarineNavEnv3
+objects: per step one torch policy call, one env-step launch with an upload and a download, one host wait and the
+per-robot bookkeeping in Python. DeviceEvaluator keeps the same episodes in DeviceEnvBatches:
+
+  * the configs are parsed once, exactly as evaluate_configs parses them (MarineNavEnv3.reset_with_eval_config on a
+    copy of the template env's curriculum attributes), grouped by env_key(), and each group's host image (robot
+    state, flags, counts, obstacles, cores; set_batch_params for the launch parameters) is loaded into one batch;
+    a device copy of that state is kept, so every later evaluation restores by copy;
+  * an evaluation is the observation pass and then closed-loop windows of `chunk` steps, one launch each
+    (DeviceEnvBatch.policy_rollout with hold_done, the greedy Actor of an MlpPack), or, teacher-forced, open-loop
+    windows over a caller's action table (DeviceEnvBatch.rollout);
+  * behind every window one asvrl_eval_metrics launch folds the window's records into the evaluation's carried
+    state by trainer.py:286-303: discounted return, time, energy, deactivation, and the evaluation's end rule (the
+    step limit, ANY collision, or every robot deactivated). Its `alive` output is the next window's env_mask;
+  * one copy at the end brings the per-robot sums, outcomes and lengths to the host.
+
+Perception noise in the closed loop is the rollout's Philox stream (seed, env, robot, step; f32 draws), not each
+robot's numpy RandomState: the results agree with evaluate_configs in distribution, and exactly under teacher
+forcing with the noise given (tests/test_device_eval_gpu.py). Observation, action and trajectory histories are not
+kept.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from .. import _abi
+from ..device_env import DeviceEnvBatch
+from ..envs.marinenav.env import MarineNavEnv3, set_batch_params
+
+RECORDS = ("reward", "info", "rs")
+OBS_COUNTER = 0x80000000   # the observation pass's Philox counter (VecMarineNavEnv.reset's); step t draws at t
+
+
+def eval_metrics(L, K, E, R, rec, n_robots, dt, N, pc, state, gamma, episode_limit, stream=None):
+    """asvrl_eval_metrics of library L on one window: rec has reward [K, NT] f64, info [K, NT] u8, rs [K, 17, NT]
+    f64 and steps_run [E] i32; state has length, ended, alive, deact, outcome, ret, time, energy (updated in
+    place)."""
+    NT = E * R
+    m = _abi.AsvEvalMetrics()
+    m.n_steps, m.n_envs, m.max_robots, m.episode_limit = int(K), int(E), int(R), int(episode_limit)
+    m.gamma = float(gamma)
+    shapes = dict(reward=((K, NT), torch.float64), info=((K, NT), torch.uint8),
+                  rs=((K, _abi.NUM_FIELDS, NT), torch.float64), steps_run=((E,), torch.int32),
+                  n_robots=((E,), torch.int32), dt=((NT,), torch.float64), N=((NT,), torch.float64),
+                  pc=((NT,), torch.float64), length=((E,), torch.int32), ended=((E,), torch.uint8),
+                  alive=((E,), torch.uint8), deact=((NT,), torch.uint8), outcome=((NT,), torch.uint8),
+                  ret=((NT,), torch.float64), time=((NT,), torch.float64), energy=((NT,), torch.float64))
+    given = dict(n_robots=n_robots, dt=dt, N=N, pc=pc)
+    for name, (shape, dtype) in shapes.items():
+        t = given[name] if name in given else (rec[name] if name in ("reward", "info", "rs", "steps_run")
+                                               else state[name])
+        assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape, name
+        setattr(m, name, t.data_ptr())
+    rc = L.asvrl_eval_metrics(C.byref(m), _abi.stream_ptr(stream))
+    _abi.check(rc, "asvrl_eval_metrics", L)
+
+
+def new_metrics_state(E, R, device):
+    """The carried state of asvrl_eval_metrics before the first window."""
+    NT = E * R
+    u8 = dict(dtype=torch.uint8, device=device)
+    f64 = dict(dtype=torch.float64, device=device)
+    return dict(length=torch.zeros(E, dtype=torch.int32, device=device), ended=torch.zeros(E, **u8),
+                alive=torch.ones(E, **u8), deact=torch.zeros(NT, **u8), outcome=torch.zeros(NT, **u8),
+                ret=torch.zeros(NT, **f64), time=torch.zeros(NT, **f64), energy=torch.zeros(NT, **f64))
+
+
+class _Group:
+    """The configs that share env-level parameters: one DeviceEnvBatch, its initial state and carried metrics."""
+
+    def __init__(self, members, envs, device):
+        self.members = members
+        self.envs = envs
+        E = len(envs)
+        R = max(max(len(env.robots) for env in envs), 1)
+        O = max(max(len(env.obstacles) for env in envs), 1)
+        Cm = max(max(len(env.cores) for env in envs), 1)
+        b = self.batch = DeviceEnvBatch(E, R, O, Cm, device=device, obs64=True)
+        set_batch_params(b, envs)
+        NT = E * R
+        rs = np.zeros((_abi.NUM_FIELDS, NT))
+        fl = np.zeros(NT, np.uint8)
+        cnt = np.zeros((3, E), np.int32)
+        obst = np.zeros((E, O, 3))
+        cores = np.zeros((E, Cm, 4))
+        per = np.zeros((3, NT))
+        for e, env in enumerate(envs):
+            pk = env._pack(None, True, R, O, Cm)   # the host image one env-step launch uploads
+            sl = slice(e * R, (e + 1) * R)
+            rs[:, sl], fl[sl] = pk["rs"], pk["fl"]
+            cnt[:, e] = (pk["n"], pk["n_obs"], pk["n_cores"])
+            obst[e], cores[e] = pk["obst"], pk["cores"]
+            for i, rob in enumerate(env.robots):
+                per[:, e * R + i] = (rob.dt, rob.N, rob.power_coefficient)
+        self.host = dict(rs=rs, rflags=fl, n_robots=cnt[0], n_obs=cnt[1], n_cores=cnt[2], obstacles=obst,
+                         cores=cores)
+        for name, a in self.host.items():
+            getattr(b, name).copy_(torch.from_numpy(np.ascontiguousarray(a)))
+        b.ep_ts.zero_()
+        self.initial = dict(rs=b.rs.clone(), rflags=b.rflags.clone())
+        self.dt, self.N, self.pc = (torch.from_numpy(per[k].copy()).to(device) for k in range(3))
+        self.state = new_metrics_state(E, R, device)
+        self.step = torch.zeros(1, dtype=torch.int64, device=device)
+        self._rec = {}
+
+    def restore(self):
+        b = self.batch
+        b.rs.copy_(self.initial["rs"])
+        b.rflags.copy_(self.initial["rflags"])
+        b.ep_ts.zero_()
+        b.stats.zero_()
+        for name, t in self.state.items():
+            t.fill_(1) if name == "alive" else t.zero_()
+
+    def records(self, K):
+        """The window's records, allocated once per window length. Rows an env does not take keep whatever an
+        earlier window left: asvrl_eval_metrics reads no row at or behind steps_run."""
+        rec = self._rec.get(K)
+        if rec is None:
+            b = self.batch
+            specs = b._record_specs()
+            rec = {n: torch.full((K,) + specs[n][0], specs[n][2], dtype=specs[n][1], device=b.device)
+                   for n in RECORDS}
+            rec["steps_run"] = torch.zeros(b.n_envs, dtype=torch.int32, device=b.device)
+            self._rec[K] = rec
+        return rec
+
+
+class DeviceEvaluator:
+    def __init__(self, configs, template_env=None, device=None, chunk=64, gamma=0.99):
+        """configs: the eval configs (MarineNavEnv3.episode_data); template_env: the eval env whose current
+        curriculum attributes seed the robots (evaluate_configs' argument); chunk: steps per window; gamma: the
+        discount of the returns (agent.GAMMA)."""
+        dev = torch.device(device) if device is not None else (template_env._device if template_env is not None
+                                                               else torch.device("cuda"))
+        if int(chunk) < 1:
+            raise ValueError("chunk must be >= 1")
+        self.device, self.chunk, self.gamma = dev, int(chunk), float(gamma)
+        self.envs, self.initial_states = [], []
+        for cfg in configs:
+            env = MarineNavEnv3(seed=0, is_eval_env=True, device=dev)
+            if template_env is not None:   # evaluate_configs: env.py:569 seeds robots from the CURRENT attributes
+                for k in ("num_robots", "num_cores", "num_obs", "min_start_goal_dis"):
+                    setattr(env, k, getattr(template_env, k))
+            st, _, _ = env.reset_with_eval_config(cfg)
+            self.envs.append(env)
+            self.initial_states.append(st)
+        self.n_robots = [len(env.robots) for env in self.envs]
+        by_key = {}
+        for e, env in enumerate(self.envs):
+            by_key.setdefault(env.env_key(), []).append(e)
+        self.groups = [_Group(members, [self.envs[e] for e in members], dev) for members in by_key.values()]
+        self.windows = 0       # windows of the last run
+        self.steps = 0         # env-steps the last run enqueued per env, at most
+
+    # ------------------------------------------------------------------ pieces
+    def rows(self, config):
+        """(group index, first row) of a config's robots in its group's batch."""
+        for g, grp in enumerate(self.groups):
+            if config in grp.members:
+                return g, grp.members.index(config) * grp.batch.max_robots
+        raise IndexError(config)
+
+    def zero_noise(self, T=None):
+        """Explicit zero perception noise for every group: [T, NT, O + R, 5] f64 (T None: one pass)."""
+        out = []
+        for grp in self.groups:
+            b = grp.batch
+            shape = (b.n_envs * b.max_robots, b.max_obs + b.max_robots, 5)
+            out.append(torch.zeros(shape if T is None else (int(T),) + shape, dtype=torch.float64, device=self.device))
+        return out
+
+    def _per_group(self, x, what):
+        if x is None:
+            return [None] * len(self.groups)
+        if torch.is_tensor(x):
+            if len(self.groups) != 1:
+                raise ValueError(f"{what}: {len(self.groups)} parameter groups need a list, one tensor per group")
+            return [x]
+        if len(x) != len(self.groups):
+            raise ValueError(f"{what}: {len(x)} tensors for {len(self.groups)} parameter groups")
+        return list(x)
+
+    def observe(self, noise=None, seed=0):
+        """Restore the initial state, zero the carried metrics and run the observation pass (the do_dynamics = 0
+        step of VecMarineNavEnv.reset) into every batch's obs / obs64 / obj_cnt. noise: explicit draws per group
+        ([NT, O + R, 5] f64) instead of the Philox stream."""
+        noise = self._per_group(noise, "observe noise")
+        for g, grp in enumerate(self.groups):
+            grp.restore()
+            grp.batch.step(None, do_dynamics=False, noise=noise[g], seed=seed + g, counter=OBS_COUNTER,
+                           fast_noise=True)
+
+    @torch.no_grad()
+    def run(self, pack=None, *, actions=None, noise=None, obs_noise=None, seed=0, episode_limit=1000, sync=True):
+        """One evaluation of every config. pack: the Actor's MlpPack, greedy in closed-loop windows; or actions: a
+        [T, NT, 2] f64 table per group (a tensor when there is one group, else a list) applied open loop, with
+        noise ([T, NT, O + R, 5] f64 per group) or the Philox stream. obs_noise: the observation pass's explicit
+        draws. sync: one host wait per window to stop once every episode has ended; False enqueues the
+        ceil((episode_limit + 1) / chunk) windows without a host wait. Returns evaluate_configs' per-config lists
+        (rewards, successes, times, energies, lengths; observations / actions / trajectories / relations empty per
+        robot) and the per-robot arrays robot_rewards, robot_times, robot_energies, robot_outcomes (0 running at
+        the end, 1 goal, 2 collision)."""
+        if (pack is None) == (actions is None):
+            raise ValueError("run takes the Actor's pack or an action table, not both")
+        if pack is not None and pack.kind != "actor":
+            raise ValueError("run: pack must be an MlpPack of kind 'actor'")
+        episode_limit = int(episode_limit)
+        actions = self._per_group(actions, "actions")
+        noise = self._per_group(noise, "noise")
+        total = episode_limit + 1
+        if pack is None:
+            T = min(int(a.shape[0]) for a in actions)
+            total = min(total, T)
+        L = pack.L if pack is not None else _abi.lib()
+        self.observe(obs_noise, seed)
+        t0 = self.windows = 0
+        while t0 < total:
+            k = min(self.chunk, total - t0)
+            for g, grp in enumerate(self.groups):
+                b, st = grp.batch, grp.state
+                rec = grp.records(k)
+                if pack is not None:
+                    grp.step.fill_(t0)
+                    b.policy_rollout(pack, k, b.obs, keep=rec, hold_done=True, trainer_deactivate=True,
+                                     step_dev=grp.step, env_mask=st["alive"], seed=seed + g, counter=t0,
+                                     fast_noise=True)
+                else:
+                    nz = noise[g]
+                    b.rollout(actions[g][t0:t0 + k], None if nz is None else nz[t0:t0 + k], keep=rec,
+                              hold_done=True, trainer_deactivate=True, env_mask=st["alive"], seed=seed + g,
+                              counter=t0, fast_noise=True)
+                eval_metrics(L, k, b.n_envs, b.max_robots, rec, b.n_robots, grp.dt, grp.N, grp.pc, st, self.gamma,
+                             episode_limit)
+            t0 += k
+            self.windows += 1
+            if sync and not any(bool(grp.state["alive"].any().item()) for grp in self.groups):
+                break   # one host wait per window
+        self.steps = t0
+        return self._result(check_ended=pack is None and total < episode_limit + 1)
+
+    def _result(self, check_ended=False):
+        # one copy: every group's lengths, ended flags, outcomes and sums in one f64 tensor
+        parts = []
+        for grp in self.groups:
+            st = grp.state
+            parts += [st["length"].double(), st["ended"].double(), st["outcome"].double(), st["ret"], st["time"],
+                      st["energy"]]
+        flat = torch.cat(parts).cpu().numpy()
+        n = len(self.envs)
+        out = dict(observations=[None] * n, actions=[None] * n, trajectories=[None] * n, rewards=[None] * n,
+                   successes=[None] * n, times=[None] * n, energies=[None] * n, relations=[None] * n,
+                   lengths=[None] * n, robot_rewards=[None] * n, robot_times=[None] * n, robot_energies=[None] * n,
+                   robot_outcomes=[None] * n)
+        at = 0
+        for grp in self.groups:
+            E, R = grp.batch.n_envs, grp.batch.max_robots
+            NT = E * R
+            length, ended = flat[at:at + E], flat[at + E:at + 2 * E]
+            at += 2 * E
+            outcome, ret, tim, en = (flat[at + q * NT:at + (q + 1) * NT].reshape(E, R) for q in range(4))
+            at += 4 * NT
+            if check_ended and not ended.all():
+                raise ValueError("the action table ran out before every episode ended")
+            for le, c in enumerate(grp.members):
+                k = self.n_robots[c]
+                out["robot_rewards"][c] = ret[le, :k].copy()
+                out["robot_times"][c] = tim[le, :k].copy()
+                out["robot_energies"][c] = en[le, :k].copy()
+                out["robot_outcomes"][c] = outcome[le, :k].astype(np.uint8)
+                out["rewards"][c] = np.mean(ret[le, :k])          # trainer.py:347-365
+                out["successes"][c] = bool((outcome[le, :k] == 1).all())
+                out["times"][c] = np.mean(tim[le, :k])
+                out["energies"][c] = np.mean(en[le, :k])
+                out["lengths"][c] = int(length[le])
+                for name in ("observations", "actions", "trajectories", "relations"):
+                    out[name][c] = [[] for _ in range(k)]
+        return out

@@ -12,6 +12,8 @@ reads only its own keys from it (env.py:75-94). An optional "vectorized" dict in
 (ignored by the reference) makes learn() drive VecTrainer instead: {"n_envs": E, "batch_size": B,
 "num_tau": N, ...} are VecTrainer's keyword arguments. Evaluation, evaluations.npz and the model
 files keep the reference's cadence and format; the trained networks are copied into rl_agent first.
+With "device_eval": true in that dict (AC-IQN) the evaluations run on the device with the batched
+trainer's own actor (evaluation(batched="device"), policy/device_eval.py).
 """
 import json
 import os
@@ -163,6 +165,9 @@ class Trainer:
             raise ValueError(f"vectorized training covers AC-IQN, IQN and Rainbow, not {agent.agent_type}")
         sched = {k: v for k, v in self.train_env.schedule.items() if k != "vectorized"}
         kw = dict(vec)
+        # "device_eval": true evaluates on the device with the batched trainer's own actor (AC-IQN;
+        # evaluation(batched="device")) instead of copying the networks out and stepping the Python eval envs
+        device_eval = bool(kw.pop("device_eval", False)) and agent.agent_type == "AC-IQN"
         kw.setdefault("graphs", True)
         for key, sk in (("num_robots", "num_robots"), ("num_obs", "num_obstacles"), ("num_cores", "num_cores")):
             if sk in sched:
@@ -189,8 +194,8 @@ class Trainer:
             self.current_timestep += tr.E
             if learning and (next_eval is None or self.current_timestep >= next_eval):
                 next_eval = (self.current_timestep // eval_freq + 1) * eval_freq
-                self._sync_agent(tr)
-                self.evaluation()
+                self._sync_agent(tr)   # the checkpoint below saves rl_agent's networks
+                self.evaluation(batched="device" if device_eval else None)
                 self.save_evaluation(eval_log_path)
                 if agent.training:
                     agent.save_latest_model(eval_log_path)
@@ -304,7 +309,19 @@ class Trainer:
 
     def evaluation(self, batched=None):
         batched = self.batched_eval if batched is None else batched
-        if batched:
+        if isinstance(batched, str):
+            if batched != "device":
+                raise ValueError(f"evaluation(batched={batched!r}): True, False or 'device'")
+            tr = getattr(self, "vec_trainer", None)
+            if tr is None:
+                raise RuntimeError("evaluation(batched='device') runs on learn_vectorized's VecTrainer")
+            print(f"Evaluating episodes 0-{len(self.eval_config) - 1} (on the device)")
+            # the batched trainer's own actor on device-resident eval configs (policy/device_eval.py)
+            res = tr.evaluate(self.eval_config, template_env=self.eval_env)
+            obs_d, act_d, traj_d = res["observations"], res["actions"], res["trajectories"]
+            rew_d, succ_d, time_d, en_d, rel_d = (res["rewards"], res["successes"], res["times"], res["energies"],
+                                                  res["relations"])
+        elif batched:
             from .batched_eval import evaluate_configs
             print(f"Evaluating episodes 0-{len(self.eval_config) - 1} (one batch)")
             res = evaluate_configs(self.rl_agent, self.eval_config, template_env=self.eval_env)

@@ -238,6 +238,24 @@ class VecTrainer:
                 break
         return dict(env.episode_stats(), steps_run=steps_run.cpu().numpy())
 
+    @torch.no_grad()
+    def evaluate(self, configs, chunk=64, template_env=None, **kw):
+        """Trainer.evaluation's schedule on the device (policy/device_eval.DeviceEvaluator): the eval `configs`
+        (MarineNavEnv3.episode_data) are loaded into env batches once and cached; every call restores them, runs the
+        current local actor greedily in closed-loop windows of `chunk` steps and reduces the windows to the
+        reference's per-config rewards / successes / times / energies / lengths on the device. kw: run()'s seed,
+        episode_limit and sync. The actor's packed images are the learner's own, so no copy into a drop-in agent is
+        needed; the training env, the replay and the step counter are not touched. AC-IQN only."""
+        if self.fused2 is None:
+            raise NotImplementedError("evaluate runs the AC-IQN actor; IQN and Rainbow act inside their own kernels")
+        from .policy.device_eval import DeviceEvaluator
+        cached = getattr(self, "_dev_eval", None)
+        if cached is None or cached[0] is not configs or cached[1] != (len(configs), int(chunk), template_env):
+            ev = DeviceEvaluator(configs, template_env=template_env, device=self.device, chunk=chunk,
+                                 gamma=self.gamma)
+            cached = self._dev_eval = (configs, (len(configs), int(chunk), template_env), ev)
+        return cached[2].run(self.fused2.actor, **kw)
+
     def _push(self, snap=None):
         """The replay push of every robot that acted; for the uniform ring it is one launch that also
         increments the env step counter (and writes the new ring state to `snap` when given). Returns

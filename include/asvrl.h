@@ -1083,6 +1083,48 @@ int asvrl_replay_push_window(const float* obs_prev, const float* obs_next, const
                              int64_t capacity, int64_t* ring_state, int32_t* work, int64_t* snap,
                              int64_t* counter_inc, int64_t counter_by, void* stream);
 
+/* ---------------------------------------------------------------- evaluation bookkeeping over rollout windows */
+
+/* Trainer.evaluation's per-step bookkeeping (trainer.py:286-303) over the records of one hold_done window, folded
+ * into state that is carried from window to window. For every env with ended == 0 and t = 0 .. steps_run[e] - 1:
+ * each existing robot (slot < n_robots[e]) that is not deact adds pow(gamma, length) * reward to ret, dt * N to time
+ * and pc * |TL| * dt * N + pc * |TR| * dt * N (left to right; the thrusts after the step) to energy; info
+ * ASVRL_INFO_COLLISION / ASVRL_INFO_REACH_GOAL set outcome (2 / 1) and deact; then
+ * end = length >= episode_limit || a robot collided at this step || every existing robot is deact; length += 1;
+ * on end the env is marked ended and the window's later rows of that env are ignored (the rollout steps an env on
+ * after a collision until all its robots are deactivated: ignoring those rows is the evaluation's end rule).
+ * Rows t >= steps_run[e] are never read. alive[e] = !ended[e] is written for every env, ready to be the next
+ * window's env_mask. One launch, no atomics; the caller zeroes the carried state before the first window. */
+typedef struct AsvEvalMetrics {
+  int32_t n_steps;         /* K >= 1, the window's rows */
+  int32_t n_envs;          /* E >= 1 */
+  int32_t max_robots;      /* 1..32; NT = n_envs * max_robots */
+  int32_t episode_limit;   /* trainer.py:297: 1000 */
+  double gamma;
+  /* the window's records and the batch (read only) */
+  const double*  reward;     /* [K][NT] */
+  const uint8_t* info;       /* [K][NT] */
+  const double*  rs;         /* [K][ASVRL_NUM_FIELDS][NT]; only the ASVRL_F_TL and ASVRL_F_TR planes are read */
+  const int32_t* steps_run;  /* [E] */
+  const int32_t* n_robots;   /* [E] */
+  const double*  dt;         /* [NT] every robot row's own dt, N and power coefficient */
+  const double*  N;          /* [NT] */
+  const double*  pc;         /* [NT] */
+  /* carried state (read and written) */
+  int32_t* length;   /* [E] steps the evaluation counted */
+  uint8_t* ended;    /* [E] */
+  uint8_t* alive;    /* [E] written only: !ended */
+  uint8_t* deact;    /* [NT] */
+  uint8_t* outcome;  /* [NT] 0 running, 1 reached its goal, 2 collided */
+  double*  ret;      /* [NT] */
+  double*  time;     /* [NT] */
+  double*  energy;   /* [NT] */
+} AsvEvalMetrics;
+
+int asvrl_eval_metrics(const AsvEvalMetrics* m, void* stream);
+/* sizeof(AsvEvalMetrics) as compiled. */
+int64_t asvrl_eval_metrics_struct_size(void);
+
 /* ---------------------------------------------------------------- misc */
 const char* asvrl_last_error(void);
 int asvrl_abi_version(void);
