@@ -203,6 +203,26 @@ class AsvEvalMetrics(C.Structure):
                                    "alive", "deact", "outcome", "ret", "time", "energy")]
 
 
+DQN_MAX_ACTIONS = 32
+
+
+class AsvDqnWeights(C.Structure):
+    _fields_ = [("trunk", AsvMlpWeights), ("head_frag", _VP), ("n_actions", _I32), ("_pad0", _I32)]
+
+
+class AsvDqnActIO(C.Structure):
+    _fields_ = [("x", _VP), ("ldx", _I64), ("n", _I32), ("_pad0", _I32), ("act_out", _VP), ("ld_act", _I64),
+                ("q_out", _VP), ("step_dev", _VP), ("eps_steps_per_count", _D), ("eps_total", _D),
+                ("eps_fraction", _D), ("eps_initial", _D), ("eps_final", _D), ("seed", _U64)]
+
+
+DQN_GRAD_ARRAYS = ("xb", "h0", "h1", "h2", "q_sel", "q_next", "dz_out", "dz2", "dz1", "dz0", "tile_loss")
+
+
+class AsvDqnGradIO(C.Structure):
+    _fields_ = [("rows", _VP), ("ld_rows", _I64), ("B", _I32), ("gamma", _F)] + [(n, _VP) for n in DQN_GRAD_ARRAYS]
+
+
 class AsvSampleArgs(C.Structure):
     _fields_ = [("ring", _VP), ("capacity", _I64), ("ring_state", _VP), ("seed", _U64), ("counter", _U64),
                 ("counter_dev", _VP), ("guard", _I64), ("B", _I32), ("tau_sets", _I32), ("tau_n", _I32),
@@ -373,6 +393,12 @@ EXPORTS = [
                                            _VP, _VP, _VP, _I64, _VP]),
     ("asvrl_eval_metrics", C.c_int, [C.POINTER(AsvEvalMetrics), _VP]),
     ("asvrl_eval_metrics_struct_size", _I64, []),
+    ("asvrl_dqn_pack", C.c_int, [C.POINTER(AsvMlpSrc), _VP, C.POINTER(AsvDqnWeights), _VP]),
+    ("asvrl_dqn_act", C.c_int, [C.POINTER(AsvDqnWeights), C.POINTER(AsvDqnActIO), _VP]),
+    ("asvrl_dqn_grad", C.c_int, [C.POINTER(AsvDqnWeights), C.POINTER(AsvDqnWeights), C.POINTER(AsvDqnGradIO), _VP]),
+    ("asvrl_dqn_weights_struct_size", _I64, []),
+    ("asvrl_dqn_act_struct_size", _I64, []),
+    ("asvrl_dqn_grad_struct_size", _I64, []),
 ]
 
 _libs = {}

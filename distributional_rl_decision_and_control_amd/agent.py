@@ -15,12 +15,14 @@ save_latest_model / load_model surfaces and return types. Differences:
     of the same operand build, pinned to the reference's train_Rainbow by
     tests/test_rainbow_golden_gpu.py; set_learner("torch") (or network dims the kernels do not take)
     runs learner.rainbow_update (torch autograd + the C51 kernel). Every learner's optimiser: FusedAdam
-    (asvrl_adam_*, pinned to torch.optim.Adam at 1e-5) for AC-IQN / IQN, torch.optim.Adam for Rainbow
-    and DQN;
+    (asvrl_adam_*, pinned to torch.optim.Adam at 1e-5) for AC-IQN / IQN (and DQN on a fused learner),
+    torch.optim.Adam for Rainbow and for DQN's default torch learner;
   * load_model rebuilds the optimizers for the loaded networks (the reference keeps
     optimizing the replaced ones, agent.py:684-698 vs :75-76,98);
-  * DQN runs as the reference's plain torch update (BASELINE config 1 is the DQN plumbing run of
-    train_RL_agents.py); DDPG / SAC (non-distributional baselines) are out of scope and raise.
+  * DQN (BASELINE config 1) starts on the reference's plain torch update; set_learner("fused-f32") /
+    set_learner("fused-bf16") switch train_DQN to the hand-written learner (fused_dqn.dqn_update_fused with
+    FusedAdam, pinned to the reference's train_DQN by tests/test_fused_dqn_gpu.py), set_learner("torch") switches
+    back. DDPG / SAC (non-distributional baselines) are out of scope and raise.
 """
 import copy
 import random
@@ -31,7 +33,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _abi
-from . import fused_iqn, fused_rainbow, fused_update
+from . import fused_dqn, fused_iqn, fused_rainbow, fused_update
 from .learn_ops import rows_from_batch
 from .learner import FlatGrads, FusedAdam, ac_iqn_update, iqn_update, rainbow_update
 from .policy.AC_IQN_model import AC_IQN_Policy
@@ -90,7 +92,8 @@ class Agent:
         self._rb_seed = int(seed) + 999   # the kernel path's target-noise Philox stream
         self.num_tau = 8  # training quantiles N = N' (AC_IQN_model.py:462, IQN_model.py:74)
         self.tau_override = None  # optional list of pre-drawn taus for the next train() (tests)
-        self.learner = "fused-f32"
+        # DQN starts on the torch learner (the reference's update as it stands); set_learner selects the kernels
+        self.learner = "torch" if agent_type == "DQN" else "fused-f32"
         self._fused = None   # (B, N) -> FusedACIQNState / FusedIQNState, built on the first train()
         self._net_args = (self_dimension, object_dimension, max_object_num, self_feature_dimension,
                           object_feature_dimension, concat_feature_dimension, hidden_dimension)
@@ -128,14 +131,15 @@ class Agent:
 
     def _make_optimizers(self):
         """optim.Adam(lr) + clip 0.5 (agent.py:75-76,98): FusedAdam (asvrl_adam_*) of the learner's
-        operand build for AC-IQN / IQN, torch Adam for Rainbow / DQN."""
+        operand build for AC-IQN / IQN and for DQN on a fused learner, torch Adam for Rainbow and DQN's torch
+        learner."""
         self._fused = None
         ops = LEARNERS[self.learner] or "bf16"
         if self.agent_type == "AC-IQN":
             self.actor_optimizer = FusedAdam(self.policy_local.actor.parameters(), lr=self.LR, operands=ops)
             self.critic_optimizer = FusedAdam(self.policy_local.critic.parameters(), lr=self.LR, operands=ops)
             self.actor_grads, self.critic_grads = self.actor_optimizer.grads, self.critic_optimizer.grads
-        elif self.agent_type == "IQN":
+        elif self.agent_type == "IQN" or (self.agent_type == "DQN" and LEARNERS[self.learner] is not None):
             self.optimizer = FusedAdam(self.policy_local.parameters(), lr=self.LR, operands=ops)
             self.grads = self.optimizer.grads
         else:
@@ -143,8 +147,8 @@ class Agent:
             self.optimizer = torch.optim.Adam(self.policy_local.parameters(), lr=self.LR)
 
     def set_learner(self, learner):
-        """Select train_AC_IQN / train_IQN's learner (LEARNERS); rebuilds the optimisers (fresh Adam
-        state, as load_model does)."""
+        """Select train_AC_IQN / train_IQN / train_DQN's learner (LEARNERS); rebuilds the optimisers (fresh
+        Adam state, as load_model does)."""
         if learner not in LEARNERS:
             raise ValueError(f"learner must be one of {sorted(LEARNERS)}")
         self.learner = learner
@@ -167,6 +171,9 @@ class Agent:
                 ok = fused_update.supported(self.policy_local, B, self.num_tau)
                 st = fused_update.FusedACIQNState(self.policy_local, self.policy_target, B, self.num_tau,
                                                   operands=ops) if ok else None
+            elif self.agent_type == "DQN":
+                ok = fused_dqn.supported(self.policy_local, B)
+                st = fused_dqn.FusedDQNState(self.policy_local, self.policy_target, B, operands=ops) if ok else None
             else:
                 ok = fused_iqn.supported(self.policy_local, B, self.num_tau)
                 # nothing runs beside the drop-in's update: the target's max inside the fused launch (bf16 build)
@@ -343,8 +350,16 @@ class Agent:
         return loss
 
     def train_DQN(self):
-        """agent.py:518-545: max-over-actions target, smooth L1, clip 0.5, Adam (plain torch)."""
+        """agent.py:518-545: max-over-actions target, smooth L1, clip 0.5, Adam. The torch learner (default) is
+        the reference's update as it stands; a fused learner runs fused_dqn.dqn_update_fused."""
         s, a, r, ns, d = self.memory.sample()
+        st = self._fused_state(s[0].shape[0]) if isinstance(self.optimizer, FusedAdam) else None
+        if st is not None:   # the hand-written learner
+            loss, _ = fused_dqn.dqn_update_fused(st, self.policy_local, self.optimizer, self.grads,
+                                                 rows_from_batch(s, a[:, :1], r, ns, d), gamma=self.GAMMA)
+            return loss.cpu().numpy()
+        if isinstance(self.optimizer, FusedAdam):   # a shape the kernels do not take: autograd into the flat grads
+            return self._train_dqn_autograd_fused_adam(s, a, r, ns, d)
         actions = a[:, :1].to(torch.int64)
         self.optimizer.zero_grad()
         with torch.no_grad():
@@ -354,6 +369,19 @@ class Agent:
         loss = F.smooth_l1_loss(q_expected, q_targets)
         loss.backward()
         torch.nn.utils.clip_grad_norm_(self.policy_local.parameters(), 0.5)
+        self.optimizer.step()
+        return loss.detach().cpu().numpy()
+
+    def _train_dqn_autograd_fused_adam(self, s, a, r, ns, d):
+        """train_DQN's torch-autograd update with the fused optimiser (a fused learner on a network shape the
+        kernels do not take; _fused_state has warned)."""
+        actions = a[:, :1].to(torch.int64)
+        self.grads.zero_()
+        with torch.no_grad():
+            q_next = self.policy_target(ns).max(dim=1, keepdim=True)[0]
+            q_targets = r + (1 - d) * self.GAMMA * q_next
+        loss = F.smooth_l1_loss(self.policy_local(s).gather(1, actions), q_targets)
+        self.grads.assign(torch.autograd.grad(loss, self.grads.params))
         self.optimizer.step()
         return loss.detach().cpu().numpy()
 

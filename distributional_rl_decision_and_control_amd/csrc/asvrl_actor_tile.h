@@ -3,7 +3,8 @@
 // 128 -> 128, output_layer 128 -> 2 with (2/pi) atan, and the epsilon-greedy draw of the batched act
 // (agent.py:207-225). Shared by asvrl_mlp.hip (actor_kernel, encode_kernel) and asvrl_env.hip
 // (env_policy_rollout_kernel, the Actor in front of every env step): the same MFMAs in the same order, so a row's
-// action does not depend on which kernel computed it.
+// action does not depend on which kernel computed it. asvrl_dqn.hip runs the same trunk (trunk_chain) under
+// DQN_Policy's 25-wide head.
 #pragma once
 #include "asvrl_common.h"
 #include "asvrl_mfma.h"
@@ -115,10 +116,14 @@ __device__ __forceinline__ void stage_actor(ActorLds& L, const AsvMlpWeights& w,
 // The forward chain of one tile: the lane's row (`row`, written only when `valid`) from its encoder operand
 // to the pre-atan outputs (z0, z1) and the actions (a0, a1), in every lane of the row's pair (h = 0, 1).
 // MLP_TRAIN saves the activations the backward reads.
-template <int MODE>
+// HEAD = false (trunk_chain below: DQN_Policy has the same trunk under another output layer, asvrl_dqn.hip):
+// the chain stops behind hidden_layer_2 and leaves h2 in `h2v` -- element j of chained k-step group
+// grp = 2 mb + s is feature feat(mb, 8 s + j, h), what a following layer's B operand packs; z and a are not
+// written. The Actor's own instantiation is the same statements as before the split.
+template <int MODE, bool HEAD = true>
 __device__ __forceinline__ void actor_chain(const AsvMlpWeights& w, const AsvMlpIO& io, const ActorLds& L, int row,
                                             bool valid, int lane, const frag8 (&bx)[2], const float (&mk)[kObjN],
-                                            float& z0, float& z1, float& a0, float& a1) {
+                                            float& z0, float& z1, float& a0, float& a1, float (*h2v)[8] = nullptr) {
   const int h = lane >> 5;
   // encoders -> h0 (chained B operand of hidden_layer)
   frag8 fpk[16];
@@ -171,16 +176,31 @@ __device__ __forceinline__ void actor_chain(const AsvMlpWeights& w, const AsvMlp
         const int m = feat(mb, 8 * s + j, h);
         const float x = acc2[mb][8 * s + j] + L.b2[m];
         v[j] = relu(x);
-        p0 += L.wout[m] * v[j];
-        p1 += L.wout[kHid + m] * v[j];
+        if constexpr (HEAD) {
+          p0 += L.wout[m] * v[j];
+          p1 += L.wout[kHid + m] * v[j];
+        } else {
+          h2v[mb * 2 + s][j] = v[j];
+        }
       }
       if (MODE == MLP_TRAIN)
       store16(valid ? bp(io.h2) + static_cast<int64_t>(row) * kHid + mb * 32 + 16 * s : nullptr, v, h);
     }
-  z0 = p0 + __shfl_xor(p0, 32, 64) + L.bout[0];
-  z1 = p1 + __shfl_xor(p1, 32, 64) + L.bout[1];
-  a0 = w.out_scale * atanf(z0);   // atan_scale * torch.atan(actions)
-  a1 = w.out_scale * atanf(z1);
+  if constexpr (HEAD) {
+    z0 = p0 + __shfl_xor(p0, 32, 64) + L.bout[0];
+    z1 = p1 + __shfl_xor(p1, 32, 64) + L.bout[1];
+    a0 = w.out_scale * atanf(z0);   // atan_scale * torch.atan(actions)
+    a1 = w.out_scale * atanf(z1);
+  }
+}
+
+// The trunk alone: h2 of the lane's row as the eight chained k-step groups of a following layer's B operand.
+template <int MODE>
+__device__ __forceinline__ void trunk_chain(const AsvMlpWeights& w, const AsvMlpIO& io, const ActorLds& L, int row,
+                                            bool valid, int lane, const frag8 (&bx)[2], const float (&mk)[kObjN],
+                                            float (&h2v)[8][8]) {
+  float z0, z1, a0, a1;   // not written with HEAD = false
+  actor_chain<MODE, false>(w, io, L, row, valid, lane, bx, mk, z0, z1, a0, a1, h2v);
 }
 
 // epsilon-greedy (agent.py:207-225): greedy iff random() > eps, else uniform(-1, 1) per dim; eps: linear

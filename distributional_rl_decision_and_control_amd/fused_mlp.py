@@ -68,7 +68,8 @@ class MlpPack:
             else:
                 w.b1, w.b2 = net.hidden_layer.bias.data_ptr(), net.hidden_layer_2.bias.data_ptr()
                 w.wout, w.bout = net.output_layer.weight.data_ptr(), net.output_layer.bias.data_ptr()
-            w.out_scale = float(net.atan_scale.float().item())
+            # DQN_Policy (fused_dqn.DqnPack) has the Actor's trunk and no atan squash: the scale is unused there
+            w.out_scale = float(net.atan_scale.float().item()) if hasattr(net, "atan_scale") else 1.0
         elif kind == "critic":
             t["ae"] = torch.zeros(HID * 16, **bf)
             w.ae_frag = t["ae"].data_ptr()

@@ -161,8 +161,8 @@ class Trainer:
 
         from ..vec_trainer import VecTrainer
         agent = self.rl_agent
-        if agent.agent_type not in ("AC-IQN", "IQN", "Rainbow"):
-            raise ValueError(f"vectorized training covers AC-IQN, IQN and Rainbow, not {agent.agent_type}")
+        if agent.agent_type not in ("AC-IQN", "IQN", "Rainbow", "DQN"):
+            raise ValueError(f"vectorized training covers AC-IQN, IQN, Rainbow and DQN, not {agent.agent_type}")
         sched = {k: v for k, v in self.train_env.schedule.items() if k != "vectorized"}
         kw = dict(vec)
         # "device_eval": true evaluates on the device with the batched trainer's own actor (AC-IQN;

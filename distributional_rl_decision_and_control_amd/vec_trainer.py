@@ -8,7 +8,7 @@ One iteration (= one `step` of bench.py):
   3. replay push of the transitions of robots that acted (asvrl_replay_push, trainer.py:157-166)
   4. device reset of finished envs + their first observation (asvrl_env_reset, trainer.py:212-245)
   5. learn: sample B transitions (asvrl_replay_sample) and one distributional update
-     (AC-IQN: two dependent optimizer steps, critic then actor; IQN: one)
+     (AC-IQN: two dependent optimizer steps, critic then actor; IQN, Rainbow and DQN: one)
   6. hard target update every `target_update_interval` learn steps (agent.py:643-679, TAU=1)
 
 Cadence in the batched setting: one learn step of batch B per iteration (after
@@ -22,6 +22,8 @@ import torch
 
 from . import streams
 from .fused_update import FusedACIQNState, ac_iqn_update_fused2, learn_prologue
+from .fused_dqn import FusedDQNState, dqn_update_fused
+from .fused_dqn import supported as fused_dqn_supported
 from .fused_iqn import FusedIQNState, iqn_update_fused
 from .fused_iqn import supported as fused_iqn_supported
 from .fused_rainbow import FusedRainbow
@@ -29,6 +31,7 @@ from .fused_update import supported as fused2_supported
 from .learn_ops import DevicePER, DeviceReplay
 from .learner import FusedAdam
 from .policy.AC_IQN_model import AC_IQN_Policy
+from .policy.DQN_model import DQN_Policy
 from .policy.IQN_model import IQN_Policy
 from .policy.Rainbow_model import Rainbow_Policy
 from .vec_env import VecMarineNavEnv
@@ -44,7 +47,7 @@ class VecTrainer:
                  exploration_fraction=0.25, initial_eps=0.6, final_eps=0.05, seed=0,
                  device="cuda", sync=None, graphs=False, schedule=None, net_seed=100, overlap=True, unroll=1,
                  chain=None, operands="bf16", target_after_env=False, push_after_actor=None):
-        """Every learner runs on the hand-written kernels (fused_update / fused_iqn / fused_rainbow) with
+        """Every learner runs on the hand-written kernels (fused_update / fused_iqn / fused_rainbow / fused_dqn) with
         FusedAdam; operands="f32" takes them from the f32-operand parity build (libasvrl_f32.so). Shapes
         the kernels do not take raise ValueError."""
         self.device = torch.device(device)
@@ -70,7 +73,7 @@ class VecTrainer:
         self.total_timesteps = total_timesteps
         self.exploration_fraction, self.initial_eps, self.final_eps = exploration_fraction, initial_eps, final_eps
         self.learning_starts = learning_starts if learning_starts is not None else batch_size
-        self.fused2 = self.fused_iqn = self.fused_rb = None
+        self.fused2 = self.fused_iqn = self.fused_rb = self.fused_dqn = None
         if agent_type == "AC-IQN":
             self.local = AC_IQN_Policy(**DEFAULT_NET, value_ranges_of_action=[[-1.0, 1.0], [-1.0, 1.0]],
                                        device=self.device, seed=net_seed)
@@ -114,8 +117,21 @@ class VecTrainer:
             self.support = torch.linspace(-1.0, 1.0, 51, device=self.device)
             # noisy weights, the network, loss gradient and act on hand-written kernels (fused_rainbow.py)
             self.fused_rb = FusedRainbow(self.local, self.target, batch_size, self.support, operands)
+        elif agent_type == "DQN":
+            # DQN_Policy: the Actor's trunk with a 25-wide head (fused_dqn.py); the uniform ring, one optimiser
+            self.local = DQN_Policy(**DEFAULT_NET, action_size=25, device=self.device, seed=net_seed).to(self.device)
+            self.target = DQN_Policy(**DEFAULT_NET, action_size=25, device=self.device, seed=net_seed).to(self.device)
+            for p in self.target.parameters():
+                p.requires_grad_(False)
+            if not fused_dqn_supported(self.local, batch_size):
+                raise ValueError(f"DQN learner kernels: B={batch_size} (a positive multiple of 32)")
+            self.opt = FusedAdam(self.local.parameters(), lr=lr, operands=operands)
+            self.grads = self.opt.grads
+            self.action_dim = 1
+            self.fused_dqn = FusedDQNState(self.local, self.target, batch_size, operands)
         else:
-            raise NotImplementedError(f"VecTrainer agent_type {agent_type!r} (AC-IQN, IQN and Rainbow are batched)")
+            raise NotImplementedError(f"VecTrainer agent_type {agent_type!r} (AC-IQN, IQN, Rainbow and DQN are "
+                                      "batched)")
         NT = self.E * self.R
         self.per = None
         if agent_type == "Rainbow":
@@ -197,6 +213,8 @@ class VecTrainer:
             self.fused_rb.act(*args)
         elif self.fused_iqn is not None:   # K = 32 quantiles per robot, mean, argmax, explore
             self.fused_iqn.act(*args)
+        elif self.fused_dqn is not None:   # Q per robot, argmax, explore
+            self.fused_dqn.act(*args)
         else:   # actor on every robot row, explore
             self.fused2.act(*args)
 
@@ -221,8 +239,8 @@ class VecTrainer:
         max_steps. Returns that batch's episode_stats() plus steps_run, the steps every env took. The training
         env, the replay and the step counter are not touched. AC-IQN only."""
         if self.fused2 is None:
-            raise NotImplementedError("greedy_episodes runs the AC-IQN actor; IQN and Rainbow act inside their own "
-                                      "kernels")
+            raise NotImplementedError("greedy_episodes runs the AC-IQN actor; IQN, Rainbow and DQN act inside their "
+                                      "own kernels")
         env = self._eval_env()
         alive = torch.ones(self.E, dtype=torch.uint8, device=self.device)
         steps_run = torch.zeros(self.E, dtype=torch.int32, device=self.device)
@@ -247,7 +265,8 @@ class VecTrainer:
         episode_limit and sync. The actor's packed images are the learner's own, so no copy into a drop-in agent is
         needed; the training env, the replay and the step counter are not touched. AC-IQN only."""
         if self.fused2 is None:
-            raise NotImplementedError("evaluate runs the AC-IQN actor; IQN and Rainbow act inside their own kernels")
+            raise NotImplementedError("evaluate runs the AC-IQN actor; IQN, Rainbow and DQN act inside their own "
+                                      "kernels")
         from .policy.device_eval import DeviceEvaluator
         cached = getattr(self, "_dev_eval", None)
         if cached is None or cached[0] is not configs or cached[1] != (len(configs), int(chunk), template_env):
@@ -307,8 +326,8 @@ class VecTrainer:
         reward, done, actions, steps_run, pushed, resets). AC-IQN with the uniform ring only; the caller accounts for
         the host-side step count (env.advance_host() per step) as iteration() does."""
         if self.fused2 is None or self.per is not None:
-            raise NotImplementedError("collect runs the AC-IQN actor and pushes into the uniform ring; IQN and Rainbow "
-                                      "act inside their own kernels")
+            raise NotImplementedError("collect runs the AC-IQN actor and pushes into the uniform ring; IQN, Rainbow "
+                                      "and DQN act inside their own kernels")
         K = int(K)
         buf = self._collect_buffers(K)
         buf["obj_cnt"].fill_(-1)   # a row no env took is never pushed
@@ -345,6 +364,11 @@ class VecTrainer:
                                         self.actor_grads, rows, gamma=self.gamma, sync=self.sync,
                                         actor_wait=actor_wait, taus=self.taus, counter=self.learn_counter,
                                         prologue_done=True, target_wait=target_wait, actor_done=actor_done)
+        if self.fused_dqn is not None:   # no quantile fractions to draw
+            rows = self.replay.sample(self.B, seed=self.seed + 777, counter_dev=self.learn_counter,
+                                      out=self.batch_rows, state=state, guard=guard)
+            return dqn_update_fused(self.fused_dqn, self.local, self.opt, self.grads, rows, gamma=self.gamma,
+                                    sync=self.sync, act_wait=actor_wait, counter=self.learn_counter)
         # the update's quantile fractions are drawn by the sampling launch
         rows = self.replay.sample(self.B, seed=self.seed + 777, counter_dev=self.learn_counter, out=self.batch_rows,
                                   state=state, guard=guard, taus=self.taus)
@@ -366,6 +390,8 @@ class VecTrainer:
                 self.fused_iqn.target_changed()
             if self.fused_rb is not None:
                 self.fused_rb.target_changed()
+            if self.fused_dqn is not None:
+                self.fused_dqn.target_changed()
 
     @torch.no_grad()
     def load_policies(self, local, target):
@@ -392,6 +418,9 @@ class VecTrainer:
             self.fused_rb.pack.compose()
             self.fused_rb.img.refresh()
             self.fused_rb.target_changed()
+        if self.fused_dqn is not None:
+            self.fused_dqn.local.refresh()
+            self.fused_dqn.target_changed()
 
     # ------------------------------------------------------------------ iteration
     def _iteration_body(self, do_learn):

@@ -1125,6 +1125,69 @@ int asvrl_eval_metrics(const AsvEvalMetrics* m, void* stream);
 /* sizeof(AsvEvalMetrics) as compiled. */
 int64_t asvrl_eval_metrics_struct_size(void);
 
+/* ---------------------------------------------------------------- DQN (agent.py:271-287, 518-545)
+ * DQN_Policy (DQN_model.py) has the Actor's trunk layer for layer (both observation encoders, hidden_layer,
+ * hidden_layer_2) and a 128 -> A output layer (A = 25) without a squash. Its images are the Actor's
+ * (AsvMlpWeights) plus the output layer padded to ASVRL_DQN_MAX_ACTIONS rows as one chained fragment image.
+ * Columns >= A never enter a max, an arg-max or a gradient. New entry points only: the ABI version stays 29. */
+#define ASVRL_DQN_MAX_ACTIONS 32
+typedef struct AsvDqnWeights {
+  AsvMlpWeights trunk;    /* wout: f32 output_layer.weight [A][128], bout: [A]; ae_frag, b_ae, out_scale unused */
+  const void* head_frag;  /* output layer, 32 x 128 chained image, rows A.. zero (written by the pack) */
+  int32_t n_actions;      /* A, 2..ASVRL_DQN_MAX_ACTIONS */
+  int32_t _pad0;
+} AsvDqnWeights;
+
+/* Batched act: Q on n packed observation rows, arg-max (first maximum), epsilon-greedy with the linear
+ * schedule on the device step counter (trainer.py:257-264): greedy iff random() > eps, else uniform over 0..A-1.
+ * act_out[row * ld_act] = action index, act_out[row * ld_act + 1] = 0. */
+typedef struct AsvDqnActIO {
+  const float* x;         /* [n] rows of ASVRL_OBS_DIM at stride ldx floats, 16-byte aligned */
+  int64_t ldx;
+  int32_t n;
+  int32_t _pad0;
+  double* act_out;        /* f64 [n][ld_act], ld_act >= 2 */
+  int64_t ld_act;
+  float* q_out;           /* optional f32 [n][A]: the Q rows the arg-max was taken over */
+  const int64_t* step_dev;      /* device step counter (NULL: step 0) */
+  double eps_steps_per_count;   /* timesteps per counter tick (= n_envs) */
+  double eps_total, eps_fraction, eps_initial, eps_final;
+  uint64_t seed;                /* Philox key of the exploration draws */
+} AsvDqnActIO;
+
+/* One DQN gradient over B replay rows (ASVRL_TR_DIM layout: s | s' | action index | . | reward | done):
+ * q = Q_local(s)[a], q_next = max_a Q_target(s'), y = r + (1 - d) gamma q_next, loss = mean smooth_l1(q - y)
+ * (beta 1), dQ[b][a_b] = clamp(q - y, -1, 1) / B, and the backward to every layer's pre-activation gradient.
+ * Saved activations and gradients are in the build's operand type (bf16 / f32). */
+typedef struct AsvDqnGradIO {
+  const float* rows;      /* [B] replay rows at stride ld_rows floats, 16-byte aligned */
+  int64_t ld_rows;
+  int32_t B;              /* a positive multiple of 32 */
+  float gamma;
+  void* xb;               /* out [B][32]: obs columns 0..31 of s (operand of the encoder weight gradient) */
+  void* h0;               /* out [B][256] */
+  void* h1;               /* out [B][128] */
+  void* h2;               /* out [B][128] */
+  float* q_sel;           /* out [B]: Q_local(s)[a] */
+  float* q_next;          /* out [B]: max_a Q_target(s') */
+  void* dz_out;           /* out [B][32]: dQ at column a, zero elsewhere */
+  void* dz2;              /* out [B][128] */
+  void* dz1;              /* out [B][128] */
+  void* dz0;              /* out [B][256] */
+  float* tile_loss;       /* out [B / 32]: per-tile loss partials, loss = their sum */
+} AsvDqnGradIO;
+
+/* The trunk images (as asvrl_mlp_pack) and the head image of `w` from the f32 parameters. */
+int asvrl_dqn_pack(const AsvMlpSrc* src, const float* wout, const AsvDqnWeights* w, void* stream);
+int asvrl_dqn_act(const AsvDqnWeights* w, const AsvDqnActIO* io, void* stream);
+/* Two launches, no host sync: both forwards (local on s saving activations, target on s'), then loss + backward.
+ * The weight gradients follow from (dz_out, h2), (dz2, h1), (dz1, h0), (dz0, xb) by asvrl_linear_wgrad_multi. */
+int asvrl_dqn_grad(const AsvDqnWeights* local, const AsvDqnWeights* target, const AsvDqnGradIO* io, void* stream);
+/* sizeof(AsvDqnWeights), sizeof(AsvDqnActIO), sizeof(AsvDqnGradIO) as compiled. */
+int64_t asvrl_dqn_weights_struct_size(void);
+int64_t asvrl_dqn_act_struct_size(void);
+int64_t asvrl_dqn_grad_struct_size(void);
+
 /* ---------------------------------------------------------------- misc */
 const char* asvrl_last_error(void);
 int asvrl_abi_version(void);
