@@ -1858,171 +1858,100 @@ PairLaunch pair_launch(int R, int O, int n_envs, int blk_req, int epb_req, int v
 
 using namespace asvrl;
 
-extern "C" int asvrl_env_step_ex(const AsvParams* params, const AsvEnvState* state, const double* actions,
-                                 const double* noise, const AsvStepCtl* ctl, const AsvStepOut* out,
-                                 const AsvEnvLaunch* launch, void* stream) {
-  ASVRL_REQUIRE(params && state && ctl && out, "asvrl_env_step: null argument");
-  ASVRL_REQUIRE(state->max_robots >= 1 && state->max_robots <= kBlock, "asvrl_env_step: max_robots must be in [1, 256]");
-  ASVRL_REQUIRE(state->max_obs >= 0 && state->max_cores >= 0 && state->max_cores <= kMaxCoresStep,
-                "asvrl_env_step: bad max_obs/max_cores");
-  ASVRL_REQUIRE(params->max_obj_num >= 0 && params->max_obj_num <= ASVRL_MAX_OBJ, "asvrl_env_step: max_obj_num > 5");
-  ASVRL_REQUIRE(params->N >= 1, "asvrl_env_step: N < 1");
-  ASVRL_REQUIRE(out->obs && out->obj_cnt && out->reward && out->done && out->info, "asvrl_env_step: null output");
-  ASVRL_REQUIRE(ctl->noise_mode != 0 || noise != nullptr, "asvrl_env_step: noise_mode 0 needs injected noise");
-  ASVRL_REQUIRE(!ctl->do_dynamics || actions != nullptr, "asvrl_env_step: actions required");
-  ASVRL_REQUIRE(state->rs && state->rflags && state->n_robots && state->n_obs && state->n_cores && state->ep_ts,
-                "asvrl_env_step: null state array");
-  if (state->n_envs == 0) return 0;
-  const AsvEnvLaunch lz{};
-  const AsvEnvLaunch& lc = launch != nullptr ? *launch : lz;
-  ASVRL_REQUIRE(lc.layout >= 0 && lc.layout <= 2, "asvrl_env_step: layout must be 0 (auto), 1 (pairs) or 2 (sweep)");
-  ASVRL_REQUIRE(lc.block == 0 || lc.block == 64 || lc.block == 128 || lc.block == 256,
-                "asvrl_env_step: block must be 0, 64, 128 or 256");
-  ASVRL_REQUIRE(lc.envs_per_block >= 0 && lc.max_groups >= 0, "asvrl_env_step: negative envs_per_block / max_groups");
-  const int nm = ctl->noise_mode == 0 ? 0 : (ctl->noise_mode == 1 ? 1 : 2);
-  const PairLaunch pl = pair_launch(state->max_robots, state->max_obs, state->n_envs, lc.block, lc.envs_per_block,
-                                    nm == 2 ? 4 : 8);
-  const bool per_robot = state->robot_params != nullptr;
-  ASVRL_REQUIRE(lc.layout != 1 || pl.smem <= 150 * 1024, "asvrl_env_step: the pair layout's LDS does not fit");
-  ASVRL_REQUIRE(lc.layout != 1 || !per_robot, "asvrl_env_step: per-robot parameters take the sweep layout (2)");
-  if (lc.layout != 2 && !per_robot && pl.smem <= 150 * 1024) {
-    const int groups = (state->n_envs + pl.epb - 1) / pl.epb;
-    const int chunk = lc.max_groups > 0 && lc.max_groups < groups ? lc.max_groups : groups;
-    auto go = [&](auto kern) {
-      PairsArgs a{*params, *state, *ctl, *out, actions, noise, pl.epb, 0};
-      for (int g0 = 0; g0 < groups; g0 += chunk) {
-        a.group0 = g0;
-        hipLaunchKernelGGL(kern, dim3(groups - g0 < chunk ? groups - g0 : chunk), dim3(pl.blk), pl.smem,
-                           as_stream(stream), a);
-      }
-    };
-    if (pl.blk == 64)
-      nm == 0 ? go(env_pairs_kernel<64, 0>) : nm == 1 ? go(env_pairs_kernel<64, 1>) : go(env_pairs_kernel<64, 2>);
-    else if (pl.blk == 128)
-      nm == 0 ? go(env_pairs_kernel<128, 0>) : nm == 1 ? go(env_pairs_kernel<128, 1>) : go(env_pairs_kernel<128, 2>);
-    else
-      nm == 0 ? go(env_pairs_kernel<256, 0>) : nm == 1 ? go(env_pairs_kernel<256, 1>) : go(env_pairs_kernel<256, 2>);
-    return check_launch("asvrl_env_step");
+// ------------------------------------------------------------------ the env step and its four rollout calls
+// One host path. Each call is: env_checks (its arguments), env_plan (the launch shape, and whether the
+// pair-parallel kernel is taken), then launch_groups (that kernel) or, for the rollouts, rollout_fallback (K single
+// steps).
+
+// the groups of checks a call takes beyond the step's own
+enum : unsigned { kRollout = 1, kClosedLoop = 2, kAutoReset = 4 };
+
+static int env_fail(const char* who, const char* what) {
+  set_error(std::string(who) + ": " + what);
+  return 1;
+}
+#define ENV_REQUIRE(cond, what)                  \
+  do {                                           \
+    if (!(cond)) return env_fail(who, what);     \
+  } while (0)
+
+// The argument checks of the five calls, in the order each call reports them (`who` names the call in the error
+// text). actions / noise: the single step's; the rollouts carry theirs in ro.
+static int env_checks(const char* who, unsigned kind, const AsvParams* params, const AsvEnvState* state,
+                      const double* actions, const double* noise, const AsvStepCtl* ctl, const AsvStepOut* out,
+                      const AsvRollout* ro, const AsvPolicy* pi, const AsvAutoReset* ar, const AsvEnvLaunch* launch) {
+  const bool roll = (kind & kRollout) != 0, closed = (kind & kClosedLoop) != 0, reset = (kind & kAutoReset) != 0;
+  ENV_REQUIRE(params && state && ctl && out && (ro || !roll), "null argument");
+  if (reset) {   // what the two _ar calls refuse beyond their plain calls' checks
+    ENV_REQUIRE(ar != nullptr, "null ar (the auto-reset description)");
+    ENV_REQUIRE(!ro->hold_done, "ro->hold_done cannot be combined with the auto-reset");
+    ENV_REQUIRE(ctl->trainer_deactivate && out->env_done != nullptr,
+                "the auto-reset needs ctl->trainer_deactivate and last->env_done");
+    ENV_REQUIRE(ctl->noise_mode == 1 || ctl->noise_mode == 2,
+                "noise_mode 0 (recorded noise) cannot cover a sampled reset; Philox noise only (mode 1 or 2)");
+    ENV_REQUIRE(closed || ar->obs_prev == nullptr || ar->obs_in != nullptr,
+                "ar->obs_prev needs ar->obs_in (the rows in front of step 0)");
+    ENV_REQUIRE(ar->cfg.num_robots >= 0 && ar->cfg.num_robots <= kResetMaxR && state->max_robots <= kResetMaxR,
+                "ar->cfg.num_robots / max_robots beyond the reset sampler's 32");
+    ENV_REQUIRE(ar->cfg.num_obs >= 0 && ar->cfg.num_obs <= kResetMaxO && state->max_obs <= kResetMaxO,
+                "ar->cfg.num_obs / max_obs beyond the reset sampler's 32");
+    ENV_REQUIRE(ar->cfg.num_cores >= 0 && ar->cfg.num_cores <= kMaxCores && state->max_cores <= kMaxCores,
+                "ar->cfg.num_cores / max_cores beyond the reset sampler's 16");
+    ENV_REQUIRE(ar->cfg.width > 4.0 && ar->cfg.height > 4.0, "ar->cfg map too small");
   }
-  const int blk = step_block(state->max_robots);
-  const int epb = blk / state->max_robots;
-  const int grid = (state->n_envs + epb - 1) / epb;
-  const size_t smem = env_sweep_smem(state->max_robots, state->max_obs);
-  ASVRL_REQUIRE(smem <= 160 * 1024, "asvrl_env_step: max_obs too large for LDS");
-  auto sweep = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(blk), smem, as_stream(stream), *params, *state, actions, noise, *ctl,
-                       *out);
-  };
-  if (blk == 64)
-    per_robot ? sweep(env_sweep_kernel<64, true>) : sweep(env_sweep_kernel<64, false>);
-  else
-    per_robot ? sweep(env_sweep_kernel<256, true>) : sweep(env_sweep_kernel<256, false>);
-  return check_launch("asvrl_env_step");
-}
-
-extern "C" int asvrl_env_step(const AsvParams* params, const AsvEnvState* state, const double* actions,
-                              const double* noise, const AsvStepCtl* ctl, const AsvStepOut* out, void* stream) {
-  return asvrl_env_step_ex(params, state, actions, noise, ctl, out, nullptr, stream);
-}
-
-// the argument checks asvrl_env_rollout and asvrl_policy_rollout share (`who` names the call in the error text)
-static int rollout_checks(const std::string& who, const AsvParams* params, const AsvEnvState* state,
-                          const AsvStepCtl* ctl, const AsvStepOut* out, const AsvRollout* ro,
-                          const AsvEnvLaunch* launch) {
-  ASVRL_REQUIRE(ctl->do_dynamics, who + ": do_dynamics must be 1");
-  ASVRL_REQUIRE(!ro->hold_done || ctl->trainer_deactivate, who + ": hold_done needs trainer_deactivate");
-  ASVRL_REQUIRE(ctl->noise_mode != 0 || ro->noise != nullptr, who + ": noise_mode 0 needs injected noise");
-  ASVRL_REQUIRE(!(ro->hold_done || ro->env_done) || (ctl->trainer_deactivate && out->env_done),
-                who + ": hold_done and the env_done record need trainer_deactivate and out->env_done");
-  ASVRL_REQUIRE(state->max_robots >= 1 && state->max_robots <= kBlock, who + ": max_robots must be in [1, 256]");
-  ASVRL_REQUIRE(state->max_obs >= 0 && state->max_cores >= 0 && state->max_cores <= kMaxCoresStep,
-                who + ": bad max_obs/max_cores");
-  ASVRL_REQUIRE(params->max_obj_num >= 0 && params->max_obj_num <= ASVRL_MAX_OBJ, who + ": max_obj_num > 5");
-  ASVRL_REQUIRE(params->N >= 1, who + ": N < 1");
-  ASVRL_REQUIRE(out->obs && out->obj_cnt && out->reward && out->done && out->info, who + ": null output");
-  ASVRL_REQUIRE(state->rs && state->rflags && state->n_robots && state->n_obs && state->n_cores && state->ep_ts,
-                who + ": null state array");
+  if (roll) {
+    ENV_REQUIRE(ro->n_steps >= 1, "n_steps must be >= 1");
+    if (!closed) ENV_REQUIRE(ro->actions != nullptr, "null actions");
+  }
+  if (closed) {
+    ENV_REQUIRE(ro->actions == nullptr, "ro->actions must be null (the policy supplies the actions)");
+    ENV_REQUIRE(pi != nullptr, "null policy");
+    ENV_REQUIRE(pi->obs_in != nullptr, "null obs_in");
+    ENV_REQUIRE(ctl->is_continuous, "is_continuous must be 1 (the Actor is the continuous agent)");
+    const AsvMlpWeights& w = pi->w;
+    ENV_REQUIRE(w.enc_frag && w.b_enc && w.w1_frag && w.w2_frag && w.b1 && w.b2 && w.wout && w.bout,
+                "null actor image");
+  }
+  if (roll) {
+    ENV_REQUIRE(ctl->do_dynamics, "do_dynamics must be 1");
+    ENV_REQUIRE(!ro->hold_done || ctl->trainer_deactivate, "hold_done needs trainer_deactivate");
+    ENV_REQUIRE(ctl->noise_mode != 0 || ro->noise != nullptr, "noise_mode 0 needs injected noise");
+    ENV_REQUIRE(!(ro->hold_done || ro->env_done) || (ctl->trainer_deactivate && out->env_done),
+                "hold_done and the env_done record need trainer_deactivate and out->env_done");
+  }
+  ENV_REQUIRE(state->max_robots >= 1 && state->max_robots <= kBlock, "max_robots must be in [1, 256]");
+  ENV_REQUIRE(state->max_obs >= 0 && state->max_cores >= 0 && state->max_cores <= kMaxCoresStep,
+              "bad max_obs/max_cores");
+  ENV_REQUIRE(params->max_obj_num >= 0 && params->max_obj_num <= ASVRL_MAX_OBJ, "max_obj_num > 5");
+  ENV_REQUIRE(params->N >= 1, "N < 1");
+  ENV_REQUIRE(out->obs && out->obj_cnt && out->reward && out->done && out->info, "null output");
+  if (!roll) {
+    ENV_REQUIRE(ctl->noise_mode != 0 || noise != nullptr, "noise_mode 0 needs injected noise");
+    ENV_REQUIRE(!ctl->do_dynamics || actions != nullptr, "actions required");
+  }
+  ENV_REQUIRE(state->rs && state->rflags && state->n_robots && state->n_obs && state->n_cores && state->ep_ts,
+              "null state array");
   if (launch != nullptr && state->n_envs != 0) {
-    ASVRL_REQUIRE(launch->layout >= 0 && launch->layout <= 2, who + ": layout must be 0 (auto), 1 (pairs) or 2 (sweep)");
-    ASVRL_REQUIRE(launch->block == 0 || launch->block == 64 || launch->block == 128 || launch->block == 256,
-                  who + ": block must be 0, 64, 128 or 256");
-    ASVRL_REQUIRE(launch->envs_per_block >= 0 && launch->max_groups >= 0,
-                  who + ": negative envs_per_block / max_groups");
+    ENV_REQUIRE(launch->layout >= 0 && launch->layout <= 2, "layout must be 0 (auto), 1 (pairs) or 2 (sweep)");
+    ENV_REQUIRE(launch->block == 0 || launch->block == 64 || launch->block == 128 || launch->block == 256,
+                "block must be 0, 64, 128 or 256");
+    ENV_REQUIRE(launch->envs_per_block >= 0 && launch->max_groups >= 0, "negative envs_per_block / max_groups");
   }
+  if (closed)
+    ENV_REQUIRE(reinterpret_cast<uintptr_t>(pi->obs_in) % 16 == 0 && reinterpret_cast<uintptr_t>(out->obs) % 16 == 0 &&
+                    (!reset || reinterpret_cast<uintptr_t>(ar->obs_prev) % 16 == 0),
+                "observation rows must be 16-byte aligned");
+  else if (reset)
+    ENV_REQUIRE(ar->obs_prev == nullptr || (reinterpret_cast<uintptr_t>(ar->obs_in) % 16 == 0 &&
+                                            reinterpret_cast<uintptr_t>(ar->obs_prev) % 16 == 0),
+                "ar->obs_in / ar->obs_prev rows must be 16-byte aligned");
   return 0;
-}
-
-extern "C" int asvrl_env_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
-                                 const AsvStepOut* out, const AsvRollout* ro, const AsvEnvLaunch* launch,
-                                 void* stream) {
-  ASVRL_REQUIRE(params && state && ctl && out && ro, "asvrl_env_rollout: null argument");
-  ASVRL_REQUIRE(ro->n_steps >= 1, "asvrl_env_rollout: n_steps must be >= 1");
-  ASVRL_REQUIRE(ro->actions != nullptr, "asvrl_env_rollout: null actions");
-  if (int rc = rollout_checks("asvrl_env_rollout", params, state, ctl, out, ro, launch)) return rc;
-  if (state->n_envs == 0) return 0;
-  const AsvEnvLaunch lz{};
-  const AsvEnvLaunch& lc = launch != nullptr ? *launch : lz;
-  const int nm = ctl->noise_mode == 0 ? 0 : (ctl->noise_mode == 1 ? 1 : 2);
-  const PairLaunch pl = pair_launch(state->max_robots, state->max_obs, state->n_envs, lc.block, lc.envs_per_block,
-                                    nm == 2 ? 4 : 8);
-  const bool per_robot = state->robot_params != nullptr;
-  ASVRL_REQUIRE(lc.layout != 1 || pl.smem <= 150 * 1024, "asvrl_env_rollout: the pair layout's LDS does not fit");
-  ASVRL_REQUIRE(lc.layout != 1 || !per_robot, "asvrl_env_rollout: per-robot parameters take the sweep layout (2)");
-  hipStream_t st = as_stream(stream);
-  if (ro->steps_run != nullptr && hipMemsetAsync(ro->steps_run, 0, sizeof(int32_t) * state->n_envs, st) != hipSuccess)
-    return check_launch("asvrl_env_rollout");
-  if (lc.layout != 2 && !per_robot && pl.smem <= 150 * 1024) {
-    const int groups = (state->n_envs + pl.epb - 1) / pl.epb;
-    const int chunk = lc.max_groups > 0 && lc.max_groups < groups ? lc.max_groups : groups;
-    auto go = [&](auto kern) {
-      RolloutArgs a{PairsArgs{*params, *state, *ctl, *out, ro->actions, ro->noise, pl.epb, 0}, *ro};
-      for (int g0 = 0; g0 < groups; g0 += chunk) {
-        a.k.group0 = g0;
-        hipLaunchKernelGGL(kern, dim3(groups - g0 < chunk ? groups - g0 : chunk), dim3(pl.blk), pl.smem, st, a);
-      }
-    };
-    if (pl.blk == 64)
-      nm == 0 ? go(env_rollout_kernel<64, 0>) : nm == 1 ? go(env_rollout_kernel<64, 1>) : go(env_rollout_kernel<64, 2>);
-    else if (pl.blk == 128)
-      nm == 0 ? go(env_rollout_kernel<128, 0>) : nm == 1 ? go(env_rollout_kernel<128, 1>) : go(env_rollout_kernel<128, 2>);
-    else
-      nm == 0 ? go(env_rollout_kernel<256, 0>) : nm == 1 ? go(env_rollout_kernel<256, 1>) : go(env_rollout_kernel<256, 2>);
-    return check_launch("asvrl_env_rollout");
-  }
-  // the sweep layout: K single launches; hold_done's mask lives in a stream-ordered scratch of n_envs bytes
-  const size_t NT = static_cast<size_t>(state->n_envs) * state->max_robots;
-  const size_t noise_row = NT * (static_cast<size_t>(state->max_obs) + state->max_robots) * 5;
-  uint8_t* hold_mask = nullptr;
-  if (ro->hold_done) {
-    if (hipMallocAsync(reinterpret_cast<void**>(&hold_mask), state->n_envs, st) != hipSuccess)
-      return check_launch("asvrl_env_rollout");
-    if (ctl->env_mask != nullptr)
-      (void)hipMemcpyAsync(hold_mask, ctl->env_mask, state->n_envs, hipMemcpyDeviceToDevice, st);
-    else
-      (void)hipMemsetAsync(hold_mask, 1, state->n_envs, st);
-  }
-  int rc = 0;
-  for (int t = 0; t < ro->n_steps && rc == 0; ++t) {
-    AsvStepCtl c = *ctl;
-    c.counter = ctl->counter + static_cast<uint64_t>(t);
-    if (hold_mask != nullptr) c.env_mask = hold_mask;
-    rc = asvrl_env_step_ex(params, state, ro->actions + static_cast<size_t>(t) * 2 * NT,
-                           ro->noise != nullptr ? ro->noise + static_cast<size_t>(t) * noise_row : nullptr, &c, out,
-                           launch, stream);
-    if (rc == 0) {
-      hipLaunchKernelGGL(rollout_record_kernel, dim3((state->n_envs + kBlock - 1) / kBlock), dim3(kBlock), 0, st,
-                         *state, *out, *ro, t, c.env_mask, hold_mask);
-      rc = check_launch("asvrl_env_rollout");
-    }
-  }
-  if (hold_mask != nullptr) (void)hipFreeAsync(hold_mask, st);
-  return rc;
 }
 
 // The closed-loop launch's shape: 256-lane workgroups, one per CU (the Actor's weights fill most of its LDS), so
 // enough envs per workgroup that the batch makes about one workgroup per CU (4096 envs x 5 robots: 16 envs, 256
 // workgroups), never fewer than the open-loop shape's, and as many as the LDS left beside the weights holds.
-// AsvEnvLaunch overrides block and envs_per_block. fits = false: the sweep fallback.
+// AsvEnvLaunch overrides block and envs_per_block. fits = false: the K-launch fallback.
 struct PolicyLaunch {
   PairLaunch pl;
   size_t smem;   // dynamic: the pair carve + the observation rows and action pairs
@@ -2054,193 +1983,206 @@ static PolicyLaunch policy_launch(int R, int O, int n_envs, int blk_req, int epb
   return L;
 }
 
-extern "C" int asvrl_policy_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
-                                    const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi,
-                                    const AsvEnvLaunch* launch, void* stream) {
-  ASVRL_REQUIRE(params && state && ctl && out && ro, "asvrl_policy_rollout: null argument");
-  ASVRL_REQUIRE(ro->n_steps >= 1, "asvrl_policy_rollout: n_steps must be >= 1");
-  ASVRL_REQUIRE(ro->actions == nullptr, "asvrl_policy_rollout: ro->actions must be null (the policy supplies the actions)");
-  ASVRL_REQUIRE(pi != nullptr, "asvrl_policy_rollout: null policy");
-  ASVRL_REQUIRE(pi->obs_in != nullptr, "asvrl_policy_rollout: null obs_in");
-  ASVRL_REQUIRE(ctl->is_continuous, "asvrl_policy_rollout: is_continuous must be 1 (the Actor is the continuous agent)");
-  const AsvMlpWeights& w = pi->w;
-  ASVRL_REQUIRE(w.enc_frag && w.b_enc && w.w1_frag && w.w2_frag && w.b1 && w.b2 && w.wout && w.bout,
-                "asvrl_policy_rollout: null actor image");
-  if (int rc = rollout_checks("asvrl_policy_rollout", params, state, ctl, out, ro, launch)) return rc;
-  ASVRL_REQUIRE(reinterpret_cast<uintptr_t>(pi->obs_in) % 16 == 0 && reinterpret_cast<uintptr_t>(out->obs) % 16 == 0,
-                "asvrl_policy_rollout: observation rows must be 16-byte aligned");
-  if (state->n_envs == 0) return 0;
+// The resolved launch of one call.
+struct EnvPlan {
+  int nm;              // the kernels' noise argument: 0 recorded rows, 1 Philox, 2 Philox with f32 radius draws
+  bool per_robot;      // per-robot parameters: the sweep layout only
+  bool fused;          // the pair-parallel kernel is taken; false: the sweep step / the K-launch fallback
+  PairLaunch pl;       // (fused only, as everything below)
+  size_t smem;         // dynamic LDS: the pair carve, the policy rows (closed loop), the auto-reset's LDS
+  int ar_off;          // where the auto-reset's LDS starts in it
+  int groups, chunk;   // workgroups in all and per launch (AsvEnvLaunch max_groups)
+};
+// The open loop takes the pair layout where its carve fits 150 KB, and refuses an explicit layout 1 that cannot be
+// had; the closed loop takes it where policy_launch fits the carve beside the Actor, and falls back otherwise.
+static int env_plan(const char* who, const AsvEnvState* state, const AsvStepCtl* ctl, const AsvEnvLaunch* launch,
+                    bool closed, bool ar, EnvPlan* plan) {
   const AsvEnvLaunch lz{};
   const AsvEnvLaunch& lc = launch != nullptr ? *launch : lz;
-  const int nm = ctl->noise_mode == 0 ? 0 : (ctl->noise_mode == 1 ? 1 : 2);
-  const bool per_robot = state->robot_params != nullptr;
-  hipStream_t st = as_stream(stream);
-  const size_t NT = static_cast<size_t>(state->n_envs) * state->max_robots;
-  if (ro->steps_run != nullptr && hipMemsetAsync(ro->steps_run, 0, sizeof(int32_t) * state->n_envs, st) != hipSuccess)
-    return check_launch("asvrl_policy_rollout");
-  if (lc.layout != 2 && !per_robot) {
-    const PolicyLaunch L = policy_launch(state->max_robots, state->max_obs, state->n_envs, lc.block, lc.envs_per_block,
-                                         nm == 2 ? 4 : 8);
-    if (L.fits) {
-      const PairLaunch& pl = L.pl;
-      const int groups = (state->n_envs + pl.epb - 1) / pl.epb;
-      const int chunk = lc.max_groups > 0 && lc.max_groups < groups ? lc.max_groups : groups;
-      auto go = [&](auto kern) {
-        PolicyArgs a{PairsArgs{*params, *state, *ctl, *out, nullptr, ro->noise, pl.epb, 0}, *ro, *pi};
-        for (int g0 = 0; g0 < groups; g0 += chunk) {
-          a.k.group0 = g0;
-          hipLaunchKernelGGL(kern, dim3(groups - g0 < chunk ? groups - g0 : chunk), dim3(pl.blk), L.smem, st, a);
-        }
-      };
-      if (pl.blk == 64)
-        nm == 0 ? go(env_policy_rollout_kernel<64, 0>) : nm == 1 ? go(env_policy_rollout_kernel<64, 1>) : go(env_policy_rollout_kernel<64, 2>);
-      else if (pl.blk == 128)
-        nm == 0 ? go(env_policy_rollout_kernel<128, 0>) : nm == 1 ? go(env_policy_rollout_kernel<128, 1>) : go(env_policy_rollout_kernel<128, 2>);
-      else
-        nm == 0 ? go(env_policy_rollout_kernel<256, 0>) : nm == 1 ? go(env_policy_rollout_kernel<256, 1>) : go(env_policy_rollout_kernel<256, 2>);
-      return check_launch("asvrl_policy_rollout");
+  EnvPlan P{};
+  P.nm = ctl->noise_mode == 0 ? 0 : (ctl->noise_mode == 1 ? 1 : 2);
+  P.per_robot = state->robot_params != nullptr;
+  const int vm_bytes = P.nm == 2 ? 4 : 8;
+  if (!closed) {
+    P.pl = pair_launch(state->max_robots, state->max_obs, state->n_envs, lc.block, lc.envs_per_block, vm_bytes);
+    P.smem = P.pl.smem;
+    if (ar) {
+      P.ar_off = static_cast<int>(policy_rows_offset(P.pl.smem));
+      P.smem = P.ar_off + autoreset_lds(P.pl.blk, P.pl.epb);
     }
+    ENV_REQUIRE(lc.layout != 1 || P.smem <= 150 * 1024, "the pair layout's LDS does not fit");
+    ENV_REQUIRE(lc.layout != 1 || !P.per_robot, "per-robot parameters take the sweep layout (2)");
+    P.fused = lc.layout != 2 && !P.per_robot && P.smem <= 150 * 1024;
+  } else if (lc.layout != 2 && !P.per_robot) {
+    const PolicyLaunch L = policy_launch(state->max_robots, state->max_obs, state->n_envs, lc.block, lc.envs_per_block,
+                                         vm_bytes, ar);
+    P.pl = L.pl;
+    P.smem = L.smem;
+    if (ar) P.ar_off = static_cast<int>(L.smem - autoreset_lds(L.pl.blk, L.pl.epb));
+    P.fused = L.fits;
   }
-  // the fallback: K x (the act launch into a stream-ordered scratch, the single step, the record launches)
-  const size_t noise_row = NT * (static_cast<size_t>(state->max_obs) + state->max_robots) * 5;
-  double* act = nullptr;       // [NT][2] f64, then the act launch's step count (i64)
-  uint8_t* hold_mask = nullptr;
-  if (hipMallocAsync(reinterpret_cast<void**>(&act), sizeof(double) * 2 * NT + sizeof(int64_t), st) != hipSuccess)
-    return check_launch("asvrl_policy_rollout");
-  int64_t* step = reinterpret_cast<int64_t*>(act + 2 * NT);
+  if (P.fused) {
+    P.groups = (state->n_envs + P.pl.epb - 1) / P.pl.epb;
+    P.chunk = lc.max_groups > 0 && lc.max_groups < P.groups ? lc.max_groups : P.groups;
+  }
+  *plan = P;
+  return 0;
+}
+
+// The kernel family of an argument struct, and the PairsArgs in it. The auto-reset kernels exist for Philox noise only.
+template <int B, int NM> static auto kernel_of(const PairsArgs&) { return &env_pairs_kernel<B, NM>; }
+template <int B, int NM> static auto kernel_of(const RolloutArgs&) { return &env_rollout_kernel<B, NM>; }
+template <int B, int NM> static auto kernel_of(const PolicyArgs&) { return &env_policy_rollout_kernel<B, NM>; }
+template <int B, int NM> static auto kernel_of(const RolloutArArgs&) { return &env_rollout_ar_kernel<B, NM>; }
+template <int B, int NM> static auto kernel_of(const PolicyArArgs&) { return &env_policy_rollout_ar_kernel<B, NM>; }
+template <class Args>
+constexpr bool kPhiloxOnly = std::is_same<Args, RolloutArArgs>::value || std::is_same<Args, PolicyArArgs>::value;
+static PairsArgs& pairs_of(PairsArgs& a) { return a; }
+template <class Args> static PairsArgs& pairs_of(Args& a) { return a.k; }
+
+template <int B, class Args>
+static auto kernel_for_noise(int nm, const Args& a) -> void (*)(Args) {
+  if constexpr (!kPhiloxOnly<Args>) {
+    if (nm == 0) return kernel_of<B, 0>(a);
+  }
+  return nm == 1 ? kernel_of<B, 1>(a) : kernel_of<B, 2>(a);
+}
+// The pair-parallel launch of any of the five kernels: P.groups workgroups in launches of at most P.chunk, each
+// told its first group.
+template <class Args>
+static int launch_groups(const char* who, const EnvPlan& P, Args a, hipStream_t st) {
+  void (*const kern)(Args) = P.pl.blk == 64    ? kernel_for_noise<64>(P.nm, a)
+                             : P.pl.blk == 128 ? kernel_for_noise<128>(P.nm, a)
+                                               : kernel_for_noise<256>(P.nm, a);
+  for (int g0 = 0; g0 < P.groups; g0 += P.chunk) {
+    pairs_of(a).group0 = g0;
+    hipLaunchKernelGGL(kern, dim3(P.groups - g0 < P.chunk ? P.groups - g0 : P.chunk), dim3(P.pl.blk), P.smem, st, a);
+  }
+  return check_launch(who);
+}
+
+extern "C" int asvrl_env_step_ex(const AsvParams* params, const AsvEnvState* state, const double* actions,
+                                 const double* noise, const AsvStepCtl* ctl, const AsvStepOut* out,
+                                 const AsvEnvLaunch* launch, void* stream) {
+  const char* who = "asvrl_env_step";
+  if (int rc = env_checks(who, 0, params, state, actions, noise, ctl, out, nullptr, nullptr, nullptr, launch)) return rc;
+  if (state->n_envs == 0) return 0;
+  EnvPlan P;
+  if (int rc = env_plan(who, state, ctl, launch, false, false, &P)) return rc;
+  if (P.fused)
+    return launch_groups(who, P, PairsArgs{*params, *state, *ctl, *out, actions, noise, P.pl.epb, 0}, as_stream(stream));
+  const int blk = step_block(state->max_robots);
+  const int epb = blk / state->max_robots;
+  const int grid = (state->n_envs + epb - 1) / epb;
+  const size_t smem = env_sweep_smem(state->max_robots, state->max_obs);
+  ASVRL_REQUIRE(smem <= 160 * 1024, "asvrl_env_step: max_obs too large for LDS");
+  auto sweep = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(blk), smem, as_stream(stream), *params, *state, actions, noise, *ctl,
+                       *out);
+  };
+  if (blk == 64)
+    P.per_robot ? sweep(env_sweep_kernel<64, true>) : sweep(env_sweep_kernel<64, false>);
+  else
+    P.per_robot ? sweep(env_sweep_kernel<256, true>) : sweep(env_sweep_kernel<256, false>);
+  return check_launch(who);
+}
+
+extern "C" int asvrl_env_step(const AsvParams* params, const AsvEnvState* state, const double* actions,
+                              const double* noise, const AsvStepCtl* ctl, const AsvStepOut* out, void* stream) {
+  return asvrl_env_step_ex(params, state, actions, noise, ctl, out, nullptr, stream);
+}
+
+// the Actor's act launch over n rows x: the actions into act, the step count read from step
+static AsvMlpIO act_io(const AsvPolicy* pi, const float* x, size_t n, double* act, const int64_t* step) {
+  AsvMlpIO io{};
+  io.x = x;
+  io.ldx = ASVRL_OBS_DIM;
+  io.n = static_cast<int32_t>(n);
+  io.a_out64 = act;
+  io.step_dev = step;
+  io.eps_steps_per_count = pi->eps_steps_per_count;
+  io.eps_total = pi->eps_total;
+  io.eps_fraction = pi->eps_fraction;
+  io.eps_initial = pi->eps_initial;
+  io.eps_final = pi->eps_final;
+  io.seed = pi->seed;
+  return io;
+}
+
+// The K-launch form of the four rollout calls (per-robot parameters, layout 2, a carve that does not fit). Per step:
+// the act launch (closed loop), the obs_prev row (auto-reset), the single step and its record launch; then, for the
+// auto-reset, the reset mask and counts and the reset of the ended envs with their observation
+// (asvrl_env_reset_observe, or the two launches where that call does not apply). pi null: the open loop, the actions
+// out of ro. ar null: a plain call, which alone can hold ended envs (hold_done: env_checks refuses it with ar).
+static int rollout_fallback(const char* who, const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                            const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi, const AsvAutoReset* ar,
+                            const AsvEnvLaunch* launch, void* stream) {
+  hipStream_t st = as_stream(stream);
+  const int E = state->n_envs, R = state->max_robots;
+  const size_t NT = static_cast<size_t>(E) * R;
+  const size_t noise_row = NT * (static_cast<size_t>(state->max_obs) + R) * 5;
+  const unsigned egrid = (static_cast<unsigned>(E) + kBlock - 1) / kBlock;
+  const unsigned agrid = (static_cast<unsigned>(NT) + kBlock - 1) / kBlock;
+  const unsigned qgrid = (static_cast<unsigned>(NT) * (ASVRL_OBS_DIM / 4) + kBlock - 1) / kBlock;
+  // stream-ordered scratch: the actions [NT][2] f64 and the act launch's step count (closed loop), then the reset
+  // mask [E] (auto-reset); hold_done's mask [E] is an allocation of its own
+  const size_t act_bytes = pi != nullptr ? sizeof(double) * 2 * NT + sizeof(int64_t) : 0;
+  const size_t scratch_bytes = act_bytes + (ar != nullptr ? E : 0);
+  unsigned char* scratch = nullptr;
+  if (scratch_bytes != 0 && hipMallocAsync(reinterpret_cast<void**>(&scratch), scratch_bytes, st) != hipSuccess)
+    return check_launch(who);
+  double* act = reinterpret_cast<double*>(scratch);
+  int64_t* step = pi != nullptr ? reinterpret_cast<int64_t*>(act + 2 * NT) : nullptr;
+  uint8_t* rmask = ar != nullptr ? scratch + act_bytes : nullptr;
   int rc = 0;
+  uint8_t* hold_mask = nullptr;
   if (ro->hold_done) {
-    if (hipMallocAsync(reinterpret_cast<void**>(&hold_mask), state->n_envs, st) != hipSuccess)
-      rc = check_launch("asvrl_policy_rollout");
+    if (hipMallocAsync(reinterpret_cast<void**>(&hold_mask), E, st) != hipSuccess)
+      rc = check_launch(who);
     else if (ctl->env_mask != nullptr)
-      (void)hipMemcpyAsync(hold_mask, ctl->env_mask, state->n_envs, hipMemcpyDeviceToDevice, st);
+      (void)hipMemcpyAsync(hold_mask, ctl->env_mask, E, hipMemcpyDeviceToDevice, st);
     else
-      (void)hipMemsetAsync(hold_mask, 1, state->n_envs, st);
+      (void)hipMemsetAsync(hold_mask, 1, E, st);
   }
+  bool one_launch = false;   // the auto-reset's reset and observation in one launch
+  if (ar != nullptr) {
+    const PairLaunch one = pair_launch(R, state->max_obs, E, kWave, 1, ctl->noise_mode == 2 ? 4 : 8);
+    one_launch = state->robot_params == nullptr && one.blk == kWave && one.epb == 1 && one.smem <= 60 * 1024;
+  }
+  AsvStepOut oo = *out;   // the observation pass's outputs: no episode bookkeeping
+  oo.env_done = nullptr;
+  oo.stats = nullptr;
+  const float* obs_first = pi != nullptr ? pi->obs_in : (ar != nullptr ? ar->obs_in : nullptr);
   for (int t = 0; t < ro->n_steps && rc == 0; ++t) {
     AsvStepCtl c = *ctl;
     c.counter = ctl->counter + static_cast<uint64_t>(t);
     if (hold_mask != nullptr) c.env_mask = hold_mask;
-    hipLaunchKernelGGL(policy_step_count_kernel, dim3(1), dim3(1), 0, st, pi->step_dev, step, t);
-    AsvMlpIO io{};
-    io.x = t == 0 ? pi->obs_in : out->obs;   // the observation the step before wrote
-    io.ldx = ASVRL_OBS_DIM;
-    io.n = static_cast<int32_t>(NT);
-    io.a_out64 = act;
-    io.step_dev = step;
-    io.eps_steps_per_count = pi->eps_steps_per_count;
-    io.eps_total = pi->eps_total;
-    io.eps_fraction = pi->eps_fraction;
-    io.eps_initial = pi->eps_initial;
-    io.eps_final = pi->eps_final;
-    io.seed = pi->seed;
-    rc = asvrl_actor_forward(&pi->w, &io, atile::MLP_ACT, stream);
-    if (rc == 0 && pi->actions != nullptr)
-      hipLaunchKernelGGL(policy_actions_kernel, dim3((static_cast<unsigned>(NT) + kBlock - 1) / kBlock), dim3(kBlock), 0, st,
-                         act, pi->actions + static_cast<size_t>(t) * 2 * NT, c.env_mask, state->n_envs,
-                         state->max_robots);
-    if (rc == 0)
-      rc = asvrl_env_step_ex(params, state, act, ro->noise != nullptr ? ro->noise + static_cast<size_t>(t) * noise_row : nullptr,
-                             &c, out, launch, stream);
-    if (rc == 0) {
-      hipLaunchKernelGGL(rollout_record_kernel, dim3((state->n_envs + kBlock - 1) / kBlock), dim3(kBlock), 0, st,
-                         *state, *out, *ro, t, c.env_mask, hold_mask);
-      rc = check_launch("asvrl_policy_rollout");
-    }
-  }
-  if (hold_mask != nullptr) (void)hipFreeAsync(hold_mask, st);
-  (void)hipFreeAsync(act, st);
-  return rc;
-}
-
-extern "C" int64_t asvrl_policy_struct_size(void) { return sizeof(AsvPolicy); }
-
-// ------------------------------------------------------------------ auto-reset inside the rollout windows
-// what the two _ar calls refuse beyond their plain calls' checks (`who` names the call)
-static int autoreset_checks(const std::string& who, const AsvEnvState* state, const AsvStepCtl* ctl,
-                            const AsvStepOut* out, const AsvRollout* ro, const AsvAutoReset* ar, bool open_loop) {
-  ASVRL_REQUIRE(ar != nullptr, who + ": null ar (the auto-reset description)");
-  ASVRL_REQUIRE(!ro->hold_done, who + ": ro->hold_done cannot be combined with the auto-reset");
-  ASVRL_REQUIRE(ctl->trainer_deactivate && out->env_done != nullptr,
-                who + ": the auto-reset needs ctl->trainer_deactivate and last->env_done");
-  ASVRL_REQUIRE(ctl->noise_mode == 1 || ctl->noise_mode == 2,
-                who + ": noise_mode 0 (recorded noise) cannot cover a sampled reset; Philox noise only (mode 1 or 2)");
-  ASVRL_REQUIRE(!open_loop || ar->obs_prev == nullptr || ar->obs_in != nullptr,
-                who + ": ar->obs_prev needs ar->obs_in (the rows in front of step 0)");
-  ASVRL_REQUIRE(ar->cfg.num_robots >= 0 && ar->cfg.num_robots <= kResetMaxR && state->max_robots <= kResetMaxR,
-                who + ": ar->cfg.num_robots / max_robots beyond the reset sampler's 32");
-  ASVRL_REQUIRE(ar->cfg.num_obs >= 0 && ar->cfg.num_obs <= kResetMaxO && state->max_obs <= kResetMaxO,
-                who + ": ar->cfg.num_obs / max_obs beyond the reset sampler's 32");
-  ASVRL_REQUIRE(ar->cfg.num_cores >= 0 && ar->cfg.num_cores <= kMaxCores && state->max_cores <= kMaxCores,
-                who + ": ar->cfg.num_cores / max_cores beyond the reset sampler's 16");
-  ASVRL_REQUIRE(ar->cfg.width > 4.0 && ar->cfg.height > 4.0, who + ": ar->cfg map too small");
-  return 0;
-}
-
-// The K-launch form of both calls (per-robot parameters, layout 2, a carve that does not fit): per step the act
-// launch (closed loop), the obs_prev row, the single step, its record launch, the reset mask and counts, and the
-// reset of the ended envs with their observation (asvrl_env_reset_observe, or the two launches where that call does
-// not apply). pi null: the open loop.
-static int autoreset_fallback(const char* who, const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
-                              const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi, const AsvAutoReset* ar,
-                              const AsvEnvLaunch* launch, void* stream) {
-  hipStream_t st = as_stream(stream);
-  const int E = state->n_envs, R = state->max_robots;
-  const size_t NT = static_cast<size_t>(E) * R;
-  const unsigned egrid = (static_cast<unsigned>(E) + kBlock - 1) / kBlock;
-  const unsigned qgrid = (static_cast<unsigned>(NT) * (ASVRL_OBS_DIM / 4) + kBlock - 1) / kBlock;
-  // scratch: the actions [NT][2] f64 and the act launch's step count (closed loop), then the reset mask [E]
-  unsigned char* scratch = nullptr;
-  const size_t act_bytes = pi != nullptr ? sizeof(double) * 2 * NT + sizeof(int64_t) : 0;
-  if (hipMallocAsync(reinterpret_cast<void**>(&scratch), act_bytes + E, st) != hipSuccess) return check_launch(who);
-  double* act = reinterpret_cast<double*>(scratch);
-  int64_t* step = reinterpret_cast<int64_t*>(scratch + sizeof(double) * 2 * NT);
-  uint8_t* rmask = scratch + act_bytes;
-  const PairLaunch one = pair_launch(R, state->max_obs, E, kWave, 1, ctl->noise_mode == 2 ? 4 : 8);
-  const bool one_launch = state->robot_params == nullptr && one.blk == kWave && one.epb == 1 && one.smem <= 60 * 1024;
-  AsvStepOut oo = *out;   // the observation pass's outputs: no episode bookkeeping
-  oo.env_done = nullptr;
-  oo.stats = nullptr;
-  const float* obs_first = pi != nullptr ? pi->obs_in : ar->obs_in;
-  int rc = 0;
-  for (int t = 0; t < ro->n_steps && rc == 0; ++t) {
-    AsvStepCtl c = *ctl;
-    c.counter = ctl->counter + static_cast<uint64_t>(t);
     const float* obs_t = t == 0 ? obs_first : out->obs;   // the observation the step before (or its reset) wrote
-    const double* actions = nullptr;
+    const double* actions = act;
     if (pi != nullptr) {
       hipLaunchKernelGGL(policy_step_count_kernel, dim3(1), dim3(1), 0, st, pi->step_dev, step, t);
-      AsvMlpIO io{};
-      io.x = obs_t;
-      io.ldx = ASVRL_OBS_DIM;
-      io.n = static_cast<int32_t>(NT);
-      io.a_out64 = act;
-      io.step_dev = step;
-      io.eps_steps_per_count = pi->eps_steps_per_count;
-      io.eps_total = pi->eps_total;
-      io.eps_fraction = pi->eps_fraction;
-      io.eps_initial = pi->eps_initial;
-      io.eps_final = pi->eps_final;
-      io.seed = pi->seed;
+      const AsvMlpIO io = act_io(pi, obs_t, NT, act, step);
       rc = asvrl_actor_forward(&pi->w, &io, atile::MLP_ACT, stream);
       if (rc == 0 && pi->actions != nullptr)
-        hipLaunchKernelGGL(policy_actions_kernel, dim3((static_cast<unsigned>(NT) + kBlock - 1) / kBlock), dim3(kBlock), 0, st,
-                           act, pi->actions + static_cast<size_t>(t) * 2 * NT, c.env_mask, E, R);
-      actions = act;
+        hipLaunchKernelGGL(policy_actions_kernel, dim3(agrid), dim3(kBlock), 0, st, act,
+                           pi->actions + static_cast<size_t>(t) * 2 * NT, c.env_mask, E, R);
     } else {
       actions = ro->actions + static_cast<size_t>(t) * 2 * NT;
     }
-    if (rc == 0 && ar->obs_prev != nullptr)
+    if (rc == 0 && ar != nullptr && ar->obs_prev != nullptr)
       hipLaunchKernelGGL(autoreset_obs_prev_kernel, dim3(qgrid), dim3(kBlock), 0, st, obs_t,
                          ar->obs_prev + static_cast<size_t>(t) * NT * ASVRL_OBS_DIM, c.env_mask, E, R);
-    if (rc == 0) rc = asvrl_env_step_ex(params, state, actions, nullptr, &c, out, launch, stream);
+    // recorded noise rows go to the plain calls only: the auto-reset is Philox noise throughout (env_checks)
+    const double* noise = ar == nullptr && ro->noise != nullptr ? ro->noise + static_cast<size_t>(t) * noise_row : nullptr;
+    if (rc == 0) rc = asvrl_env_step_ex(params, state, actions, noise, &c, out, launch, stream);
     if (rc != 0) break;
     hipLaunchKernelGGL(rollout_record_kernel, dim3(egrid), dim3(kBlock), 0, st, *state, *out, *ro, t, c.env_mask,
-                       static_cast<uint8_t*>(nullptr));
-    hipLaunchKernelGGL(autoreset_mask_kernel, dim3(egrid), dim3(kBlock), 0, st, out->env_done, c.env_mask, out->obj_cnt,
-                       E, R, rmask, ar->resets, ar->pushed != nullptr ? ar->pushed + t : nullptr);
+                       hold_mask);
+    if (ar != nullptr)
+      hipLaunchKernelGGL(autoreset_mask_kernel, dim3(egrid), dim3(kBlock), 0, st, out->env_done, c.env_mask, out->obj_cnt,
+                         E, R, rmask, ar->resets, ar->pushed != nullptr ? ar->pushed + t : nullptr);
     rc = check_launch(who);
-    if (rc != 0) break;
+    if (rc != 0 || ar == nullptr) continue;
     AsvStepCtl co{};
     co.is_continuous = ctl->is_continuous;
     co.noise_mode = ctl->noise_mode;
@@ -2256,112 +2198,61 @@ static int autoreset_fallback(const char* who, const AsvParams* params, const As
       if (rc == 0) rc = asvrl_env_step_ex(params, state, nullptr, nullptr, &co, &oo, launch, stream);
     }
   }
-  (void)hipFreeAsync(scratch, st);
+  if (hold_mask != nullptr) (void)hipFreeAsync(hold_mask, st);
+  if (scratch != nullptr) (void)hipFreeAsync(scratch, st);
   return rc;
 }
+
+// The four rollout calls: check, plan, zero the counts the window adds to, then the one launch or the fallback.
+// pi: the closed loop (ro->actions is null then); ar: the auto-reset (Philox noise only: no recorded rows).
+static int rollout_call(const char* who, unsigned kind, const AsvParams* params, const AsvEnvState* state,
+                        const AsvStepCtl* ctl, const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi,
+                        const AsvAutoReset* ar, const AsvEnvLaunch* launch, void* stream) {
+  if (int rc = env_checks(who, kind, params, state, nullptr, nullptr, ctl, out, ro, pi, ar, launch)) return rc;
+  if (state->n_envs == 0) return 0;
+  EnvPlan P;
+  if (int rc = env_plan(who, state, ctl, launch, pi != nullptr, ar != nullptr, &P)) return rc;
+  hipStream_t st = as_stream(stream);
+  if (ro->steps_run != nullptr && hipMemsetAsync(ro->steps_run, 0, sizeof(int32_t) * state->n_envs, st) != hipSuccess)
+    return check_launch(who);
+  if (ar != nullptr && ar->resets != nullptr &&
+      hipMemsetAsync(ar->resets, 0, sizeof(int32_t) * state->n_envs, st) != hipSuccess)
+    return check_launch(who);
+  if (!P.fused) return rollout_fallback(who, params, state, ctl, out, ro, pi, ar, launch, stream);
+  const PairsArgs k{*params, *state, *ctl, *out, ro->actions, ar != nullptr ? nullptr : ro->noise, P.pl.epb, 0};
+  if (pi != nullptr && ar != nullptr) return launch_groups(who, P, PolicyArArgs{k, *ro, *pi, *ar, P.ar_off}, st);
+  if (ar != nullptr) return launch_groups(who, P, RolloutArArgs{k, *ro, *ar, P.ar_off}, st);
+  if (pi != nullptr) return launch_groups(who, P, PolicyArgs{k, *ro, *pi}, st);
+  return launch_groups(who, P, RolloutArgs{k, *ro}, st);
+}
+
+extern "C" int asvrl_env_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                                 const AsvStepOut* out, const AsvRollout* ro, const AsvEnvLaunch* launch,
+                                 void* stream) {
+  return rollout_call("asvrl_env_rollout", kRollout, params, state, ctl, out, ro, nullptr, nullptr, launch, stream);
+}
+
+extern "C" int asvrl_policy_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                                    const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi,
+                                    const AsvEnvLaunch* launch, void* stream) {
+  return rollout_call("asvrl_policy_rollout", kRollout | kClosedLoop, params, state, ctl, out, ro, pi, nullptr, launch,
+                      stream);
+}
+
+extern "C" int64_t asvrl_policy_struct_size(void) { return sizeof(AsvPolicy); }
 
 extern "C" int asvrl_env_rollout_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                     const AsvStepOut* out, const AsvRollout* ro, const AsvAutoReset* ar,
                                     const AsvEnvLaunch* launch, void* stream) {
-  const char* who = "asvrl_env_rollout_ar";
-  ASVRL_REQUIRE(params && state && ctl && out && ro, "asvrl_env_rollout_ar: null argument");
-  if (int rc = autoreset_checks(who, state, ctl, out, ro, ar, true)) return rc;
-  ASVRL_REQUIRE(ro->n_steps >= 1, "asvrl_env_rollout_ar: n_steps must be >= 1");
-  ASVRL_REQUIRE(ro->actions != nullptr, "asvrl_env_rollout_ar: null actions");
-  if (int rc = rollout_checks(who, params, state, ctl, out, ro, launch)) return rc;
-  ASVRL_REQUIRE(ar->obs_prev == nullptr || (reinterpret_cast<uintptr_t>(ar->obs_in) % 16 == 0 &&
-                                            reinterpret_cast<uintptr_t>(ar->obs_prev) % 16 == 0),
-                "asvrl_env_rollout_ar: ar->obs_in / ar->obs_prev rows must be 16-byte aligned");
-  if (state->n_envs == 0) return 0;
-  const AsvEnvLaunch lz{};
-  const AsvEnvLaunch& lc = launch != nullptr ? *launch : lz;
-  const int nm = ctl->noise_mode == 1 ? 1 : 2;
-  const PairLaunch pl = pair_launch(state->max_robots, state->max_obs, state->n_envs, lc.block, lc.envs_per_block,
-                                    nm == 2 ? 4 : 8);
-  const bool per_robot = state->robot_params != nullptr;
-  const size_t ar_off = policy_rows_offset(pl.smem), smem = ar_off + autoreset_lds(pl.blk, pl.epb);
-  ASVRL_REQUIRE(lc.layout != 1 || smem <= 150 * 1024, "asvrl_env_rollout_ar: the pair layout's LDS does not fit");
-  ASVRL_REQUIRE(lc.layout != 1 || !per_robot, "asvrl_env_rollout_ar: per-robot parameters take the sweep layout (2)");
-  hipStream_t st = as_stream(stream);
-  if (ro->steps_run != nullptr && hipMemsetAsync(ro->steps_run, 0, sizeof(int32_t) * state->n_envs, st) != hipSuccess)
-    return check_launch(who);
-  if (ar->resets != nullptr && hipMemsetAsync(ar->resets, 0, sizeof(int32_t) * state->n_envs, st) != hipSuccess)
-    return check_launch(who);
-  if (lc.layout != 2 && !per_robot && smem <= 150 * 1024) {
-    const int groups = (state->n_envs + pl.epb - 1) / pl.epb;
-    const int chunk = lc.max_groups > 0 && lc.max_groups < groups ? lc.max_groups : groups;
-    auto go = [&](auto kern) {
-      RolloutArArgs a{PairsArgs{*params, *state, *ctl, *out, ro->actions, nullptr, pl.epb, 0}, *ro, *ar,
-                      static_cast<int>(ar_off)};
-      for (int g0 = 0; g0 < groups; g0 += chunk) {
-        a.k.group0 = g0;
-        hipLaunchKernelGGL(kern, dim3(groups - g0 < chunk ? groups - g0 : chunk), dim3(pl.blk), smem, st, a);
-      }
-    };
-    if (pl.blk == 64)
-      nm == 1 ? go(env_rollout_ar_kernel<64, 1>) : go(env_rollout_ar_kernel<64, 2>);
-    else if (pl.blk == 128)
-      nm == 1 ? go(env_rollout_ar_kernel<128, 1>) : go(env_rollout_ar_kernel<128, 2>);
-    else
-      nm == 1 ? go(env_rollout_ar_kernel<256, 1>) : go(env_rollout_ar_kernel<256, 2>);
-    return check_launch(who);
-  }
-  return autoreset_fallback(who, params, state, ctl, out, ro, nullptr, ar, launch, stream);
+  return rollout_call("asvrl_env_rollout_ar", kRollout | kAutoReset, params, state, ctl, out, ro, nullptr, ar, launch,
+                      stream);
 }
 
 extern "C" int asvrl_policy_rollout_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                        const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi,
                                        const AsvAutoReset* ar, const AsvEnvLaunch* launch, void* stream) {
-  const char* who = "asvrl_policy_rollout_ar";
-  ASVRL_REQUIRE(params && state && ctl && out && ro, "asvrl_policy_rollout_ar: null argument");
-  if (int rc = autoreset_checks(who, state, ctl, out, ro, ar, false)) return rc;
-  ASVRL_REQUIRE(ro->n_steps >= 1, "asvrl_policy_rollout_ar: n_steps must be >= 1");
-  ASVRL_REQUIRE(ro->actions == nullptr, "asvrl_policy_rollout_ar: ro->actions must be null (the policy supplies the actions)");
-  ASVRL_REQUIRE(pi != nullptr, "asvrl_policy_rollout_ar: null policy");
-  ASVRL_REQUIRE(pi->obs_in != nullptr, "asvrl_policy_rollout_ar: null obs_in");
-  ASVRL_REQUIRE(ctl->is_continuous, "asvrl_policy_rollout_ar: is_continuous must be 1 (the Actor is the continuous agent)");
-  const AsvMlpWeights& w = pi->w;
-  ASVRL_REQUIRE(w.enc_frag && w.b_enc && w.w1_frag && w.w2_frag && w.b1 && w.b2 && w.wout && w.bout,
-                "asvrl_policy_rollout_ar: null actor image");
-  if (int rc = rollout_checks(who, params, state, ctl, out, ro, launch)) return rc;
-  ASVRL_REQUIRE(reinterpret_cast<uintptr_t>(pi->obs_in) % 16 == 0 && reinterpret_cast<uintptr_t>(out->obs) % 16 == 0 &&
-                    reinterpret_cast<uintptr_t>(ar->obs_prev) % 16 == 0,
-                "asvrl_policy_rollout_ar: observation rows must be 16-byte aligned");
-  if (state->n_envs == 0) return 0;
-  const AsvEnvLaunch lz{};
-  const AsvEnvLaunch& lc = launch != nullptr ? *launch : lz;
-  const int nm = ctl->noise_mode == 1 ? 1 : 2;
-  const bool per_robot = state->robot_params != nullptr;
-  hipStream_t st = as_stream(stream);
-  if (ro->steps_run != nullptr && hipMemsetAsync(ro->steps_run, 0, sizeof(int32_t) * state->n_envs, st) != hipSuccess)
-    return check_launch(who);
-  if (ar->resets != nullptr && hipMemsetAsync(ar->resets, 0, sizeof(int32_t) * state->n_envs, st) != hipSuccess)
-    return check_launch(who);
-  if (lc.layout != 2 && !per_robot) {
-    const PolicyLaunch L = policy_launch(state->max_robots, state->max_obs, state->n_envs, lc.block, lc.envs_per_block,
-                                         nm == 2 ? 4 : 8, true);
-    if (L.fits) {
-      const PairLaunch& pl = L.pl;
-      const int groups = (state->n_envs + pl.epb - 1) / pl.epb;
-      const int chunk = lc.max_groups > 0 && lc.max_groups < groups ? lc.max_groups : groups;
-      auto go = [&](auto kern) {
-        PolicyArArgs a{PairsArgs{*params, *state, *ctl, *out, nullptr, nullptr, pl.epb, 0}, *ro, *pi, *ar,
-                       static_cast<int>(L.smem - autoreset_lds(pl.blk, pl.epb))};
-        for (int g0 = 0; g0 < groups; g0 += chunk) {
-          a.k.group0 = g0;
-          hipLaunchKernelGGL(kern, dim3(groups - g0 < chunk ? groups - g0 : chunk), dim3(pl.blk), L.smem, st, a);
-        }
-      };
-      if (pl.blk == 64)
-        nm == 1 ? go(env_policy_rollout_ar_kernel<64, 1>) : go(env_policy_rollout_ar_kernel<64, 2>);
-      else if (pl.blk == 128)
-        nm == 1 ? go(env_policy_rollout_ar_kernel<128, 1>) : go(env_policy_rollout_ar_kernel<128, 2>);
-      else
-        nm == 1 ? go(env_policy_rollout_ar_kernel<256, 1>) : go(env_policy_rollout_ar_kernel<256, 2>);
-      return check_launch(who);
-    }
-  }
-  return autoreset_fallback(who, params, state, ctl, out, ro, pi, ar, launch, stream);
+  return rollout_call("asvrl_policy_rollout_ar", kRollout | kClosedLoop | kAutoReset, params, state, ctl, out, ro, pi, ar,
+                      launch, stream);
 }
 
 extern "C" int64_t asvrl_autoreset_struct_size(void) { return sizeof(AsvAutoReset); }

@@ -6,6 +6,7 @@ Both the vectorised training env (vec_env.VecMarineNavEnv) and the drop-in singl
 MarineNavEnv3 (envs/marinenav/env.py) sit on top of it.
 """
 import ctypes as C
+import types
 
 import torch
 
@@ -185,6 +186,57 @@ class DeviceEnvBatch:
         ar.pushed, ar.resets = pushed.data_ptr(), resets.data_ptr()
         return ar, pushed, resets
 
+    def _rollout_args(self, who, K, extra_specs, *, noise, keep, hold_done, is_continuous, trainer_deactivate, seed,
+                      counter, counter_dev, gamma, env_mask, obs, obj_cnt, fast_noise, launch, auto_reset):
+        """What rollout() and policy_rollout() build alike: a namespace of the AsvStepCtl (ctl), the AsvRollout
+        without its actions (ro), the AsvAutoReset or None (ar, with pushed / resets), the kept records (specs, rec,
+        steps_run), the state and output structs (st, out) and the launch (ln)."""
+        if noise is not None:
+            assert noise.dtype == torch.float64 and noise.is_contiguous()
+            assert noise.numel() == K * self.n_envs * self.max_robots * (self.max_obs + self.max_robots) * 5
+        specs = self._record_specs()
+        specs.update(extra_specs)
+        ar = pushed = resets = None
+        if auto_reset is not None:
+            ar, pushed, resets = self._auto_reset(who, auto_reset, K, specs)
+        rec, steps_run = self._records(who, keep, K, specs, trainer_deactivate)
+        ctl = _abi.AsvStepCtl()
+        ctl.is_continuous = int(bool(is_continuous))
+        ctl.do_dynamics = 1
+        ctl.trainer_deactivate = int(bool(trainer_deactivate))
+        ctl.noise_mode = 0 if noise is not None else (2 if fast_noise else 1)
+        ctl.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        ctl.counter = int(counter) & 0xFFFFFFFFFFFFFFFF
+        ctl.counter_dev = counter_dev.data_ptr() if counter_dev is not None else None
+        ctl.gamma = float(gamma)
+        ctl.env_mask = env_mask.data_ptr() if env_mask is not None else None
+        ro = _abi.AsvRollout()
+        ro.n_steps, ro.hold_done = K, int(bool(hold_done))
+        ro.noise = noise.data_ptr() if noise is not None else None
+        for name, t in rec.items():
+            if name not in ("actions", "obs_prev"):   # (AsvPolicy's and AsvAutoReset's records)
+                setattr(ro, name, t.data_ptr())
+        ro.steps_run = steps_run.data_ptr()
+        if ar is not None:
+            ar.obs_prev = rec["obs_prev"].data_ptr() if "obs_prev" in rec else None
+        ln = C.byref(_abi.AsvEnvLaunch(*(int(v) for v in launch))) if launch is not None else None
+        return types.SimpleNamespace(ctl=ctl, ro=ro, ar=ar, pushed=pushed, resets=resets, specs=specs, rec=rec,
+                                     steps_run=steps_run, st=self.state_struct(), ln=ln,
+                                     out=self.out_struct(obs, obj_cnt, with_env_done=trainer_deactivate))
+
+    def _rollout_call(self, b, L, name, extra, stream):
+        """Call `name` of library L on _rollout_args' b (its _ar form under auto_reset), `extra` the arguments between
+        the AsvRollout and the auto-reset; returns the namespace of the kept records and counts."""
+        args = [C.byref(self.params), C.byref(b.st), C.byref(b.ctl), C.byref(b.out), C.byref(b.ro)] + extra
+        counts = {}
+        if b.ar is not None:
+            name += "_ar"
+            args.append(C.byref(b.ar))
+            counts = dict(resets=b.resets, pushed=b.pushed)
+        rc = getattr(L, name)(*args, b.ln, _abi.stream_ptr(stream))
+        _abi.check(rc, name, L)
+        return types.SimpleNamespace(steps_run=b.steps_run, **counts, **{n: b.rec.get(n) for n in b.specs})
+
     def rollout(self, actions, noise=None, *, keep=("reward", "done", "info"), hold_done=False, is_continuous=True,
                 trainer_deactivate=False, seed=0, counter=0, counter_dev=None, gamma=0.0, env_mask=None, obs=None,
                 obj_cnt=None, fast_noise=False, launch=None, stream=None, auto_reset=None):
@@ -203,50 +255,15 @@ class DeviceEnvBatch:
         step. Needs trainer_deactivate and Philox noise, not hold_done. keep then also takes "obs_prev"
         (f32 [K, E*R, 40]: the observation every robot row of a stepping env had in front of step t; needs
         auto_reset's obs_in), and the namespace gains resets [E] i32 and pushed [K] i32 (rows with obj_cnt >= 0)."""
-        import types
         assert actions.dtype == torch.float64 and actions.is_contiguous() and actions.dim() == 3
         K, NT = int(actions.shape[0]), self.n_envs * self.max_robots
         assert tuple(actions.shape[1:]) == (NT, 2)
-        if noise is not None:
-            assert noise.dtype == torch.float64 and noise.is_contiguous()
-            assert noise.numel() == K * NT * (self.max_obs + self.max_robots) * 5
-        specs = self._record_specs()
-        ar = pushed = resets = None
-        if auto_reset is not None:
-            ar, pushed, resets = self._auto_reset("rollout", auto_reset, K, specs)
-        rec, steps_run = self._records("rollout", keep, K, specs, trainer_deactivate)
-        ctl = _abi.AsvStepCtl()
-        ctl.is_continuous = int(bool(is_continuous))
-        ctl.do_dynamics = 1
-        ctl.trainer_deactivate = int(bool(trainer_deactivate))
-        ctl.noise_mode = 0 if noise is not None else (2 if fast_noise else 1)
-        ctl.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        ctl.counter = int(counter) & 0xFFFFFFFFFFFFFFFF
-        ctl.counter_dev = counter_dev.data_ptr() if counter_dev is not None else None
-        ctl.gamma = float(gamma)
-        ctl.env_mask = env_mask.data_ptr() if env_mask is not None else None
-        ro = _abi.AsvRollout()
-        ro.n_steps, ro.hold_done = K, int(bool(hold_done))
-        ro.actions = actions.data_ptr()
-        ro.noise = noise.data_ptr() if noise is not None else None
-        for name, t in rec.items():
-            if name != "obs_prev":
-                setattr(ro, name, t.data_ptr())
-        ro.steps_run = steps_run.data_ptr()
-        st = self.state_struct()
-        out = self.out_struct(obs, obj_cnt, with_env_done=trainer_deactivate)
-        ln = C.byref(_abi.AsvEnvLaunch(*(int(v) for v in launch))) if launch is not None else None
-        if ar is not None:
-            ar.obs_prev = rec["obs_prev"].data_ptr() if "obs_prev" in rec else None
-            rc = _abi.lib().asvrl_env_rollout_ar(C.byref(self.params), C.byref(st), C.byref(ctl), C.byref(out),
-                                                 C.byref(ro), C.byref(ar), ln, _abi.stream_ptr(stream))
-            _abi.check(rc, "asvrl_env_rollout_ar")
-            return types.SimpleNamespace(steps_run=steps_run, resets=resets, pushed=pushed,
-                                         **{n: rec.get(n) for n in specs})
-        rc = _abi.lib().asvrl_env_rollout(C.byref(self.params), C.byref(st), C.byref(ctl), C.byref(out), C.byref(ro),
-                                          ln, _abi.stream_ptr(stream))
-        _abi.check(rc, "asvrl_env_rollout")
-        return types.SimpleNamespace(steps_run=steps_run, **{n: rec.get(n) for n in specs})
+        b = self._rollout_args("rollout", K, {}, noise=noise, keep=keep, hold_done=hold_done,
+                               is_continuous=is_continuous, trainer_deactivate=trainer_deactivate, seed=seed,
+                               counter=counter, counter_dev=counter_dev, gamma=gamma, env_mask=env_mask, obs=obs,
+                               obj_cnt=obj_cnt, fast_noise=fast_noise, launch=launch, auto_reset=auto_reset)
+        b.ro.actions = actions.data_ptr()
+        return self._rollout_call(b, _abi.lib(), "asvrl_env_rollout", [], stream)
 
     def policy_rollout(self, pack, K, obs_in, *, noise=None, keep=("reward", "done", "info"), hold_done=False,
                        step_dev=None, eps=(1.0, 1.0, 1.0, 0.0, 0.0), policy_seed=0, trainer_deactivate=False, seed=0,
@@ -264,39 +281,17 @@ class DeviceEnvBatch:
         record passed in by the caller (and steps_run) the call can be graph-captured.
         auto_reset (asvrl_policy_rollout_ar): as rollout()'s; the Actor acts on a reset env's reset observation at the
         next step, and "obs_prev" records the rows it acted on at every step (obs_in comes from this call's own)."""
-        import types
         K, NT = int(K), self.n_envs * self.max_robots
         assert pack.kind == "actor"
         assert obs_in.dtype == torch.float32 and obs_in.is_contiguous() and tuple(obs_in.shape) == (NT, OBS_DIM)
-        if noise is not None:
-            assert noise.dtype == torch.float64 and noise.is_contiguous()
-            assert noise.numel() == K * NT * (self.max_obs + self.max_robots) * 5
         if step_dev is not None:
             assert step_dev.dtype == torch.int64 and step_dev.numel() >= 1
-        specs = self._record_specs()
-        specs["actions"] = ((NT, 2), torch.float64, 0)
-        ar = pushed = resets = None
-        if auto_reset is not None:
-            ar, pushed, resets = self._auto_reset("policy_rollout", auto_reset, K, specs)
-            ar.obs_in = None
-        rec, steps_run = self._records("policy_rollout", keep, K, specs, trainer_deactivate)
-        ctl = _abi.AsvStepCtl()
-        ctl.is_continuous = 1
-        ctl.do_dynamics = 1
-        ctl.trainer_deactivate = int(bool(trainer_deactivate))
-        ctl.noise_mode = 0 if noise is not None else (2 if fast_noise else 1)
-        ctl.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        ctl.counter = int(counter) & 0xFFFFFFFFFFFFFFFF
-        ctl.counter_dev = counter_dev.data_ptr() if counter_dev is not None else None
-        ctl.gamma = float(gamma)
-        ctl.env_mask = env_mask.data_ptr() if env_mask is not None else None
-        ro = _abi.AsvRollout()
-        ro.n_steps, ro.hold_done = K, int(bool(hold_done))
-        ro.noise = noise.data_ptr() if noise is not None else None
-        for name, t in rec.items():
-            if name not in ("actions", "obs_prev"):
-                setattr(ro, name, t.data_ptr())
-        ro.steps_run = steps_run.data_ptr()
+        b = self._rollout_args("policy_rollout", K, {"actions": ((NT, 2), torch.float64, 0)}, noise=noise, keep=keep,
+                               hold_done=hold_done, is_continuous=True, trainer_deactivate=trainer_deactivate,
+                               seed=seed, counter=counter, counter_dev=counter_dev, gamma=gamma, env_mask=env_mask,
+                               obs=obs, obj_cnt=obj_cnt, fast_noise=fast_noise, launch=launch, auto_reset=auto_reset)
+        if b.ar is not None:
+            b.ar.obs_in = None
         pi = _abi.AsvPolicy()
         pi.w = pack.w
         pi.obs_in = obs_in.data_ptr()
@@ -304,21 +299,8 @@ class DeviceEnvBatch:
         (pi.eps_steps_per_count, pi.eps_total, pi.eps_fraction, pi.eps_initial,
          pi.eps_final) = (float(v) for v in eps)
         pi.seed = int(policy_seed) & 0xFFFFFFFFFFFFFFFF
-        pi.actions = rec["actions"].data_ptr() if "actions" in rec else None
-        st = self.state_struct()
-        out = self.out_struct(obs, obj_cnt, with_env_done=trainer_deactivate)
-        ln = C.byref(_abi.AsvEnvLaunch(*(int(v) for v in launch))) if launch is not None else None
-        if ar is not None:
-            ar.obs_prev = rec["obs_prev"].data_ptr() if "obs_prev" in rec else None
-            rc = pack.L.asvrl_policy_rollout_ar(C.byref(self.params), C.byref(st), C.byref(ctl), C.byref(out),
-                                                C.byref(ro), C.byref(pi), C.byref(ar), ln, _abi.stream_ptr(stream))
-            _abi.check(rc, "asvrl_policy_rollout_ar", pack.L)
-            return types.SimpleNamespace(steps_run=steps_run, resets=resets, pushed=pushed,
-                                         **{n: rec.get(n) for n in specs})
-        rc = pack.L.asvrl_policy_rollout(C.byref(self.params), C.byref(st), C.byref(ctl), C.byref(out), C.byref(ro),
-                                         C.byref(pi), ln, _abi.stream_ptr(stream))
-        _abi.check(rc, "asvrl_policy_rollout", pack.L)
-        return types.SimpleNamespace(steps_run=steps_run, **{n: rec.get(n) for n in specs})
+        pi.actions = b.rec["actions"].data_ptr() if "actions" in b.rec else None
+        return self._rollout_call(b, pack.L, "asvrl_policy_rollout", [C.byref(pi)], stream)
 
     def reset(self, cfg, env_mask=None, seed=0, counter=0, counter_dev=None, stream=None):
         st = self.state_struct()
