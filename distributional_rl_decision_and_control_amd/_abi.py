@@ -216,6 +216,12 @@ class AsvDqnActIO(C.Structure):
                 ("eps_fraction", _D), ("eps_initial", _D), ("eps_final", _D), ("seed", _U64)]
 
 
+class AsvDqnPolicy(C.Structure):
+    _fields_ = [("w", AsvDqnWeights), ("obs_in", _VP), ("step_dev", _VP), ("eps_steps_per_count", _D),
+                ("eps_total", _D), ("eps_fraction", _D), ("eps_initial", _D), ("eps_final", _D), ("seed", _U64),
+                ("actions", _VP)]
+
+
 DQN_GRAD_ARRAYS = ("xb", "h0", "h1", "h2", "q_sel", "q_next", "dz_out", "dz2", "dz1", "dz0", "tile_loss")
 
 
@@ -399,6 +405,13 @@ EXPORTS = [
     ("asvrl_dqn_weights_struct_size", _I64, []),
     ("asvrl_dqn_act_struct_size", _I64, []),
     ("asvrl_dqn_grad_struct_size", _I64, []),
+    ("asvrl_dqn_rollout", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), C.POINTER(AsvStepCtl),
+                                    C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvDqnPolicy),
+                                    C.POINTER(AsvEnvLaunch), _VP]),
+    ("asvrl_dqn_rollout_ar", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), C.POINTER(AsvStepCtl),
+                                       C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvDqnPolicy),
+                                       C.POINTER(AsvAutoReset), C.POINTER(AsvEnvLaunch), _VP]),
+    ("asvrl_dqn_policy_struct_size", _I64, []),
 ]
 
 _libs = {}

@@ -22,6 +22,7 @@
 #include "asvrl_common.h"
 #include "asvrl_vonmises_k1.h"
 #include "asvrl_actor_tile.h"
+#include "asvrl_dqn_tile.h"
 
 namespace asvrl {
 namespace {
@@ -677,6 +678,9 @@ __host__ __device__ constexpr size_t autoreset_lds(int blk, int epb) {
 // 32-row tiles w, w + waves, ...; it reads the rows of an LDS copy of the observation (PI->obs_in before step 0,
 // then what the phases of the step before wrote: they write it beside their global outputs) and leaves the f64
 // action pairs in LDS, where phase 1 takes the lane's action instead of from A->actions.
+// POL = kPolDqn (env_dqn_rollout_kernel): the same closed loop under DQN_Policy -- the Actor's trunk staged the same
+// way, the 25-wide head's fragments and bias read from L2 (asvrl_dqn_tile.h: dqn_act_kernel's functions), the first
+// arg-max and the epsilon-greedy index left as the pair (index, 0.0), which phase 1 takes as a discrete action.
 // AR (asvrl_env_rollout_ar / asvrl_policy_rollout_ar, with ROLL): episodes restart inside the window. After the
 // phases of step t the workgroup votes on "an env of mine ended in this step"; if so its waves reset the ended envs
 // (reset_env, one wave per env, the waves taking them in turn, each in its own ResetLds behind the carve and the
@@ -693,12 +697,19 @@ __host__ __device__ constexpr size_t autoreset_lds(int blk, int epb) {
 // sequence as the step (the act and the env-end sections, which it skips, are skipped by all lanes alike). No lane
 // leaves the step loop early (hold_done is refused with AR), and since every lane of an env reads the env's alive
 // count for `end`, the vote is also the barrier between those reads and the next step's reset of the count.
-template <int BLOCK, int NM, bool DYN = true, bool ROLL = false, bool POL = false, bool AR = false>   // DYN false: an observation pass only (do_dynamics = 0)
+// the policy in front of every step of a closed-loop rollout, and its argument struct
+enum : int { kPolNone = 0, kPolActor = 1, kPolDqn = 2 };
+template <int POL> struct PolicyOf { using type = AsvPolicy; };
+template <> struct PolicyOf<kPolDqn> { using type = AsvDqnPolicy; };
+__device__ __forceinline__ const AsvMlpWeights& trunk_of(const AsvPolicy& p) { return p.w; }
+__device__ __forceinline__ const AsvMlpWeights& trunk_of(const AsvDqnPolicy& p) { return p.w.trunk; }
+template <int BLOCK, int NM, bool DYN = true, bool ROLL = false, int POL = kPolNone, bool AR = false>   // DYN false: an observation pass only (do_dynamics = 0)
 __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int bid, unsigned char* smem,
-                                                KArg<AsvRollout> RO = nullptr, KArg<AsvPolicy> PI = nullptr,
+                                                KArg<AsvRollout> RO = nullptr,
+                                                KArg<typename PolicyOf<POL>::type> PI = nullptr,
                                                 atile::ActorLds* AL = nullptr, KArg<AsvAutoReset> RS = nullptr,
                                                 unsigned char* ar_lds = nullptr) {
-  static_assert(!POL || ROLL, "the policy runs inside the rollout's step loop");
+  static_assert(POL == kPolNone || ROLL, "the policy runs inside the rollout's step loop");
   static_assert(!AR || ROLL, "the auto-reset runs inside the rollout's step loop");
   const int R = A->s.max_robots;
   const int O = A->s.max_obs;
@@ -733,7 +744,7 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
   // POL: the robots' observation rows [nrb][ASVRL_OBS_DIM] f32 and action pairs [nrb][2] f64, 16-byte aligned
   float* sobs = reinterpret_cast<float*>(smem + policy_rows_offset(reinterpret_cast<unsigned char*>(scnt + nrb) - smem));
   double* sa64 = reinterpret_cast<double*>(sobs + static_cast<size_t>(nrb) * ASVRL_OBS_DIM);
-  const size_t row0 = POL ? static_cast<size_t>(bid) * nrb : 0;   // the workgroup's first global robot row
+  const size_t row0 = POL != kPolNone ? static_cast<size_t>(bid) * nrb : 0;   // the workgroup's first global robot row
 
   const bool rlane = tid < nrb;
   int le = tid / R;
@@ -797,9 +808,9 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
       ret = A->s.rs[ASVRL_F_RET * NT + idx];
     }
   }
-  if constexpr (POL) {
+  if constexpr (POL != kPolNone) {
     // the weights once per workgroup; the rows step 0 acts on (rows past the batch: zeros, never consumed)
-    atile::stage_actor<BLOCK>(*AL, kref(PI).w, tid);
+    atile::stage_actor<BLOCK>(*AL, trunk_of(kref(PI)), tid);
     constexpr int kRowV = ASVRL_OBS_DIM / 4;
     const float4* src = reinterpret_cast<const float4*>(PI->obs_in);
     for (int k = tid; k < nrb * kRowV; k += BLOCK) {
@@ -810,7 +821,7 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
   }
   if constexpr (AR) {   // row 0 of the acted-on observations: the caller's rows in front of step 0
     const KArg<AsvAutoReset> Q = kfresh(RS);
-    const float* src0 = POL ? PI->obs_in : Q->obs_in;
+    const float* src0 = POL != kPolNone ? PI->obs_in : Q->obs_in;
     if (env_on0 && Q->obs_prev != nullptr) {
       const float4* src = reinterpret_cast<const float4*>(src0 + idx * ASVRL_OBS_DIM);
       float4* dst = reinterpret_cast<float4*>(Q->obs_prev + idx * ASVRL_OBS_DIM);
@@ -866,7 +877,7 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
     } else if constexpr (ROLL) {
       f(rec_row(), std::true_type{}, size_t{0});
     }
-    if constexpr (POL) {   // the rows the Actor reads at the next step
+    if constexpr (POL != kPolNone) {   // the rows the Actor reads at the next step
       AsvStepOut o{};
       o.obs = sobs;
       f(o, std::true_type{}, row0);
@@ -884,7 +895,7 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
   if constexpr (AR) {
     if (obsp) goto acted;   // (workgroup-uniform) the observation pass acts on nothing
   }
-  if constexpr (POL) {
+  if constexpr (POL == kPolActor) {
     const KArg<AsvPolicy> P = kfresh(PI);
     const uint64_t step = (P->step_dev != nullptr ? static_cast<uint64_t>(*P->step_dev) : 0ull) + static_cast<uint64_t>(t);
     const int ln = tid & (kWave - 1), wv = __builtin_amdgcn_readfirstlane(tid / kWave);
@@ -910,6 +921,38 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
       rec[0] = sa64[2 * tid];
       rec[1] = sa64[2 * tid + 1];
     }
+  } else if constexpr (POL == kPolDqn) {
+    // DQN_Policy on the workgroup's rows: dqn_act_kernel's Q tile, arg-max and draw (asvrl_dqn_tile.h)
+    const KArg<AsvDqnPolicy> P = kfresh(PI);
+    const uint64_t step = (P->step_dev != nullptr ? static_cast<uint64_t>(*P->step_dev) : 0ull) + static_cast<uint64_t>(t);
+    const int ln = tid & (kWave - 1), wv = __builtin_amdgcn_readfirstlane(tid / kWave);
+    for (int tile = wv; tile * 32 < nrb; tile += BLOCK / kWave) {   // wave-uniform: the MFMAs run with every lane on
+      asm volatile("" ::: "memory");   // (the tile's LDS reads stay inside the loop, as the Actor's)
+      const int lr = tile * 32 + (ln & 31);
+      const bool valid = lr < nrb;
+      frag8 bx[2];
+      float mk[atile::kObjN];
+      atile::load_obs(sobs, ASVRL_OBS_DIM, valid ? lr : nrb - 1, ln >> 5, bx, mk);
+      float q[16];
+      dqtile::dqn_q_tile<atile::MLP_ACT>(kref(P).w, AsvMlpIO{}, *AL, 0, false, ln, bx, mk, q);
+      float best;
+      int bi;
+      const int nact = P->w.n_actions;
+      dqtile::dqn_argmax(q, ln >> 5, nact, best, bi);   // (every lane of the wave is live at its shuffle)
+      if (valid && ln < 32) {
+        const int act = dqtile::dqn_explore(step, atile::EpsSchedule{P->eps_steps_per_count, P->eps_total, P->eps_fraction,
+                                                                     P->eps_initial, P->eps_final},
+                                            P->seed, static_cast<int>(row0 + lr), bi, nact);
+        sa64[2 * lr] = static_cast<double>(act);
+        sa64[2 * lr + 1] = 0.0;
+      }
+    }
+    __syncthreads();
+    if (env_on && P->actions != nullptr) {   // the action every robot slot of a stepping env was given
+      double* rec = P->actions + (static_cast<size_t>(t) * NT + idx) * 2;
+      rec[0] = sa64[2 * tid];
+      rec[1] = sa64[2 * tid + 1];
+    }
   }
   [[maybe_unused]] acted:
 
@@ -926,7 +969,7 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
       const int nc = A->s.n_cores[e];
       const double* cores = A->s.cores + static_cast<size_t>(e) * A->s.max_cores * 4;
       // the lane's action: the Actor's (LDS), or row t of the caller's
-      const double* act = POL ? sa64 + 2 * tid : A->actions + (ROLL ? static_cast<size_t>(t) * 2 * NT : 0) + 2 * idx;
+      const double* act = POL != kPolNone ? sa64 + 2 * tid : A->actions + (ROLL ? static_cast<size_t>(t) * 2 * NT : 0) + 2 * idx;
       robot_act(ParamsKArg{&A->p}, r, act[0], act[1], A->ctl.is_continuous, cores,
                 nc < A->s.max_cores ? nc : A->s.max_cores);
       const double d_after = sqrt((gx - r.x) * (gx - r.x) + (gy - r.y) * (gy - r.y));
@@ -1443,7 +1486,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(ASVRL_ENV
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ __attribute__((aligned(16))) atile::ActorLds AL;
   const KArg<PolicyArgs> PA = kargs<PolicyArgs>();
-  env_pairs_block<BLOCK, NM, true, true, true>(
+  env_pairs_block<BLOCK, NM, true, true, kPolActor>(
       &PA->k, PA->k.epb, PA->k.group0 + xcd_group(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x)), smem,
       &PA->ro, &PA->pi, &AL);
 }
@@ -1461,7 +1504,7 @@ template <int BLOCK, int NM>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(NM == 1 ? 1 : ASVRL_ENV_ROLLOUT_WPE))) void env_rollout_ar_kernel(RolloutArArgs) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const KArg<RolloutArArgs> RA = kargs<RolloutArArgs>();
-  env_pairs_block<BLOCK, NM, true, true, false, true>(
+  env_pairs_block<BLOCK, NM, true, true, kPolNone, true>(
       &RA->k, RA->k.epb, RA->k.group0 + xcd_group(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x)), smem,
       &RA->ro, nullptr, nullptr, &RA->ar, smem + RA->ar_off);
 }
@@ -1477,7 +1520,41 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(ASVRL_ENV
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ __attribute__((aligned(16))) atile::ActorLds AL;
   const KArg<PolicyArArgs> PA = kargs<PolicyArArgs>();
-  env_pairs_block<BLOCK, NM, true, true, true, true>(
+  env_pairs_block<BLOCK, NM, true, true, kPolActor, true>(
+      &PA->k, PA->k.epb, PA->k.group0 + xcd_group(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x)), smem,
+      &PA->ro, &PA->pi, &AL, &PA->ar, smem + PA->ar_off);
+}
+
+// The closed loop under DQN_Policy (asvrl_dqn_rollout / asvrl_dqn_rollout_ar): env_policy_rollout_kernel and
+// env_policy_rollout_ar_kernel with env_pairs_block<kPolDqn> -- the same static ActorLds (the trunk's images; the
+// head's 8 KB image and its bias stay in L2), the same dynamic carve, one workgroup per CU.
+struct DqnRolloutArgs {
+  PairsArgs k;   // actions null; noise: row 0 of the rollout's
+  AsvRollout ro;
+  AsvDqnPolicy pi;
+};
+template <int BLOCK, int NM>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(ASVRL_ENV_POLICY_WPE))) void env_dqn_rollout_kernel(DqnRolloutArgs) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ __attribute__((aligned(16))) atile::ActorLds AL;
+  const KArg<DqnRolloutArgs> PA = kargs<DqnRolloutArgs>();
+  env_pairs_block<BLOCK, NM, true, true, kPolDqn>(
+      &PA->k, PA->k.epb, PA->k.group0 + xcd_group(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x)), smem,
+      &PA->ro, &PA->pi, &AL);
+}
+struct DqnRolloutArArgs {
+  PairsArgs k;
+  AsvRollout ro;
+  AsvDqnPolicy pi;
+  AsvAutoReset ar;
+  int ar_off;
+};
+template <int BLOCK, int NM>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(ASVRL_ENV_POLICY_WPE))) void env_dqn_rollout_ar_kernel(DqnRolloutArArgs) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ __attribute__((aligned(16))) atile::ActorLds AL;
+  const KArg<DqnRolloutArArgs> PA = kargs<DqnRolloutArArgs>();
+  env_pairs_block<BLOCK, NM, true, true, kPolDqn, true>(
       &PA->k, PA->k.epb, PA->k.group0 + xcd_group(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x)), smem,
       &PA->ro, &PA->pi, &AL, &PA->ar, smem + PA->ar_off);
 }
@@ -1858,13 +1935,13 @@ PairLaunch pair_launch(int R, int O, int n_envs, int blk_req, int epb_req, int v
 
 using namespace asvrl;
 
-// ------------------------------------------------------------------ the env step and its four rollout calls
+// ------------------------------------------------------------------ the env step and its six rollout calls
 // One host path. Each call is: env_checks (its arguments), env_plan (the launch shape, and whether the
 // pair-parallel kernel is taken), then launch_groups (that kernel) or, for the rollouts, rollout_fallback (K single
 // steps).
 
 // the groups of checks a call takes beyond the step's own
-enum : unsigned { kRollout = 1, kClosedLoop = 2, kAutoReset = 4 };
+enum : unsigned { kRollout = 1, kClosedLoop = 2, kAutoReset = 4, kDqnPolicy = 8 };   // (kDqnPolicy: with kClosedLoop)
 
 static int env_fail(const char* who, const char* what) {
   set_error(std::string(who) + ": " + what);
@@ -1875,12 +1952,14 @@ static int env_fail(const char* who, const char* what) {
     if (!(cond)) return env_fail(who, what);     \
   } while (0)
 
-// The argument checks of the five calls, in the order each call reports them (`who` names the call in the error
+// The argument checks of the seven calls, in the order each call reports them (`who` names the call in the error
 // text). actions / noise: the single step's; the rollouts carry theirs in ro.
 static int env_checks(const char* who, unsigned kind, const AsvParams* params, const AsvEnvState* state,
                       const double* actions, const double* noise, const AsvStepCtl* ctl, const AsvStepOut* out,
-                      const AsvRollout* ro, const AsvPolicy* pi, const AsvAutoReset* ar, const AsvEnvLaunch* launch) {
+                      const AsvRollout* ro, const AsvPolicy* pi, const AsvDqnPolicy* dq, const AsvAutoReset* ar,
+                      const AsvEnvLaunch* launch) {
   const bool roll = (kind & kRollout) != 0, closed = (kind & kClosedLoop) != 0, reset = (kind & kAutoReset) != 0;
+  const bool dqn = (kind & kDqnPolicy) != 0;   // the closed loop's policy: dq (DQN_Policy), else pi (the Actor)
   ENV_REQUIRE(params && state && ctl && out && (ro || !roll), "null argument");
   if (reset) {   // what the two _ar calls refuse beyond their plain calls' checks
     ENV_REQUIRE(ar != nullptr, "null ar (the auto-reset description)");
@@ -1905,12 +1984,20 @@ static int env_checks(const char* who, unsigned kind, const AsvParams* params, c
   }
   if (closed) {
     ENV_REQUIRE(ro->actions == nullptr, "ro->actions must be null (the policy supplies the actions)");
-    ENV_REQUIRE(pi != nullptr, "null policy");
-    ENV_REQUIRE(pi->obs_in != nullptr, "null obs_in");
-    ENV_REQUIRE(ctl->is_continuous, "is_continuous must be 1 (the Actor is the continuous agent)");
-    const AsvMlpWeights& w = pi->w;
+    ENV_REQUIRE(dqn ? dq != nullptr : pi != nullptr, "null policy");
+    ENV_REQUIRE((dqn ? dq->obs_in : pi->obs_in) != nullptr, "null obs_in");
+    if (dqn)
+      ENV_REQUIRE(!ctl->is_continuous, "is_continuous must be 0 (DQN's actions are indices)");
+    else
+      ENV_REQUIRE(ctl->is_continuous, "is_continuous must be 1 (the Actor is the continuous agent)");
+    const AsvMlpWeights& w = dqn ? dq->w.trunk : pi->w;
     ENV_REQUIRE(w.enc_frag && w.b_enc && w.w1_frag && w.w2_frag && w.b1 && w.b2 && w.wout && w.bout,
-                "null actor image");
+                dqn ? "null DQN image" : "null actor image");
+    if (dqn) {
+      ENV_REQUIRE(dq->w.head_frag != nullptr, "null pi->w.head_frag");
+      // >= 2: the tile's staging reads the first two output rows (the Actor's whole output layer)
+      ENV_REQUIRE(dq->w.n_actions >= 2 && dq->w.n_actions <= ASVRL_DQN_MAX_ACTIONS, "pi->w.n_actions must be in 2..32");
+    }
   }
   if (roll) {
     ENV_REQUIRE(ctl->do_dynamics, "do_dynamics must be 1");
@@ -1938,7 +2025,8 @@ static int env_checks(const char* who, unsigned kind, const AsvParams* params, c
     ENV_REQUIRE(launch->envs_per_block >= 0 && launch->max_groups >= 0, "negative envs_per_block / max_groups");
   }
   if (closed)
-    ENV_REQUIRE(reinterpret_cast<uintptr_t>(pi->obs_in) % 16 == 0 && reinterpret_cast<uintptr_t>(out->obs) % 16 == 0 &&
+    ENV_REQUIRE(reinterpret_cast<uintptr_t>(dqn ? dq->obs_in : pi->obs_in) % 16 == 0 &&
+                    reinterpret_cast<uintptr_t>(out->obs) % 16 == 0 &&
                     (!reset || reinterpret_cast<uintptr_t>(ar->obs_prev) % 16 == 0),
                 "observation rows must be 16-byte aligned");
   else if (reset)
@@ -2035,8 +2123,11 @@ template <int B, int NM> static auto kernel_of(const RolloutArgs&) { return &env
 template <int B, int NM> static auto kernel_of(const PolicyArgs&) { return &env_policy_rollout_kernel<B, NM>; }
 template <int B, int NM> static auto kernel_of(const RolloutArArgs&) { return &env_rollout_ar_kernel<B, NM>; }
 template <int B, int NM> static auto kernel_of(const PolicyArArgs&) { return &env_policy_rollout_ar_kernel<B, NM>; }
+template <int B, int NM> static auto kernel_of(const DqnRolloutArgs&) { return &env_dqn_rollout_kernel<B, NM>; }
+template <int B, int NM> static auto kernel_of(const DqnRolloutArArgs&) { return &env_dqn_rollout_ar_kernel<B, NM>; }
 template <class Args>
-constexpr bool kPhiloxOnly = std::is_same<Args, RolloutArArgs>::value || std::is_same<Args, PolicyArArgs>::value;
+constexpr bool kPhiloxOnly = std::is_same<Args, RolloutArArgs>::value || std::is_same<Args, PolicyArArgs>::value ||
+                             std::is_same<Args, DqnRolloutArArgs>::value;
 static PairsArgs& pairs_of(PairsArgs& a) { return a; }
 template <class Args> static PairsArgs& pairs_of(Args& a) { return a.k; }
 
@@ -2047,7 +2138,7 @@ static auto kernel_for_noise(int nm, const Args& a) -> void (*)(Args) {
   }
   return nm == 1 ? kernel_of<B, 1>(a) : kernel_of<B, 2>(a);
 }
-// The pair-parallel launch of any of the five kernels: P.groups workgroups in launches of at most P.chunk, each
+// The pair-parallel launch of any of the seven kernels: P.groups workgroups in launches of at most P.chunk, each
 // told its first group.
 template <class Args>
 static int launch_groups(const char* who, const EnvPlan& P, Args a, hipStream_t st) {
@@ -2065,7 +2156,8 @@ extern "C" int asvrl_env_step_ex(const AsvParams* params, const AsvEnvState* sta
                                  const double* noise, const AsvStepCtl* ctl, const AsvStepOut* out,
                                  const AsvEnvLaunch* launch, void* stream) {
   const char* who = "asvrl_env_step";
-  if (int rc = env_checks(who, 0, params, state, actions, noise, ctl, out, nullptr, nullptr, nullptr, launch)) return rc;
+  if (int rc = env_checks(who, 0, params, state, actions, noise, ctl, out, nullptr, nullptr, nullptr, nullptr, launch))
+    return rc;
   if (state->n_envs == 0) return 0;
   EnvPlan P;
   if (int rc = env_plan(who, state, ctl, launch, false, false, &P)) return rc;
@@ -2109,15 +2201,37 @@ static AsvMlpIO act_io(const AsvPolicy* pi, const float* x, size_t n, double* ac
   return io;
 }
 
-// The K-launch form of the four rollout calls (per-robot parameters, layout 2, a carve that does not fit). Per step:
+// DQN_Policy's act launch over n rows x: the (index, 0.0) pairs into act
+static AsvDqnActIO dqn_act_io(const AsvDqnPolicy* dq, const float* x, size_t n, double* act, const int64_t* step) {
+  AsvDqnActIO io{};
+  io.x = x;
+  io.ldx = ASVRL_OBS_DIM;
+  io.n = static_cast<int32_t>(n);
+  io.act_out = act;
+  io.ld_act = 2;
+  io.step_dev = step;
+  io.eps_steps_per_count = dq->eps_steps_per_count;
+  io.eps_total = dq->eps_total;
+  io.eps_fraction = dq->eps_fraction;
+  io.eps_initial = dq->eps_initial;
+  io.eps_final = dq->eps_final;
+  io.seed = dq->seed;
+  return io;
+}
+
+// The K-launch form of the six rollout calls (per-robot parameters, layout 2, a carve that does not fit). Per step:
 // the act launch (closed loop), the obs_prev row (auto-reset), the single step and its record launch; then, for the
 // auto-reset, the reset mask and counts and the reset of the ended envs with their observation
 // (asvrl_env_reset_observe, or the two launches where that call does not apply). pi null: the open loop, the actions
-// out of ro. ar null: a plain call, which alone can hold ended envs (hold_done: env_checks refuses it with ar).
+// out of ro; dq instead of pi: DQN_Policy's act launch (asvrl_dqn_act) in the Actor's place. ar null: a plain call, which alone can hold ended envs (hold_done: env_checks refuses it with ar).
 static int rollout_fallback(const char* who, const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
-                            const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi, const AsvAutoReset* ar,
-                            const AsvEnvLaunch* launch, void* stream) {
+                            const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi, const AsvDqnPolicy* dq,
+                            const AsvAutoReset* ar, const AsvEnvLaunch* launch, void* stream) {
   hipStream_t st = as_stream(stream);
+  const bool closed = pi != nullptr || dq != nullptr;
+  const float* pol_obs = dq != nullptr ? dq->obs_in : (pi != nullptr ? pi->obs_in : nullptr);
+  const int64_t* pol_step = dq != nullptr ? dq->step_dev : (pi != nullptr ? pi->step_dev : nullptr);
+  double* pol_actions = dq != nullptr ? dq->actions : (pi != nullptr ? pi->actions : nullptr);
   const int E = state->n_envs, R = state->max_robots;
   const size_t NT = static_cast<size_t>(E) * R;
   const size_t noise_row = NT * (static_cast<size_t>(state->max_obs) + R) * 5;
@@ -2126,13 +2240,13 @@ static int rollout_fallback(const char* who, const AsvParams* params, const AsvE
   const unsigned qgrid = (static_cast<unsigned>(NT) * (ASVRL_OBS_DIM / 4) + kBlock - 1) / kBlock;
   // stream-ordered scratch: the actions [NT][2] f64 and the act launch's step count (closed loop), then the reset
   // mask [E] (auto-reset); hold_done's mask [E] is an allocation of its own
-  const size_t act_bytes = pi != nullptr ? sizeof(double) * 2 * NT + sizeof(int64_t) : 0;
+  const size_t act_bytes = closed ? sizeof(double) * 2 * NT + sizeof(int64_t) : 0;
   const size_t scratch_bytes = act_bytes + (ar != nullptr ? E : 0);
   unsigned char* scratch = nullptr;
   if (scratch_bytes != 0 && hipMallocAsync(reinterpret_cast<void**>(&scratch), scratch_bytes, st) != hipSuccess)
     return check_launch(who);
   double* act = reinterpret_cast<double*>(scratch);
-  int64_t* step = pi != nullptr ? reinterpret_cast<int64_t*>(act + 2 * NT) : nullptr;
+  int64_t* step = closed ? reinterpret_cast<int64_t*>(act + 2 * NT) : nullptr;
   uint8_t* rmask = ar != nullptr ? scratch + act_bytes : nullptr;
   int rc = 0;
   uint8_t* hold_mask = nullptr;
@@ -2152,20 +2266,25 @@ static int rollout_fallback(const char* who, const AsvParams* params, const AsvE
   AsvStepOut oo = *out;   // the observation pass's outputs: no episode bookkeeping
   oo.env_done = nullptr;
   oo.stats = nullptr;
-  const float* obs_first = pi != nullptr ? pi->obs_in : (ar != nullptr ? ar->obs_in : nullptr);
+  const float* obs_first = closed ? pol_obs : (ar != nullptr ? ar->obs_in : nullptr);
   for (int t = 0; t < ro->n_steps && rc == 0; ++t) {
     AsvStepCtl c = *ctl;
     c.counter = ctl->counter + static_cast<uint64_t>(t);
     if (hold_mask != nullptr) c.env_mask = hold_mask;
     const float* obs_t = t == 0 ? obs_first : out->obs;   // the observation the step before (or its reset) wrote
     const double* actions = act;
-    if (pi != nullptr) {
-      hipLaunchKernelGGL(policy_step_count_kernel, dim3(1), dim3(1), 0, st, pi->step_dev, step, t);
-      const AsvMlpIO io = act_io(pi, obs_t, NT, act, step);
-      rc = asvrl_actor_forward(&pi->w, &io, atile::MLP_ACT, stream);
-      if (rc == 0 && pi->actions != nullptr)
+    if (closed) {
+      hipLaunchKernelGGL(policy_step_count_kernel, dim3(1), dim3(1), 0, st, pol_step, step, t);
+      if (dq != nullptr) {
+        const AsvDqnActIO io = dqn_act_io(dq, obs_t, NT, act, step);
+        rc = asvrl_dqn_act(&dq->w, &io, stream);
+      } else {
+        const AsvMlpIO io = act_io(pi, obs_t, NT, act, step);
+        rc = asvrl_actor_forward(&pi->w, &io, atile::MLP_ACT, stream);
+      }
+      if (rc == 0 && pol_actions != nullptr)
         hipLaunchKernelGGL(policy_actions_kernel, dim3(agrid), dim3(kBlock), 0, st, act,
-                           pi->actions + static_cast<size_t>(t) * 2 * NT, c.env_mask, E, R);
+                           pol_actions + static_cast<size_t>(t) * 2 * NT, c.env_mask, E, R);
     } else {
       actions = ro->actions + static_cast<size_t>(t) * 2 * NT;
     }
@@ -2203,23 +2322,25 @@ static int rollout_fallback(const char* who, const AsvParams* params, const AsvE
   return rc;
 }
 
-// The four rollout calls: check, plan, zero the counts the window adds to, then the one launch or the fallback.
-// pi: the closed loop (ro->actions is null then); ar: the auto-reset (Philox noise only: no recorded rows).
+// The six rollout calls: check, plan, zero the counts the window adds to, then the one launch or the fallback.
+// pi or dq: the closed loop under the Actor or DQN_Policy (ro->actions is null then); ar: the auto-reset (Philox noise only: no recorded rows).
 static int rollout_call(const char* who, unsigned kind, const AsvParams* params, const AsvEnvState* state,
                         const AsvStepCtl* ctl, const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi,
-                        const AsvAutoReset* ar, const AsvEnvLaunch* launch, void* stream) {
-  if (int rc = env_checks(who, kind, params, state, nullptr, nullptr, ctl, out, ro, pi, ar, launch)) return rc;
+                        const AsvDqnPolicy* dq, const AsvAutoReset* ar, const AsvEnvLaunch* launch, void* stream) {
+  if (int rc = env_checks(who, kind, params, state, nullptr, nullptr, ctl, out, ro, pi, dq, ar, launch)) return rc;
   if (state->n_envs == 0) return 0;
   EnvPlan P;
-  if (int rc = env_plan(who, state, ctl, launch, pi != nullptr, ar != nullptr, &P)) return rc;
+  if (int rc = env_plan(who, state, ctl, launch, pi != nullptr || dq != nullptr, ar != nullptr, &P)) return rc;
   hipStream_t st = as_stream(stream);
   if (ro->steps_run != nullptr && hipMemsetAsync(ro->steps_run, 0, sizeof(int32_t) * state->n_envs, st) != hipSuccess)
     return check_launch(who);
   if (ar != nullptr && ar->resets != nullptr &&
       hipMemsetAsync(ar->resets, 0, sizeof(int32_t) * state->n_envs, st) != hipSuccess)
     return check_launch(who);
-  if (!P.fused) return rollout_fallback(who, params, state, ctl, out, ro, pi, ar, launch, stream);
+  if (!P.fused) return rollout_fallback(who, params, state, ctl, out, ro, pi, dq, ar, launch, stream);
   const PairsArgs k{*params, *state, *ctl, *out, ro->actions, ar != nullptr ? nullptr : ro->noise, P.pl.epb, 0};
+  if (dq != nullptr && ar != nullptr) return launch_groups(who, P, DqnRolloutArArgs{k, *ro, *dq, *ar, P.ar_off}, st);
+  if (dq != nullptr) return launch_groups(who, P, DqnRolloutArgs{k, *ro, *dq}, st);
   if (pi != nullptr && ar != nullptr) return launch_groups(who, P, PolicyArArgs{k, *ro, *pi, *ar, P.ar_off}, st);
   if (ar != nullptr) return launch_groups(who, P, RolloutArArgs{k, *ro, *ar, P.ar_off}, st);
   if (pi != nullptr) return launch_groups(who, P, PolicyArgs{k, *ro, *pi}, st);
@@ -2229,14 +2350,15 @@ static int rollout_call(const char* who, unsigned kind, const AsvParams* params,
 extern "C" int asvrl_env_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                  const AsvStepOut* out, const AsvRollout* ro, const AsvEnvLaunch* launch,
                                  void* stream) {
-  return rollout_call("asvrl_env_rollout", kRollout, params, state, ctl, out, ro, nullptr, nullptr, launch, stream);
+  return rollout_call("asvrl_env_rollout", kRollout, params, state, ctl, out, ro, nullptr, nullptr, nullptr, launch,
+                      stream);
 }
 
 extern "C" int asvrl_policy_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                     const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi,
                                     const AsvEnvLaunch* launch, void* stream) {
-  return rollout_call("asvrl_policy_rollout", kRollout | kClosedLoop, params, state, ctl, out, ro, pi, nullptr, launch,
-                      stream);
+  return rollout_call("asvrl_policy_rollout", kRollout | kClosedLoop, params, state, ctl, out, ro, pi, nullptr, nullptr,
+                      launch, stream);
 }
 
 extern "C" int64_t asvrl_policy_struct_size(void) { return sizeof(AsvPolicy); }
@@ -2244,16 +2366,32 @@ extern "C" int64_t asvrl_policy_struct_size(void) { return sizeof(AsvPolicy); }
 extern "C" int asvrl_env_rollout_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                     const AsvStepOut* out, const AsvRollout* ro, const AsvAutoReset* ar,
                                     const AsvEnvLaunch* launch, void* stream) {
-  return rollout_call("asvrl_env_rollout_ar", kRollout | kAutoReset, params, state, ctl, out, ro, nullptr, ar, launch,
-                      stream);
+  return rollout_call("asvrl_env_rollout_ar", kRollout | kAutoReset, params, state, ctl, out, ro, nullptr, nullptr, ar,
+                      launch, stream);
 }
 
 extern "C" int asvrl_policy_rollout_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                        const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi,
                                        const AsvAutoReset* ar, const AsvEnvLaunch* launch, void* stream) {
-  return rollout_call("asvrl_policy_rollout_ar", kRollout | kClosedLoop | kAutoReset, params, state, ctl, out, ro, pi, ar,
-                      launch, stream);
+  return rollout_call("asvrl_policy_rollout_ar", kRollout | kClosedLoop | kAutoReset, params, state, ctl, out, ro, pi,
+                      nullptr, ar, launch, stream);
 }
+
+extern "C" int asvrl_dqn_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                                 const AsvStepOut* out, const AsvRollout* ro, const AsvDqnPolicy* pi,
+                                 const AsvEnvLaunch* launch, void* stream) {
+  return rollout_call("asvrl_dqn_rollout", kRollout | kClosedLoop | kDqnPolicy, params, state, ctl, out, ro, nullptr, pi,
+                      nullptr, launch, stream);
+}
+
+extern "C" int asvrl_dqn_rollout_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                                    const AsvStepOut* out, const AsvRollout* ro, const AsvDqnPolicy* pi,
+                                    const AsvAutoReset* ar, const AsvEnvLaunch* launch, void* stream) {
+  return rollout_call("asvrl_dqn_rollout_ar", kRollout | kClosedLoop | kAutoReset | kDqnPolicy, params, state, ctl, out,
+                      ro, nullptr, pi, ar, launch, stream);
+}
+
+extern "C" int64_t asvrl_dqn_policy_struct_size(void) { return sizeof(AsvDqnPolicy); }
 
 extern "C" int64_t asvrl_autoreset_struct_size(void) { return sizeof(AsvAutoReset); }
 

@@ -280,27 +280,32 @@ class DeviceEnvBatch:
         take stay 0). The call goes to pack.L, so an f32 pack runs the f32-operand build. No host sync; with every
         record passed in by the caller (and steps_run) the call can be graph-captured.
         auto_reset (asvrl_policy_rollout_ar): as rollout()'s; the Actor acts on a reset env's reset observation at the
-        next step, and "obs_prev" records the rows it acted on at every step (obs_in comes from this call's own)."""
+        next step, and "obs_prev" records the rows it acted on at every step (obs_in comes from this call's own).
+        A fused_dqn.DqnPack (DQN_Policy; also an MlpPack of kind "actor") goes to asvrl_dqn_rollout /
+        asvrl_dqn_rollout_ar instead: the rounds are fused_dqn.dqn_act(pack, obs, act64, step, *eps, policy_seed)
+        and step(act64, is_continuous=False, ...), and "actions" holds (action index, 0.0)."""
+        from .fused_dqn import DqnPack   # (fused_dqn imports nothing from this module)
         K, NT = int(K), self.n_envs * self.max_robots
         assert pack.kind == "actor"
+        dqn = isinstance(pack, DqnPack)
         assert obs_in.dtype == torch.float32 and obs_in.is_contiguous() and tuple(obs_in.shape) == (NT, OBS_DIM)
         if step_dev is not None:
             assert step_dev.dtype == torch.int64 and step_dev.numel() >= 1
         b = self._rollout_args("policy_rollout", K, {"actions": ((NT, 2), torch.float64, 0)}, noise=noise, keep=keep,
-                               hold_done=hold_done, is_continuous=True, trainer_deactivate=trainer_deactivate,
+                               hold_done=hold_done, is_continuous=not dqn, trainer_deactivate=trainer_deactivate,
                                seed=seed, counter=counter, counter_dev=counter_dev, gamma=gamma, env_mask=env_mask,
                                obs=obs, obj_cnt=obj_cnt, fast_noise=fast_noise, launch=launch, auto_reset=auto_reset)
         if b.ar is not None:
             b.ar.obs_in = None
-        pi = _abi.AsvPolicy()
-        pi.w = pack.w
+        pi = _abi.AsvDqnPolicy() if dqn else _abi.AsvPolicy()
+        pi.w = pack.dw if dqn else pack.w
         pi.obs_in = obs_in.data_ptr()
         pi.step_dev = step_dev.data_ptr() if step_dev is not None else None
         (pi.eps_steps_per_count, pi.eps_total, pi.eps_fraction, pi.eps_initial,
          pi.eps_final) = (float(v) for v in eps)
         pi.seed = int(policy_seed) & 0xFFFFFFFFFFFFFFFF
         pi.actions = b.rec["actions"].data_ptr() if "actions" in b.rec else None
-        return self._rollout_call(b, pack.L, "asvrl_policy_rollout", [C.byref(pi)], stream)
+        return self._rollout_call(b, pack.L, "asvrl_dqn_rollout" if dqn else "asvrl_policy_rollout", [C.byref(pi)], stream)
 
     def reset(self, cfg, env_mask=None, seed=0, counter=0, counter_dev=None, stream=None):
         st = self.state_struct()

@@ -9,8 +9,8 @@ per-robot bookkeeping in Python. DeviceEvaluator keeps the same episodes in Devi
     state, flags, counts, obstacles, cores; set_batch_params for the launch parameters) is loaded into one batch;
     a device copy of that state is kept, so every later evaluation restores by copy;
   * an evaluation is the observation pass and then closed-loop windows of `chunk` steps, one launch each
-    (DeviceEnvBatch.policy_rollout with hold_done, the greedy Actor of an MlpPack), or, teacher-forced, open-loop
-    windows over a caller's action table (DeviceEnvBatch.rollout);
+    (DeviceEnvBatch.policy_rollout with hold_done, the greedy Actor of an MlpPack or the greedy DQN_Policy of a
+    DqnPack), or, teacher-forced, open-loop windows over a caller's action table (DeviceEnvBatch.rollout);
   * behind every window one asvrl_eval_metrics launch folds the window's records into the evaluation's carried
     state by trainer.py:286-303: discounted return, time, energy, deactivation, and the evaluation's end rule (the
     step limit, ANY collision, or every robot deactivated). Its `alive` output is the next window's env_mask;
@@ -29,6 +29,7 @@ import torch
 from .. import _abi
 from ..device_env import DeviceEnvBatch
 from ..envs.marinenav.env import MarineNavEnv3, set_batch_params
+from ..fused_dqn import DqnPack
 
 RECORDS = ("reward", "info", "rs")
 OBS_COUNTER = 0x80000000   # the observation pass's Philox counter (VecMarineNavEnv.reset's); step t draws at t
@@ -195,10 +196,13 @@ class DeviceEvaluator:
                            fast_noise=True)
 
     @torch.no_grad()
-    def run(self, pack=None, *, actions=None, noise=None, obs_noise=None, seed=0, episode_limit=1000, sync=True):
-        """One evaluation of every config. pack: the Actor's MlpPack, greedy in closed-loop windows; or actions: a
-        [T, NT, 2] f64 table per group (a tensor when there is one group, else a list) applied open loop, with
-        noise ([T, NT, O + R, 5] f64 per group) or the Philox stream. obs_noise: the observation pass's explicit
+    def run(self, pack=None, *, actions=None, noise=None, obs_noise=None, seed=0, episode_limit=1000, sync=True,
+            is_continuous=None):
+        """One evaluation of every config. pack: the Actor's MlpPack or DQN's DqnPack, greedy in closed-loop
+        windows; or actions: a [T, NT, 2] f64 table per group (a tensor when there is one group, else a list)
+        applied open loop, with noise ([T, NT, O + R, 5] f64 per group) or the Philox stream. is_continuous: what
+        the table's rows are -- True (also None, the default) thrust commands, False column 0 is the action index;
+        with a pack it follows the pack (None) and a value that contradicts it is a ValueError. obs_noise: the observation pass's explicit
         draws. sync: one host wait per window to stop once every episode has ended; False enqueues the
         ceil((episode_limit + 1) / chunk) windows without a host wait. Returns evaluate_configs' per-config lists
         (rewards, successes, times, energies, lengths; observations / actions / trajectories / relations empty per
@@ -208,6 +212,10 @@ class DeviceEvaluator:
             raise ValueError("run takes the Actor's pack or an action table, not both")
         if pack is not None and pack.kind != "actor":
             raise ValueError("run: pack must be an MlpPack of kind 'actor'")
+        if pack is not None and is_continuous is not None and bool(is_continuous) == isinstance(pack, DqnPack):
+            raise ValueError("run: is_continuous=%s does not match the pack (a DqnPack picks discrete actions, the "
+                             "Actor continuous ones)" % bool(is_continuous))
+        is_continuous = True if is_continuous is None else bool(is_continuous)
         episode_limit = int(episode_limit)
         actions = self._per_group(actions, "actions")
         noise = self._per_group(noise, "noise")
@@ -231,8 +239,8 @@ class DeviceEvaluator:
                 else:
                     nz = noise[g]
                     b.rollout(actions[g][t0:t0 + k], None if nz is None else nz[t0:t0 + k], keep=rec,
-                              hold_done=True, trainer_deactivate=True, env_mask=st["alive"], seed=seed + g,
-                              counter=t0, fast_noise=True)
+                              hold_done=True, is_continuous=is_continuous, trainer_deactivate=True,
+                              env_mask=st["alive"], seed=seed + g, counter=t0, fast_noise=True)
                 eval_metrics(L, k, b.n_envs, b.max_robots, rec, b.n_robots, grp.dt, grp.N, grp.pc, st, self.gamma,
                              episode_limit)
             t0 += k

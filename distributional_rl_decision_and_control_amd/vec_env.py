@@ -132,8 +132,14 @@ class VecMarineNavEnv:
         cnt_next and the step counter advanced by K on the device. eps: the linear epsilon schedule over the step
         counter (the default is greedy). The contract is otherwise rollout()'s. Returns the kept per-step records
         (keep also takes "actions"). auto_reset, count: as rollout()'s (the Actor acts on a reset env's reset
-        observation at the next step)."""
-        if not self.is_continuous:
+        observation at the next step). A fused_dqn.DqnPack drives an env built with is_continuous=False the same
+        way (fused_dqn.dqn_act in the Actor's place; "actions" holds (action index, 0.0))."""
+        from .fused_dqn import DqnPack
+        if isinstance(pack, DqnPack):
+            if self.is_continuous:
+                raise ValueError("policy_rollout: a DqnPack picks discrete actions, this env was built with "
+                                 "is_continuous=True")
+        elif not self.is_continuous:
             raise ValueError("policy_rollout: the Actor drives continuous-action envs")
         ar = self._auto_reset(auto_reset, False)
         rec = self.batch.policy_rollout(pack, K, self.obs_cur, keep=keep, hold_done=hold_done and ar is None,

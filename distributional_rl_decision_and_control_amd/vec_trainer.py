@@ -267,13 +267,29 @@ class VecTrainer:
         if self.fused2 is None:
             raise NotImplementedError("evaluate runs the AC-IQN actor; IQN, Rainbow and DQN act inside their own "
                                       "kernels")
+        return self.device_evaluator(configs, chunk, template_env).run(self.fused2.actor, **kw)
+
+    def policy_pack(self):
+        """The pack the closed-loop windows take (DeviceEnvBatch.policy_rollout, DeviceEvaluator.run): the learner's
+        own local images -- AC-IQN's actor or DQN's local net. IQN and Rainbow act inside their own kernels."""
+        if self.fused2 is not None:
+            return self.fused2.actor
+        if self.fused_dqn is not None:
+            return self.fused_dqn.local
+        raise NotImplementedError(f"policy_pack: the closed-loop windows run the AC-IQN actor or DQN_Policy, not "
+                                  f"{self.agent_type}")
+
+    def device_evaluator(self, configs, chunk=64, template_env=None):
+        """The DeviceEvaluator of the eval `configs`, built once and cached (one per configs list, chunk and
+        template env): device_evaluator(...).run(policy_pack()) is an evaluation that touches neither the training
+        env nor the replay nor the step counter."""
         from .policy.device_eval import DeviceEvaluator
         cached = getattr(self, "_dev_eval", None)
         if cached is None or cached[0] is not configs or cached[1] != (len(configs), int(chunk), template_env):
             ev = DeviceEvaluator(configs, template_env=template_env, device=self.device, chunk=chunk,
                                  gamma=self.gamma)
             cached = self._dev_eval = (configs, (len(configs), int(chunk), template_env), ev)
-        return cached[2].run(self.fused2.actor, **kw)
+        return cached[2]
 
     def _push(self, snap=None):
         """The replay push of every robot that acted; for the uniform ring it is one launch that also

@@ -1188,6 +1188,38 @@ int64_t asvrl_dqn_weights_struct_size(void);
 int64_t asvrl_dqn_act_struct_size(void);
 int64_t asvrl_dqn_grad_struct_size(void);
 
+/* ---------------------------------------------------------------- closed-loop rollout windows for DQN
+ * New entry points only: the ABI version stays 29. */
+
+/* DQN_Policy driving asvrl_dqn_rollout. */
+typedef struct AsvDqnPolicy {
+  AsvDqnWeights w;                /* asvrl_dqn_pack's images */
+  const float* obs_in;            /* [NT][ASVRL_OBS_DIM] the observation step 0 acts on (16-byte aligned) */
+  const int64_t* step_dev;        /* epsilon schedule / exploration key: step = *step_dev + t (NULL: 0 + t) */
+  double eps_steps_per_count, eps_total, eps_fraction, eps_initial, eps_final;   /* as AsvDqnActIO's */
+  uint64_t seed;                  /* Philox key of the exploration draws */
+  double* actions;                /* optional record [K][NT][2]: (action index, 0.0) of every robot slot */
+} AsvDqnPolicy;
+
+/* asvrl_policy_rollout and asvrl_policy_rollout_ar under DQN_Policy: for t < ro->n_steps, asvrl_dqn_act on every
+ * robot row (the same MFMA chain, the first arg-max, the same Philox draw keyed by the global row and
+ * step = *step_dev + t) and then the env step on the discrete action -- bit for bit the 2 K launches of
+ * asvrl_dqn_act and asvrl_env_step_ex (and, with the auto-reset, asvrl_env_reset_observe) they replace. The
+ * contract is the two Actor calls' word for word, except: ctl->is_continuous must be 0, pi->w.n_actions must be in
+ * 2..ASVRL_DQN_MAX_ACTIONS and pi->w.head_frag must be non-null. The trunk's images are staged into LDS as the
+ * Actor's are; the head's image and bias are read from L2. The caller's step counter is only read. Per-robot
+ * parameters, layout 2 and an env group whose arrays do not fit the LDS beside the weights run K x (asvrl_dqn_act
+ * into a stream-ordered scratch, the single step, the record launches and, with the auto-reset, the reset
+ * launches) instead. */
+int asvrl_dqn_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                      const AsvStepOut* last, const AsvRollout* ro, const AsvDqnPolicy* pi,
+                      const AsvEnvLaunch* launch /* NULL: automatic */, void* stream);
+int asvrl_dqn_rollout_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                         const AsvStepOut* last, const AsvRollout* ro, const AsvDqnPolicy* pi,
+                         const AsvAutoReset* ar, const AsvEnvLaunch* launch /* NULL: automatic */, void* stream);
+/* sizeof(AsvDqnPolicy) as compiled. */
+int64_t asvrl_dqn_policy_struct_size(void);
+
 /* ---------------------------------------------------------------- misc */
 const char* asvrl_last_error(void);
 int asvrl_abi_version(void);

@@ -12,6 +12,10 @@ run's success rate and mean reward are printed next to the golden's for the reco
 another stream, so nothing is asserted on them. One process, no retries; run it under a timeout:
 
     timeout 600 python tools/bench_device_eval.py [--out profiles/device_eval.json]
+
+--agent DQN: the same procedure with a seeded Agent(agent_type="DQN") (no trained DQN network is shipped) and its
+DqnPack in the closed-loop windows; the default output is profiles/device_eval_dqn.json (its golden_* fields stay
+the trained AC-IQN network's, for the record only).
 """
 import argparse
 import json
@@ -34,12 +38,16 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--chunk", type=int, default=64)
     ap.add_argument("--kernel-launches", type=int, default=200)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "device_eval.json"))
+    ap.add_argument("--agent", default="AC-IQN", choices=("AC-IQN", "DQN"))
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "device_eval_dqn.json" if a.agent == "DQN" else "device_eval.json")
     assert torch.cuda.is_available(), "this benchmark needs the GPU"
     from distributional_rl_decision_and_control_amd import _abi
     from distributional_rl_decision_and_control_amd.agent import Agent
     from distributional_rl_decision_and_control_amd.envs.marinenav.env import MarineNavEnv3
+    from distributional_rl_decision_and_control_amd.fused_dqn import DqnPack
     from distributional_rl_decision_and_control_amd.fused_mlp import MlpPack
     from distributional_rl_decision_and_control_amd.policy.batched_eval import evaluate_configs
     from distributional_rl_decision_and_control_amd.policy.device_eval import DeviceEvaluator, eval_metrics
@@ -48,11 +56,12 @@ def main():
     z = np.load(os.path.join(ROOT, "tests", "golden", "eval60_ref.npz"))
     configs = json.loads(str(z["trained/configs"]))
     torch.manual_seed(0)
-    agent = Agent(seed=100, agent_type="AC-IQN")
-    agent.policy_local.actor.load_state_dict({k[len("trained/net/"):]: torch.from_numpy(z[k]) for k in z.files
-                                              if k.startswith("trained/net/")})
+    agent = Agent(seed=100, agent_type=a.agent)
+    if a.agent == "AC-IQN":
+        agent.policy_local.actor.load_state_dict({k[len("trained/net/"):]: torch.from_numpy(z[k]) for k in z.files
+                                                  if k.startswith("trained/net/")})
     tr = Trainer(MarineNavEnv3(seed=1), MarineNavEnv3(seed=253, is_eval_env=True), SCHEDULE, agent)
-    pack = MlpPack(agent.policy_local.actor, "actor")
+    pack = DqnPack(agent.policy_local) if a.agent == "DQN" else MlpPack(agent.policy_local.actor, "actor")
 
     def clock(fn):
         torch.cuda.synchronize()
@@ -118,7 +127,7 @@ def main():
     med = lambda v: sorted(v)[len(v) // 2]   # noqa: E731
     dev = last["device_sync"]
     res = {
-        "configs": len(configs), "chunk": K, "reps": a.reps, "groups": len(ev.groups),
+        "agent": a.agent, "configs": len(configs), "chunk": K, "reps": a.reps, "groups": len(ev.groups),
         "per_robot_params": b.robot_params is not None, "load_s": load_s,
         "host_s": times["host"], "device_sync_s": times["device_sync"], "device_nosync_s": times["device_nosync"],
         "host_s_median": med(times["host"]), "device_sync_s_median": med(times["device_sync"]),
