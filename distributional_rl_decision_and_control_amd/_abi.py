@@ -229,6 +229,23 @@ class AsvDqnGradIO(C.Structure):
     _fields_ = [("rows", _VP), ("ld_rows", _I64), ("B", _I32), ("gamma", _F)] + [(n, _VP) for n in DQN_GRAD_ARRAYS]
 
 
+class AsvDdpgWeights(C.Structure):
+    _fields_ = [("trunk", AsvMlpWeights), ("wae", _VP), ("bae", _VP)]
+
+
+DDPG_GRAD_ARRAYS = ("xb", "h0", "h1", "p", "h2", "q", "q_next", "dq", "dz2", "dz1", "dzG", "dz0", "tile_loss")
+
+
+class AsvDdpgGradIO(C.Structure):
+    _fields_ = [("rows", _VP), ("ld_rows", _I64), ("B", _I32), ("gamma", _F), ("na", _VP), ("ld_na", _I64)] + \
+               [(n, _VP) for n in DDPG_GRAD_ARRAYS]
+
+
+class AsvDdpgActorIO(C.Structure):
+    _fields_ = [("x", _VP), ("ldx", _I64), ("act", _VP), ("lda", _I64), ("B", _I32), ("_pad0", _I32), ("q", _VP),
+                ("dA", _VP), ("tile_loss", _VP)]
+
+
 class AsvSampleArgs(C.Structure):
     _fields_ = [("ring", _VP), ("capacity", _I64), ("ring_state", _VP), ("seed", _U64), ("counter", _U64),
                 ("counter_dev", _VP), ("guard", _I64), ("B", _I32), ("tau_sets", _I32), ("tau_n", _I32),
@@ -412,6 +429,12 @@ EXPORTS = [
                                        C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvDqnPolicy),
                                        C.POINTER(AsvAutoReset), C.POINTER(AsvEnvLaunch), _VP]),
     ("asvrl_dqn_policy_struct_size", _I64, []),
+    ("asvrl_ddpg_grad", C.c_int, [C.POINTER(AsvDdpgWeights), C.POINTER(AsvDdpgWeights), C.POINTER(AsvDdpgGradIO),
+                                  _VP]),
+    ("asvrl_ddpg_actor_grad", C.c_int, [C.POINTER(AsvDdpgWeights), C.POINTER(AsvDdpgActorIO), _VP]),
+    ("asvrl_ddpg_weights_struct_size", _I64, []),
+    ("asvrl_ddpg_grad_struct_size", _I64, []),
+    ("asvrl_ddpg_actor_struct_size", _I64, []),
 ]
 
 _libs = {}

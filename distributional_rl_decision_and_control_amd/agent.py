@@ -22,7 +22,11 @@ save_latest_model / load_model surfaces and return types. Differences:
   * DQN (BASELINE config 1) starts on the reference's plain torch update; set_learner("fused-f32") /
     set_learner("fused-bf16") switch train_DQN to the hand-written learner (fused_dqn.dqn_update_fused with
     FusedAdam, pinned to the reference's train_DQN by tests/test_fused_dqn_gpu.py), set_learner("torch") switches
-    back. DDPG / SAC (non-distributional baselines) are out of scope and raise.
+    back. DDPG (the continuous-action baseline AC-IQN is compared against) does the same: train_DDPG starts on the
+    reference's torch update over this project's DDPG_Policy with two torch Adam optimisers, and a fused learner
+    runs fused_ddpg.ddpg_update_fused with two FusedAdam (pinned to the reference's train_DDPG by
+    tests/test_fused_ddpg_gpu.py). SAC (twin critics, a stochastic actor, an entropy term) is out of scope and
+    raises.
 """
 import copy
 import random
@@ -33,10 +37,11 @@ import torch
 import torch.nn.functional as F
 
 from . import _abi
-from . import fused_dqn, fused_iqn, fused_rainbow, fused_update
+from . import fused_ddpg, fused_dqn, fused_iqn, fused_rainbow, fused_update
 from .learn_ops import rows_from_batch
 from .learner import FlatGrads, FusedAdam, ac_iqn_update, iqn_update, rainbow_update
 from .policy.AC_IQN_model import AC_IQN_Policy
+from .policy.DDPG_model import DDPG_Policy
 from .policy.DQN_model import DQN_Policy
 from .policy.IQN_model import IQN_Policy
 from .policy.Rainbow_model import Rainbow_Policy
@@ -44,7 +49,7 @@ from .policy.replay_memory_rainbow import ReplayMemory
 from .utils.replay_buffer import ReplayBuffer
 
 DISTRIBUTIONAL = ("AC-IQN", "IQN", "Rainbow")
-SUPPORTED = DISTRIBUTIONAL + ("DQN",)
+SUPPORTED = DISTRIBUTIONAL + ("DQN", "DDPG")
 # learners of train_AC_IQN / train_IQN: the hand-written kernels with f32 operands (default, the
 # reference's arithmetic), the same kernels with bf16 operands (the batched trainer's build), or
 # the torch-autograd restatement
@@ -92,15 +97,16 @@ class Agent:
         self._rb_seed = int(seed) + 999   # the kernel path's target-noise Philox stream
         self.num_tau = 8  # training quantiles N = N' (AC_IQN_model.py:462, IQN_model.py:74)
         self.tau_override = None  # optional list of pre-drawn taus for the next train() (tests)
-        # DQN starts on the torch learner (the reference's update as it stands); set_learner selects the kernels
-        self.learner = "torch" if agent_type == "DQN" else "fused-f32"
+        # DQN and DDPG start on the torch learner (the reference's update as it stands); set_learner selects the
+        # kernels
+        self.learner = "torch" if agent_type in ("DQN", "DDPG") else "fused-f32"
         self._fused = None   # (B, N) -> FusedACIQNState / FusedIQNState, built on the first train()
         self._net_args = (self_dimension, object_dimension, max_object_num, self_feature_dimension,
                           object_feature_dimension, concat_feature_dimension, hidden_dimension)
         if agent_type not in SUPPORTED:
-            if agent_type in ("DDPG", "SAC"):
-                raise NotImplementedError(f"{agent_type} is a non-distributional baseline, outside this "
-                                          "framework's hot path (SURVEY.md section 2, row 14)")
+            if agent_type == "SAC":
+                raise NotImplementedError("SAC is a non-distributional baseline, outside this framework's hot path "
+                                          "(SURVEY.md section 2, row 14)")
             raise RuntimeError("Agent type not implemented!")
         if training:
             self.policy_local = self._make_policy(seed, value_ranges_of_action, action_size)
@@ -123,6 +129,8 @@ class Agent:
         a = self._net_args
         if self.agent_type == "AC-IQN":
             return AC_IQN_Policy(*a, value_ranges_of_action, self.device, seed)
+        if self.agent_type == "DDPG":
+            return DDPG_Policy(*a, value_ranges_of_action, self.device, seed)
         if self.agent_type == "IQN":
             return IQN_Policy(*a, action_size, self.device, seed).to(self.device)
         if self.agent_type == "DQN":
@@ -131,11 +139,16 @@ class Agent:
 
     def _make_optimizers(self):
         """optim.Adam(lr) + clip 0.5 (agent.py:75-76,98): FusedAdam (asvrl_adam_*) of the learner's
-        operand build for AC-IQN / IQN and for DQN on a fused learner, torch Adam for Rainbow and DQN's torch
-        learner."""
+        operand build for AC-IQN / IQN and for DQN / DDPG on a fused learner, torch Adam for Rainbow and the torch
+        learner of DQN / DDPG."""
         self._fused = None
         ops = LEARNERS[self.learner] or "bf16"
-        if self.agent_type == "AC-IQN":
+        if self.agent_type == "DDPG" and LEARNERS[self.learner] is None:
+            self.actor_grads = FlatGrads(self.policy_local.actor.parameters())
+            self.critic_grads = FlatGrads(self.policy_local.critic.parameters())
+            self.actor_optimizer = torch.optim.Adam(self.policy_local.actor.parameters(), lr=self.LR)
+            self.critic_optimizer = torch.optim.Adam(self.policy_local.critic.parameters(), lr=self.LR)
+        elif self.agent_type in ("AC-IQN", "DDPG"):
             self.actor_optimizer = FusedAdam(self.policy_local.actor.parameters(), lr=self.LR, operands=ops)
             self.critic_optimizer = FusedAdam(self.policy_local.critic.parameters(), lr=self.LR, operands=ops)
             self.actor_grads, self.critic_grads = self.actor_optimizer.grads, self.critic_optimizer.grads
@@ -171,6 +184,9 @@ class Agent:
                 ok = fused_update.supported(self.policy_local, B, self.num_tau)
                 st = fused_update.FusedACIQNState(self.policy_local, self.policy_target, B, self.num_tau,
                                                   operands=ops) if ok else None
+            elif self.agent_type == "DDPG":
+                ok = fused_ddpg.supported(self.policy_local, B)
+                st = fused_ddpg.FusedDDPGState(self.policy_local, self.policy_target, B, operands=ops) if ok else None
             elif self.agent_type == "DQN":
                 ok = fused_dqn.supported(self.policy_local, B)
                 st = fused_dqn.FusedDQNState(self.policy_local, self.policy_target, B, operands=ops) if ok else None
@@ -271,10 +287,11 @@ class Agent:
             return np.argmax(action_values.cpu().data.numpy())
         return random.choice(np.arange(self.action_size))
 
-    def act_ddpg(self, *a, **k):
-        raise NotImplementedError("DDPG is outside this framework's hot path")
+    def act_ddpg(self, state, eps=0.0, use_eval=True):  # agent.py:252-269: act_ac_iqn's exploration and actor
+        return self.act_ac_iqn(state, eps, use_eval=use_eval)
 
-    act_sac = act_ddpg
+    def act_sac(self, *a, **k):
+        raise NotImplementedError("SAC is outside this framework's hot path")
 
     # ------------------------------------------------------------------ learning (agent.py:370-641)
     def train(self):
@@ -286,6 +303,8 @@ class Agent:
             return self.train_Rainbow()
         if self.agent_type == "DQN":
             return self.train_DQN()
+        if self.agent_type == "DDPG":
+            return self.train_DDPG()
         raise RuntimeError("Agent type not implemented!")
 
     def _taus(self, k):
@@ -385,9 +404,41 @@ class Agent:
         self.optimizer.step()
         return loss.detach().cpu().numpy()
 
+    def train_DDPG(self):
+        """agent.py:478-516: the target critic on the target actor's action, smooth L1, clip 0.5, Adam; then the
+        actor through the updated critic. The torch learner (default) is the reference's update as it stands; a
+        fused learner runs fused_ddpg.ddpg_update_fused."""
+        s, a, r, ns, d = self.memory.sample()
+        fused = isinstance(self.critic_optimizer, FusedAdam)
+        st = self._fused_state(s[0].shape[0]) if fused else None
+        if st is not None:   # the hand-written learner
+            cl, al, _, _ = fused_ddpg.ddpg_update_fused(
+                st, self.policy_local, self.actor_optimizer, self.critic_optimizer, self.critic_grads,
+                self.actor_grads, rows_from_batch(s, a, r, ns, d), gamma=self.GAMMA)
+            return cl.cpu().numpy(), al.cpu().numpy()
+        actor, critic = self.policy_local.actor, self.policy_local.critic
+        # a fused learner on a network shape the kernels do not take (_fused_state has warned): the same autograd
+        # update into the flat gradients and the fused optimisers
+        self.critic_grads.zero_()
+        with torch.no_grad():
+            q_next = self.policy_target.critic(ns, self.policy_target.actor(ns))
+            q_targets = r + self.GAMMA * q_next * (1.0 - d)
+        critic_loss = F.smooth_l1_loss(critic(s, a), q_targets)
+        self.critic_grads.assign(torch.autograd.grad(critic_loss, self.critic_grads.params))
+        if not fused:
+            torch.nn.utils.clip_grad_norm_(critic.parameters(), 0.5)
+        self.critic_optimizer.step()
+        self.actor_grads.zero_()
+        actor_loss = -critic(s, actor(s)).mean()
+        self.actor_grads.assign(torch.autograd.grad(actor_loss, self.actor_grads.params))
+        if not fused:
+            torch.nn.utils.clip_grad_norm_(actor.parameters(), 0.5)
+        self.actor_optimizer.step()
+        return critic_loss.detach().cpu().numpy(), actor_loss.detach().cpu().numpy()
+
     def soft_update(self):
         """theta_t <- TAU theta + (1 - TAU) theta_t (agent.py:643-679)."""
-        if self.agent_type == "AC-IQN":
+        if self.agent_type in ("AC-IQN", "DDPG"):
             pairs = list(zip(self.policy_target.actor.parameters(), self.policy_local.actor.parameters())) + \
                 list(zip(self.policy_target.critic.parameters(), self.policy_local.critic.parameters()))
         else:
@@ -404,7 +455,7 @@ class Agent:
     def load_model(self, path, device="cpu"):
         dev = resolve_device(device)
         cls = {"AC-IQN": AC_IQN_Policy, "IQN": IQN_Policy, "Rainbow": Rainbow_Policy,
-               "DQN": DQN_Policy}[self.agent_type]
+               "DQN": DQN_Policy, "DDPG": DDPG_Policy}[self.agent_type]
         self.policy_local = cls.load(path, dev)
         if self.training:
             self._make_optimizers()

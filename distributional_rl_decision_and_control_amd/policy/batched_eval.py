@@ -45,7 +45,7 @@ def batched_greedy_actions(agent, states, taus=None):
     injected by the parity test."""
     kind = agent.agent_type
     s = agent.state_to_tensor(agent.memory.state_batch(states))
-    if kind == "AC-IQN":
+    if kind in ("AC-IQN", "DDPG"):
         net = agent.policy_local.actor
         net.eval()
         a = net(s).float().cpu().numpy()
@@ -75,7 +75,7 @@ def batched_greedy_actions(agent, states, taus=None):
     for g in greedy:
         if random.random() > 0.0:
             out.append(g)
-        elif kind == "AC-IQN":
+        elif kind in ("AC-IQN", "DDPG"):
             out.append([np.random.uniform(low=lo, high=hi) for lo, hi in agent.value_ranges_of_action])
         else:
             out.append(random.choice(np.arange(agent.action_size)))

@@ -12,7 +12,7 @@ reads only its own keys from it (env.py:75-94). An optional "vectorized" dict in
 (ignored by the reference) makes learn() drive VecTrainer instead: {"n_envs": E, "batch_size": B,
 "num_tau": N, ...} are VecTrainer's keyword arguments. Evaluation, evaluations.npz and the model
 files keep the reference's cadence and format; the trained networks are copied into rl_agent first.
-With "device_eval": true in that dict (AC-IQN and DQN) the evaluations run on the device with the batched
+With "device_eval": true in that dict (AC-IQN, DDPG and DQN) the evaluations run on the device with the batched
 trainer's own actor or Q network (evaluation(batched="device"), policy/device_eval.py).
 """
 import json
@@ -88,6 +88,8 @@ class Trainer:
                 return agent.act_rainbow(state, eps, use_eval=False)
             if kind == "DQN":
                 return agent.act_dqn(state, eps, use_eval=False)
+            if kind == "DDPG":
+                return agent.act_ddpg(state, eps, use_eval=False)
         else:
             if kind == "AC-IQN":
                 return agent.act_ac_iqn(state)
@@ -97,11 +99,13 @@ class Trainer:
                 return agent.act_rainbow(state)
             if kind == "DQN":
                 return agent.act_dqn(state)
+            if kind == "DDPG":
+                return agent.act_ddpg(state)
         raise RuntimeError("Agent type not implemented!")
 
     def _gather_actions(self, env, states, eps, training):
         agent = self.rl_agent
-        if training and not self.imitation and agent.agent_type == "AC-IQN":
+        if training and not self.imitation and agent.agent_type in ("AC-IQN", "DDPG"):
             # every active robot's act in one actor call, the same random draws in the same robot order
             # (Agent.act_ac_iqn_robots); IQN keeps per-robot calls (each draws its own quantile fractions)
             active = [i for i, rob in enumerate(env.robots) if not rob.deactivated]
@@ -161,13 +165,13 @@ class Trainer:
 
         from ..vec_trainer import VecTrainer
         agent = self.rl_agent
-        if agent.agent_type not in ("AC-IQN", "IQN", "Rainbow", "DQN"):
-            raise ValueError(f"vectorized training covers AC-IQN, IQN, Rainbow and DQN, not {agent.agent_type}")
+        if agent.agent_type not in ("AC-IQN", "IQN", "Rainbow", "DQN", "DDPG"):
+            raise ValueError(f"vectorized training covers AC-IQN, IQN, Rainbow, DQN and DDPG, not {agent.agent_type}")
         sched = {k: v for k, v in self.train_env.schedule.items() if k != "vectorized"}
         kw = dict(vec)
-        # "device_eval": true evaluates on the device with the batched trainer's own actor (AC-IQN) or Q network
+        # "device_eval": true evaluates on the device with the batched trainer's own actor (AC-IQN, DDPG) or Q network
         # (DQN; evaluation(batched="device")) instead of copying the networks out and stepping the Python eval envs
-        device_eval = bool(kw.pop("device_eval", False)) and agent.agent_type in ("AC-IQN", "DQN")
+        device_eval = bool(kw.pop("device_eval", False)) and agent.agent_type in ("AC-IQN", "DQN", "DDPG")
         kw.setdefault("graphs", True)
         for key, sk in (("num_robots", "num_robots"), ("num_obs", "num_obstacles"), ("num_cores", "num_cores")):
             if sk in sched:

@@ -8,7 +8,7 @@ One iteration (= one `step` of bench.py):
   3. replay push of the transitions of robots that acted (asvrl_replay_push, trainer.py:157-166)
   4. device reset of finished envs + their first observation (asvrl_env_reset, trainer.py:212-245)
   5. learn: sample B transitions (asvrl_replay_sample) and one distributional update
-     (AC-IQN: two dependent optimizer steps, critic then actor; IQN, Rainbow and DQN: one)
+     (AC-IQN and DDPG: two dependent optimizer steps, critic then actor; IQN, Rainbow and DQN: one)
   6. hard target update every `target_update_interval` learn steps (agent.py:643-679, TAU=1)
 
 Cadence in the batched setting: one learn step of batch B per iteration (after
@@ -22,6 +22,9 @@ import torch
 
 from . import streams
 from .fused_update import FusedACIQNState, ac_iqn_update_fused2, learn_prologue
+from .fused_ddpg import FusedDDPGState, ddpg_update_fused
+from .fused_ddpg import learn_prologue as ddpg_learn_prologue
+from .fused_ddpg import supported as fused_ddpg_supported
 from .fused_dqn import FusedDQNState, dqn_update_fused
 from .fused_dqn import supported as fused_dqn_supported
 from .fused_iqn import FusedIQNState, iqn_update_fused
@@ -31,6 +34,7 @@ from .fused_update import supported as fused2_supported
 from .learn_ops import DevicePER, DeviceReplay
 from .learner import FusedAdam
 from .policy.AC_IQN_model import AC_IQN_Policy
+from .policy.DDPG_model import DDPG_Policy
 from .policy.DQN_model import DQN_Policy
 from .policy.IQN_model import IQN_Policy
 from .policy.Rainbow_model import Rainbow_Policy
@@ -47,7 +51,8 @@ class VecTrainer:
                  exploration_fraction=0.25, initial_eps=0.6, final_eps=0.05, seed=0,
                  device="cuda", sync=None, graphs=False, schedule=None, net_seed=100, overlap=True, unroll=1,
                  chain=None, operands="bf16", target_after_env=False, push_after_actor=None):
-        """Every learner runs on the hand-written kernels (fused_update / fused_iqn / fused_rainbow / fused_dqn) with
+        """Every learner runs on the hand-written kernels (fused_update / fused_iqn / fused_rainbow / fused_dqn /
+        fused_ddpg) with
         FusedAdam; operands="f32" takes them from the f32-operand parity build (libasvrl_f32.so). Shapes
         the kernels do not take raise ValueError."""
         self.device = torch.device(device)
@@ -61,7 +66,7 @@ class VecTrainer:
         # of the same iteration instead of running beside it (None: wherever the chained AC-IQN graph runs)
         self._paa_arg = push_after_actor
         self.push_after_actor = bool(push_after_actor)
-        self.continuous = agent_type == "AC-IQN"
+        self.continuous = agent_type in ("AC-IQN", "DDPG")
         self.env = VecMarineNavEnv(n_envs, num_robots, num_obs, num_cores, min_start_goal_dis, width, seed=seed,
                                    device=self.device, is_continuous=self.continuous, gamma=gamma, schedule=schedule)
         self.E, self.R = n_envs, self.env.max_robots
@@ -73,7 +78,7 @@ class VecTrainer:
         self.total_timesteps = total_timesteps
         self.exploration_fraction, self.initial_eps, self.final_eps = exploration_fraction, initial_eps, final_eps
         self.learning_starts = learning_starts if learning_starts is not None else batch_size
-        self.fused2 = self.fused_iqn = self.fused_rb = self.fused_dqn = None
+        self.fused2 = self.fused_iqn = self.fused_rb = self.fused_dqn = self.fused_ddpg = None
         if agent_type == "AC-IQN":
             self.local = AC_IQN_Policy(**DEFAULT_NET, value_ranges_of_action=[[-1.0, 1.0], [-1.0, 1.0]],
                                        device=self.device, seed=net_seed)
@@ -129,8 +134,28 @@ class VecTrainer:
             self.grads = self.opt.grads
             self.action_dim = 1
             self.fused_dqn = FusedDQNState(self.local, self.target, batch_size, operands)
+        elif agent_type == "DDPG":
+            # DDPG_Policy: AC-IQN's Actor and a one-scalar critic (fused_ddpg.py); set up like AC-IQN's branch --
+            # the uniform ring, two optimisers, a double actor image set
+            self.local = DDPG_Policy(**DEFAULT_NET, value_ranges_of_action=[[-1.0, 1.0], [-1.0, 1.0]],
+                                     device=self.device, seed=net_seed)
+            self.target = DDPG_Policy(**DEFAULT_NET, value_ranges_of_action=[[-1.0, 1.0], [-1.0, 1.0]],
+                                      device=self.device, seed=net_seed)
+            for p in list(self.target.actor.parameters()) + list(self.target.critic.parameters()):
+                p.requires_grad_(False)
+            if not fused_ddpg_supported(self.local, batch_size):
+                raise ValueError(f"DDPG learner kernels: B={batch_size} (a positive multiple of 32)")
+            self.actor_opt = FusedAdam(self.local.actor.parameters(), lr=lr, operands=operands)
+            self.critic_opt = FusedAdam(self.local.critic.parameters(), lr=lr, operands=operands)
+            self.actor_grads, self.critic_grads = self.actor_opt.grads, self.critic_opt.grads
+            self.action_dim = 2
+            # two actor image sets flip at every update, host-side: a captured graph of an odd number of iterations
+            # would replay on the set it was captured on and never see the other one written -- one set there, and
+            # the update waits for the act kernel instead (ddpg_update_fused's actor_wait)
+            self.fused_ddpg = FusedDDPGState(self.local, self.target, batch_size, operands,
+                                             double_actor=not graphs or max(1, int(unroll)) % 2 == 0)
         else:
-            raise NotImplementedError(f"VecTrainer agent_type {agent_type!r} (AC-IQN, IQN, Rainbow and DQN are "
+            raise NotImplementedError(f"VecTrainer agent_type {agent_type!r} (AC-IQN, IQN, Rainbow, DQN and DDPG are "
                                       "batched)")
         NT = self.E * self.R
         self.per = None
@@ -180,6 +205,10 @@ class VecTrainer:
         # AC-IQN only (measured 0.346 -> 0.340 ms/step; IQN, whose act kernel fills the GPU, 0.363 ->
         # 0.366: profiles/r02_chain_schedule_ab.txt)
         self.chain = (agent_type == "AC-IQN") if chain is None else bool(chain)
+        if self.chain and self.fused_ddpg is not None:
+            # not built for DDPG: refused rather than silently run as the joined schedule
+            raise ValueError("the dependency-chained schedule is not available for DDPG (chain=None or False: the "
+                             "joined schedule)")
         if self.target_after_env and not (self.fused2 is not None and self.graphs and self._chained()):
             # the knob orders two nodes of the chained AC-IQN graph; anywhere else it would be silently ignored
             # and a bench config recording it would be mislabelled
@@ -215,8 +244,15 @@ class VecTrainer:
             self.fused_iqn.act(*args)
         elif self.fused_dqn is not None:   # Q per robot, argmax, explore
             self.fused_dqn.act(*args)
+        elif self.fused_ddpg is not None:   # DDPG's actor (the AC-IQN Actor) on every robot row, explore
+            self.fused_ddpg.act(*args)
         else:   # actor on every robot row, explore
             self.fused2.act(*args)
+
+    def _actor_pack(self):
+        """The local Actor's images (AC-IQN and DDPG, whose policy is that Actor), or None."""
+        st = self.fused2 if self.fused2 is not None else self.fused_ddpg
+        return st.actor if st is not None else None
 
     def _eval_env(self):
         """A fresh env batch of the training env's shape, parameters and current curriculum stage, with its own
@@ -237,17 +273,17 @@ class VecTrainer:
         closed-loop windows of `chunk` steps, one launch each (VecMarineNavEnv.policy_rollout with epsilon 0 and
         hold_done; an env that ended stays out of the later windows), until every env has ended or after
         max_steps. Returns that batch's episode_stats() plus steps_run, the steps every env took. The training
-        env, the replay and the step counter are not touched. AC-IQN only."""
-        if self.fused2 is None:
-            raise NotImplementedError("greedy_episodes runs the AC-IQN actor; IQN, Rainbow and DQN act inside their "
-                                      "own kernels")
+        env, the replay and the step counter are not touched. AC-IQN and DDPG only."""
+        if self._actor_pack() is None:
+            raise NotImplementedError("greedy_episodes runs the AC-IQN / DDPG actor; IQN, Rainbow and DQN act inside "
+                                      "their own kernels")
         env = self._eval_env()
         alive = torch.ones(self.E, dtype=torch.uint8, device=self.device)
         steps_run = torch.zeros(self.E, dtype=torch.int32, device=self.device)
         done = 0
         while done < max_steps:
             k = min(int(chunk), max_steps - done)
-            rec = env.policy_rollout(self.fused2.actor, k, hold_done=True, keep=("env_done",), env_mask=alive)
+            rec = env.policy_rollout(self._actor_pack(), k, hold_done=True, keep=("env_done",), env_mask=alive)
             env.advance_device(counted=True)   # the next window acts on this one's last observation
             steps_run += rec.steps_run
             alive *= (rec.env_done.sum(0) == 0).to(torch.uint8)
@@ -263,20 +299,21 @@ class VecTrainer:
         current local actor greedily in closed-loop windows of `chunk` steps and reduces the windows to the
         reference's per-config rewards / successes / times / energies / lengths on the device. kw: run()'s seed,
         episode_limit and sync. The actor's packed images are the learner's own, so no copy into a drop-in agent is
-        needed; the training env, the replay and the step counter are not touched. AC-IQN only."""
-        if self.fused2 is None:
-            raise NotImplementedError("evaluate runs the AC-IQN actor; IQN, Rainbow and DQN act inside their own "
-                                      "kernels")
-        return self.device_evaluator(configs, chunk, template_env).run(self.fused2.actor, **kw)
+        needed; the training env, the replay and the step counter are not touched. AC-IQN and DDPG only."""
+        if self._actor_pack() is None:
+            raise NotImplementedError("evaluate runs the AC-IQN / DDPG actor; IQN, Rainbow and DQN act inside their "
+                                      "own kernels")
+        return self.device_evaluator(configs, chunk, template_env).run(self._actor_pack(), **kw)
 
     def policy_pack(self):
         """The pack the closed-loop windows take (DeviceEnvBatch.policy_rollout, DeviceEvaluator.run): the learner's
-        own local images -- AC-IQN's actor or DQN's local net. IQN and Rainbow act inside their own kernels."""
-        if self.fused2 is not None:
-            return self.fused2.actor
+        own local images -- AC-IQN's or DDPG's actor or DQN's local net. IQN and Rainbow act inside their own
+        kernels."""
+        if self._actor_pack() is not None:
+            return self._actor_pack()
         if self.fused_dqn is not None:
             return self.fused_dqn.local
-        raise NotImplementedError(f"policy_pack: the closed-loop windows run the AC-IQN actor or DQN_Policy, not "
+        raise NotImplementedError(f"policy_pack: the closed-loop windows run the AC-IQN / DDPG actor or DQN_Policy, not "
                                   f"{self.agent_type}")
 
     def device_evaluator(self, configs, chunk=64, template_env=None):
@@ -339,16 +376,16 @@ class VecTrainer:
         auto_reset), recorded into persistent buffers, then one push of the whole window into the uniform ring
         (DeviceReplay.push_window), which also advances the step counter by K. No host sync: the call can be
         graph-captured. Returns the window's records (views of the persistent buffers: obs, obs_prev, obj_cnt,
-        reward, done, actions, steps_run, pushed, resets). AC-IQN with the uniform ring only; the caller accounts for
-        the host-side step count (env.advance_host() per step) as iteration() does."""
-        if self.fused2 is None or self.per is not None:
-            raise NotImplementedError("collect runs the AC-IQN actor and pushes into the uniform ring; IQN, Rainbow "
-                                      "and DQN act inside their own kernels")
+        reward, done, actions, steps_run, pushed, resets). AC-IQN and DDPG (the uniform ring) only; the caller accounts
+        for the host-side step count (env.advance_host() per step) as iteration() does."""
+        if self._actor_pack() is None or self.per is not None:
+            raise NotImplementedError("collect runs the AC-IQN / DDPG actor and pushes into the uniform ring; IQN, "
+                                      "Rainbow and DQN act inside their own kernels")
         K = int(K)
         buf = self._collect_buffers(K)
         buf["obj_cnt"].fill_(-1)   # a row no env took is never pushed
         keep = {k: buf[k] for k in ("obs", "obs_prev", "obj_cnt", "reward", "done", "actions", "steps_run")}
-        rec = self.env.policy_rollout(self.fused2.actor, K, hold_done=False, keep=keep,
+        rec = self.env.policy_rollout(self._actor_pack(), K, hold_done=False, keep=keep,
                                       eps=(self.E, self.total_timesteps, self.exploration_fraction, self.initial_eps,
                                            self.final_eps), policy_seed=self.seed + 4242,
                                       auto_reset=dict(pushed=buf["pushed"], resets=buf["resets"]), count=False)
@@ -380,6 +417,13 @@ class VecTrainer:
                                         self.actor_grads, rows, gamma=self.gamma, sync=self.sync,
                                         actor_wait=actor_wait, taus=self.taus, counter=self.learn_counter,
                                         prologue_done=True, target_wait=target_wait, actor_done=actor_done)
+        if self.fused_ddpg is not None:
+            # one launch: the draw (no quantile fractions), the actor's training forward and the target actor
+            rows = ddpg_learn_prologue(self.fused_ddpg, self.replay, self.seed + 777, counter_dev=self.learn_counter,
+                                       out=self.batch_rows, state=state, guard=guard)
+            return ddpg_update_fused(self.fused_ddpg, self.local, self.actor_opt, self.critic_opt, self.critic_grads,
+                                     self.actor_grads, rows, gamma=self.gamma, sync=self.sync, actor_wait=actor_wait,
+                                     counter=self.learn_counter, prologue_done=True)
         if self.fused_dqn is not None:   # no quantile fractions to draw
             rows = self.replay.sample(self.B, seed=self.seed + 777, counter_dev=self.learn_counter,
                                       out=self.batch_rows, state=state, guard=guard)
@@ -394,7 +438,7 @@ class VecTrainer:
     def hard_update(self):
         """soft_update with TAU = 1.0 (agent.py:643-679): target <- local."""
         with torch.no_grad():
-            if self.agent_type == "AC-IQN":
+            if self.agent_type in ("AC-IQN", "DDPG"):
                 pairs = list(zip(self.target.actor.parameters(), self.local.actor.parameters())) + \
                     list(zip(self.target.critic.parameters(), self.local.critic.parameters()))
             else:
@@ -408,6 +452,8 @@ class VecTrainer:
                 self.fused_rb.target_changed()
             if self.fused_dqn is not None:
                 self.fused_dqn.target_changed()
+            if self.fused_ddpg is not None:
+                self.fused_ddpg.target_changed()
 
     @torch.no_grad()
     def load_policies(self, local, target):
@@ -437,6 +483,10 @@ class VecTrainer:
         if self.fused_dqn is not None:
             self.fused_dqn.local.refresh()
             self.fused_dqn.target_changed()
+        if self.fused_ddpg is not None:
+            self.fused_ddpg.local.refresh()
+            self.fused_ddpg.actor.refresh()
+            self.fused_ddpg.target_changed()
 
     # ------------------------------------------------------------------ iteration
     def _iteration_body(self, do_learn):

@@ -1220,6 +1220,70 @@ int asvrl_dqn_rollout_ar(const AsvParams* params, const AsvEnvState* state, cons
 /* sizeof(AsvDqnPolicy) as compiled. */
 int64_t asvrl_dqn_policy_struct_size(void);
 
+/* ---------------------------------------------------------------- DDPG (agent.py:252-269, 478-516)
+ * DDPG_model.Actor is the AC-IQN Actor layer for layer and runs its kernels unchanged. DDPG_model.Critic is one
+ * scalar per sample: both observation encoders -> F (256), hidden_layer 256 -> 128 (h1), the product with
+ * G = relu(action_encoder(a)), hidden_layer_2 128 -> 128 (h2) and a 128 -> 1 output. It runs the one-wave Actor
+ * tile: its images are the Actor's (AsvMlpWeights, asvrl_mlp_pack) and the action encoder is read as f32.
+ * New entry points only: the ABI version stays 29. */
+typedef struct AsvDdpgWeights {
+  AsvMlpWeights trunk;    /* enc / w1 / w2 images (w2t / w1t for a backward), b1, b2; wout: f32 [2][128], row 0
+                             output_layer.weight, row 1 padding; bout: f32 [2], element 0 output_layer.bias;
+                             ae_frag, b_ae, out_scale unused */
+  const float* wae;       /* action_encoder weight, f32 [128][2] */
+  const float* bae;       /* action_encoder bias, f32 [128] */
+} AsvDdpgWeights;
+
+/* One DDPG critic gradient over B replay rows (ASVRL_TR_DIM layout: s | s' | action (2) | reward | done):
+ * q = Q_local(s, a), q_next = Q_target(s', na), y = r + gamma (1 - d) q_next, loss = mean smooth_l1(q - y)
+ * (beta 1), dq = clamp(q - y, -1, 1) / B, and the backward to every layer's pre-activation gradient. Saved
+ * activations and gradients are in the build's operand type (bf16 / f32) unless marked f32. */
+typedef struct AsvDdpgGradIO {
+  const float* rows;      /* [B] replay rows at stride ld_rows floats, 16-byte aligned */
+  int64_t ld_rows;
+  int32_t B;              /* a positive multiple of 32 */
+  float gamma;
+  const float* na;        /* [B] the target actor's action on s' at stride ld_na floats */
+  int64_t ld_na;
+  void* xb;               /* out [B][32]: obs columns 0..31 of s (operand of the encoder weight gradient) */
+  void* h0;               /* out [B][256]: F */
+  void* h1;               /* out [B][128] */
+  void* p;                /* out [B][128]: h1 * G, hidden_layer_2's input */
+  void* h2;               /* out [B][128] */
+  float* q;               /* out f32 [B] */
+  float* q_next;          /* out f32 [B] */
+  float* dq;              /* out f32 [B]: the output layer's pre-activation gradient */
+  void* dz2;              /* out [B][128] */
+  void* dz1;              /* out [B][128] */
+  float* dzG;             /* out f32 [B][128]: the action encoder's pre-activation gradient */
+  void* dz0;              /* out [B][256]: dzF */
+  float* tile_loss;       /* out f32 [B / 32]: per-tile loss partials, loss = their sum */
+} AsvDdpgGradIO;
+
+/* The actor step's gradient to the action (agent.py:504-507): q = Q_local(s, a_pi), loss = -mean q,
+ * dA = d loss / d a_pi, in one launch without saved activations. */
+typedef struct AsvDdpgActorIO {
+  const float* x;         /* [B] observation rows at stride ldx floats, 16-byte aligned */
+  int64_t ldx;
+  const float* act;       /* [B] the actor's actions at stride lda floats */
+  int64_t lda;
+  int32_t B;              /* a positive multiple of 32 */
+  int32_t _pad0;
+  float* q;               /* optional out f32 [B] */
+  float* dA;              /* out f32 [B][2] */
+  float* tile_loss;       /* out f32 [B / 32]: per-tile partials of -mean q */
+} AsvDdpgActorIO;
+
+/* Two launches, no host sync: both forwards (local on (s, a) saving activations, target on (s', na)), then
+ * loss + backward. The weight gradients follow from (dq, h2), (dz2, p), (dz1, h0), (dzG, a), (dz0, xb) by
+ * asvrl_linear_wgrad_multi. */
+int asvrl_ddpg_grad(const AsvDdpgWeights* local, const AsvDdpgWeights* target, const AsvDdpgGradIO* io, void* stream);
+int asvrl_ddpg_actor_grad(const AsvDdpgWeights* local, const AsvDdpgActorIO* io, void* stream);
+/* sizeof(AsvDdpgWeights), sizeof(AsvDdpgGradIO), sizeof(AsvDdpgActorIO) as compiled. */
+int64_t asvrl_ddpg_weights_struct_size(void);
+int64_t asvrl_ddpg_grad_struct_size(void);
+int64_t asvrl_ddpg_actor_struct_size(void);
+
 /* ---------------------------------------------------------------- misc */
 const char* asvrl_last_error(void);
 int asvrl_abi_version(void);

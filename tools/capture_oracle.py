@@ -24,6 +24,7 @@ Fixture families:
   learn_rainbow_full.npz F6b  the same at the default network size (the size the kernels take),
                         networks from a numpy-seeded generator (oracle/learn_ref.py)
   learn_dqn.npz     F8  Agent.train_DQN / act_dqn (agent.py:518-545, 271-287)
+  learn_ddpg.npz    F8b Agent.train_DDPG / act_ddpg (agent.py:478-516, 252-269) and the critic's q (capture_ddpg)
   eval_ref.npz      F9  Trainer.evaluation (trainer.py:266-392), AC-IQN and Rainbow
   eval_iqn_ref.npz  F9b the same for IQN with every act_iqn call's K = 32 taus recorded (capture_eval_iqn)
   eval60_ref.npz    F10 Trainer.evaluation on config/ac_iqn.json's 60-episode eval_schedule, the seeded
@@ -1014,6 +1015,46 @@ def capture_dqn():
     out["act/q"] = np.asarray(q)
     np.savez_compressed(os.path.join(OUT, "learn_dqn.npz"), **out)
     print("dqn keys:", len(out))
+
+
+def capture_ddpg():
+    """F8b: Agent.train_DDPG (agent.py:478-516) x 2 steps on continuous transitions, and act_ddpg's action
+    (agent.py:252-269) with the critic's q for that state and action, both at the initial weights."""
+    out = {}
+    trans = collect_transitions(300, seed=7)
+    rs = np.random.RandomState(71)
+    agent = ref_agent_mod.Agent(device="cpu", seed=100, agent_type="DDPG")
+    out.update(sd_arrays("init/actor/", agent.policy_local.actor))
+    out.update(sd_arrays("init/critic/", agent.policy_local.critic))
+    # the target nets start as copies of the local ones (the same seeds): recorded as that fact, not as a second
+    # copy of 100 k weights, which would put the file over the size limit for a committed fixture
+    for kind in ("actor", "critic"):
+        tsd, lsd = getattr(agent.policy_target, kind).state_dict(), getattr(agent.policy_local, kind).state_dict()
+        assert list(tsd) == list(lsd) and all(torch.equal(tsd[k], lsd[k]) for k in lsd)
+    out["target/equals_init"] = np.bool_(True)
+    st = trans[7][0]
+    a = agent.act_ddpg(st, eps=0.0)
+    with torch.no_grad():
+        q = agent.policy_local.critic(agent.state_to_tensor(agent.memory.state_batch([st])),
+                                      torch.tensor([a]).float()).numpy()
+    out["act/state_self"] = np.array(st[0], dtype=np.float64)
+    out["act/state_obj"] = np.array(st[1], dtype=np.float64).reshape(-1, 5)
+    out["act/action"] = np.array(a, dtype=np.float64)
+    out["act/q"] = np.asarray(q)
+    for step in range(2):
+        idx = rs.choice(len(trans), 64, replace=False)
+        batch = make_batch(agent, trans, idx)
+        out.update(batch_arrays(f"step{step}/", *batch, 64))
+        agent.memory.sample = (lambda b=batch: b)
+        with ClipRecorder() as cr:
+            closs, aloss = agent.train_DDPG()
+        out[f"step{step}/critic_loss"] = np.float64(closs)
+        out[f"step{step}/actor_loss"] = np.float64(aloss)
+        out[f"step{step}/grad_norms"] = np.array(cr.norms)  # critic, actor (pre-clip)
+    out.update(sd_arrays("after1/actor/", agent.policy_local.actor))
+    out.update(sd_arrays("after1/critic/", agent.policy_local.critic))
+    np.savez_compressed(os.path.join(OUT, "learn_ddpg.npz"), **out)
+    print("ddpg keys:", len(out))
 
 
 EVAL_SCHEDULE = {"num_episodes": [2, 2], "num_robots": [3, 5], "num_cores": [0, 2], "num_obstacles": [2, 4],
