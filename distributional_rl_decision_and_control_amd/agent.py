@@ -37,14 +37,11 @@ import torch
 import torch.nn.functional as F
 
 from . import _abi
-from . import fused_ddpg, fused_dqn, fused_iqn, fused_rainbow, fused_update
+from . import fused_ddpg, fused_dqn, fused_iqn, fused_update
 from .learn_ops import rows_from_batch
 from .learner import FlatGrads, FusedAdam, ac_iqn_update, iqn_update, rainbow_update
-from .policy.AC_IQN_model import AC_IQN_Policy
-from .policy.DDPG_model import DDPG_Policy
-from .policy.DQN_model import DQN_Policy
-from .policy.IQN_model import IQN_Policy
-from .policy.Rainbow_model import Rainbow_Policy
+from .learners import LEARNERS as SPECS
+from .learners import policy_parameters
 from .policy.replay_memory_rainbow import ReplayMemory
 from .utils.replay_buffer import ReplayBuffer
 
@@ -126,16 +123,8 @@ class Agent:
 
     # ------------------------------------------------------------------ construction
     def _make_policy(self, seed, value_ranges_of_action, action_size):
-        a = self._net_args
-        if self.agent_type == "AC-IQN":
-            return AC_IQN_Policy(*a, value_ranges_of_action, self.device, seed)
-        if self.agent_type == "DDPG":
-            return DDPG_Policy(*a, value_ranges_of_action, self.device, seed)
-        if self.agent_type == "IQN":
-            return IQN_Policy(*a, action_size, self.device, seed).to(self.device)
-        if self.agent_type == "DQN":
-            return DQN_Policy(*a, action_size, self.device, seed).to(self.device)
-        return Rainbow_Policy(*a, action_size, 51, self.device, seed).to(self.device)
+        return SPECS[self.agent_type].make_policy(self._net_args, self.device, seed, value_ranges_of_action,
+                                                  action_size)
 
     def _make_optimizers(self):
         """optim.Adam(lr) + clip 0.5 (agent.py:75-76,98): FusedAdam (asvrl_adam_*) of the learner's
@@ -148,7 +137,7 @@ class Agent:
             self.critic_grads = FlatGrads(self.policy_local.critic.parameters())
             self.actor_optimizer = torch.optim.Adam(self.policy_local.actor.parameters(), lr=self.LR)
             self.critic_optimizer = torch.optim.Adam(self.policy_local.critic.parameters(), lr=self.LR)
-        elif self.agent_type in ("AC-IQN", "DDPG"):
+        elif SPECS[self.agent_type].actor_critic:
             self.actor_optimizer = FusedAdam(self.policy_local.actor.parameters(), lr=self.LR, operands=ops)
             self.critic_optimizer = FusedAdam(self.policy_local.critic.parameters(), lr=self.LR, operands=ops)
             self.actor_grads, self.critic_grads = self.actor_optimizer.grads, self.critic_optimizer.grads
@@ -176,25 +165,10 @@ class Agent:
             return None
         key = (B, self.num_tau)
         if self._fused is None or self._fused[0] != key:
-            if self.agent_type == "Rainbow":
-                ok = fused_rainbow.supported(self.policy_local, B)
-                st = fused_rainbow.FusedRainbow(self.policy_local, self.policy_target, B, self.support,
-                                                operands=ops) if ok else None
-            elif self.agent_type == "AC-IQN":
-                ok = fused_update.supported(self.policy_local, B, self.num_tau)
-                st = fused_update.FusedACIQNState(self.policy_local, self.policy_target, B, self.num_tau,
-                                                  operands=ops) if ok else None
-            elif self.agent_type == "DDPG":
-                ok = fused_ddpg.supported(self.policy_local, B)
-                st = fused_ddpg.FusedDDPGState(self.policy_local, self.policy_target, B, operands=ops) if ok else None
-            elif self.agent_type == "DQN":
-                ok = fused_dqn.supported(self.policy_local, B)
-                st = fused_dqn.FusedDQNState(self.policy_local, self.policy_target, B, operands=ops) if ok else None
-            else:
-                ok = fused_iqn.supported(self.policy_local, B, self.num_tau)
-                # nothing runs beside the drop-in's update: the target's max inside the fused launch (bf16 build)
-                st = fused_iqn.FusedIQNState(self.policy_local, self.policy_target, B, self.num_tau,
-                                             operands=ops, target_in_fused=True) if ok else None
+            spec, st = SPECS[self.agent_type], None
+            if spec.supported(self.policy_local, B, self.num_tau):
+                st = spec.state(self.policy_local, self.policy_target, B, self.num_tau, ops,
+                                support=getattr(self, "support", None))
             if st is None:
                 # not silent: this batch / network shape runs on the torch-autograd learner (learner.py), not on
                 # the hand-written kernels
@@ -438,13 +412,8 @@ class Agent:
 
     def soft_update(self):
         """theta_t <- TAU theta + (1 - TAU) theta_t (agent.py:643-679)."""
-        if self.agent_type in ("AC-IQN", "DDPG"):
-            pairs = list(zip(self.policy_target.actor.parameters(), self.policy_local.actor.parameters())) + \
-                list(zip(self.policy_target.critic.parameters(), self.policy_local.critic.parameters()))
-        else:
-            pairs = list(zip(self.policy_target.parameters(), self.policy_local.parameters()))
         with torch.no_grad():
-            for t, l in pairs:
+            for t, l in zip(policy_parameters(self.policy_target), policy_parameters(self.policy_local)):
                 t.data.copy_(self.TAU * l.data + (1.0 - self.TAU) * t.data)
         if self._fused is not None and self._fused[1] is not None:
             self._fused[1].target_changed()   # re-pack the target networks' weight images
@@ -454,8 +423,6 @@ class Agent:
 
     def load_model(self, path, device="cpu"):
         dev = resolve_device(device)
-        cls = {"AC-IQN": AC_IQN_Policy, "IQN": IQN_Policy, "Rainbow": Rainbow_Policy,
-               "DQN": DQN_Policy, "DDPG": DDPG_Policy}[self.agent_type]
-        self.policy_local = cls.load(path, dev)
+        self.policy_local = SPECS[self.agent_type].policy.load(path, dev)
         if self.training:
             self._make_optimizers()

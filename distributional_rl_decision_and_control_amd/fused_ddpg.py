@@ -36,9 +36,7 @@ from . import _abi
 from .fused_critic import PartialArena
 from .fused_mlp import (ENC, HID, OBSK, ActorBuffers, ActorGrads, MlpPack, actor_act, actor_backward, actor_forward,
                         actor_train_forward)
-from .fused_mlp import actor_grads as actor_grads_launch
-from .fused_update import _reduce_and_step
-from .learner import FusedAdam, clip_and_step
+from .fused_update import _actor_step, _reduce_and_step, learn_prologue
 
 OBS = 40
 
@@ -107,7 +105,8 @@ class FusedDDPGState:
         self.B, self.device, self.operands = B, dev, operands
         self.local = DdpgCriticPack(policy_local.critic, operands)
         self.target = DdpgCriticPack(policy_target.critic, operands)
-        self.actor = MlpPack(policy_local.actor, "actor", operands, double=double_actor)
+        self.actor = self.actor_pack = self.policy_pack = MlpPack(policy_local.actor, "actor", operands,
+                                                                  double=double_actor)
         self.target_actor = MlpPack(policy_target.actor, "actor", operands)
         self.abufs = ActorBuffers(B, dev, operands)
         self.agrads = ActorGrads(B, dev, operands)
@@ -136,28 +135,22 @@ class FusedDDPGState:
         self.target.refresh()
         self.target_actor.refresh()
 
+    def refresh_local(self):
+        """Re-pack the local networks after their parameters were loaded (eager, outside graphs)."""
+        self.local.refresh()
+        self.actor.refresh()
+
     def act(self, obs_rows, actions64, step_dev, steps_per_count, total, fraction, initial, final, seed):
         actor_act(self.actor, obs_rows, actions64, step_dev, steps_per_count, total, fraction, initial, final, seed)
 
-
-def learn_prologue(st, replay, seed, counter_dev=None, counter=0, out=None, state=None, guard=0, stream=None):
-    """asvrl_learn_prologue without quantile fractions: B rows drawn from the device ring, the local actor's TRAIN
-    forward on s (its activations in st.abufs) and the target actor's forward on s' (st.na) in ONE launch,
-    bit-identical to replay.sample + actor_train_forward + actor_forward. Returns the rows [B][88]."""
-    B = st.B
-    out = out if out is not None else torch.empty((B, 88), dtype=torch.float32, device=st.device)
-    sa = _abi.AsvSampleArgs()
-    sa.ring, sa.capacity = replay.ring.data_ptr(), replay.capacity
-    sa.ring_state = (state if state is not None else replay.state).data_ptr()
-    sa.seed, sa.counter = int(seed) & 0xFFFFFFFFFFFFFFFF, int(counter) & 0xFFFFFFFFFFFFFFFF
-    sa.counter_dev = _abi.ptr(counter_dev)
-    sa.guard, sa.B, sa.tau_sets, sa.tau_n = int(guard), B, 0, 0
-    sa.out, sa.taus = out.data_ptr(), None
-    io = st.abufs.io()
-    _abi.check(st.actor.L.asvrl_learn_prologue(C.byref(sa), C.byref(st.actor.w), C.byref(io),
-                                                C.byref(st.target_actor.w), st.na.data_ptr(),
-                                                _abi.stream_ptr(stream)), "asvrl_learn_prologue", st.actor.L)
-    return out
+    def learn(self, tr, state=None, guard=0, actor_wait=None, target_wait=None, actor_done=None):
+        """VecTrainer.learn: the draw from tr's ring into tr's buffers, then the update on tr's optimisers."""
+        # one launch: the draw (no quantile fractions), the actor's training forward and the target actor
+        rows = learn_prologue(self, tr.replay, None, tr.seed + 777, counter_dev=tr.learn_counter, out=tr.batch_rows,
+                              state=state, guard=guard)
+        return ddpg_update_fused(self, tr.local, tr.actor_opt, tr.critic_opt, tr.critic_grads, tr.actor_grads, rows,
+                                 gamma=tr.gamma, sync=tr.sync, actor_wait=actor_wait, counter=tr.learn_counter,
+                                 prologue_done=True)
 
 
 def ddpg_critic_grads(st, critic, rows, gamma=0.99, flush=True, stream=None):
@@ -218,30 +211,5 @@ def ddpg_update_fused(st, policy_local, actor_opt, critic_opt, critic_grads, act
     # ---- actor through the updated critic (agent.py:504-511)
     ddpg_actor_grad(st, s_rows, ab.a_out, q=st.q_pi)
     actor_backward(st.actor, ab)
-    # every actor .grad, the actor loss, the norm partials and the Adam step count in one launch
-    fused_opt = sync is None and isinstance(actor_opt, FusedAdam)
-    actor_grads_launch(st.agrads, ab, actor, st.tile_loss[1], st.losses[1:2],
-                       step=actor_opt.step_t if fused_opt else None, norm=fused_opt)
-    if isinstance(actor_opt, FusedAdam):
-        assert actor_opt.max_norm == max_norm, (actor_opt.max_norm, max_norm)
-        if sync is not None:
-            sync(actor_grads)
-        # a concurrent act kernel reads the current actor images: with two sets the step writes the other one
-        if actor_wait is not None and not st.actor.double:
-            torch.cuda.current_stream().wait_event(actor_wait)
-        if fused_opt:
-            agn = actor_opt.step_prenormed(st.agrads.norm_parts, st.agrads.nparts,
-                                           pack=st.actor.adam_segments(actor_opt), counter=counter)
-        else:   # data-parallel: the norm over the all-reduced gradient, then the same packing step
-            agn = actor_opt.step_synced(pack=st.actor.adam_segments(actor_opt), counter=counter)
-        st.actor.flip()
-    else:
-        if sync is not None:
-            sync(actor_grads)
-        if actor_wait is not None:
-            torch.cuda.current_stream().wait_event(actor_wait)
-        agn = clip_and_step(actor_opt, actor_grads, max_norm)
-        st.actor.refresh()
-        if counter is not None:
-            counter += 1
+    agn = _actor_step(st, actor, actor_opt, actor_grads, sync, max_norm, actor_wait, counter)
     return st.losses[0], st.losses[1], cgn, agn

@@ -111,7 +111,8 @@ class FusedDQNState:
             raise ValueError(f"DQN learner kernels: B={B} (a positive multiple of 32), the default network, 25 actions")
         dev = net_local.output_layer.weight.device
         self.B, self.device, self.operands = B, dev, operands
-        self.local = DqnPack(net_local, operands)
+        self.local = self.policy_pack = DqnPack(net_local, operands)   # the closed-loop windows run the Q network
+        self.actor_pack = None
         self.target = DqnPack(net_target, operands)
         bf = dict(dtype=_abi.operand_dtype(operands), device=dev)
         f = dict(dtype=torch.float32, device=dev)
@@ -132,9 +133,21 @@ class FusedDQNState:
         """Re-pack the target network after a hard/soft update (eager, outside graphs)."""
         self.target.refresh()
 
+    def refresh_local(self):
+        """Re-pack the local network after its parameters were loaded (eager, outside graphs)."""
+        self.local.refresh()
+
     def act(self, obs_rows, actions64, step_dev, steps_per_count, total, fraction, initial, final, seed, q_out=None):
         dqn_act(self.local, obs_rows, actions64, step_dev, steps_per_count, total, fraction, initial, final, seed,
                 q_out=q_out)
+
+    def learn(self, tr, state=None, guard=0, actor_wait=None, target_wait=None, actor_done=None):
+        """VecTrainer.learn: the draw from tr's ring into tr's buffers (no quantile fractions), then the update on
+        tr's optimiser."""
+        rows = tr.replay.sample(tr.B, seed=tr.seed + 777, counter_dev=tr.learn_counter, out=tr.batch_rows,
+                                state=state, guard=guard)
+        return dqn_update_fused(self, tr.local, tr.opt, tr.grads, rows, gamma=tr.gamma, sync=tr.sync,
+                                act_wait=actor_wait, counter=tr.learn_counter)
 
 
 def dqn_grads(st, net, rows, gamma=0.99, flush=True):

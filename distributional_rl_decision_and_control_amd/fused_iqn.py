@@ -190,6 +190,7 @@ class FusedIQNState:
     """Packs and buffers of the fused IQN update (allocated once, pointer-stable for graphs).
     operands="f32": every kernel from libasvrl_f32.so (the parity build; the optimiser must be a
     FusedAdam of the same operands)."""
+    actor_pack = policy_pack = None   # act_iqn runs inside its own kernel, not in the closed-loop windows
 
     def __init__(self, net_local, net_target, B, N, operands="bf16", target_in_fused=None):
         dev = net_local.cos_embedding.weight.device
@@ -215,9 +216,21 @@ class FusedIQNState:
         """Re-pack the target network after a hard/soft update (eager, outside graphs)."""
         self.target.refresh()
 
+    def refresh_local(self):
+        """Re-pack the local network after its parameters were loaded (eager, outside graphs)."""
+        self.local.refresh()
+
     def act(self, obs_rows, actions64, step_dev, steps_per_count, total, fraction, initial, final, seed):
         iqn_act(self.local, None, actions64, step_dev, steps_per_count, total, fraction, initial, final, seed,
                 obs=obs_rows)
+
+    def learn(self, tr, state=None, guard=0, actor_wait=None, target_wait=None, actor_done=None):
+        """VecTrainer.learn: the draw from tr's ring into tr's buffers, then the update on tr's optimiser."""
+        # the update's quantile fractions are drawn by the sampling launch
+        rows = tr.replay.sample(tr.B, seed=tr.seed + 777, counter_dev=tr.learn_counter, out=tr.batch_rows,
+                                state=state, guard=guard, taus=tr.taus)
+        return iqn_update_fused(self, tr.local, tr.opt, tr.grads, rows, gamma=tr.gamma, sync=tr.sync,
+                                act_wait=actor_wait, taus=tr.taus[:2], counter=tr.learn_counter)
 
 
 def iqn_grads(st, net, rows, taus, gamma=0.99, flush=True):

@@ -193,6 +193,7 @@ class RainbowNetImage:
 
 class FusedRainbow:
     """Packs and buffers (pointer-stable for graph replay) of the batched Rainbow path."""
+    actor_pack = policy_pack = None   # act_rainbow runs inside its own kernel, not in the closed-loop windows
 
     def __init__(self, local, target, B, support, operands="bf16"):
         self.local, self.target, self.B = local, target, B
@@ -222,6 +223,22 @@ class FusedRainbow:
     def target_changed(self):
         self.tpack.compose()
         self.timg.refresh()
+
+    def refresh_local(self):
+        self.pack.compose()
+        self.img.refresh()
+
+    def learn(self, tr, state=None, guard=0, actor_wait=None, target_wait=None, actor_done=None):
+        """VecTrainer.learn: the draw from tr's prioritised tree, the update on tr's optimiser, the priorities."""
+        rows, idx = tr.per.sample(tr.B, seed=tr.seed + 777, counter_dev=tr.learn_counter, out=tr.batch_rows,
+                                  out_idx=tr.per_idx)
+        # act() composed the online noisy weights this iteration
+        loss, gn = self.update(tr.opt, tr.grads, rows, gamma=tr.gamma, n=tr.n_step, sync=tr.sync, seed=tr.seed + 999,
+                               counter_dev=tr.learn_counter, compose=False)
+        # update_priorities(idxs, loss) (agent.py:639); the reported loss mean and the learn counter in its last
+        # launch
+        tr.per.update_priorities(idx, loss, mean_out=tr.loss_mean, learn_counter=tr.learn_counter)
+        return tr.loss_mean[0], gn
 
     @torch.no_grad()
     def act(self, obs_rows, actions64, step_dev, steps_per_count, total, fraction, initial, final, seed):

@@ -81,7 +81,8 @@ class FusedACIQNState:
         self.target_trunk = CriticPack(policy_target.critic, operands)
         # double_actor (the batched loop): two actor image sets, the optimiser writing the one the act kernel
         # does not read (MlpPack)
-        self.actor = MlpPack(policy_local.actor, "actor", operands, double=double_actor)
+        self.actor = self.actor_pack = self.policy_pack = MlpPack(policy_local.actor, "actor", operands,
+                                                                  double=double_actor)
         self.target_actor = MlpPack(policy_target.actor, "actor", operands)
         self.abufs = ActorBuffers(B, dev, operands)
         self.agrads = ActorGrads(B, dev, operands)
@@ -102,8 +103,24 @@ class FusedACIQNState:
         self.target_trunk.refresh()
         self.target_actor.refresh()
 
+    def refresh_local(self):
+        """Re-pack the local networks after their parameters were loaded (eager, outside graphs)."""
+        self.local_trunk.refresh()
+        self.actor.refresh()
+
     def act(self, obs_rows, actions64, step_dev, steps_per_count, total, fraction, initial, final, seed):
         actor_act(self.actor, obs_rows, actions64, step_dev, steps_per_count, total, fraction, initial, final, seed)
+
+    def learn(self, tr, state=None, guard=0, actor_wait=None, target_wait=None, actor_done=None):
+        """VecTrainer.learn: the draw from tr's ring into tr's buffers, then the update on tr's optimisers."""
+        # one launch: the draw (rows + the update's quantile fractions), the actor's training forward
+        # and the target actor
+        rows = learn_prologue(self, tr.replay, tr.taus, tr.seed + 777, counter_dev=tr.learn_counter,
+                              out=tr.batch_rows, state=state, guard=guard)
+        return ac_iqn_update_fused2(self, tr.local, tr.actor_opt, tr.critic_opt, tr.critic_grads, tr.actor_grads,
+                                    rows, gamma=tr.gamma, sync=tr.sync, actor_wait=actor_wait, taus=tr.taus,
+                                    counter=tr.learn_counter, prologue_done=True, target_wait=target_wait,
+                                    actor_done=actor_done)
 
 
 def _reduce_and_step(arena, opt, grads, sync, max_norm, wait=None, pack=None, counter=None):
@@ -151,6 +168,40 @@ def _step_unfused(arena, opt, grads, sync, max_norm, wait):
     return clip_and_step(opt, grads, max_norm)
 
 
+def _actor_step(st, actor, actor_opt, actor_grads, sync, max_norm, actor_wait, counter):
+    """The actor half of a two-optimiser update (AC-IQN, DDPG) behind actor_backward, on st.abufs / st.agrads /
+    st.tile_loss[1] / st.losses[1]: the gradients, then clip + Adam + re-pack of st.actor. actor_wait: an event to
+    wait for before the actor's weights change (a concurrent act kernel). Returns the gradient norm."""
+    # every actor .grad, the actor loss, the norm partials and the Adam step count in one launch
+    fused_opt = sync is None and isinstance(actor_opt, FusedAdam)
+    actor_grads_launch(st.agrads, st.abufs, actor, st.tile_loss[1], st.losses[1:2],
+                       step=actor_opt.step_t if fused_opt else None, norm=fused_opt)
+    if isinstance(actor_opt, FusedAdam):
+        assert actor_opt.max_norm == max_norm, (actor_opt.max_norm, max_norm)
+        if sync is not None:
+            sync(actor_grads)
+        # a concurrent act kernel reads the current actor images: with two sets the step writes the other one
+        # and no wait is needed (its cross-stream dependency costs ~7 us in a replayed graph)
+        if actor_wait is not None and not st.actor.double:
+            torch.cuda.current_stream().wait_event(actor_wait)
+        if fused_opt:
+            agn = actor_opt.step_prenormed(st.agrads.norm_parts, st.agrads.nparts,
+                                           pack=st.actor.adam_segments(actor_opt), counter=counter)
+        else:   # data-parallel: the norm over the all-reduced gradient, then the same packing step
+            agn = actor_opt.step_synced(pack=st.actor.adam_segments(actor_opt), counter=counter)
+        st.actor.flip()
+        return agn
+    if sync is not None:
+        sync(actor_grads)
+    if actor_wait is not None:
+        torch.cuda.current_stream().wait_event(actor_wait)
+    agn = clip_and_step(actor_opt, actor_grads, max_norm)
+    st.actor.refresh()
+    if counter is not None:
+        counter += 1
+    return agn
+
+
 def target_q(st, rows, tau0, q_out, na):
     """Q_targets_next of agent.py:397-400 for the rows' next states: target actor, then the target
     critic with the target encoders inside the trunk kernel (q_out [B*N])."""
@@ -163,17 +214,19 @@ def learn_prologue(st, replay, taus, seed, counter_dev=None, counter=0, out=None
     """asvrl_learn_prologue: B rows drawn from the device ring (replay_buffer.py:26-45) with the update's
     quantile fractions `taus` (3, B, N), the local actor's TRAIN forward on s (its activations in st.abufs)
     and the target actor's forward on s' (st.na) in ONE launch, bit-identical to replay.sample +
-    actor_train_forward + actor_forward. Returns the rows [B][88]."""
+    actor_train_forward + actor_forward. taus=None (DDPG's st: no quantile fractions): none are drawn. Returns the
+    rows [B][88]."""
     B = st.B
     out = out if out is not None else torch.empty((B, 88), dtype=torch.float32, device=st.device)
-    assert taus.is_contiguous() and taus.shape[1] == B and taus.dtype == torch.float32
     sa = _abi.AsvSampleArgs()
     sa.ring, sa.capacity = replay.ring.data_ptr(), replay.capacity
     sa.ring_state = (state if state is not None else replay.state).data_ptr()
     sa.seed, sa.counter = int(seed) & 0xFFFFFFFFFFFFFFFF, int(counter) & 0xFFFFFFFFFFFFFFFF
     sa.counter_dev = _abi.ptr(counter_dev)
-    sa.guard, sa.B, sa.tau_sets, sa.tau_n = int(guard), B, taus.shape[0], taus.shape[2]
-    sa.out, sa.taus = out.data_ptr(), taus.data_ptr()
+    sa.guard, sa.B, sa.out = int(guard), B, out.data_ptr()
+    if taus is not None:
+        assert taus.is_contiguous() and taus.shape[1] == B and taus.dtype == torch.float32
+        sa.tau_sets, sa.tau_n, sa.taus = taus.shape[0], taus.shape[2], taus.data_ptr()
     io = st.abufs.io()
     _abi.check(st.actor.L.asvrl_learn_prologue(C.byref(sa), C.byref(st.actor.w), C.byref(io),
                                                 C.byref(st.target_actor.w), st.na.data_ptr(),
@@ -238,31 +291,5 @@ def ac_iqn_update_fused2(st, policy_local, actor_opt, critic_opt, critic_grads, 
     if actor_done is not None:   # behind the ACTOR pass (behind the actor's backward measured no better, r05aq)
         actor_done.record(torch.cuda.current_stream())
     actor_backward(st.actor, ab)
-    # every actor .grad, the actor loss, the norm partials and the Adam step count in one launch
-    fused_opt = sync is None and isinstance(actor_opt, FusedAdam)
-    actor_grads_launch(st.agrads, ab, actor, st.tile_loss[1], st.losses[1:2],
-                       step=actor_opt.step_t if fused_opt else None, norm=fused_opt)
-    if isinstance(actor_opt, FusedAdam):
-        assert actor_opt.max_norm == max_norm, (actor_opt.max_norm, max_norm)
-        if sync is not None:
-            sync(actor_grads)
-        # a concurrent act kernel reads the current actor images: with two sets the step writes the other one
-        # and no wait is needed (its cross-stream dependency costs ~7 us in a replayed graph)
-        if actor_wait is not None and not st.actor.double:
-            torch.cuda.current_stream().wait_event(actor_wait)
-        if fused_opt:
-            agn = actor_opt.step_prenormed(st.agrads.norm_parts, st.agrads.nparts,
-                                           pack=st.actor.adam_segments(actor_opt), counter=counter)
-        else:   # data-parallel: the norm over the all-reduced gradient, then the same packing step
-            agn = actor_opt.step_synced(pack=st.actor.adam_segments(actor_opt), counter=counter)
-        st.actor.flip()
-    else:
-        if sync is not None:
-            sync(actor_grads)
-        if actor_wait is not None:
-            torch.cuda.current_stream().wait_event(actor_wait)
-        agn = clip_and_step(actor_opt, actor_grads, max_norm)
-        st.actor.refresh()
-        if counter is not None:
-            counter += 1
+    agn = _actor_step(st, actor, actor_opt, actor_grads, sync, max_norm, actor_wait, counter)
     return st.losses[0], st.losses[1], cgn, agn

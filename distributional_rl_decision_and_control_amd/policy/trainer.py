@@ -213,14 +213,12 @@ class Trainer:
     def _sync_agent(self, tr):
         """rl_agent's local / target networks <- the batched trainer's (same architectures)."""
         import torch
+        from ..learners import policy_modules
         pairs = [(self.rl_agent.policy_local, tr.local), (self.rl_agent.policy_target, tr.target)]
         with torch.no_grad():
             for dst, src in pairs:
-                if hasattr(src, "actor"):   # AC_IQN_Policy holds two modules
-                    dst.actor.load_state_dict(src.actor.state_dict())
-                    dst.critic.load_state_dict(src.critic.state_dict())
-                else:
-                    dst.load_state_dict(src.state_dict())
+                for d, s in zip(policy_modules(dst), policy_modules(src)):
+                    d.load_state_dict(s.state_dict())
         if hasattr(self.rl_agent, "_fused"):
             self.rl_agent._fused = None   # the drop-in learner re-packs its weight images on its next train()
 

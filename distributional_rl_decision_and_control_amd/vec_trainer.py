@@ -21,23 +21,9 @@ import time
 import torch
 
 from . import streams
-from .fused_update import FusedACIQNState, ac_iqn_update_fused2, learn_prologue
-from .fused_ddpg import FusedDDPGState, ddpg_update_fused
-from .fused_ddpg import learn_prologue as ddpg_learn_prologue
-from .fused_ddpg import supported as fused_ddpg_supported
-from .fused_dqn import FusedDQNState, dqn_update_fused
-from .fused_dqn import supported as fused_dqn_supported
-from .fused_iqn import FusedIQNState, iqn_update_fused
-from .fused_iqn import supported as fused_iqn_supported
-from .fused_rainbow import FusedRainbow
-from .fused_update import supported as fused2_supported
 from .learn_ops import DevicePER, DeviceReplay
 from .learner import FusedAdam
-from .policy.AC_IQN_model import AC_IQN_Policy
-from .policy.DDPG_model import DDPG_Policy
-from .policy.DQN_model import DQN_Policy
-from .policy.IQN_model import IQN_Policy
-from .policy.Rainbow_model import Rainbow_Policy
+from .learners import LEARNERS, policy_modules, policy_parameters
 from .vec_env import VecMarineNavEnv
 
 DEFAULT_NET = dict(self_dimension=7, object_dimension=5, max_object_num=5, self_feature_dimension=56,
@@ -51,10 +37,12 @@ class VecTrainer:
                  exploration_fraction=0.25, initial_eps=0.6, final_eps=0.05, seed=0,
                  device="cuda", sync=None, graphs=False, schedule=None, net_seed=100, overlap=True, unroll=1,
                  chain=None, operands="bf16", target_after_env=False, push_after_actor=None):
-        """Every learner runs on the hand-written kernels (fused_update / fused_iqn / fused_rainbow / fused_dqn /
-        fused_ddpg) with
-        FusedAdam; operands="f32" takes them from the f32-operand parity build (libasvrl_f32.so). Shapes
-        the kernels do not take raise ValueError."""
+        """Every learner (learners.LEARNERS) runs on the hand-written kernels with FusedAdam; operands="f32" takes
+        them from the f32-operand parity build (libasvrl_f32.so). Shapes the kernels do not take raise ValueError."""
+        if agent_type not in LEARNERS:
+            raise NotImplementedError(f"VecTrainer agent_type {agent_type!r} (AC-IQN, IQN, Rainbow, DQN and DDPG are "
+                                      "batched)")
+        spec = LEARNERS[agent_type]
         self.device = torch.device(device)
         self.agent_type = agent_type
         # chained schedule knob: the AC-IQN learner's target critic waits for the same iteration's env step
@@ -66,7 +54,7 @@ class VecTrainer:
         # of the same iteration instead of running beside it (None: wherever the chained AC-IQN graph runs)
         self._paa_arg = push_after_actor
         self.push_after_actor = bool(push_after_actor)
-        self.continuous = agent_type in ("AC-IQN", "DDPG")
+        self.continuous = spec.continuous
         self.env = VecMarineNavEnv(n_envs, num_robots, num_obs, num_cores, min_start_goal_dis, width, seed=seed,
                                    device=self.device, is_continuous=self.continuous, gamma=gamma, schedule=schedule)
         self.E, self.R = n_envs, self.env.max_robots
@@ -78,88 +66,31 @@ class VecTrainer:
         self.total_timesteps = total_timesteps
         self.exploration_fraction, self.initial_eps, self.final_eps = exploration_fraction, initial_eps, final_eps
         self.learning_starts = learning_starts if learning_starts is not None else batch_size
-        self.fused2 = self.fused_iqn = self.fused_rb = self.fused_dqn = self.fused_ddpg = None
-        if agent_type == "AC-IQN":
-            self.local = AC_IQN_Policy(**DEFAULT_NET, value_ranges_of_action=[[-1.0, 1.0], [-1.0, 1.0]],
-                                       device=self.device, seed=net_seed)
-            self.target = AC_IQN_Policy(**DEFAULT_NET, value_ranges_of_action=[[-1.0, 1.0], [-1.0, 1.0]],
-                                        device=self.device, seed=net_seed)
-            for p in list(self.target.actor.parameters()) + list(self.target.critic.parameters()):
-                p.requires_grad_(False)
-            if not fused2_supported(self.local, batch_size, num_tau):
-                raise ValueError(f"AC-IQN learner kernels: B={batch_size}, N={num_tau} (B a multiple of 32, "
-                                 f"N in 8, 16, 32)")
-            # clip + Adam over flat buffers (must precede the packs, which cache parameter pointers)
+        self.local = spec.make_policy(DEFAULT_NET.values(), self.device, net_seed)
+        self.target = spec.make_policy(DEFAULT_NET.values(), self.device, net_seed)
+        for p in policy_parameters(self.target):
+            p.requires_grad_(False)
+        if spec.refusal is not None and not spec.supported(self.local, batch_size, num_tau):
+            raise ValueError(spec.refusal.format(B=batch_size, N=num_tau))
+        # clip + Adam over flat buffers (must precede the packs, which cache parameter pointers)
+        if spec.actor_critic:
             self.actor_opt = FusedAdam(self.local.actor.parameters(), lr=lr, operands=operands)
             self.critic_opt = FusedAdam(self.local.critic.parameters(), lr=lr, operands=operands)
             self.actor_grads, self.critic_grads = self.actor_opt.grads, self.critic_opt.grads
-            self.action_dim = 2
-            self.fused2 = FusedACIQNState(self.local, self.target, batch_size, num_tau, operands, double_actor=True)
-        elif agent_type == "IQN":
-            self.local = IQN_Policy(**DEFAULT_NET, action_size=25, device=self.device, seed=net_seed).to(self.device)
-            self.target = IQN_Policy(**DEFAULT_NET, action_size=25, device=self.device, seed=net_seed).to(self.device)
-            for p in self.target.parameters():
-                p.requires_grad_(False)
-            if not fused_iqn_supported(self.local, batch_size, num_tau):
-                raise ValueError(f"IQN learner kernels: B={batch_size}, N={num_tau}")
-            self.opt = FusedAdam(self.local.parameters(), lr=lr, operands=operands)
-            self.grads = self.opt.grads
-            self.action_dim = 1
-            self.fused_iqn = FusedIQNState(self.local, self.target, batch_size, num_tau, operands)
-        elif agent_type == "Rainbow":
-            # Rainbow_Policy (dueling NoisyNet C51, 51 atoms on [-1, 1]) with the prioritised n-step
-            # replay in HBM, one stream per robot (agent.py:597-641, replay_memory_rainbow.py)
-            self.local = Rainbow_Policy(**DEFAULT_NET, action_size=25, atoms=51, device=self.device,
-                                        seed=net_seed).to(self.device)
-            self.target = Rainbow_Policy(**DEFAULT_NET, action_size=25, atoms=51, device=self.device,
-                                         seed=net_seed).to(self.device)
-            for p in self.target.parameters():
-                p.requires_grad_(False)
-            self.opt = FusedAdam(self.local.parameters(), lr=lr, operands=operands)
-            self.grads = self.opt.grads
-            self.action_dim = 1
-            self.n_step = 3
-            self.support = torch.linspace(-1.0, 1.0, 51, device=self.device)
-            # noisy weights, the network, loss gradient and act on hand-written kernels (fused_rainbow.py)
-            self.fused_rb = FusedRainbow(self.local, self.target, batch_size, self.support, operands)
-        elif agent_type == "DQN":
-            # DQN_Policy: the Actor's trunk with a 25-wide head (fused_dqn.py); the uniform ring, one optimiser
-            self.local = DQN_Policy(**DEFAULT_NET, action_size=25, device=self.device, seed=net_seed).to(self.device)
-            self.target = DQN_Policy(**DEFAULT_NET, action_size=25, device=self.device, seed=net_seed).to(self.device)
-            for p in self.target.parameters():
-                p.requires_grad_(False)
-            if not fused_dqn_supported(self.local, batch_size):
-                raise ValueError(f"DQN learner kernels: B={batch_size} (a positive multiple of 32)")
-            self.opt = FusedAdam(self.local.parameters(), lr=lr, operands=operands)
-            self.grads = self.opt.grads
-            self.action_dim = 1
-            self.fused_dqn = FusedDQNState(self.local, self.target, batch_size, operands)
-        elif agent_type == "DDPG":
-            # DDPG_Policy: AC-IQN's Actor and a one-scalar critic (fused_ddpg.py); set up like AC-IQN's branch --
-            # the uniform ring, two optimisers, a double actor image set
-            self.local = DDPG_Policy(**DEFAULT_NET, value_ranges_of_action=[[-1.0, 1.0], [-1.0, 1.0]],
-                                     device=self.device, seed=net_seed)
-            self.target = DDPG_Policy(**DEFAULT_NET, value_ranges_of_action=[[-1.0, 1.0], [-1.0, 1.0]],
-                                      device=self.device, seed=net_seed)
-            for p in list(self.target.actor.parameters()) + list(self.target.critic.parameters()):
-                p.requires_grad_(False)
-            if not fused_ddpg_supported(self.local, batch_size):
-                raise ValueError(f"DDPG learner kernels: B={batch_size} (a positive multiple of 32)")
-            self.actor_opt = FusedAdam(self.local.actor.parameters(), lr=lr, operands=operands)
-            self.critic_opt = FusedAdam(self.local.critic.parameters(), lr=lr, operands=operands)
-            self.actor_grads, self.critic_grads = self.actor_opt.grads, self.critic_opt.grads
-            self.action_dim = 2
-            # two actor image sets flip at every update, host-side: a captured graph of an odd number of iterations
-            # would replay on the set it was captured on and never see the other one written -- one set there, and
-            # the update waits for the act kernel instead (ddpg_update_fused's actor_wait)
-            self.fused_ddpg = FusedDDPGState(self.local, self.target, batch_size, operands,
-                                             double_actor=not graphs or max(1, int(unroll)) % 2 == 0)
         else:
-            raise NotImplementedError(f"VecTrainer agent_type {agent_type!r} (AC-IQN, IQN, Rainbow, DQN and DDPG are "
-                                      "batched)")
+            self.opt = FusedAdam(self.local.parameters(), lr=lr, operands=operands)
+            self.grads = self.opt.grads
+        self.action_dim = spec.action_dim
+        self.n_step = 3 if spec.per else None
+        self.support = torch.linspace(-1.0, 1.0, 51, device=self.device) if spec.per else None
+        # the learner's packs and buffers on the hand-written kernels: the one fused field that is not None
+        self.fused2 = self.fused_iqn = self.fused_rb = self.fused_dqn = self.fused_ddpg = None
+        self.learner = spec.state(self.local, self.target, batch_size, num_tau, operands, support=self.support,
+                                  batched=(graphs, max(1, int(unroll))))
+        setattr(self, spec.field, self.learner)
         NT = self.E * self.R
         self.per = None
-        if agent_type == "Rainbow":
+        if spec.per:
             slots = max(min(buffer_size, 1 << 22) // NT, self.n_step + 3)
             self.per = DevicePER(slots * NT, stride=NT, n_step=self.n_step, discount=gamma, deferred=True,
                                  device=self.device)
@@ -205,15 +136,15 @@ class VecTrainer:
         # AC-IQN only (measured 0.346 -> 0.340 ms/step; IQN, whose act kernel fills the GPU, 0.363 ->
         # 0.366: profiles/r02_chain_schedule_ab.txt)
         self.chain = (agent_type == "AC-IQN") if chain is None else bool(chain)
-        if self.chain and self.fused_ddpg is not None:
+        if self.chain and agent_type == "DDPG":
             # not built for DDPG: refused rather than silently run as the joined schedule
             raise ValueError("the dependency-chained schedule is not available for DDPG (chain=None or False: the "
                              "joined schedule)")
-        if self.target_after_env and not (self.fused2 is not None and self.graphs and self._chained()):
+        paa_ok = agent_type == "AC-IQN" and self.graphs and self._chained()
+        if self.target_after_env and not paa_ok:
             # the knob orders two nodes of the chained AC-IQN graph; anywhere else it would be silently ignored
             # and a bench config recording it would be mislabelled
             raise ValueError("target_after_env applies only to the chained, graph-captured AC-IQN schedule")
-        paa_ok = self.fused2 is not None and self.graphs and self._chained()
         if self._paa_arg is None:
             self.push_after_actor = paa_ok
         elif self.push_after_actor and not paa_ok:
@@ -238,21 +169,7 @@ class VecTrainer:
         (trainer.py:106-135, agent.py:207-250,308-324), one kernel per agent type."""
         args = (self.env.obs_cur, self.actions, self.env.counter, self.E, self.total_timesteps,
                 self.exploration_fraction, self.initial_eps, self.final_eps, self.seed + 4242)
-        if self.fused_rb is not None:   # composed noisy weights, logits, head: expected Q, argmax, explore
-            self.fused_rb.act(*args)
-        elif self.fused_iqn is not None:   # K = 32 quantiles per robot, mean, argmax, explore
-            self.fused_iqn.act(*args)
-        elif self.fused_dqn is not None:   # Q per robot, argmax, explore
-            self.fused_dqn.act(*args)
-        elif self.fused_ddpg is not None:   # DDPG's actor (the AC-IQN Actor) on every robot row, explore
-            self.fused_ddpg.act(*args)
-        else:   # actor on every robot row, explore
-            self.fused2.act(*args)
-
-    def _actor_pack(self):
-        """The local Actor's images (AC-IQN and DDPG, whose policy is that Actor), or None."""
-        st = self.fused2 if self.fused2 is not None else self.fused_ddpg
-        return st.actor if st is not None else None
+        self.learner.act(*args)
 
     def _eval_env(self):
         """A fresh env batch of the training env's shape, parameters and current curriculum stage, with its own
@@ -274,7 +191,7 @@ class VecTrainer:
         hold_done; an env that ended stays out of the later windows), until every env has ended or after
         max_steps. Returns that batch's episode_stats() plus steps_run, the steps every env took. The training
         env, the replay and the step counter are not touched. AC-IQN and DDPG only."""
-        if self._actor_pack() is None:
+        if self.learner.actor_pack is None:
             raise NotImplementedError("greedy_episodes runs the AC-IQN / DDPG actor; IQN, Rainbow and DQN act inside "
                                       "their own kernels")
         env = self._eval_env()
@@ -283,7 +200,7 @@ class VecTrainer:
         done = 0
         while done < max_steps:
             k = min(int(chunk), max_steps - done)
-            rec = env.policy_rollout(self._actor_pack(), k, hold_done=True, keep=("env_done",), env_mask=alive)
+            rec = env.policy_rollout(self.learner.actor_pack, k, hold_done=True, keep=("env_done",), env_mask=alive)
             env.advance_device(counted=True)   # the next window acts on this one's last observation
             steps_run += rec.steps_run
             alive *= (rec.env_done.sum(0) == 0).to(torch.uint8)
@@ -300,19 +217,17 @@ class VecTrainer:
         reference's per-config rewards / successes / times / energies / lengths on the device. kw: run()'s seed,
         episode_limit and sync. The actor's packed images are the learner's own, so no copy into a drop-in agent is
         needed; the training env, the replay and the step counter are not touched. AC-IQN and DDPG only."""
-        if self._actor_pack() is None:
+        if self.learner.actor_pack is None:
             raise NotImplementedError("evaluate runs the AC-IQN / DDPG actor; IQN, Rainbow and DQN act inside their "
                                       "own kernels")
-        return self.device_evaluator(configs, chunk, template_env).run(self._actor_pack(), **kw)
+        return self.device_evaluator(configs, chunk, template_env).run(self.learner.actor_pack, **kw)
 
     def policy_pack(self):
         """The pack the closed-loop windows take (DeviceEnvBatch.policy_rollout, DeviceEvaluator.run): the learner's
         own local images -- AC-IQN's or DDPG's actor or DQN's local net. IQN and Rainbow act inside their own
         kernels."""
-        if self._actor_pack() is not None:
-            return self._actor_pack()
-        if self.fused_dqn is not None:
-            return self.fused_dqn.local
+        if self.learner.policy_pack is not None:
+            return self.learner.policy_pack
         raise NotImplementedError(f"policy_pack: the closed-loop windows run the AC-IQN / DDPG actor or DQN_Policy, not "
                                   f"{self.agent_type}")
 
@@ -378,14 +293,14 @@ class VecTrainer:
         graph-captured. Returns the window's records (views of the persistent buffers: obs, obs_prev, obj_cnt,
         reward, done, actions, steps_run, pushed, resets). AC-IQN and DDPG (the uniform ring) only; the caller accounts
         for the host-side step count (env.advance_host() per step) as iteration() does."""
-        if self._actor_pack() is None or self.per is not None:
+        if self.learner.actor_pack is None or self.per is not None:
             raise NotImplementedError("collect runs the AC-IQN / DDPG actor and pushes into the uniform ring; IQN, "
                                       "Rainbow and DQN act inside their own kernels")
         K = int(K)
         buf = self._collect_buffers(K)
         buf["obj_cnt"].fill_(-1)   # a row no env took is never pushed
         keep = {k: buf[k] for k in ("obs", "obs_prev", "obj_cnt", "reward", "done", "actions", "steps_run")}
-        rec = self.env.policy_rollout(self._actor_pack(), K, hold_done=False, keep=keep,
+        rec = self.env.policy_rollout(self.learner.actor_pack, K, hold_done=False, keep=keep,
                                       eps=(self.E, self.total_timesteps, self.exploration_fraction, self.initial_eps,
                                            self.final_eps), policy_seed=self.seed + 4242,
                                       auto_reset=dict(pushed=buf["pushed"], resets=buf["resets"]), count=False)
@@ -397,63 +312,13 @@ class VecTrainer:
         """One learn step of batch B: sample (uniform ring, or the prioritised tree for Rainbow) and the
         agent's fused update. state / guard: the ring snapshot to sample against and the newest entries to
         skip (the overlapped schedule); actor_wait: an event to wait for before the actor's weights change."""
-        if self.per is not None:
-            rows, idx = self.per.sample(self.B, seed=self.seed + 777, counter_dev=self.learn_counter,
-                                        out=self.batch_rows, out_idx=self.per_idx)
-            # act() composed the online noisy weights this iteration
-            loss, gn = self.fused_rb.update(self.opt, self.grads, rows, gamma=self.gamma, n=self.n_step,
-                                            sync=self.sync, seed=self.seed + 999, counter_dev=self.learn_counter,
-                                            compose=False)
-            # update_priorities(idxs, loss) (agent.py:639); the reported loss mean and the learn counter in its last
-            # launch
-            self.per.update_priorities(idx, loss, mean_out=self.loss_mean, learn_counter=self.learn_counter)
-            return self.loss_mean[0], gn
-        if self.fused2 is not None:
-            # one launch: the draw (rows + the update's quantile fractions), the actor's training forward
-            # and the target actor
-            rows = learn_prologue(self.fused2, self.replay, self.taus, self.seed + 777, counter_dev=self.learn_counter,
-                                  out=self.batch_rows, state=state, guard=guard)
-            return ac_iqn_update_fused2(self.fused2, self.local, self.actor_opt, self.critic_opt, self.critic_grads,
-                                        self.actor_grads, rows, gamma=self.gamma, sync=self.sync,
-                                        actor_wait=actor_wait, taus=self.taus, counter=self.learn_counter,
-                                        prologue_done=True, target_wait=target_wait, actor_done=actor_done)
-        if self.fused_ddpg is not None:
-            # one launch: the draw (no quantile fractions), the actor's training forward and the target actor
-            rows = ddpg_learn_prologue(self.fused_ddpg, self.replay, self.seed + 777, counter_dev=self.learn_counter,
-                                       out=self.batch_rows, state=state, guard=guard)
-            return ddpg_update_fused(self.fused_ddpg, self.local, self.actor_opt, self.critic_opt, self.critic_grads,
-                                     self.actor_grads, rows, gamma=self.gamma, sync=self.sync, actor_wait=actor_wait,
-                                     counter=self.learn_counter, prologue_done=True)
-        if self.fused_dqn is not None:   # no quantile fractions to draw
-            rows = self.replay.sample(self.B, seed=self.seed + 777, counter_dev=self.learn_counter,
-                                      out=self.batch_rows, state=state, guard=guard)
-            return dqn_update_fused(self.fused_dqn, self.local, self.opt, self.grads, rows, gamma=self.gamma,
-                                    sync=self.sync, act_wait=actor_wait, counter=self.learn_counter)
-        # the update's quantile fractions are drawn by the sampling launch
-        rows = self.replay.sample(self.B, seed=self.seed + 777, counter_dev=self.learn_counter, out=self.batch_rows,
-                                  state=state, guard=guard, taus=self.taus)
-        return iqn_update_fused(self.fused_iqn, self.local, self.opt, self.grads, rows, gamma=self.gamma,
-                                sync=self.sync, act_wait=actor_wait, taus=self.taus[:2], counter=self.learn_counter)
+        return self.learner.learn(self, state, guard, actor_wait, target_wait, actor_done)
 
     def hard_update(self):
         """soft_update with TAU = 1.0 (agent.py:643-679): target <- local."""
         with torch.no_grad():
-            if self.agent_type in ("AC-IQN", "DDPG"):
-                pairs = list(zip(self.target.actor.parameters(), self.local.actor.parameters())) + \
-                    list(zip(self.target.critic.parameters(), self.local.critic.parameters()))
-            else:
-                pairs = list(zip(self.target.parameters(), self.local.parameters()))
-            torch._foreach_copy_([t for t, _ in pairs], [l for _, l in pairs])
-            if self.fused2 is not None:   # eager, outside any captured graph
-                self.fused2.target_changed()
-            if self.fused_iqn is not None:
-                self.fused_iqn.target_changed()
-            if self.fused_rb is not None:
-                self.fused_rb.target_changed()
-            if self.fused_dqn is not None:
-                self.fused_dqn.target_changed()
-            if self.fused_ddpg is not None:
-                self.fused_ddpg.target_changed()
+            torch._foreach_copy_(policy_parameters(self.target), policy_parameters(self.local))
+            self.learner.target_changed()   # eager, outside any captured graph
 
     @torch.no_grad()
     def load_policies(self, local, target):
@@ -462,31 +327,13 @@ class VecTrainer:
         are views of the optimisers' flat buffers) and every weight image is re-packed. Eager, before
         the first captured graph."""
         assert self._graph is None, "load_policies before the first captured iteration"
-        pairs = [(self.local, local), (self.target, target)]
-        for dst, src in pairs:
-            mods = [(dst.actor, src.actor), (dst.critic, src.critic)] if hasattr(dst, "actor") else [(dst, src)]
-            for d, s in mods:
+        for dst, src in ((self.local, local), (self.target, target)):
+            for d, s in zip(policy_modules(dst), policy_modules(src)):
                 sd = s.state_dict()
                 for name, t in d.state_dict(keep_vars=True).items():
                     t.data.copy_(sd[name].to(device=t.device, dtype=t.dtype))
-        if self.fused2 is not None:
-            self.fused2.local_trunk.refresh()
-            self.fused2.actor.refresh()
-            self.fused2.target_changed()
-        if self.fused_iqn is not None:
-            self.fused_iqn.local.refresh()
-            self.fused_iqn.target_changed()
-        if self.fused_rb is not None:
-            self.fused_rb.pack.compose()
-            self.fused_rb.img.refresh()
-            self.fused_rb.target_changed()
-        if self.fused_dqn is not None:
-            self.fused_dqn.local.refresh()
-            self.fused_dqn.target_changed()
-        if self.fused_ddpg is not None:
-            self.fused_ddpg.local.refresh()
-            self.fused_ddpg.actor.refresh()
-            self.fused_ddpg.target_changed()
+        self.learner.refresh_local()
+        self.learner.target_changed()
 
     # ------------------------------------------------------------------ iteration
     def _iteration_body(self, do_learn):
@@ -579,8 +426,7 @@ class VecTrainer:
         ev_actor = [torch.cuda.Event() for _ in range(U)]
         # the events live as long as the graph: the captured cross-stream waits may refer to them at replay
         self._chain_events = (ev_act, ev_snap, ev_learn, ev_env, ev_actor)
-        tae = self.target_after_env and self.fused2 is not None
-        paa = self.push_after_actor and self.fused2 is not None
+        tae, paa = self.target_after_env, self.push_after_actor   # AC-IQN only (__init__)
         s_roll.wait_stream(main)
         out = None
 
