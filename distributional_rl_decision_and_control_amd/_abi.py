@@ -246,6 +246,35 @@ class AsvDdpgActorIO(C.Structure):
                 ("dA", _VP), ("tile_loss", _VP)]
 
 
+class AsvSacActorWeights(C.Structure):
+    _fields_ = [("trunk", AsvMlpWeights), ("head", _VP), ("bhead", _VP)]
+
+
+class AsvSacActIO(C.Structure):
+    _fields_ = [("x", _VP), ("ldx", _I64), ("n", _I32), ("_pad0", _I32), ("a_out64", _VP), ("eps_in", _VP),
+                ("eps_out", _VP), ("step_dev", _VP), ("eps_steps_per_count", _D), ("eps_total", _D),
+                ("eps_fraction", _D), ("eps_initial", _D), ("eps_final", _D), ("seed", _U64)]
+
+
+SAC_ACTOR_ARRAYS = ("xb", "h0", "h1", "h2", "mu", "ls", "sigma", "z", "a", "eps", "logp", "na", "logp_next",
+                    "eps_next", "dA", "q_pi", "dhead", "dz2", "dz1", "dz0", "tile_loss")
+
+
+class AsvSacActorIO(C.Structure):
+    _fields_ = [("rows", _VP), ("ld_rows", _I64), ("B", _I32), ("alpha", _F), ("eps_local_in", _VP),
+                ("eps_target_in", _VP), ("seed", _U64), ("counter", _U64), ("counter_dev", _VP)] + \
+               [(n, _VP) for n in SAC_ACTOR_ARRAYS]
+
+
+class AsvSacGradIO(C.Structure):
+    _fields_ = [("c", AsvDdpgGradIO * 2), ("logp_next", _VP), ("y", _VP), ("alpha", _F), ("_pad0", _I32)]
+
+
+class AsvSacActorGradIO(C.Structure):
+    _fields_ = [("x", _VP), ("ldx", _I64), ("act", _VP), ("lda", _I64), ("B", _I32), ("_pad0", _I32), ("q_pi", _VP),
+                ("dA", _VP)]
+
+
 class AsvSampleArgs(C.Structure):
     _fields_ = [("ring", _VP), ("capacity", _I64), ("ring_state", _VP), ("seed", _U64), ("counter", _U64),
                 ("counter_dev", _VP), ("guard", _I64), ("B", _I32), ("tau_sets", _I32), ("tau_n", _I32),
@@ -435,6 +464,19 @@ EXPORTS = [
     ("asvrl_ddpg_weights_struct_size", _I64, []),
     ("asvrl_ddpg_grad_struct_size", _I64, []),
     ("asvrl_ddpg_actor_struct_size", _I64, []),
+    ("asvrl_sac_act", C.c_int, [C.POINTER(AsvSacActorWeights), C.POINTER(AsvSacActIO), _VP]),
+    ("asvrl_sac_actor_forward", C.c_int, [C.POINTER(AsvSacActorWeights), C.POINTER(AsvSacActorWeights),
+                                          C.POINTER(AsvSacActorIO), _VP]),
+    ("asvrl_sac_grad", C.c_int, [C.POINTER(AsvDdpgWeights), C.POINTER(AsvDdpgWeights), C.POINTER(AsvDdpgWeights),
+                                 C.POINTER(AsvDdpgWeights), C.POINTER(AsvSacGradIO), _VP]),
+    ("asvrl_sac_actor_grad", C.c_int, [C.POINTER(AsvDdpgWeights), C.POINTER(AsvDdpgWeights),
+                                       C.POINTER(AsvSacActorGradIO), _VP]),
+    ("asvrl_sac_actor_backward", C.c_int, [C.POINTER(AsvSacActorWeights), C.POINTER(AsvSacActorIO), _VP]),
+    ("asvrl_sac_actor_weights_struct_size", _I64, []),
+    ("asvrl_sac_act_struct_size", _I64, []),
+    ("asvrl_sac_actor_struct_size", _I64, []),
+    ("asvrl_sac_grad_struct_size", _I64, []),
+    ("asvrl_sac_actor_grad_struct_size", _I64, []),
 ]
 
 _libs = {}

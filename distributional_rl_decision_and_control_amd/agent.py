@@ -25,8 +25,8 @@ save_latest_model / load_model surfaces and return types. Differences:
     back. DDPG (the continuous-action baseline AC-IQN is compared against) does the same: train_DDPG starts on the
     reference's torch update over this project's DDPG_Policy with two torch Adam optimisers, and a fused learner
     runs fused_ddpg.ddpg_update_fused with two FusedAdam (pinned to the reference's train_DDPG by
-    tests/test_fused_ddpg_gpu.py). SAC (twin critics, a stochastic actor, an entropy term) is out of scope and
-    raises.
+    tests/test_fused_ddpg_gpu.py). SAC (twin critics, a stochastic actor, an entropy term) runs on the batched loop
+    only (VecTrainer, fused_sac.py) and raises here.
 """
 import copy
 import random
@@ -102,8 +102,8 @@ class Agent:
                           object_feature_dimension, concat_feature_dimension, hidden_dimension)
         if agent_type not in SUPPORTED:
             if agent_type == "SAC":
-                raise NotImplementedError("SAC is a non-distributional baseline, outside this framework's hot path "
-                                          "(SURVEY.md section 2, row 14)")
+                raise NotImplementedError("SAC runs on the batched loop only: VecTrainer(agent_type=\"SAC\") "
+                                          "(fused_sac.py); the drop-in Agent does not take it yet")
             raise RuntimeError("Agent type not implemented!")
         if training:
             self.policy_local = self._make_policy(seed, value_ranges_of_action, action_size)
@@ -265,7 +265,7 @@ class Agent:
         return self.act_ac_iqn(state, eps, use_eval=use_eval)
 
     def act_sac(self, *a, **k):
-        raise NotImplementedError("SAC is outside this framework's hot path")
+        raise NotImplementedError("act_sac: SAC runs on the batched loop only (VecTrainer(agent_type=\"SAC\"))")
 
     # ------------------------------------------------------------------ learning (agent.py:370-641)
     def train(self):

@@ -18,7 +18,8 @@ ROOT = os.path.dirname(HERE)
 SOURCES = [os.path.join(HERE, "csrc", f) for f in ("asvrl_env.hip", "asvrl_learn.hip", "asvrl_critic.hip", "asvrl_critic_fused.hip",
                                                              "asvrl_optim.hip", "asvrl_wgrad.hip", "asvrl_mlp.hip",
                                                              "asvrl_per.hip", "asvrl_rainbow.hip", "asvrl_rainbow_net.hip",
-                                                             "asvrl_eval.hip", "asvrl_dqn.hip", "asvrl_ddpg.hip")]
+                                                             "asvrl_eval.hip", "asvrl_dqn.hip", "asvrl_ddpg.hip",
+                                                             "asvrl_sac.hip")]
 HEADERS = [os.path.join(HERE, "csrc", "asvrl_common.h"), os.path.join(HERE, "csrc", "asvrl_mfma.h"),
            os.path.join(HERE, "csrc", "asvrl_lds.h"), os.path.join(HERE, "csrc", "asvrl_vonmises_k1.h"),
            os.path.join(HERE, "csrc", "asvrl_critic_tile.h"), os.path.join(HERE, "csrc", "asvrl_actor_tile.h"),

@@ -135,6 +135,14 @@ struct StreamF {
     a = rad * __cosf(t);
     b = rad * __sinf(t);
   }
+  // the same pair with the accurate logf / sqrtf / sincosf (the learner's noise, asvrl_sac.hip: one call per row)
+  static __device__ void box_muller_accurate(float u1, float u2, float& a, float& b) {
+    const float rad = sqrtf(-2.0f * logf(u1));   // u1 in (0, 1]: the log is finite
+    float s, c;
+    sincosf(6.2831853f * u2, &s, &c);
+    a = rad * c;
+    b = rad * s;
+  }
   __device__ void normal4(float& a, float& b, float& c, float& d) const {
     const U4 w = philox4x32_10(U4{0u, c1, c2, c3}, k0, k1);
     box_muller(u24(w.x), u24(w.y), a, b);

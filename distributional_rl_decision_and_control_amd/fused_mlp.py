@@ -114,11 +114,22 @@ class MlpPack:
         if dst in self._segs:
             return self._segs[dst]
         n, t = self.net, self.sets[dst]
+        segs = self._trunk_segments(opt, t)
+        if self.double:
+            for k, p in (("b1", n.hidden_layer.bias), ("b2", n.hidden_layer_2.bias),
+                         ("wout", n.output_layer.weight), ("bout", n.output_layer.bias)):
+                segs.append(opt.pack_seg(p.reshape(-1), t[k], f32=True))
+        self._segs[dst] = segs
+        return segs
+
+    def _trunk_segments(self, opt, t):
+        """The eight segments of image set `t` that every Actor-shaped trunk has (fused_sac.SacActorPack too)."""
+        n = self.net
         se, oe = n.self_encoder[0], n.object_encoder[0]
         nso, nsi = se.weight.shape
         noo, noi = oe.weight.shape
         W1, W2 = n.hidden_layer.weight, n.hidden_layer_2.weight
-        segs = [opt.pack_seg(se.weight, t["enc"], K=OBSK),
+        return [opt.pack_seg(se.weight, t["enc"], K=OBSK),
                 opt.pack_seg(oe.weight, t["enc"], K=OBSK, row0=nso, col0=nsi, nrep=MAX_OBJ, rep_row=noo, rep_col=noi),
                 opt.pack_seg(se.bias, t["b_enc"], f32=True),
                 opt.pack_seg(oe.bias, t["b_enc"], f32=True, row0=nso, nrep=MAX_OBJ, rep_row=noo),
@@ -126,12 +137,6 @@ class MlpPack:
                 opt.pack_seg(W1, t["w1t"], K=HID, chained=True, transposed=True),
                 opt.pack_seg(W2, t["w2"], K=HID, chained=True),
                 opt.pack_seg(W2, t["w2t"], K=HID, chained=True, transposed=True)]
-        if self.double:
-            for k, p in (("b1", n.hidden_layer.bias), ("b2", n.hidden_layer_2.bias),
-                         ("wout", n.output_layer.weight), ("bout", n.output_layer.bias)):
-                segs.append(opt.pack_seg(p.reshape(-1), t[k], f32=True))
-        self._segs[dst] = segs
-        return segs
 
     def refresh(self, stream=None):
         """Re-pack every image set from the f32 parameters (eager: initial packs, loads, the DP path)."""

@@ -10,24 +10,26 @@ buffers) is built. The Fused*State classes share one surface, so neither front e
 from dataclasses import dataclass
 from typing import Callable, Optional
 
-from . import fused_ddpg, fused_dqn, fused_iqn, fused_rainbow, fused_update
+from . import fused_ddpg, fused_dqn, fused_iqn, fused_rainbow, fused_sac, fused_update
 from .policy.AC_IQN_model import AC_IQN_Policy
 from .policy.DDPG_model import DDPG_Policy
 from .policy.DQN_model import DQN_Policy
 from .policy.IQN_model import IQN_Policy
 from .policy.Rainbow_model import Rainbow_Policy
+from .policy.SAC_model import SAC_Policy
 
 
 @dataclass(frozen=True)
 class Learner:
     policy: type
-    field: str              # VecTrainer's attribute that holds the state (the other four stay None)
+    field: str              # VecTrainer's attribute that holds the state (the other five stay None)
     supported: Callable     # (policy, B, N) -> the kernels take this network and batch
     state: Callable         # (local, target, B, N, operands, support, batched) -> the Fused*State; batched: VecTrainer's
                             # (graphs, unroll), None for the drop-in Agent (nothing runs beside its update)
     refusal: Optional[str] = None   # VecTrainer's ValueError for an unsupported shape (None: not checked there)
     actor_critic: bool = False      # actor + critic with an optimiser each and a continuous 2-d action; otherwise one
                                     # network, one optimiser, an action index
+    twin: bool = False              # actor_critic with two critics (critic_1, critic_2), an optimiser each (SAC)
     policy_args: tuple = ()         # constructor arguments behind action_size
     per: bool = False               # the prioritised n-step tree instead of the uniform ring
 
@@ -52,6 +54,11 @@ def _ddpg_state(local, target, B, N, operands, support=None, batched=None):
     # the update waits for the act kernel instead (fused_update._actor_step's actor_wait)
     double = batched is not None and (not batched[0] or batched[1] % 2 == 0)
     return fused_ddpg.FusedDDPGState(local, target, B, operands, double_actor=double)
+
+
+def _sac_state(local, target, B, N, operands, support=None, batched=None):
+    double = batched is not None and (not batched[0] or batched[1] % 2 == 0)   # the same odd-unroll rule
+    return fused_sac.FusedSACState(local, target, B, operands, double_actor=double)
 
 
 LEARNERS = {
@@ -81,11 +88,18 @@ LEARNERS = {
     "DDPG": Learner(
         DDPG_Policy, "fused_ddpg", lambda p, B, N: fused_ddpg.supported(p, B), _ddpg_state,
         "DDPG learner kernels: B={B} (a positive multiple of 32)", actor_critic=True),
+    # SAC_Policy: the Actor's trunk under a sampled head and two DDPG critics (fused_sac.py); the batched loop only
+    "SAC": Learner(
+        SAC_Policy, "fused_sac", lambda p, B, N: fused_sac.supported(p, B), _sac_state,
+        "SAC learner kernels: B={B} (a positive multiple of 32)", actor_critic=True, twin=True),
 }
 
 
 def policy_modules(policy):
-    """[actor, critic] of an actor-critic policy, [policy] of a single network."""
+    """[actor, critic] of an actor-critic policy ([actor, critic_1, critic_2] of SAC's), [policy] of a single
+    network."""
+    if hasattr(policy, "critic_1"):
+        return [policy.actor, policy.critic_1, policy.critic_2]
     return [policy.actor, policy.critic] if hasattr(policy, "actor") else [policy]
 
 

@@ -8,7 +8,8 @@ One iteration (= one `step` of bench.py):
   3. replay push of the transitions of robots that acted (asvrl_replay_push, trainer.py:157-166)
   4. device reset of finished envs + their first observation (asvrl_env_reset, trainer.py:212-245)
   5. learn: sample B transitions (asvrl_replay_sample) and one distributional update
-     (AC-IQN and DDPG: two dependent optimizer steps, critic then actor; IQN, Rainbow and DQN: one)
+     (AC-IQN and DDPG: two dependent optimizer steps, critic then actor; SAC: three, both critics then the
+     actor; IQN, Rainbow and DQN: one)
   6. hard target update every `target_update_interval` learn steps (agent.py:643-679, TAU=1)
 
 Cadence in the batched setting: one learn step of batch B per iteration (after
@@ -40,8 +41,8 @@ class VecTrainer:
         """Every learner (learners.LEARNERS) runs on the hand-written kernels with FusedAdam; operands="f32" takes
         them from the f32-operand parity build (libasvrl_f32.so). Shapes the kernels do not take raise ValueError."""
         if agent_type not in LEARNERS:
-            raise NotImplementedError(f"VecTrainer agent_type {agent_type!r} (AC-IQN, IQN, Rainbow, DQN and DDPG are "
-                                      "batched)")
+            raise NotImplementedError(f"VecTrainer agent_type {agent_type!r} (AC-IQN, IQN, Rainbow, DQN, DDPG and SAC "
+                                      "are batched)")
         spec = LEARNERS[agent_type]
         self.device = torch.device(device)
         self.agent_type = agent_type
@@ -75,8 +76,13 @@ class VecTrainer:
         # clip + Adam over flat buffers (must precede the packs, which cache parameter pointers)
         if spec.actor_critic:
             self.actor_opt = FusedAdam(self.local.actor.parameters(), lr=lr, operands=operands)
-            self.critic_opt = FusedAdam(self.local.critic.parameters(), lr=lr, operands=operands)
-            self.actor_grads, self.critic_grads = self.actor_opt.grads, self.critic_opt.grads
+            self.actor_grads = self.actor_opt.grads
+            if spec.twin:   # SAC: each critic is clipped by its own norm and takes its own Adam step
+                self.critic_opts = [FusedAdam(c.parameters(), lr=lr, operands=operands)
+                                    for c in (self.local.critic_1, self.local.critic_2)]
+            else:
+                self.critic_opt = FusedAdam(self.local.critic.parameters(), lr=lr, operands=operands)
+                self.critic_grads = self.critic_opt.grads
         else:
             self.opt = FusedAdam(self.local.parameters(), lr=lr, operands=operands)
             self.grads = self.opt.grads
@@ -84,7 +90,7 @@ class VecTrainer:
         self.n_step = 3 if spec.per else None
         self.support = torch.linspace(-1.0, 1.0, 51, device=self.device) if spec.per else None
         # the learner's packs and buffers on the hand-written kernels: the one fused field that is not None
-        self.fused2 = self.fused_iqn = self.fused_rb = self.fused_dqn = self.fused_ddpg = None
+        self.fused2 = self.fused_iqn = self.fused_rb = self.fused_dqn = self.fused_ddpg = self.fused_sac = None
         self.learner = spec.state(self.local, self.target, batch_size, num_tau, operands, support=self.support,
                                   batched=(graphs, max(1, int(unroll))))
         setattr(self, spec.field, self.learner)
@@ -136,10 +142,10 @@ class VecTrainer:
         # AC-IQN only (measured 0.346 -> 0.340 ms/step; IQN, whose act kernel fills the GPU, 0.363 ->
         # 0.366: profiles/r02_chain_schedule_ab.txt)
         self.chain = (agent_type == "AC-IQN") if chain is None else bool(chain)
-        if self.chain and agent_type == "DDPG":
-            # not built for DDPG: refused rather than silently run as the joined schedule
-            raise ValueError("the dependency-chained schedule is not available for DDPG (chain=None or False: the "
-                             "joined schedule)")
+        if self.chain and agent_type in ("DDPG", "SAC"):
+            # not built for DDPG or SAC: refused rather than silently run as the joined schedule
+            raise ValueError(f"the dependency-chained schedule is not available for {agent_type} (chain=None or "
+                             "False: the joined schedule)")
         paa_ok = agent_type == "AC-IQN" and self.graphs and self._chained()
         if self.target_after_env and not paa_ok:
             # the knob orders two nodes of the chained AC-IQN graph; anywhere else it would be silently ignored

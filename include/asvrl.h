@@ -1284,6 +1284,119 @@ int64_t asvrl_ddpg_weights_struct_size(void);
 int64_t asvrl_ddpg_grad_struct_size(void);
 int64_t asvrl_ddpg_actor_struct_size(void);
 
+/* ---------------------------------------------------------------- SAC (agent.py:289-306, 547-595)
+ * SAC_model.Critic is DDPG_model.Critic (AsvDdpgWeights, the one-scalar critic tile) twice. SAC_model.Actor is the
+ * Actor's trunk under two 128 -> 2 heads: mu = Wmu h2 + bmu, ls = clamp(Wls h2 + bls, -20, 2), sigma = exp(ls),
+ * z = mu + sigma eps, a = (2/pi) atan(z), logp = sum_d [-eps_d^2 / 2 - ls_d - log sqrt(2 pi) - log(1 - a_d^2 + 1e-6)]
+ * (SAC_model.py:175-199). eps: an optional [n][2] f32 input used as is; NULL draws it in the kernel by Philox +
+ * Box-Muller keyed by (row, counter, seed) in one of three streams (target actor, local actor, act) that never share
+ * draws. The eps used is always written out. New entry points only: the ABI version stays 29. */
+typedef struct AsvSacActorWeights {
+  AsvMlpWeights trunk;    /* enc / w1 / w2 images (w2t / w1t for the backward), b1, b2, out_scale; wout: `head`,
+                             bout: `bhead` (the Actor's staging reads their leading two rows); ae_frag, b_ae unused */
+  const float* head;      /* f32 [4][128]: output_layer_mu.weight (rows 0, 1), output_layer_log_std.weight (2, 3) */
+  const float* bhead;     /* f32 [4]: output_layer_mu.bias, output_layer_log_std.bias */
+} AsvSacActorWeights;
+
+/* Batched act (act_sac): greedy iff random() > eps_explore -- the sampled action -- else uniform per dimension; the
+ * schedule and the greedy / uniform draw are asvrl_actor_forward's ACT mode, the noise counter is the step count. */
+typedef struct AsvSacActIO {
+  const float* x;         /* [n] rows of ASVRL_OBS_DIM at stride ldx floats, 16-byte aligned */
+  int64_t ldx;
+  int32_t n;
+  int32_t _pad0;
+  double* a_out64;        /* out [n][2] */
+  const float* eps_in;    /* optional [n][2] */
+  float* eps_out;         /* out [n][2]: the eps of the sampled action (also of rows that explore) */
+  const int64_t* step_dev;   /* optional device step counter */
+  double eps_steps_per_count, eps_total, eps_fraction, eps_initial, eps_final;   /* as AsvMlpIO's */
+  uint64_t seed;
+} AsvSacActIO;
+
+/* The sampled actor over B replay rows, forward (asvrl_sac_actor_forward: the local actor on s saving what the
+ * backward reads, the target actor on s') and backward (asvrl_sac_actor_backward). Saved activations and gradients
+ * are in the build's operand type (bf16 / f32) unless marked f32. */
+typedef struct AsvSacActorIO {
+  const float* rows;      /* [B] replay rows at stride ld_rows floats, 16-byte aligned */
+  int64_t ld_rows;
+  int32_t B;              /* a positive multiple of 32 */
+  float alpha;            /* entropy weight (backward) */
+  const float* eps_local_in;    /* optional [B][2] */
+  const float* eps_target_in;   /* optional [B][2] */
+  uint64_t seed;
+  uint64_t counter;             /* noise counter = counter + *counter_dev */
+  const int64_t* counter_dev;   /* optional device counter (the learn counter) */
+  void* xb;               /* out [B][32] */
+  void* h0;               /* out [B][256] */
+  void* h1;               /* out [B][128] */
+  void* h2;               /* out [B][128] */
+  float* mu;              /* out f32 [B][2] */
+  float* ls;              /* out f32 [B][2]: log_std before the clamp */
+  float* sigma;           /* out f32 [B][2] */
+  float* z;               /* out f32 [B][2] */
+  float* a;               /* out f32 [B][2]: a_pi */
+  float* eps;             /* out f32 [B][2] */
+  float* logp;            /* out f32 [B] */
+  float* na;              /* out f32 [B][2]: the target actor's sampled action on s' */
+  float* logp_next;       /* out f32 [B] */
+  float* eps_next;        /* out f32 [B][2] */
+  /* backward */
+  const float* dA;        /* f32 [2][B][2]: each critic's share of d(-Qmin)/da (asvrl_sac_actor_grad); summed here */
+  const float* q_pi;      /* f32 [2][B]: Q1, Q2(s, a_pi) */
+  float* dhead;           /* out f32 [4][B]: dmu (rows 0, 1), dls (2, 3): the head's pre-activation gradients */
+  void* dz2;              /* out [B][128] */
+  void* dz1;              /* out [B][128] */
+  void* dz0;              /* out [B][256] */
+  float* tile_loss;       /* out f32 [B / 32]: per-tile partials of mean(alpha logp - min(Q1, Q2)) */
+} AsvSacActorIO;
+
+/* The twin critic gradient over B replay rows: c[k] is critic k's AsvDdpgGradIO (the same rows, ld_rows, B, gamma,
+ * na and ld_na in both; every buffer its own). q_k = Q_k(s, a), q_next_k = Q_k_target(s', na),
+ * y = r + gamma (1 - d) (min(q_next_1, q_next_2) - alpha logp_next), loss_k = mean (q_k - y)^2,
+ * dq_k = 2 (q_k - y) / B, and each critic's backward as asvrl_ddpg_grad's. */
+typedef struct AsvSacGradIO {
+  AsvDdpgGradIO c[2];
+  const float* logp_next; /* f32 [B]: the target actor's log-probability on s' */
+  float* y;               /* optional out f32 [B]: the target */
+  float alpha;
+  int32_t _pad0;
+} AsvSacGradIO;
+
+/* The actor step's gradient to the action through both critics: q_pi[k] = Q_k(s, a_pi), and
+ * dA[k] = w_k d(-Q_k)/da with w_k = 1 where Q_k is the smaller, 1/2 on an exact tie, 0 otherwise (torch.min). */
+typedef struct AsvSacActorGradIO {
+  const float* x;         /* [B] observation rows at stride ldx floats, 16-byte aligned */
+  int64_t ldx;
+  const float* act;       /* [B] a_pi at stride lda floats */
+  int64_t lda;
+  int32_t B;              /* a positive multiple of 32 */
+  int32_t _pad0;
+  float* q_pi;            /* out f32 [2][B] */
+  float* dA;              /* out f32 [2][B][2] */
+} AsvSacActorGradIO;
+
+/* act_sac on n rows, one launch. */
+int asvrl_sac_act(const AsvSacActorWeights* w, const AsvSacActIO* io, void* stream);
+/* One launch: blockIdx.y = 0 the local actor on s, 1 the target actor on s'. */
+int asvrl_sac_actor_forward(const AsvSacActorWeights* local, const AsvSacActorWeights* target, const AsvSacActorIO* io,
+                            void* stream);
+/* Two launches, no host sync: the four forwards (local 1, 2 on (s, a) saving activations, target 1, 2 on
+ * (s', na)), then both losses + backwards. */
+int asvrl_sac_grad(const AsvDdpgWeights* local1, const AsvDdpgWeights* local2, const AsvDdpgWeights* target1,
+                   const AsvDdpgWeights* target2, const AsvSacGradIO* io, void* stream);
+/* Two launches: q_pi of both critics, then each critic's weighted action gradient. */
+int asvrl_sac_actor_grad(const AsvDdpgWeights* local1, const AsvDdpgWeights* local2, const AsvSacActorGradIO* io,
+                         void* stream);
+/* One launch: the head's backward from dA, the saved z / a / eps / ls / sigma and alpha, then dz2, dz1, dz0, the
+ * actor-loss partials and dhead. */
+int asvrl_sac_actor_backward(const AsvSacActorWeights* w, const AsvSacActorIO* io, void* stream);
+/* sizeof of the five SAC structs as compiled. */
+int64_t asvrl_sac_actor_weights_struct_size(void);
+int64_t asvrl_sac_act_struct_size(void);
+int64_t asvrl_sac_actor_struct_size(void);
+int64_t asvrl_sac_grad_struct_size(void);
+int64_t asvrl_sac_actor_grad_struct_size(void);
+
 /* ---------------------------------------------------------------- misc */
 const char* asvrl_last_error(void);
 int asvrl_abi_version(void);

@@ -25,6 +25,9 @@ Fixture families:
                         networks from a numpy-seeded generator (oracle/learn_ref.py)
   learn_dqn.npz     F8  Agent.train_DQN / act_dqn (agent.py:518-545, 271-287)
   learn_ddpg.npz    F8b Agent.train_DDPG / act_ddpg (agent.py:478-516, 252-269) and the critic's q (capture_ddpg)
+  learn_sac_init.npz, learn_sac.npz
+                    F8c Agent.train_SAC / the sampled actor (agent.py:547-595, SAC_model.py:175-199) with every
+                        standard normal draw recorded (capture_sac)
   eval_ref.npz      F9  Trainer.evaluation (trainer.py:266-392), AC-IQN and Rainbow
   eval_iqn_ref.npz  F9b the same for IQN with every act_iqn call's K = 32 taus recorded (capture_eval_iqn)
   eval60_ref.npz    F10 Trainer.evaluation on config/ac_iqn.json's 60-episode eval_schedule, the seeded
@@ -1055,6 +1058,72 @@ def capture_ddpg():
     out.update(sd_arrays("after1/critic/", agent.policy_local.critic))
     np.savez_compressed(os.path.join(OUT, "learn_ddpg.npz"), **out)
     print("ddpg keys:", len(out))
+
+
+def capture_sac():
+    """F8c: Agent.train_SAC (agent.py:547-595) x 2 steps on continuous transitions with both standard normal draws of
+    every step recorded (the target actor's on s', then the local actor's on s: Normal.rsample goes through
+    torch.distributions.normal._standard_normal), and the sampled actor's action and log-probability for one state
+    and recorded draw with both critics' q for them, at the initial weights. Two files, so that each stays within the
+    size limit for a committed fixture (three networks are about 0.6 MB per weight set): learn_sac_init.npz holds
+    the initial weights and the act record, learn_sac.npz the batches, draws, losses, norms and final weights."""
+    import torch.distributions.normal as tdn
+    init, out = {}, {}
+    # collect_transitions acts uniformly in (-1, 1), so almost every transition carries thrusts of hundreds of newtons
+    # in s or s'; the seeded actor's log_std then leaves the clamp's range and the atan squash saturates (1 - a^2 down
+    # to 0.05), where logp is too sensitive to z for a 1e-4 parity bar. The batches are drawn from the calm
+    # transitions (every thrust input of s and s' within 100 N, about 1 in 400), where log_std stays inside [-20, 2]
+    # and min(1 - a^2) >= 0.2; tests/test_fused_sac_gpu.py asserts both on these inputs.
+    trans = [t for t in collect_transitions(60000, seed=7)
+             if max(abs(v) for s in (t[0], t[3]) for v in s[0][5:7]) <= 100.0]
+    assert len(trans) >= 80, len(trans)
+    rs = np.random.RandomState(73)
+    agent = ref_agent_mod.Agent(device="cpu", seed=100, agent_type="SAC")
+    nets = ("actor", "critic_1", "critic_2")
+    for kind in nets:
+        init.update(sd_arrays(f"init/{kind}/", getattr(agent.policy_local, kind)))
+        tsd, lsd = getattr(agent.policy_target, kind).state_dict(), getattr(agent.policy_local, kind).state_dict()
+        assert list(tsd) == list(lsd) and all(torch.equal(tsd[k], lsd[k]) for k in lsd)
+    init["target/equals_init"] = np.bool_(True)
+    init["alpha"] = np.float64(agent.alpha)
+    draws = []
+    orig = tdn._standard_normal
+
+    def recording(shape, dtype, device):
+        e = orig(shape, dtype, device)
+        draws.append(e.detach().numpy().copy())
+        return e
+    tdn._standard_normal = recording
+    try:
+        st = trans[7][0]
+        x = agent.state_to_tensor(agent.memory.state_batch([st]))
+        with torch.no_grad():
+            a, logp = agent.policy_local.actor(x)
+            q1, q2 = agent.policy_local.critic_1(x, a), agent.policy_local.critic_2(x, a)
+        init["act/state_self"] = np.array(st[0], dtype=np.float64)
+        init["act/state_obj"] = np.array(st[1], dtype=np.float64).reshape(-1, 5)
+        init["act/eps"] = draws.pop()
+        init["act/action"], init["act/logp"] = a.numpy().copy(), logp.numpy().copy()
+        init["act/q1"], init["act/q2"] = q1.numpy().copy(), q2.numpy().copy()
+        for step in range(2):
+            idx = rs.choice(len(trans), 64, replace=False)
+            batch = make_batch(agent, trans, idx)
+            out.update(batch_arrays(f"step{step}/", *batch, 64))
+            agent.memory.sample = (lambda b=batch: b)
+            assert not draws
+            with ClipRecorder() as cr:
+                l1, l2, la = agent.train_SAC()
+            assert len(draws) == 2 and all(d.shape == (64, 2) for d in draws)
+            out[f"step{step}/eps_target"], out[f"step{step}/eps_local"] = draws.pop(0), draws.pop(0)
+            out[f"step{step}/losses"] = np.array([l1, l2, la], dtype=np.float64)   # critic_1, critic_2, actor
+            out[f"step{step}/grad_norms"] = np.array(cr.norms)   # critic_1, critic_2, actor (pre-clip)
+    finally:
+        tdn._standard_normal = orig
+    for kind in nets:
+        out.update(sd_arrays(f"after1/{kind}/", getattr(agent.policy_local, kind)))
+    np.savez_compressed(os.path.join(OUT, "learn_sac_init.npz"), **init)
+    np.savez_compressed(os.path.join(OUT, "learn_sac.npz"), **out)
+    print("sac keys:", len(init), len(out))
 
 
 EVAL_SCHEDULE = {"num_episodes": [2, 2], "num_robots": [3, 5], "num_cores": [0, 2], "num_obstacles": [2, 4],
