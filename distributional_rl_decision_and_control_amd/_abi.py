@@ -256,6 +256,12 @@ class AsvSacActIO(C.Structure):
                 ("eps_fraction", _D), ("eps_initial", _D), ("eps_final", _D), ("seed", _U64)]
 
 
+class AsvSacPolicy(C.Structure):
+    _fields_ = [("w", AsvSacActorWeights), ("obs_in", _VP), ("step_dev", _VP), ("eps_steps_per_count", _D),
+                ("eps_total", _D), ("eps_fraction", _D), ("eps_initial", _D), ("eps_final", _D), ("seed", _U64),
+                ("actions", _VP), ("deterministic", _I32), ("_pad0", _I32)]
+
+
 SAC_ACTOR_ARRAYS = ("xb", "h0", "h1", "h2", "mu", "ls", "sigma", "z", "a", "eps", "logp", "na", "logp_next",
                     "eps_next", "dA", "q_pi", "dhead", "dz2", "dz1", "dz0", "tile_loss")
 
@@ -477,6 +483,13 @@ EXPORTS = [
     ("asvrl_sac_actor_struct_size", _I64, []),
     ("asvrl_sac_grad_struct_size", _I64, []),
     ("asvrl_sac_actor_grad_struct_size", _I64, []),
+    ("asvrl_sac_rollout", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), C.POINTER(AsvStepCtl),
+                                    C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvSacPolicy),
+                                    C.POINTER(AsvEnvLaunch), _VP]),
+    ("asvrl_sac_rollout_ar", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), C.POINTER(AsvStepCtl),
+                                       C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvSacPolicy),
+                                       C.POINTER(AsvAutoReset), C.POINTER(AsvEnvLaunch), _VP]),
+    ("asvrl_sac_policy_struct_size", _I64, []),
 ]
 
 _libs = {}

@@ -24,7 +24,7 @@ HEADERS = [os.path.join(HERE, "csrc", "asvrl_common.h"), os.path.join(HERE, "csr
            os.path.join(HERE, "csrc", "asvrl_lds.h"), os.path.join(HERE, "csrc", "asvrl_vonmises_k1.h"),
            os.path.join(HERE, "csrc", "asvrl_critic_tile.h"), os.path.join(HERE, "csrc", "asvrl_actor_tile.h"),
            os.path.join(HERE, "csrc", "asvrl_dqn_tile.h"), os.path.join(HERE, "csrc", "asvrl_ddpg_tile.h"),
-           os.path.join(ROOT, "include", "asvrl.h")]
+           os.path.join(HERE, "csrc", "asvrl_sac_tile.h"), os.path.join(ROOT, "include", "asvrl.h")]
 OUT = os.path.join(HERE, "lib", "libasvrl.so")
 OUT_F32 = os.path.join(HERE, "lib", "libasvrl_f32.so")
 VARIANTS = {OUT: [], OUT_F32: ["-DASVRL_OPERAND_F32=1"]}

@@ -23,6 +23,7 @@
 #include "asvrl_vonmises_k1.h"
 #include "asvrl_actor_tile.h"
 #include "asvrl_dqn_tile.h"
+#include "asvrl_sac_tile.h"
 
 namespace asvrl {
 namespace {
@@ -681,6 +682,10 @@ __host__ __device__ constexpr size_t autoreset_lds(int blk, int epb) {
 // POL = kPolDqn (env_dqn_rollout_kernel): the same closed loop under DQN_Policy -- the Actor's trunk staged the same
 // way, the 25-wide head's fragments and bias read from L2 (asvrl_dqn_tile.h: dqn_act_kernel's functions), the first
 // arg-max and the epsilon-greedy index left as the pair (index, 0.0), which phase 1 takes as a discrete action.
+// POL = kPolSac (env_sac_rollout_kernel): the closed loop under SAC's sampled actor -- the trunk staged the same way,
+// the f32 head (2 KB) staged beside it in HL before the staging's barrier, then sac_act_kernel's statements
+// (asvrl_sac_tile.h): the two normals of (global row, step) in the act stream, or none when PI->deterministic, the
+// head without its log-probability, and atile::explore into the f64 action pair.
 // AR (asvrl_env_rollout_ar / asvrl_policy_rollout_ar, with ROLL): episodes restart inside the window. After the
 // phases of step t the workgroup votes on "an env of mine ended in this step"; if so its waves reset the ended envs
 // (reset_env, one wave per env, the waves taking them in turn, each in its own ResetLds behind the carve and the
@@ -698,17 +703,20 @@ __host__ __device__ constexpr size_t autoreset_lds(int blk, int epb) {
 // leaves the step loop early (hold_done is refused with AR), and since every lane of an env reads the env's alive
 // count for `end`, the vote is also the barrier between those reads and the next step's reset of the count.
 // the policy in front of every step of a closed-loop rollout, and its argument struct
-enum : int { kPolNone = 0, kPolActor = 1, kPolDqn = 2 };
+enum : int { kPolNone = 0, kPolActor = 1, kPolDqn = 2, kPolSac = 3 };
 template <int POL> struct PolicyOf { using type = AsvPolicy; };
 template <> struct PolicyOf<kPolDqn> { using type = AsvDqnPolicy; };
+template <> struct PolicyOf<kPolSac> { using type = AsvSacPolicy; };
 __device__ __forceinline__ const AsvMlpWeights& trunk_of(const AsvPolicy& p) { return p.w; }
 __device__ __forceinline__ const AsvMlpWeights& trunk_of(const AsvDqnPolicy& p) { return p.w.trunk; }
+__device__ __forceinline__ const AsvMlpWeights& trunk_of(const AsvSacPolicy& p) { return p.w.trunk; }
 template <int BLOCK, int NM, bool DYN = true, bool ROLL = false, int POL = kPolNone, bool AR = false>   // DYN false: an observation pass only (do_dynamics = 0)
 __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int bid, unsigned char* smem,
                                                 KArg<AsvRollout> RO = nullptr,
                                                 KArg<typename PolicyOf<POL>::type> PI = nullptr,
                                                 atile::ActorLds* AL = nullptr, KArg<AsvAutoReset> RS = nullptr,
-                                                unsigned char* ar_lds = nullptr) {
+                                                unsigned char* ar_lds = nullptr,
+                                                sactile::SacHeadLds* HL = nullptr) {
   static_assert(POL == kPolNone || ROLL, "the policy runs inside the rollout's step loop");
   static_assert(!AR || ROLL, "the auto-reset runs inside the rollout's step loop");
   const int R = A->s.max_robots;
@@ -811,6 +819,7 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
   if constexpr (POL != kPolNone) {
     // the weights once per workgroup; the rows step 0 acts on (rows past the batch: zeros, never consumed)
     atile::stage_actor<BLOCK>(*AL, trunk_of(kref(PI)), tid);
+    if constexpr (POL == kPolSac) sactile::stage_head<BLOCK>(*HL, kref(PI).w, tid);   // (the barrier below is its too)
     constexpr int kRowV = ASVRL_OBS_DIM / 4;
     const float4* src = reinterpret_cast<const float4*>(PI->obs_in);
     for (int k = tid; k < nrb * kRowV; k += BLOCK) {
@@ -946,6 +955,39 @@ __device__ __forceinline__ void env_pairs_block(KArg<PairsArgs> A, int epb, int 
         sa64[2 * lr] = static_cast<double>(act);
         sa64[2 * lr + 1] = 0.0;
       }
+    }
+    __syncthreads();
+    if (env_on && P->actions != nullptr) {   // the action every robot slot of a stepping env was given
+      double* rec = P->actions + (static_cast<size_t>(t) * NT + idx) * 2;
+      rec[0] = sa64[2 * tid];
+      rec[1] = sa64[2 * tid + 1];
+    }
+  } else if constexpr (POL == kPolSac) {
+    // SAC's actor on the workgroup's rows: sac_act_kernel's trunk, noise, head and draw (asvrl_sac_tile.h)
+    const KArg<AsvSacPolicy> P = kfresh(PI);
+    const uint64_t step = (P->step_dev != nullptr ? static_cast<uint64_t>(*P->step_dev) : 0ull) + static_cast<uint64_t>(t);
+    const int ln = tid & (kWave - 1), wv = __builtin_amdgcn_readfirstlane(tid / kWave);
+    for (int tile = wv; tile * 32 < nrb; tile += BLOCK / kWave) {   // wave-uniform: the MFMAs run with every lane on
+      asm volatile("" ::: "memory");   // (the tile's LDS reads stay inside the loop, as the Actor's)
+      const int lr = tile * 32 + (ln & 31);
+      const bool valid = lr < nrb;
+      const int rr = valid ? lr : nrb - 1;
+      // the draw in front of the trunk, where two floats ride through it: behind it (sac_act_kernel's order; the
+      // values do not depend on it) Philox and Box-Muller run with h2 live and the kernel spills three times as much
+      float eps[atile::kNa] = {0.f, 0.f};   // deterministic: z = mu, nothing drawn (workgroup-uniform)
+      if (P->deterministic == 0)
+        sactile::sac_eps(sactile::kSacActStream, static_cast<int>(row0 + rr), step, P->seed, eps[0], eps[1]);
+      frag8 bx[2];
+      float mk[atile::kObjN];
+      atile::load_obs(sobs, ASVRL_OBS_DIM, rr, ln >> 5, bx, mk);
+      float h2v[8][8];
+      atile::trunk_chain<atile::MLP_ACT>(kref(P).w.trunk, AsvMlpIO{}, *AL, 0, false, ln, bx, mk, h2v);
+      sactile::SacSample o;
+      sactile::sac_head<false>(*HL, P->w.trunk.out_scale, h2v, ln, eps, o);   // (every lane of the wave is live at its shuffle)
+      if (valid && ln < 32)
+        atile::explore(step, atile::EpsSchedule{P->eps_steps_per_count, P->eps_total, P->eps_fraction, P->eps_initial,
+                                                P->eps_final},
+                       P->seed, static_cast<int>(row0 + lr), o.a[0], o.a[1], sa64[2 * lr], sa64[2 * lr + 1]);
     }
     __syncthreads();
     if (env_on && P->actions != nullptr) {   // the action every robot slot of a stepping env was given
@@ -1559,6 +1601,42 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(ASVRL_ENV
       &PA->ro, &PA->pi, &AL, &PA->ar, smem + PA->ar_off);
 }
 
+// The closed loop under SAC's sampled actor (asvrl_sac_rollout / asvrl_sac_rollout_ar): the two kernels above with
+// env_pairs_block<kPolSac> -- the same static ActorLds and, beside it, the f32 head (SacHeadLds, 2064 B: 512 weights
+// every lane reads per tile, so they sit in LDS, not L2), the same dynamic carve, one workgroup per CU.
+struct SacRolloutArgs {
+  PairsArgs k;   // actions null; noise: row 0 of the rollout's
+  AsvRollout ro;
+  AsvSacPolicy pi;
+};
+template <int BLOCK, int NM>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(ASVRL_ENV_POLICY_WPE))) void env_sac_rollout_kernel(SacRolloutArgs) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ __attribute__((aligned(16))) atile::ActorLds AL;
+  __shared__ __attribute__((aligned(16))) sactile::SacHeadLds HL;
+  const KArg<SacRolloutArgs> PA = kargs<SacRolloutArgs>();
+  env_pairs_block<BLOCK, NM, true, true, kPolSac>(
+      &PA->k, PA->k.epb, PA->k.group0 + xcd_group(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x)), smem,
+      &PA->ro, &PA->pi, &AL, nullptr, nullptr, &HL);
+}
+struct SacRolloutArArgs {
+  PairsArgs k;
+  AsvRollout ro;
+  AsvSacPolicy pi;
+  AsvAutoReset ar;
+  int ar_off;
+};
+template <int BLOCK, int NM>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(ASVRL_ENV_POLICY_WPE))) void env_sac_rollout_ar_kernel(SacRolloutArArgs) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ __attribute__((aligned(16))) atile::ActorLds AL;
+  __shared__ __attribute__((aligned(16))) sactile::SacHeadLds HL;
+  const KArg<SacRolloutArArgs> PA = kargs<SacRolloutArArgs>();
+  env_pairs_block<BLOCK, NM, true, true, kPolSac, true>(
+      &PA->k, PA->k.epb, PA->k.group0 + xcd_group(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x)), smem,
+      &PA->ro, &PA->pi, &AL, &PA->ar, smem + PA->ar_off, &HL);
+}
+
 // The K-launch fallback of the two calls. In front of step t: row t of obs_prev, the observation (src) the stepping
 // envs' rows hold ...
 __global__ __launch_bounds__(kBlock) void autoreset_obs_prev_kernel(const float* __restrict__ src, float* __restrict__ row,
@@ -1935,13 +2013,13 @@ PairLaunch pair_launch(int R, int O, int n_envs, int blk_req, int epb_req, int v
 
 using namespace asvrl;
 
-// ------------------------------------------------------------------ the env step and its six rollout calls
+// ------------------------------------------------------------------ the env step and its eight rollout calls
 // One host path. Each call is: env_checks (its arguments), env_plan (the launch shape, and whether the
 // pair-parallel kernel is taken), then launch_groups (that kernel) or, for the rollouts, rollout_fallback (K single
 // steps).
 
 // the groups of checks a call takes beyond the step's own
-enum : unsigned { kRollout = 1, kClosedLoop = 2, kAutoReset = 4, kDqnPolicy = 8 };   // (kDqnPolicy: with kClosedLoop)
+enum : unsigned { kRollout = 1, kClosedLoop = 2, kAutoReset = 4, kDqnPolicy = 8, kSacPolicy = 16 };   // (kDqnPolicy, kSacPolicy: with kClosedLoop)
 
 static int env_fail(const char* who, const char* what) {
   set_error(std::string(who) + ": " + what);
@@ -1952,14 +2030,17 @@ static int env_fail(const char* who, const char* what) {
     if (!(cond)) return env_fail(who, what);     \
   } while (0)
 
-// The argument checks of the seven calls, in the order each call reports them (`who` names the call in the error
+// The argument checks of the nine calls, in the order each call reports them (`who` names the call in the error
 // text). actions / noise: the single step's; the rollouts carry theirs in ro.
 static int env_checks(const char* who, unsigned kind, const AsvParams* params, const AsvEnvState* state,
                       const double* actions, const double* noise, const AsvStepCtl* ctl, const AsvStepOut* out,
-                      const AsvRollout* ro, const AsvPolicy* pi, const AsvDqnPolicy* dq, const AsvAutoReset* ar,
-                      const AsvEnvLaunch* launch) {
+                      const AsvRollout* ro, const AsvPolicy* pi, const AsvDqnPolicy* dq, const AsvSacPolicy* sq,
+                      const AsvAutoReset* ar, const AsvEnvLaunch* launch) {
   const bool roll = (kind & kRollout) != 0, closed = (kind & kClosedLoop) != 0, reset = (kind & kAutoReset) != 0;
-  const bool dqn = (kind & kDqnPolicy) != 0;   // the closed loop's policy: dq (DQN_Policy), else pi (the Actor)
+  // the closed loop's policy: dq (DQN_Policy), sq (SAC's sampled actor), else pi (the Actor)
+  const bool dqn = (kind & kDqnPolicy) != 0, sac = (kind & kSacPolicy) != 0;
+  const float* pol_obs_in = nullptr;
+  if (closed) pol_obs_in = dqn ? (dq ? dq->obs_in : nullptr) : sac ? (sq ? sq->obs_in : nullptr) : (pi ? pi->obs_in : nullptr);
   ENV_REQUIRE(params && state && ctl && out && (ro || !roll), "null argument");
   if (reset) {   // what the two _ar calls refuse beyond their plain calls' checks
     ENV_REQUIRE(ar != nullptr, "null ar (the auto-reset description)");
@@ -1984,15 +2065,21 @@ static int env_checks(const char* who, unsigned kind, const AsvParams* params, c
   }
   if (closed) {
     ENV_REQUIRE(ro->actions == nullptr, "ro->actions must be null (the policy supplies the actions)");
-    ENV_REQUIRE(dqn ? dq != nullptr : pi != nullptr, "null policy");
-    ENV_REQUIRE((dqn ? dq->obs_in : pi->obs_in) != nullptr, "null obs_in");
+    ENV_REQUIRE(dqn ? dq != nullptr : (sac ? sq != nullptr : pi != nullptr), "null policy");
+    ENV_REQUIRE(pol_obs_in != nullptr, "null obs_in");
     if (dqn)
       ENV_REQUIRE(!ctl->is_continuous, "is_continuous must be 0 (DQN's actions are indices)");
+    else if (sac)
+      ENV_REQUIRE(ctl->is_continuous, "is_continuous must be 1 (SAC's actions are continuous)");
     else
       ENV_REQUIRE(ctl->is_continuous, "is_continuous must be 1 (the Actor is the continuous agent)");
-    const AsvMlpWeights& w = dqn ? dq->w.trunk : pi->w;
+    const AsvMlpWeights& w = dqn ? dq->w.trunk : (sac ? sq->w.trunk : pi->w);
     ENV_REQUIRE(w.enc_frag && w.b_enc && w.w1_frag && w.w2_frag && w.b1 && w.b2 && w.wout && w.bout,
-                dqn ? "null DQN image" : "null actor image");
+                dqn ? "null DQN image" : (sac ? "null SAC actor image" : "null actor image"));
+    if (sac) {
+      ENV_REQUIRE(sq->w.head != nullptr, "null pi->w.head");
+      ENV_REQUIRE(sq->w.bhead != nullptr, "null pi->w.bhead");
+    }
     if (dqn) {
       ENV_REQUIRE(dq->w.head_frag != nullptr, "null pi->w.head_frag");
       // >= 2: the tile's staging reads the first two output rows (the Actor's whole output layer)
@@ -2025,7 +2112,7 @@ static int env_checks(const char* who, unsigned kind, const AsvParams* params, c
     ENV_REQUIRE(launch->envs_per_block >= 0 && launch->max_groups >= 0, "negative envs_per_block / max_groups");
   }
   if (closed)
-    ENV_REQUIRE(reinterpret_cast<uintptr_t>(dqn ? dq->obs_in : pi->obs_in) % 16 == 0 &&
+    ENV_REQUIRE(reinterpret_cast<uintptr_t>(pol_obs_in) % 16 == 0 &&
                     reinterpret_cast<uintptr_t>(out->obs) % 16 == 0 &&
                     (!reset || reinterpret_cast<uintptr_t>(ar->obs_prev) % 16 == 0),
                 "observation rows must be 16-byte aligned");
@@ -2045,9 +2132,13 @@ struct PolicyLaunch {
   size_t smem;   // dynamic: the pair carve + the observation rows and action pairs
   bool fits;
 };
-static PolicyLaunch policy_launch(int R, int O, int n_envs, int blk_req, int epb_req, int vm_bytes, bool ar = false) {
+// head_bytes: static LDS beside the Actor's images (SAC's f32 head).
+static PolicyLaunch policy_launch(int R, int O, int n_envs, int blk_req, int epb_req, int vm_bytes, bool ar = false,
+                                  size_t head_bytes = 0) {
   constexpr size_t kLdsBytes = 160 * 1024;
   constexpr size_t kLdsStatic = 1024;   // room for the workgroup-vote scratch (__syncthreads_or) and alignment
+  static_assert(sizeof(atile::ActorLds) + sizeof(sactile::SacHeadLds) + kLdsStatic < kLdsBytes,
+                "the actor's images, the SAC head and the vote scratch leave room for a carve in one CU's LDS");
   constexpr int kCus = 256;
   auto total = [&](const PairLaunch& l) {
     const size_t rows = policy_rows_offset(l.smem) + static_cast<size_t>(l.epb) * R * (ASVRL_OBS_DIM * sizeof(float) + 2 * sizeof(double));
@@ -2064,7 +2155,7 @@ static PolicyLaunch policy_launch(int R, int O, int n_envs, int blk_req, int epb
   for (;;) {
     L.pl = pair_launch(R, O, n_envs, blk, epb, vm_bytes);   // (at most blk / R envs)
     L.smem = total(L.pl);
-    L.fits = sizeof(atile::ActorLds) + kLdsStatic + L.smem <= kLdsBytes;
+    L.fits = sizeof(atile::ActorLds) + head_bytes + kLdsStatic + L.smem <= kLdsBytes;
     if (L.fits || epb_req > 0 || L.pl.epb <= 1) break;
     epb = L.pl.epb - 1;
   }
@@ -2082,9 +2173,10 @@ struct EnvPlan {
   int groups, chunk;   // workgroups in all and per launch (AsvEnvLaunch max_groups)
 };
 // The open loop takes the pair layout where its carve fits 150 KB, and refuses an explicit layout 1 that cannot be
-// had; the closed loop takes it where policy_launch fits the carve beside the Actor, and falls back otherwise.
+// had; the closed loop takes it where policy_launch fits the carve beside the Actor (and head_bytes: SAC's head), and
+// falls back otherwise.
 static int env_plan(const char* who, const AsvEnvState* state, const AsvStepCtl* ctl, const AsvEnvLaunch* launch,
-                    bool closed, bool ar, EnvPlan* plan) {
+                    bool closed, bool ar, EnvPlan* plan, size_t head_bytes = 0) {
   const AsvEnvLaunch lz{};
   const AsvEnvLaunch& lc = launch != nullptr ? *launch : lz;
   EnvPlan P{};
@@ -2103,7 +2195,7 @@ static int env_plan(const char* who, const AsvEnvState* state, const AsvStepCtl*
     P.fused = lc.layout != 2 && !P.per_robot && P.smem <= 150 * 1024;
   } else if (lc.layout != 2 && !P.per_robot) {
     const PolicyLaunch L = policy_launch(state->max_robots, state->max_obs, state->n_envs, lc.block, lc.envs_per_block,
-                                         vm_bytes, ar);
+                                         vm_bytes, ar, head_bytes);
     P.pl = L.pl;
     P.smem = L.smem;
     if (ar) P.ar_off = static_cast<int>(L.smem - autoreset_lds(L.pl.blk, L.pl.epb));
@@ -2125,9 +2217,11 @@ template <int B, int NM> static auto kernel_of(const RolloutArArgs&) { return &e
 template <int B, int NM> static auto kernel_of(const PolicyArArgs&) { return &env_policy_rollout_ar_kernel<B, NM>; }
 template <int B, int NM> static auto kernel_of(const DqnRolloutArgs&) { return &env_dqn_rollout_kernel<B, NM>; }
 template <int B, int NM> static auto kernel_of(const DqnRolloutArArgs&) { return &env_dqn_rollout_ar_kernel<B, NM>; }
+template <int B, int NM> static auto kernel_of(const SacRolloutArgs&) { return &env_sac_rollout_kernel<B, NM>; }
+template <int B, int NM> static auto kernel_of(const SacRolloutArArgs&) { return &env_sac_rollout_ar_kernel<B, NM>; }
 template <class Args>
 constexpr bool kPhiloxOnly = std::is_same<Args, RolloutArArgs>::value || std::is_same<Args, PolicyArArgs>::value ||
-                             std::is_same<Args, DqnRolloutArArgs>::value;
+                             std::is_same<Args, DqnRolloutArArgs>::value || std::is_same<Args, SacRolloutArArgs>::value;
 static PairsArgs& pairs_of(PairsArgs& a) { return a; }
 template <class Args> static PairsArgs& pairs_of(Args& a) { return a.k; }
 
@@ -2138,7 +2232,7 @@ static auto kernel_for_noise(int nm, const Args& a) -> void (*)(Args) {
   }
   return nm == 1 ? kernel_of<B, 1>(a) : kernel_of<B, 2>(a);
 }
-// The pair-parallel launch of any of the seven kernels: P.groups workgroups in launches of at most P.chunk, each
+// The pair-parallel launch of any of the nine kernels: P.groups workgroups in launches of at most P.chunk, each
 // told its first group.
 template <class Args>
 static int launch_groups(const char* who, const EnvPlan& P, Args a, hipStream_t st) {
@@ -2156,7 +2250,8 @@ extern "C" int asvrl_env_step_ex(const AsvParams* params, const AsvEnvState* sta
                                  const double* noise, const AsvStepCtl* ctl, const AsvStepOut* out,
                                  const AsvEnvLaunch* launch, void* stream) {
   const char* who = "asvrl_env_step";
-  if (int rc = env_checks(who, 0, params, state, actions, noise, ctl, out, nullptr, nullptr, nullptr, nullptr, launch))
+  if (int rc = env_checks(who, 0, params, state, actions, noise, ctl, out, nullptr, nullptr, nullptr, nullptr, nullptr,
+                          launch))
     return rc;
   if (state->n_envs == 0) return 0;
   EnvPlan P;
@@ -2219,19 +2314,41 @@ static AsvDqnActIO dqn_act_io(const AsvDqnPolicy* dq, const float* x, size_t n, 
   return io;
 }
 
-// The K-launch form of the six rollout calls (per-robot parameters, layout 2, a carve that does not fit). Per step:
+// the sampled actor's act launch over n rows x: eps_in null draws the noise in the kernel, an all-zero eps_in is
+// the mean action; eps_out is the kernel's own record of the eps it used
+static AsvSacActIO sac_act_io(const AsvSacPolicy* sq, const float* x, size_t n, double* act, const float* eps_in,
+                              float* eps_out, const int64_t* step) {
+  AsvSacActIO io{};
+  io.x = x;
+  io.ldx = ASVRL_OBS_DIM;
+  io.n = static_cast<int32_t>(n);
+  io.a_out64 = act;
+  io.eps_in = eps_in;
+  io.eps_out = eps_out;
+  io.step_dev = step;
+  io.eps_steps_per_count = sq->eps_steps_per_count;
+  io.eps_total = sq->eps_total;
+  io.eps_fraction = sq->eps_fraction;
+  io.eps_initial = sq->eps_initial;
+  io.eps_final = sq->eps_final;
+  io.seed = sq->seed;
+  return io;
+}
+
+// The K-launch form of the eight rollout calls (per-robot parameters, layout 2, a carve that does not fit). Per step:
 // the act launch (closed loop), the obs_prev row (auto-reset), the single step and its record launch; then, for the
 // auto-reset, the reset mask and counts and the reset of the ended envs with their observation
 // (asvrl_env_reset_observe, or the two launches where that call does not apply). pi null: the open loop, the actions
-// out of ro; dq instead of pi: DQN_Policy's act launch (asvrl_dqn_act) in the Actor's place. ar null: a plain call, which alone can hold ended envs (hold_done: env_checks refuses it with ar).
+// out of ro; dq instead of pi: DQN_Policy's act launch (asvrl_dqn_act) in the Actor's place; sq: SAC's
+// (asvrl_sac_act, its eps_out and, when deterministic, its zero eps_in behind the actions in the scratch). ar null: a plain call, which alone can hold ended envs (hold_done: env_checks refuses it with ar).
 static int rollout_fallback(const char* who, const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                             const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi, const AsvDqnPolicy* dq,
-                            const AsvAutoReset* ar, const AsvEnvLaunch* launch, void* stream) {
+                            const AsvSacPolicy* sq, const AsvAutoReset* ar, const AsvEnvLaunch* launch, void* stream) {
   hipStream_t st = as_stream(stream);
-  const bool closed = pi != nullptr || dq != nullptr;
-  const float* pol_obs = dq != nullptr ? dq->obs_in : (pi != nullptr ? pi->obs_in : nullptr);
-  const int64_t* pol_step = dq != nullptr ? dq->step_dev : (pi != nullptr ? pi->step_dev : nullptr);
-  double* pol_actions = dq != nullptr ? dq->actions : (pi != nullptr ? pi->actions : nullptr);
+  const bool closed = pi != nullptr || dq != nullptr || sq != nullptr;
+  const float* pol_obs = dq != nullptr ? dq->obs_in : (sq != nullptr ? sq->obs_in : (pi != nullptr ? pi->obs_in : nullptr));
+  const int64_t* pol_step = dq != nullptr ? dq->step_dev : (sq != nullptr ? sq->step_dev : (pi != nullptr ? pi->step_dev : nullptr));
+  double* pol_actions = dq != nullptr ? dq->actions : (sq != nullptr ? sq->actions : (pi != nullptr ? pi->actions : nullptr));
   const int E = state->n_envs, R = state->max_robots;
   const size_t NT = static_cast<size_t>(E) * R;
   const size_t noise_row = NT * (static_cast<size_t>(state->max_obs) + R) * 5;
@@ -2240,7 +2357,11 @@ static int rollout_fallback(const char* who, const AsvParams* params, const AsvE
   const unsigned qgrid = (static_cast<unsigned>(NT) * (ASVRL_OBS_DIM / 4) + kBlock - 1) / kBlock;
   // stream-ordered scratch: the actions [NT][2] f64 and the act launch's step count (closed loop), then the reset
   // mask [E] (auto-reset); hold_done's mask [E] is an allocation of its own
-  const size_t act_bytes = closed ? sizeof(double) * 2 * NT + sizeof(int64_t) : 0;
+  // (SAC: eps_out [NT][2] f32 and, when deterministic, the zero eps_in [NT][2] f32 behind the step count)
+  const size_t pol_bytes = closed ? sizeof(double) * 2 * NT + sizeof(int64_t) : 0;
+  const size_t eps_bytes = sq != nullptr ? sizeof(float) * 2 * NT : 0;
+  const bool zero_eps = sq != nullptr && sq->deterministic != 0;
+  const size_t act_bytes = pol_bytes + eps_bytes * (zero_eps ? 2 : 1);
   const size_t scratch_bytes = act_bytes + (ar != nullptr ? E : 0);
   unsigned char* scratch = nullptr;
   if (scratch_bytes != 0 && hipMallocAsync(reinterpret_cast<void**>(&scratch), scratch_bytes, st) != hipSuccess)
@@ -2248,7 +2369,10 @@ static int rollout_fallback(const char* who, const AsvParams* params, const AsvE
   double* act = reinterpret_cast<double*>(scratch);
   int64_t* step = closed ? reinterpret_cast<int64_t*>(act + 2 * NT) : nullptr;
   uint8_t* rmask = ar != nullptr ? scratch + act_bytes : nullptr;
+  float* eps_out = sq != nullptr ? reinterpret_cast<float*>(scratch + pol_bytes) : nullptr;
+  float* eps_zero = zero_eps ? eps_out + 2 * NT : nullptr;
   int rc = 0;
+  if (eps_zero != nullptr && hipMemsetAsync(eps_zero, 0, eps_bytes, st) != hipSuccess) rc = check_launch(who);
   uint8_t* hold_mask = nullptr;
   if (ro->hold_done) {
     if (hipMallocAsync(reinterpret_cast<void**>(&hold_mask), E, st) != hipSuccess)
@@ -2278,6 +2402,9 @@ static int rollout_fallback(const char* who, const AsvParams* params, const AsvE
       if (dq != nullptr) {
         const AsvDqnActIO io = dqn_act_io(dq, obs_t, NT, act, step);
         rc = asvrl_dqn_act(&dq->w, &io, stream);
+      } else if (sq != nullptr) {
+        const AsvSacActIO io = sac_act_io(sq, obs_t, NT, act, eps_zero, eps_out, step);
+        rc = asvrl_sac_act(&sq->w, &io, stream);
       } else {
         const AsvMlpIO io = act_io(pi, obs_t, NT, act, step);
         rc = asvrl_actor_forward(&pi->w, &io, atile::MLP_ACT, stream);
@@ -2322,25 +2449,30 @@ static int rollout_fallback(const char* who, const AsvParams* params, const AsvE
   return rc;
 }
 
-// The six rollout calls: check, plan, zero the counts the window adds to, then the one launch or the fallback.
-// pi or dq: the closed loop under the Actor or DQN_Policy (ro->actions is null then); ar: the auto-reset (Philox noise only: no recorded rows).
+// The eight rollout calls: check, plan, zero the counts the window adds to, then the one launch or the fallback.
+// pi, dq or sq: the closed loop under the Actor, DQN_Policy or SAC's sampled actor (ro->actions is null then); ar: the auto-reset (Philox noise only: no recorded rows).
 static int rollout_call(const char* who, unsigned kind, const AsvParams* params, const AsvEnvState* state,
                         const AsvStepCtl* ctl, const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi,
-                        const AsvDqnPolicy* dq, const AsvAutoReset* ar, const AsvEnvLaunch* launch, void* stream) {
-  if (int rc = env_checks(who, kind, params, state, nullptr, nullptr, ctl, out, ro, pi, dq, ar, launch)) return rc;
+                        const AsvDqnPolicy* dq, const AsvSacPolicy* sq, const AsvAutoReset* ar,
+                        const AsvEnvLaunch* launch, void* stream) {
+  if (int rc = env_checks(who, kind, params, state, nullptr, nullptr, ctl, out, ro, pi, dq, sq, ar, launch)) return rc;
   if (state->n_envs == 0) return 0;
   EnvPlan P;
-  if (int rc = env_plan(who, state, ctl, launch, pi != nullptr || dq != nullptr, ar != nullptr, &P)) return rc;
+  if (int rc = env_plan(who, state, ctl, launch, pi != nullptr || dq != nullptr || sq != nullptr, ar != nullptr, &P,
+                        sq != nullptr ? sizeof(sactile::SacHeadLds) : 0))
+    return rc;
   hipStream_t st = as_stream(stream);
   if (ro->steps_run != nullptr && hipMemsetAsync(ro->steps_run, 0, sizeof(int32_t) * state->n_envs, st) != hipSuccess)
     return check_launch(who);
   if (ar != nullptr && ar->resets != nullptr &&
       hipMemsetAsync(ar->resets, 0, sizeof(int32_t) * state->n_envs, st) != hipSuccess)
     return check_launch(who);
-  if (!P.fused) return rollout_fallback(who, params, state, ctl, out, ro, pi, dq, ar, launch, stream);
+  if (!P.fused) return rollout_fallback(who, params, state, ctl, out, ro, pi, dq, sq, ar, launch, stream);
   const PairsArgs k{*params, *state, *ctl, *out, ro->actions, ar != nullptr ? nullptr : ro->noise, P.pl.epb, 0};
   if (dq != nullptr && ar != nullptr) return launch_groups(who, P, DqnRolloutArArgs{k, *ro, *dq, *ar, P.ar_off}, st);
   if (dq != nullptr) return launch_groups(who, P, DqnRolloutArgs{k, *ro, *dq}, st);
+  if (sq != nullptr && ar != nullptr) return launch_groups(who, P, SacRolloutArArgs{k, *ro, *sq, *ar, P.ar_off}, st);
+  if (sq != nullptr) return launch_groups(who, P, SacRolloutArgs{k, *ro, *sq}, st);
   if (pi != nullptr && ar != nullptr) return launch_groups(who, P, PolicyArArgs{k, *ro, *pi, *ar, P.ar_off}, st);
   if (ar != nullptr) return launch_groups(who, P, RolloutArArgs{k, *ro, *ar, P.ar_off}, st);
   if (pi != nullptr) return launch_groups(who, P, PolicyArgs{k, *ro, *pi}, st);
@@ -2350,15 +2482,15 @@ static int rollout_call(const char* who, unsigned kind, const AsvParams* params,
 extern "C" int asvrl_env_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                  const AsvStepOut* out, const AsvRollout* ro, const AsvEnvLaunch* launch,
                                  void* stream) {
-  return rollout_call("asvrl_env_rollout", kRollout, params, state, ctl, out, ro, nullptr, nullptr, nullptr, launch,
-                      stream);
+  return rollout_call("asvrl_env_rollout", kRollout, params, state, ctl, out, ro, nullptr, nullptr, nullptr, nullptr,
+                      launch, stream);
 }
 
 extern "C" int asvrl_policy_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                     const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi,
                                     const AsvEnvLaunch* launch, void* stream) {
   return rollout_call("asvrl_policy_rollout", kRollout | kClosedLoop, params, state, ctl, out, ro, pi, nullptr, nullptr,
-                      launch, stream);
+                      nullptr, launch, stream);
 }
 
 extern "C" int64_t asvrl_policy_struct_size(void) { return sizeof(AsvPolicy); }
@@ -2366,32 +2498,48 @@ extern "C" int64_t asvrl_policy_struct_size(void) { return sizeof(AsvPolicy); }
 extern "C" int asvrl_env_rollout_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                     const AsvStepOut* out, const AsvRollout* ro, const AsvAutoReset* ar,
                                     const AsvEnvLaunch* launch, void* stream) {
-  return rollout_call("asvrl_env_rollout_ar", kRollout | kAutoReset, params, state, ctl, out, ro, nullptr, nullptr, ar,
-                      launch, stream);
+  return rollout_call("asvrl_env_rollout_ar", kRollout | kAutoReset, params, state, ctl, out, ro, nullptr, nullptr, nullptr,
+                      ar, launch, stream);
 }
 
 extern "C" int asvrl_policy_rollout_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                        const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi,
                                        const AsvAutoReset* ar, const AsvEnvLaunch* launch, void* stream) {
   return rollout_call("asvrl_policy_rollout_ar", kRollout | kClosedLoop | kAutoReset, params, state, ctl, out, ro, pi,
-                      nullptr, ar, launch, stream);
+                      nullptr, nullptr, ar, launch, stream);
 }
 
 extern "C" int asvrl_dqn_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                  const AsvStepOut* out, const AsvRollout* ro, const AsvDqnPolicy* pi,
                                  const AsvEnvLaunch* launch, void* stream) {
   return rollout_call("asvrl_dqn_rollout", kRollout | kClosedLoop | kDqnPolicy, params, state, ctl, out, ro, nullptr, pi,
-                      nullptr, launch, stream);
+                      nullptr, nullptr, launch, stream);
 }
 
 extern "C" int asvrl_dqn_rollout_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                     const AsvStepOut* out, const AsvRollout* ro, const AsvDqnPolicy* pi,
                                     const AsvAutoReset* ar, const AsvEnvLaunch* launch, void* stream) {
   return rollout_call("asvrl_dqn_rollout_ar", kRollout | kClosedLoop | kAutoReset | kDqnPolicy, params, state, ctl, out,
-                      ro, nullptr, pi, ar, launch, stream);
+                      ro, nullptr, pi, nullptr, ar, launch, stream);
 }
 
 extern "C" int64_t asvrl_dqn_policy_struct_size(void) { return sizeof(AsvDqnPolicy); }
+
+extern "C" int asvrl_sac_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                                 const AsvStepOut* out, const AsvRollout* ro, const AsvSacPolicy* pi,
+                                 const AsvEnvLaunch* launch, void* stream) {
+  return rollout_call("asvrl_sac_rollout", kRollout | kClosedLoop | kSacPolicy, params, state, ctl, out, ro, nullptr,
+                      nullptr, pi, nullptr, launch, stream);
+}
+
+extern "C" int asvrl_sac_rollout_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                                    const AsvStepOut* out, const AsvRollout* ro, const AsvSacPolicy* pi,
+                                    const AsvAutoReset* ar, const AsvEnvLaunch* launch, void* stream) {
+  return rollout_call("asvrl_sac_rollout_ar", kRollout | kClosedLoop | kAutoReset | kSacPolicy, params, state, ctl, out,
+                      ro, nullptr, nullptr, pi, ar, launch, stream);
+}
+
+extern "C" int64_t asvrl_sac_policy_struct_size(void) { return sizeof(AsvSacPolicy); }
 
 extern "C" int64_t asvrl_autoreset_struct_size(void) { return sizeof(AsvAutoReset); }
 

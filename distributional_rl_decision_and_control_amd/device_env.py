@@ -268,7 +268,7 @@ class DeviceEnvBatch:
     def policy_rollout(self, pack, K, obs_in, *, noise=None, keep=("reward", "done", "info"), hold_done=False,
                        step_dev=None, eps=(1.0, 1.0, 1.0, 0.0, 0.0), policy_seed=0, trainer_deactivate=False, seed=0,
                        counter=0, counter_dev=None, gamma=0.0, env_mask=None, obs=None, obj_cnt=None,
-                       fast_noise=False, launch=None, stream=None, auto_reset=None):
+                       fast_noise=False, launch=None, stream=None, auto_reset=None, deterministic=False):
         """asvrl_policy_rollout: K closed-loop steps in one launch -- the AC-IQN Actor of `pack` (an MlpPack of
         kind "actor") acts on every robot row and the env steps on its actions, bit for bit the K rounds of
         fused_mlp.actor_act(pack, obs, act64, step, *eps, policy_seed) at step = step_dev + t followed by
@@ -283,11 +283,20 @@ class DeviceEnvBatch:
         next step, and "obs_prev" records the rows it acted on at every step (obs_in comes from this call's own).
         A fused_dqn.DqnPack (DQN_Policy; also an MlpPack of kind "actor") goes to asvrl_dqn_rollout /
         asvrl_dqn_rollout_ar instead: the rounds are fused_dqn.dqn_act(pack, obs, act64, step, *eps, policy_seed)
-        and step(act64, is_continuous=False, ...), and "actions" holds (action index, 0.0)."""
-        from .fused_dqn import DqnPack   # (fused_dqn imports nothing from this module)
+        and step(act64, is_continuous=False, ...), and "actions" holds (action index, 0.0).
+        A fused_sac.SacActorPack (SAC's sampled actor; also an MlpPack of kind "actor") goes to asvrl_sac_rollout /
+        asvrl_sac_rollout_ar: the rounds are fused_sac.sac_act(pack, obs, act64, eps_out, step, *eps, policy_seed)
+        -- the action noise drawn in the kernel on (global row, step, policy_seed) -- followed by step(act64, ...).
+        deterministic=True (a SacActorPack only; ValueError otherwise): the mean action, the rounds'
+        sac_act(..., eps_in=zeros); nothing is drawn for the sample, the epsilon schedule still applies."""
+        from .fused_dqn import DqnPack   # (fused_dqn and fused_sac import nothing from this module)
+        from .fused_sac import SacActorPack
         K, NT = int(K), self.n_envs * self.max_robots
         assert pack.kind == "actor"
-        dqn = isinstance(pack, DqnPack)
+        dqn, sac = isinstance(pack, DqnPack), isinstance(pack, SacActorPack)
+        if deterministic and not sac:
+            raise ValueError("policy_rollout: deterministic=True is the sampled actor's mean action (a SacActorPack); "
+                             "the Actor and DQN_Policy have no sample to switch off")
         assert obs_in.dtype == torch.float32 and obs_in.is_contiguous() and tuple(obs_in.shape) == (NT, OBS_DIM)
         if step_dev is not None:
             assert step_dev.dtype == torch.int64 and step_dev.numel() >= 1
@@ -297,15 +306,18 @@ class DeviceEnvBatch:
                                obs=obs, obj_cnt=obj_cnt, fast_noise=fast_noise, launch=launch, auto_reset=auto_reset)
         if b.ar is not None:
             b.ar.obs_in = None
-        pi = _abi.AsvDqnPolicy() if dqn else _abi.AsvPolicy()
-        pi.w = pack.dw if dqn else pack.w
+        pi = _abi.AsvDqnPolicy() if dqn else (_abi.AsvSacPolicy() if sac else _abi.AsvPolicy())
+        pi.w = pack.dw if dqn else (pack.sw if sac else pack.w)
+        if sac:
+            pi.deterministic = int(bool(deterministic))
         pi.obs_in = obs_in.data_ptr()
         pi.step_dev = step_dev.data_ptr() if step_dev is not None else None
         (pi.eps_steps_per_count, pi.eps_total, pi.eps_fraction, pi.eps_initial,
          pi.eps_final) = (float(v) for v in eps)
         pi.seed = int(policy_seed) & 0xFFFFFFFFFFFFFFFF
         pi.actions = b.rec["actions"].data_ptr() if "actions" in b.rec else None
-        return self._rollout_call(b, pack.L, "asvrl_dqn_rollout" if dqn else "asvrl_policy_rollout", [C.byref(pi)], stream)
+        name = "asvrl_dqn_rollout" if dqn else ("asvrl_sac_rollout" if sac else "asvrl_policy_rollout")
+        return self._rollout_call(b, pack.L, name, [C.byref(pi)], stream)
 
     def reset(self, cfg, env_mask=None, seed=0, counter=0, counter_dev=None, stream=None):
         st = self.state_struct()

@@ -24,6 +24,11 @@ Fifteen launches from given rows, sixteen with the replay draw; no host synchron
 is given by the caller (eps_target / eps_local, the parity tests) or drawn in the kernels by Philox on the device
 learn counter, so nothing depends on the host RNG and the update is capturable in a HIP graph.
 
+The closed-loop windows (csrc/asvrl_env.hip, asvrl_sac_rollout / asvrl_sac_rollout_ar) run act_sac inside the env
+kernel from a SacActorPack: the head, its noise and its sample live in csrc/asvrl_sac_tile.h, which both files
+include, so a row's action does not depend on which kernel computed it (FusedSACState.window_pack,
+DeviceEnvBatch.policy_rollout(..., deterministic=False), DeviceEvaluator.run(..., policy_seed=0, deterministic=False)).
+
 Arithmetic: bf16 MFMA operands with f32 accumulation, f32 master weights / Adam, the head and the sample in f32
 (operands="f32": the same kernels from libasvrl_f32.so, the parity build).
 """
@@ -144,8 +149,10 @@ def _arena_floats(L, B, layers, vecs, small=False):
 class FusedSACState:
     """Packs and buffers of the fused SAC update (allocated once, pointer-stable for graph replay).
     operands="f32": every kernel from libasvrl_f32.so (the parity build; the optimisers must be FusedAdam of the
-    same operands). double_actor (the batched loop): two actor image sets, as FusedDDPGState. The closed-loop
-    windows do not take a sampled head: policy_pack and actor_pack are None."""
+    same operands). double_actor (the batched loop): two actor image sets, as FusedDDPGState. window_pack (the local
+    actor's SacActorPack) is what the closed-loop windows and the device evaluation take
+    (DeviceEnvBatch.policy_rollout, DeviceEvaluator.run, VecTrainer._collect_window); policy_pack and actor_pack stay
+    None, so VecTrainer.policy_pack(), collect, greedy_episodes and evaluate still refuse a SAC trainer."""
 
     policy_pack = actor_pack = None
 
@@ -157,7 +164,7 @@ class FusedSACState:
         self.local = [DdpgCriticPack(policy_local.critic_1, operands), DdpgCriticPack(policy_local.critic_2, operands)]
         self.target = [DdpgCriticPack(policy_target.critic_1, operands),
                        DdpgCriticPack(policy_target.critic_2, operands)]
-        self.actor = SacActorPack(policy_local.actor, operands, double=double_actor)
+        self.actor = self.window_pack = SacActorPack(policy_local.actor, operands, double=double_actor)
         self.target_actor = SacActorPack(policy_target.actor, operands)
         self.L = self.actor.L
         bf = dict(dtype=_abi.operand_dtype(operands), device=dev)

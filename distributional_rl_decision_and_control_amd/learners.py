@@ -6,6 +6,10 @@ buffers) is built. The Fused*State classes share one surface, so neither front e
     learn(tr, state, guard, actor_wait, target_wait, actor_done)           VecTrainer's sample + update
     target_changed() / refresh_local()                                     re-pack the target / local weight images
     policy_pack, actor_pack                                                 what the closed-loop windows take, or None
+
+FusedSACState also has window_pack, its local actor's SacActorPack: DeviceEnvBatch.policy_rollout, DeviceEvaluator.run
+and VecTrainer._collect_window take it (the sampled head runs inside the env kernel), while its policy_pack and
+actor_pack stay None, so VecTrainer's own policy_pack() / collect / greedy_episodes / evaluate still refuse SAC.
 """
 from dataclasses import dataclass
 from typing import Callable, Optional
@@ -88,7 +92,8 @@ LEARNERS = {
     "DDPG": Learner(
         DDPG_Policy, "fused_ddpg", lambda p, B, N: fused_ddpg.supported(p, B), _ddpg_state,
         "DDPG learner kernels: B={B} (a positive multiple of 32)", actor_critic=True),
-    # SAC_Policy: the Actor's trunk under a sampled head and two DDPG critics (fused_sac.py); the batched loop only
+    # SAC_Policy: the Actor's trunk under a sampled head and two DDPG critics (fused_sac.py); the batched loop, and the
+    # closed-loop windows / device evaluation through fused_sac.window_pack
     "SAC": Learner(
         SAC_Policy, "fused_sac", lambda p, B, N: fused_sac.supported(p, B), _sac_state,
         "SAC learner kernels: B={B} (a positive multiple of 32)", actor_critic=True, twin=True),

@@ -9,15 +9,16 @@ per-robot bookkeeping in Python. DeviceEvaluator keeps the same episodes in Devi
     state, flags, counts, obstacles, cores; set_batch_params for the launch parameters) is loaded into one batch;
     a device copy of that state is kept, so every later evaluation restores by copy;
   * an evaluation is the observation pass and then closed-loop windows of `chunk` steps, one launch each
-    (DeviceEnvBatch.policy_rollout with hold_done, the greedy Actor of an MlpPack or the greedy DQN_Policy of a
-    DqnPack), or, teacher-forced, open-loop windows over a caller's action table (DeviceEnvBatch.rollout);
+    (DeviceEnvBatch.policy_rollout with hold_done, the greedy Actor of an MlpPack, the greedy DQN_Policy of a
+    DqnPack or SAC's actor of a SacActorPack, sampled as act_sac samples or its mean action), or, teacher-forced, open-loop windows over a caller's action table (DeviceEnvBatch.rollout);
   * behind every window one asvrl_eval_metrics launch folds the window's records into the evaluation's carried
     state by trainer.py:286-303: discounted return, time, energy, deactivation, and the evaluation's end rule (the
     step limit, ANY collision, or every robot deactivated). Its `alive` output is the next window's env_mask;
   * one copy at the end brings the per-robot sums, outcomes and lengths to the host.
 
 Perception noise in the closed loop is the rollout's Philox stream (seed, env, robot, step; f32 draws), not each
-robot's numpy RandomState: the results agree with evaluate_configs in distribution, and exactly under teacher
+robot's numpy RandomState, and SAC's action noise is Philox + Box-Muller on (row, step, policy_seed + group), not
+torch's generator: the results agree with evaluate_configs in distribution, and exactly under teacher
 forcing with the noise given (tests/test_device_eval_gpu.py). Observation, action and trajectory histories are not
 kept.
 """
@@ -30,6 +31,7 @@ from .. import _abi
 from ..device_env import DeviceEnvBatch
 from ..envs.marinenav.env import MarineNavEnv3, set_batch_params
 from ..fused_dqn import DqnPack
+from ..fused_sac import SacActorPack
 
 RECORDS = ("reward", "info", "rs")
 OBS_COUNTER = 0x80000000   # the observation pass's Philox counter (VecMarineNavEnv.reset's); step t draws at t
@@ -197,9 +199,11 @@ class DeviceEvaluator:
 
     @torch.no_grad()
     def run(self, pack=None, *, actions=None, noise=None, obs_noise=None, seed=0, episode_limit=1000, sync=True,
-            is_continuous=None):
+            is_continuous=None, policy_seed=0, deterministic=False):
         """One evaluation of every config. pack: the Actor's MlpPack or DQN's DqnPack, greedy in closed-loop
-        windows; or actions: a [T, NT, 2] f64 table per group (a tensor when there is one group, else a list)
+        windows, or SAC's SacActorPack, which samples its action as act_sac does in evaluation too (group g draws
+        under policy_seed + g: rows are batch-local, so two groups share no draws) or, with deterministic=True (a
+        ValueError for any other pack), takes its mean action; or actions: a [T, NT, 2] f64 table per group (a tensor when there is one group, else a list)
         applied open loop, with noise ([T, NT, O + R, 5] f64 per group) or the Philox stream. is_continuous: what
         the table's rows are -- True (also None, the default) thrust commands, False column 0 is the action index;
         with a pack it follows the pack (None) and a value that contradicts it is a ValueError. obs_noise: the observation pass's explicit
@@ -215,6 +219,8 @@ class DeviceEvaluator:
         if pack is not None and is_continuous is not None and bool(is_continuous) == isinstance(pack, DqnPack):
             raise ValueError("run: is_continuous=%s does not match the pack (a DqnPack picks discrete actions, the "
                              "Actor continuous ones)" % bool(is_continuous))
+        if deterministic and not isinstance(pack, SacActorPack):
+            raise ValueError("run: deterministic=True is the mean action of SAC's sampled actor (a SacActorPack)")
         is_continuous = True if is_continuous is None else bool(is_continuous)
         episode_limit = int(episode_limit)
         actions = self._per_group(actions, "actions")
@@ -235,7 +241,7 @@ class DeviceEvaluator:
                     grp.step.fill_(t0)
                     b.policy_rollout(pack, k, b.obs, keep=rec, hold_done=True, trainer_deactivate=True,
                                      step_dev=grp.step, env_mask=st["alive"], seed=seed + g, counter=t0,
-                                     fast_noise=True)
+                                     fast_noise=True, policy_seed=policy_seed + g, deterministic=deterministic)
                 else:
                     nz = noise[g]
                     b.rollout(actions[g][t0:t0 + k], None if nz is None else nz[t0:t0 + k], keep=rec,

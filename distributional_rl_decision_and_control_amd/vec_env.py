@@ -125,7 +125,7 @@ class VecMarineNavEnv:
         return rec
 
     def policy_rollout(self, pack, K, hold_done=True, keep=("reward", "done", "info"), eps=(1.0, 1.0, 1.0, 0.0, 0.0),
-                       policy_seed=0, env_mask=None, auto_reset=False, count=True):
+                       policy_seed=0, env_mask=None, auto_reset=False, count=True, deterministic=False):
         """K closed-loop steps in one launch (DeviceEnvBatch.policy_rollout): the AC-IQN Actor of `pack` acts on
         obs_cur and every next observation -- the values of K rounds of fused_mlp.actor_act(pack, obs_cur, actions,
         counter, *eps, policy_seed); step(actions); advance_device(), with the last step's observation in obs_next /
@@ -133,7 +133,9 @@ class VecMarineNavEnv:
         counter (the default is greedy). The contract is otherwise rollout()'s. Returns the kept per-step records
         (keep also takes "actions"). auto_reset, count: as rollout()'s (the Actor acts on a reset env's reset
         observation at the next step). A fused_dqn.DqnPack drives an env built with is_continuous=False the same
-        way (fused_dqn.dqn_act in the Actor's place; "actions" holds (action index, 0.0))."""
+        way (fused_dqn.dqn_act in the Actor's place; "actions" holds (action index, 0.0)). A fused_sac.SacActorPack
+        drives a continuous env with fused_sac.sac_act in the Actor's place, its noise drawn in the kernel on
+        (row, step counter, policy_seed); deterministic=True (that pack only) takes the mean action instead."""
         from .fused_dqn import DqnPack
         if isinstance(pack, DqnPack):
             if self.is_continuous:
@@ -147,7 +149,7 @@ class VecMarineNavEnv:
                                         eps=eps, policy_seed=policy_seed, trainer_deactivate=True, seed=self.seed,
                                         counter=0, counter_dev=self.counter, gamma=self.gamma, env_mask=env_mask,
                                         obs=self.obs_next, obj_cnt=self.cnt_next, fast_noise=True,
-                                        launch=self._launch(), auto_reset=ar)
+                                        launch=self._launch(), auto_reset=ar, deterministic=deterministic)
         if count:
             self.counter += int(K)
         return rec

@@ -302,11 +302,17 @@ class VecTrainer:
         if self.learner.actor_pack is None or self.per is not None:
             raise NotImplementedError("collect runs the AC-IQN / DDPG actor and pushes into the uniform ring; IQN, "
                                       "Rainbow and DQN act inside their own kernels")
+        return self._collect_window(self.learner.actor_pack, K, snap)
+
+    @torch.no_grad()
+    def _collect_window(self, pack, K, snap=None):
+        """collect()'s two launches under `pack`: the learner's actor_pack, or a SAC trainer's
+        fused_sac.window_pack, whose ring rows are DDPG's (K calls of rollout(), bit for bit, there too)."""
         K = int(K)
         buf = self._collect_buffers(K)
         buf["obj_cnt"].fill_(-1)   # a row no env took is never pushed
         keep = {k: buf[k] for k in ("obs", "obs_prev", "obj_cnt", "reward", "done", "actions", "steps_run")}
-        rec = self.env.policy_rollout(self.learner.actor_pack, K, hold_done=False, keep=keep,
+        rec = self.env.policy_rollout(pack, K, hold_done=False, keep=keep,
                                       eps=(self.E, self.total_timesteps, self.exploration_fraction, self.initial_eps,
                                            self.final_eps), policy_seed=self.seed + 4242,
                                       auto_reset=dict(pushed=buf["pushed"], resets=buf["resets"]), count=False)

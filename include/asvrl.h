@@ -1397,6 +1397,40 @@ int64_t asvrl_sac_actor_struct_size(void);
 int64_t asvrl_sac_grad_struct_size(void);
 int64_t asvrl_sac_actor_grad_struct_size(void);
 
+/* ---------------------------------------------------------------- closed-loop rollout windows for SAC
+ * New entry points only: the ABI version stays 29. */
+
+/* SAC's sampled actor driving asvrl_sac_rollout. */
+typedef struct AsvSacPolicy {
+  AsvSacActorWeights w;           /* the actor's images and its f32 head */
+  const float* obs_in;            /* [NT][ASVRL_OBS_DIM] the observation step 0 acts on (16-byte aligned) */
+  const int64_t* step_dev;        /* epsilon schedule, exploration and noise key: step = *step_dev + t (NULL: 0 + t) */
+  double eps_steps_per_count, eps_total, eps_fraction, eps_initial, eps_final;   /* as AsvSacActIO's */
+  uint64_t seed;                  /* Philox key of the exploration draws and of the action noise */
+  double* actions;                /* optional record [K][NT][2]: the action every robot slot was given */
+  int32_t deterministic;          /* != 0: eps = 0, nothing drawn: z = mu, the mean action (the epsilon schedule
+                                     still applies) */
+  int32_t _pad0;
+} AsvSacPolicy;
+
+/* asvrl_policy_rollout and asvrl_policy_rollout_ar under SAC's actor: for t < ro->n_steps, asvrl_sac_act on every
+ * robot row (the same MFMA chain and f32 head, the noise of stream "act" keyed by the global row, step =
+ * *step_dev + t and pi->seed, the same exploration draw) and then the env step on the action -- bit for bit the 2 K
+ * launches of asvrl_sac_act (eps_in NULL; an all-zero eps_in with pi->deterministic) and asvrl_env_step_ex (and,
+ * with the auto-reset, asvrl_env_reset_observe) they replace. The contract is the two Actor calls' word for word,
+ * except: pi->w.head and pi->w.bhead must be non-null. The trunk's images are staged into LDS as the Actor's are,
+ * and the head's 2 KB beside them. The caller's step counter is only read. Per-robot parameters, layout 2 and an
+ * env group whose arrays do not fit the LDS beside the weights run K x (asvrl_sac_act into a stream-ordered
+ * scratch, the single step, the record launches and, with the auto-reset, the reset launches) instead. */
+int asvrl_sac_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                      const AsvStepOut* last, const AsvRollout* ro, const AsvSacPolicy* pi,
+                      const AsvEnvLaunch* launch /* NULL: automatic */, void* stream);
+int asvrl_sac_rollout_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                         const AsvStepOut* last, const AsvRollout* ro, const AsvSacPolicy* pi,
+                         const AsvAutoReset* ar, const AsvEnvLaunch* launch /* NULL: automatic */, void* stream);
+/* sizeof(AsvSacPolicy) as compiled. */
+int64_t asvrl_sac_policy_struct_size(void);
+
 /* ---------------------------------------------------------------- misc */
 const char* asvrl_last_error(void);
 int asvrl_abi_version(void);
