@@ -134,6 +134,17 @@ class AsvIqnIO(C.Structure):
                 ("eps_initial", _D), ("eps_final", _D), ("seed", _U64)]
 
 
+class AsvIqnActEx(C.Structure):
+    _fields_ = [("cvar", C.c_float), ("robots_per_env", _I32), ("step_add", _I64), ("act_pair", _VP),
+                ("rec_row", _VP), ("env_mask", _VP), ("qmean_out", _VP), ("ld_q", _I64)]
+
+
+class AsvIqnPolicy(C.Structure):
+    _fields_ = [("w", AsvCriticWeights), ("head", AsvIqnHead), ("obs_in", _VP), ("step_dev", _VP),
+                ("eps_steps_per_count", _D), ("eps_total", _D), ("eps_fraction", _D), ("eps_initial", _D),
+                ("eps_final", _D), ("seed", _U64), ("actions", _VP), ("cvar", C.c_float), ("_pad0", _I32)]
+
+
 MAX_SUM_SEGS = 24
 
 
@@ -490,6 +501,16 @@ EXPORTS = [
                                        C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvSacPolicy),
                                        C.POINTER(AsvAutoReset), C.POINTER(AsvEnvLaunch), _VP]),
     ("asvrl_sac_policy_struct_size", _I64, []),
+    ("asvrl_iqn_act_ex", C.c_int, [C.POINTER(AsvCriticWeights), C.POINTER(AsvIqnHead), C.POINTER(AsvIqnIO),
+                                   C.POINTER(AsvIqnActEx), _VP]),
+    ("asvrl_iqn_act_ex_struct_size", _I64, []),
+    ("asvrl_iqn_rollout", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), C.POINTER(AsvStepCtl),
+                                    C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvIqnPolicy),
+                                    C.POINTER(AsvEnvLaunch), _VP]),
+    ("asvrl_iqn_rollout_ar", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), C.POINTER(AsvStepCtl),
+                                       C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvIqnPolicy),
+                                       C.POINTER(AsvAutoReset), C.POINTER(AsvEnvLaunch), _VP]),
+    ("asvrl_iqn_policy_struct_size", _I64, []),
 ]
 
 _libs = {}

@@ -31,6 +31,8 @@
 //              (agent.py:455-468); the output layer's gradient leaves as a one-hot bf16
 //              [R][32] matrix so its weight gradient is one more 32 x 128 MFMA reduction
 //   IQN_ACT    act_iqn (agent.py:227-256): mean over K = 32 taus per state, argmax, epsilon-greedy
+//   IQN_ACT_EX the same pass as the rollout windows launch it (asvrl_iqn_act_ex): taus * cvar, step + step_add,
+//              the (index, 0.0) pair and its masked record row, the action values
 #include "asvrl_common.h"
 #include "asvrl_mfma.h"
 #include "asvrl_lds.h"
@@ -162,9 +164,11 @@ template <int NT> struct CriticWaves { static constexpr int n = NT == 32 ? 8 : 4
 #endif
 template <int MODE, int NT> struct ModeWaves { static constexpr int n = CriticWaves<NT>::n; };
 template <> struct ModeWaves<MODE_IQN_ACT, 32> { static constexpr int n = ASVRL_IQN_ACT_WAVES; };
+template <> struct ModeWaves<MODE_IQN_ACT_EX, 32> { static constexpr int n = ASVRL_IQN_ACT_WAVES; };
 
+// one workgroup of critic_kernel (ex: IQN_ACT_EX's additions, null in every other mode)
 template <int MODE, int NT>
-__global__ __launch_bounds__((ModeWaves<MODE, NT>::n) * 64) void critic_kernel(CriticArgs a) {
+__device__ __forceinline__ void critic_block(const CriticArgs& a, const AsvIqnActEx* ex) {
   constexpr int W = ModeWaves<MODE, NT>::n, S = 32 / NT;
   __shared__ typename LdsOf<MODE>::T L;
   using FT = typename FOf<MODE>::T;
@@ -205,7 +209,7 @@ __global__ __launch_bounds__((ModeWaves<MODE, NT>::n) * 64) void critic_kernel(C
   const bool wout = MODE == MODE_TRAIN && a.acts.wout_part != nullptr;
   float* wsum = wout ? Ws + (threadIdx.x >> 6) * (kH + 1) : nullptr;
   if (tile < tiles) {
-    critic_tile<MODE, NT>(a, L, tile, lane, Fw, Gw, wsum);
+    critic_tile<MODE, NT>(a, L, tile, lane, Fw, Gw, wsum, nullptr, ex);
   } else if (wout) {
     for (int i = lane; i < kH + 1; i += 64) wsum[i] = 0.f;
   }
@@ -219,6 +223,16 @@ __global__ __launch_bounds__((ModeWaves<MODE, NT>::n) * 64) void critic_kernel(C
       a.acts.wout_part[static_cast<size_t>(blockIdx.x) * (kH + 1) + i] = acc;
     }
   }
+}
+
+template <int MODE, int NT>
+__global__ __launch_bounds__((ModeWaves<MODE, NT>::n) * 64) void critic_kernel(CriticArgs a) {
+  critic_block<MODE, NT>(a, nullptr);
+}
+
+// asvrl_iqn_act_ex: IQN_ACT's workgroup (16 waves, one state's 32 taus per wave) with the window's additions
+__global__ __launch_bounds__((ModeWaves<MODE_IQN_ACT_EX, 32>::n) * 64) void iqn_act_ex_kernel(CriticArgs a, AsvIqnActEx x) {
+  critic_block<MODE_IQN_ACT_EX, 32>(a, &x);
 }
 
 int train_b_grid(int tiles) { return (tiles + 7) / 8; }
@@ -454,5 +468,25 @@ extern "C" int asvrl_iqn_act(const AsvCriticWeights* w, const AsvIqnHead* head, 
   if (io->B == 0) return 0;
   return launch(MODE_IQN_ACT, iqn_args(w, head, io), stream);
 }
+
+extern "C" int asvrl_iqn_act_ex(const AsvCriticWeights* w, const AsvIqnHead* head, const AsvIqnIO* io,
+                                const AsvIqnActEx* ex, void* stream) {
+  if (int rc = iqn_validate(w, head, io)) return rc;
+  ASVRL_REQUIRE(ex != nullptr, "asvrl_iqn_act_ex: null ex");
+  ASVRL_REQUIRE(io->N == 32, "asvrl_iqn_act_ex: K = 32 quantile samples per state");
+  ASVRL_REQUIRE((io->act_out || ex->act_pair || ex->rec_row) && (!io->act_out || io->ld_act >= 1) &&
+                    io->eps_total > 0.0 && io->eps_fraction > 0.0,
+                "asvrl_iqn_act_ex: needs act_out with ld_act (or act_pair / rec_row) and the epsilon schedule");
+  ASVRL_REQUIRE(ex->cvar > 0.f && ex->cvar <= 1.f, "asvrl_iqn_act_ex: cvar must be in (0, 1]");
+  ASVRL_REQUIRE(ex->robots_per_env >= 1, "asvrl_iqn_act_ex: robots_per_env must be >= 1");
+  ASVRL_REQUIRE(!ex->qmean_out || ex->ld_q >= head->n_actions, "asvrl_iqn_act_ex: ld_q must cover n_actions");
+  if (io->B == 0) return 0;
+  const CriticArgs a = iqn_args(w, head, io);
+  constexpr int W = ModeWaves<MODE_IQN_ACT_EX, 32>::n;
+  hipLaunchKernelGGL(iqn_act_ex_kernel, dim3((a.B + W - 1) / W), dim3(W * 64), 0, as_stream(stream), a, *ex);
+  return check_launch("asvrl_iqn_act_ex");
+}
+
+extern "C" int64_t asvrl_iqn_act_ex_struct_size(void) { return sizeof(AsvIqnActEx); }
 
 extern "C" int32_t asvrl_critic_wout_groups(int32_t B, int32_t N) { return wout_groups(B, N); }

@@ -12,12 +12,16 @@ namespace {
 namespace ctile {
 
 constexpr int kC = 256, kH = 128, kNcos = 64;
-enum { MODE_FWD = 0, MODE_TRAIN = 1, MODE_ACTOR = 2, MODE_IQN_MAX = 3, MODE_IQN_TRAIN = 4, MODE_IQN_ACT = 5 };
+enum { MODE_FWD = 0, MODE_TRAIN = 1, MODE_ACTOR = 2, MODE_IQN_MAX = 3, MODE_IQN_TRAIN = 4, MODE_IQN_ACT = 5,
+       MODE_IQN_ACT_EX = 6 };
+// IQN_ACT_EX: the window form of IQN_ACT (asvrl_iqn_act_ex): the same tile with AsvIqnActEx's CVaR factor, step
+// offset, action pair / record row and action values; an instantiation of its own, so IQN_ACT's code stays put
+template <int MODE> constexpr bool kAct = MODE == MODE_IQN_ACT || MODE == MODE_IQN_ACT_EX;
 constexpr int kMaxA = ASVRL_IQN_MAX_ACTIONS;
 template <int MODE> constexpr bool kIqn = MODE >= MODE_IQN_MAX;
 template <int MODE> constexpr bool kTrainMode = MODE == MODE_TRAIN || MODE == MODE_IQN_TRAIN;
 // the Wc image sits in LDS for the forward-only modes; the backward modes keep W2^T there
-template <int MODE> constexpr bool kFwdOnly = MODE == MODE_FWD || MODE == MODE_IQN_MAX || MODE == MODE_IQN_ACT;
+template <int MODE> constexpr bool kFwdOnly = MODE == MODE_FWD || MODE == MODE_IQN_MAX || kAct<MODE>;
 // Every wave stages its samples' feature rows in LDS in the prologue (F as bf16 for every mode,
 // G in f32 for the AC-IQN critic modes), computing them from the observation rows / actions when
 // given (the encoders fused into the trunk) or copying F / G. The per-feature reads that follow
@@ -98,12 +102,14 @@ template <int MODE> struct LdsOf { using T = CriticLds; };
 template <> struct LdsOf<MODE_IQN_MAX> { using T = CriticLdsIqn; };
 template <> struct LdsOf<MODE_IQN_TRAIN> { using T = CriticLdsIqn; };
 template <> struct LdsOf<MODE_IQN_ACT> { using T = CriticLdsIqn; };
+template <> struct LdsOf<MODE_IQN_ACT_EX> { using T = CriticLdsIqn; };
 // the staged F rows: f32 copies of the operand-rounded values (no per-use conversion) in the AC-IQN
 // modes; operand-typed in the IQN modes, whose larger LDS image leaves no room for them
 template <int MODE> struct FOf { using T = float; };
 template <> struct FOf<MODE_IQN_MAX> { using T = elem_t; };
 template <> struct FOf<MODE_IQN_TRAIN> { using T = elem_t; };
 template <> struct FOf<MODE_IQN_ACT> { using T = elem_t; };
+template <> struct FOf<MODE_IQN_ACT_EX> { using T = elem_t; };
 static_assert(sizeof(CriticLdsIqn) <= 160 * 1024, "IQN LDS image exceeds the CU's 160 KB");
 
 // The wave's feature rows in LDS for its 32 / NT samples: F (bf16 [S][256]) = observation_processor
@@ -176,14 +182,16 @@ __device__ __forceinline__ void stage_features(const CriticArgs& a, int tile, in
 __device__ __forceinline__ float out_w(const CriticLds& L, int, int m) { return L.wo[m]; }
 __device__ __forceinline__ float out_w(const CriticLdsIqn& L, int ai, int m) { return static_cast<float>(L.wof[ai * kH + m]); }
 
-__device__ __forceinline__ uint64_t act_step(const CriticArgs& a) {
-  return a.step_dev != nullptr ? static_cast<uint64_t>(*a.step_dev) : 0ull;
+// (ex, the window form: *step_dev + ex->step_add, so step t of a window needs no counter of its own)
+__device__ __forceinline__ uint64_t act_step(const CriticArgs& a, const AsvIqnActEx* ex = nullptr) {
+  const uint64_t s = a.step_dev != nullptr ? static_cast<uint64_t>(*a.step_dev) : 0ull;
+  return ex != nullptr ? s + static_cast<uint64_t>(ex->step_add) : s;
 }
 
 // act_iqn's quantile fractions when the caller passes none: uniform [0, 1) per row (calc_cos's
 // torch.rand, IQN_model.py:63), Philox on (row, step)
-__device__ __forceinline__ float act_tau(const CriticArgs& a, int grow) {
-  const uint64_t step = act_step(a);
+__device__ __forceinline__ float act_tau(const CriticArgs& a, int grow, const AsvIqnActEx* ex = nullptr) {
+  const uint64_t step = act_step(a, ex);
   const U4 u = philox4x32_10(U4{static_cast<uint32_t>(grow), static_cast<uint32_t>(step),
                                 static_cast<uint32_t>(step >> 32), 0x1A7u},
                              static_cast<uint32_t>(a.seed), static_cast<uint32_t>(a.seed >> 32));
@@ -193,8 +201,11 @@ __device__ __forceinline__ float act_tau(const CriticArgs& a, int grow) {
 // act_iqn's selection (agent.py:240-250) for the state of this tile (its 32 rows = the K = 32
 // quantile samples): argmax_a of sum_n Q (= K * mean, same argmax; np.argmax's first maximum),
 // then greedy iff random() > eps, else a uniform action.
+// ex (IQN_ACT_EX): also the action values quantiles.mean(dim=1) (the same sums times 1/32, from the lanes that
+// hold them) into ex->qmean_out, the pair (index, 0.0) into ex->act_pair and, for a tile whose env steps
+// (ex->env_mask, one byte per ex->robots_per_env tiles), into ex->rec_row: policy_actions_kernel's copy.
 __device__ __forceinline__ void iqn_act_select(const CriticArgs& a, const CriticLdsIqn& L, const f32x16& ao,
-                                               int tile, int lane) {
+                                               int tile, int lane, const AsvIqnActEx* ex = nullptr) {
   const int h = lane >> 5, A = a.hd.n_actions;
   float best = -__builtin_inff();
   int bi = kMaxA;
@@ -203,6 +214,8 @@ __device__ __forceinline__ void iqn_act_select(const CriticArgs& a, const Critic
     const int m = feat(0, g, h);
     float v = m < A ? ao[g] + L.bo_a[m] : 0.f;
     v = seg_sum<32>(v);   // lanes 31 / 63: the sum over the state's 32 taus
+    if (ex != nullptr && ex->qmean_out != nullptr && (lane & 31) == 31 && m < A)
+      ex->qmean_out[static_cast<int64_t>(tile) * ex->ld_q + m] = v * (1.0f / 32.0f);
     if (m < A && v > best) {
       best = v;
       bi = m;
@@ -213,7 +226,7 @@ __device__ __forceinline__ void iqn_act_select(const CriticArgs& a, const Critic
   if (ob > best || (ob == best && oi < bi)) bi = oi;
   if (lane != 31) return;
   // epsilon: linear schedule of the device step counter (trainer.py:257-264)
-  const uint64_t step = act_step(a);
+  const uint64_t step = act_step(a, ex);
   const double progress = static_cast<double>(step) * a.eps_spc / a.eps_total;
   const double eps = progress < a.eps_fraction
                          ? a.eps_initial + (progress / a.eps_fraction) * (a.eps_final - a.eps_initial)
@@ -226,7 +239,17 @@ __device__ __forceinline__ void iqn_act_select(const CriticArgs& a, const Critic
   if (!(c > eps)) {   // random.choice(np.arange(action_size))
     act = static_cast<int>((static_cast<uint64_t>(u.y >> 8) * static_cast<uint64_t>(A)) >> 24);
   }
-  a.act_out[static_cast<int64_t>(tile) * a.ld_act] = static_cast<double>(act);
+  if (ex == nullptr || a.act_out != nullptr) a.act_out[static_cast<int64_t>(tile) * a.ld_act] = static_cast<double>(act);
+  if (ex == nullptr) return;
+  const int64_t o = 2 * static_cast<int64_t>(tile);
+  if (ex->act_pair != nullptr) {
+    ex->act_pair[o] = static_cast<double>(act);
+    ex->act_pair[o + 1] = 0.0;
+  }
+  if (ex->rec_row != nullptr && (ex->env_mask == nullptr || ex->env_mask[tile / ex->robots_per_env] != 0)) {
+    ex->rec_row[o] = static_cast<double>(act);
+    ex->rec_row[o + 1] = 0.0;
+  }
 }
 
 // acc[mb] += W(mb, ks) B(ks) over ks < KS for MB feature blocks, the weight fragments W (staged in LDS)
@@ -261,16 +284,18 @@ __device__ __forceinline__ void mfma_wrows(f32x16 (&acc)[MB], WF wf, BF bf) {
 
 template <int MODE, int NT, class LT, class FT>
 __device__ __forceinline__ void critic_tile(const CriticArgs& a, const LT& L, int tile, int lane, const FT* Fl,
-                                            const float* Gl, float* wsum = nullptr, const float* tau_tile = nullptr) {
+                                            const float* Gl, float* wsum = nullptr, const float* tau_tile = nullptr,
+                                            const AsvIqnActEx* ex = nullptr) {
   constexpr bool IQN = kIqn<MODE>;
   constexpr bool TRAINM = kTrainMode<MODE>;
   const int r = lane & 31, h = lane >> 5;
   const int grow = tile * 32 + r;
   const int b = grow / NT;
   float tau;
-  if (MODE == MODE_IQN_ACT && a.taus == nullptr) tau = act_tau(a, grow);
+  if (kAct<MODE> && a.taus == nullptr) tau = act_tau(a, grow, ex);
   else if (tau_tile != nullptr) tau = tau_tile[r];   // the tile's taus staged by the caller (LDS)
   else tau = a.taus[grow];
+  if constexpr (MODE == MODE_IQN_ACT_EX) tau = tau * ex->cvar;   // calc_cos's taus * cvar (IQN_model.py:68); * 1.0f is exact
   const FT* Fb = Fl + (b - tile * 32 / NT) * kC;                       // F[b], the wave's LDS row
   const float* Gb = IQN ? nullptr : Gl + (b - tile * 32 / NT) * kH;     // G[b]
   const frag8* WC = kFwdOnly<MODE> ? wimg(L.wc, a.w.wc_frag) : reinterpret_cast<const frag8*>(a.w.wc_frag);
@@ -295,7 +320,7 @@ __device__ __forceinline__ void critic_tile(const CriticArgs& a, const LT& L, in
   // QB of the eight 32-feature blocks per pass: four, or two in the 16-wave IQN_ACT launch, whose 128
   // VGPRs then hold one pass's accumulators beside the packed outputs of the passes before it (the same
   // MFMAs per block in the same k order: bit-identical)
-  constexpr int QB = MODE == MODE_IQN_ACT ? 2 : 4;
+  constexpr int QB = kAct<MODE> ? 2 : 4;
   frag8 cpk[16], hpk[16];
 #pragma unroll
   for (int half = 0; half < 8 / QB; ++half) {
@@ -342,14 +367,14 @@ __device__ __forceinline__ void critic_tile(const CriticArgs& a, const LT& L, in
 
   // ---------------- layer 1: h1 = relu(W1 h0 + b1), h1g = h1 * G[b]
   // in passes of QB1 blocks (two in IQN_ACT, for its 128 VGPRs; same per-block k order: bit-identical)
-  constexpr int QB1 = MODE == MODE_IQN_ACT ? 2 : 4;
+  constexpr int QB1 = kAct<MODE> ? 2 : 4;
   frag8 h1pk[8], gpk[8];
 #pragma unroll
   for (int pass = 0; pass < 4 / QB1; ++pass) {
     f32x16 acc1[QB1];
 #pragma unroll
     for (int q = 0; q < QB1; ++q) acc1[q] = BF ? bias_nat(L.b1, pass * QB1 + q, h) : f32x16{};
-    mfma_wrows<kC / 16, QB1, MODE != MODE_IQN_ACT>(
+    mfma_wrows<kC / 16, QB1, !kAct<MODE>>(
         acc1, [&](int q, int ks) { return W1[((pass * QB1 + q) * 16 + ks) * 64 + lane]; }, [&](int ks) { return hpk[ks]; });
 #pragma unroll
     for (int q = 0; q < QB1; ++q) {
@@ -388,7 +413,7 @@ __device__ __forceinline__ void critic_tile(const CriticArgs& a, const LT& L, in
   f32x16 acc2[4];
 #pragma unroll
   for (int mb = 0; mb < 4; ++mb) acc2[mb] = BF ? bias_nat(L.b2, mb, h) : f32x16{};
-  mfma_wrows<kH / 16, 4, MODE != MODE_IQN_ACT>(acc2, [&](int mb, int ks) { return W2[(mb * 8 + ks) * 64 + lane]; },
+  mfma_wrows<kH / 16, 4, !kAct<MODE>>(acc2, [&](int mb, int ks) { return W2[(mb * 8 + ks) * 64 + lane]; },
                          [&](int ks) { return gpk[ks]; });
   float q;
   int ai = 0;   // IQN_TRAIN: the sample's action
@@ -414,8 +439,8 @@ __device__ __forceinline__ void critic_tile(const CriticArgs& a, const LT& L, in
 #pragma unroll
     for (int ks = 0; ks < kH / 16; ++ks) ao = mfma(L.wo_img[ks * 64 + lane], h2pk[ks], ao);
     const int A = a.hd.n_actions;   // register g of half h holds action feat(0, g, h)
-    if constexpr (MODE == MODE_IQN_ACT) {
-      iqn_act_select(a, L, ao, tile, lane);
+    if constexpr (kAct<MODE>) {
+      iqn_act_select(a, L, ao, tile, lane, ex);
       return;
     }
     if constexpr (MODE == MODE_IQN_MAX) {

@@ -2013,13 +2013,13 @@ PairLaunch pair_launch(int R, int O, int n_envs, int blk_req, int epb_req, int v
 
 using namespace asvrl;
 
-// ------------------------------------------------------------------ the env step and its eight rollout calls
+// ------------------------------------------------------------------ the env step and its ten rollout calls
 // One host path. Each call is: env_checks (its arguments), env_plan (the launch shape, and whether the
 // pair-parallel kernel is taken), then launch_groups (that kernel) or, for the rollouts, rollout_fallback (K single
 // steps).
 
 // the groups of checks a call takes beyond the step's own
-enum : unsigned { kRollout = 1, kClosedLoop = 2, kAutoReset = 4, kDqnPolicy = 8, kSacPolicy = 16 };   // (kDqnPolicy, kSacPolicy: with kClosedLoop)
+enum : unsigned { kRollout = 1, kClosedLoop = 2, kAutoReset = 4, kDqnPolicy = 8, kSacPolicy = 16, kIqnPolicy = 32 };   // (kDqnPolicy, kSacPolicy, kIqnPolicy: with kClosedLoop)
 
 static int env_fail(const char* who, const char* what) {
   set_error(std::string(who) + ": " + what);
@@ -2030,17 +2030,17 @@ static int env_fail(const char* who, const char* what) {
     if (!(cond)) return env_fail(who, what);     \
   } while (0)
 
-// The argument checks of the nine calls, in the order each call reports them (`who` names the call in the error
+// The argument checks of the eleven calls, in the order each call reports them (`who` names the call in the error
 // text). actions / noise: the single step's; the rollouts carry theirs in ro.
 static int env_checks(const char* who, unsigned kind, const AsvParams* params, const AsvEnvState* state,
                       const double* actions, const double* noise, const AsvStepCtl* ctl, const AsvStepOut* out,
                       const AsvRollout* ro, const AsvPolicy* pi, const AsvDqnPolicy* dq, const AsvSacPolicy* sq,
-                      const AsvAutoReset* ar, const AsvEnvLaunch* launch) {
+                      const AsvAutoReset* ar, const AsvEnvLaunch* launch, const AsvIqnPolicy* iq = nullptr) {
   const bool roll = (kind & kRollout) != 0, closed = (kind & kClosedLoop) != 0, reset = (kind & kAutoReset) != 0;
-  // the closed loop's policy: dq (DQN_Policy), sq (SAC's sampled actor), else pi (the Actor)
-  const bool dqn = (kind & kDqnPolicy) != 0, sac = (kind & kSacPolicy) != 0;
+  // the closed loop's policy: dq (DQN_Policy), sq (SAC's sampled actor), iq (IQN_Policy), else pi (the Actor)
+  const bool dqn = (kind & kDqnPolicy) != 0, sac = (kind & kSacPolicy) != 0, iqn = (kind & kIqnPolicy) != 0;
   const float* pol_obs_in = nullptr;
-  if (closed) pol_obs_in = dqn ? (dq ? dq->obs_in : nullptr) : sac ? (sq ? sq->obs_in : nullptr) : (pi ? pi->obs_in : nullptr);
+  if (closed) pol_obs_in = iqn ? (iq ? iq->obs_in : nullptr) : dqn ? (dq ? dq->obs_in : nullptr) : sac ? (sq ? sq->obs_in : nullptr) : (pi ? pi->obs_in : nullptr);
   ENV_REQUIRE(params && state && ctl && out && (ro || !roll), "null argument");
   if (reset) {   // what the two _ar calls refuse beyond their plain calls' checks
     ENV_REQUIRE(ar != nullptr, "null ar (the auto-reset description)");
@@ -2063,7 +2063,19 @@ static int env_checks(const char* who, unsigned kind, const AsvParams* params, c
     ENV_REQUIRE(ro->n_steps >= 1, "n_steps must be >= 1");
     if (!closed) ENV_REQUIRE(ro->actions != nullptr, "null actions");
   }
-  if (closed) {
+  if (closed && iqn) {   // IQN_Policy: the critic trunk's images (no MLP trunk), the padded head, the risk level
+    ENV_REQUIRE(ro->actions == nullptr, "ro->actions must be null (the policy supplies the actions)");
+    ENV_REQUIRE(iq != nullptr, "null policy");
+    ENV_REQUIRE(pol_obs_in != nullptr, "null obs_in");
+    ENV_REQUIRE(!ctl->is_continuous, "is_continuous must be 0 (IQN's actions are indices)");
+    const AsvCriticWeights& w = iq->w;
+    ENV_REQUIRE(w.wc_frag && w.w1_frag && w.w2_frag && w.bc && w.b1 && w.b2 && w.self_w && w.self_b && w.obj_w && w.obj_b,
+                "null IQN image");
+    ENV_REQUIRE(iq->head.wo_frag != nullptr, "null pi->head.wo_frag");
+    ENV_REQUIRE(iq->head.bo != nullptr, "null pi->head.bo");
+    ENV_REQUIRE(iq->head.n_actions >= 1 && iq->head.n_actions <= ASVRL_IQN_MAX_ACTIONS, "pi->head.n_actions must be in 1..32");
+    ENV_REQUIRE(iq->cvar > 0.f && iq->cvar <= 1.f, "pi->cvar must be in (0, 1]");
+  } else if (closed) {
     ENV_REQUIRE(ro->actions == nullptr, "ro->actions must be null (the policy supplies the actions)");
     ENV_REQUIRE(dqn ? dq != nullptr : (sac ? sq != nullptr : pi != nullptr), "null policy");
     ENV_REQUIRE(pol_obs_in != nullptr, "null obs_in");
@@ -2335,20 +2347,40 @@ static AsvSacActIO sac_act_io(const AsvSacPolicy* sq, const float* x, size_t n, 
   return io;
 }
 
-// The K-launch form of the eight rollout calls (per-robot parameters, layout 2, a carve that does not fit). Per step:
+// act_iqn's launch over n rows x (K = 32 taus per state, drawn in the kernel): the window form's outputs are its
+// AsvIqnActEx's
+static AsvIqnIO iqn_act_io(const AsvIqnPolicy* iq, const float* x, size_t n, const int64_t* step) {
+  AsvIqnIO io{};
+  io.obs = x;
+  io.ld_obs = ASVRL_OBS_DIM;
+  io.B = static_cast<int32_t>(n);
+  io.N = 32;
+  io.step_dev = step;
+  io.eps_steps_per_count = iq->eps_steps_per_count;
+  io.eps_total = iq->eps_total;
+  io.eps_fraction = iq->eps_fraction;
+  io.eps_initial = iq->eps_initial;
+  io.eps_final = iq->eps_final;
+  io.seed = iq->seed;
+  return io;
+}
+
+// The K-launch form of the ten rollout calls (per-robot parameters, layout 2, a carve that does not fit; IQN_Policy always). Per step:
 // the act launch (closed loop), the obs_prev row (auto-reset), the single step and its record launch; then, for the
 // auto-reset, the reset mask and counts and the reset of the ended envs with their observation
 // (asvrl_env_reset_observe, or the two launches where that call does not apply). pi null: the open loop, the actions
 // out of ro; dq instead of pi: DQN_Policy's act launch (asvrl_dqn_act) in the Actor's place; sq: SAC's
-// (asvrl_sac_act, its eps_out and, when deterministic, its zero eps_in behind the actions in the scratch). ar null: a plain call, which alone can hold ended envs (hold_done: env_checks refuses it with ar).
+// (asvrl_sac_act, its eps_out and, when deterministic, its zero eps_in behind the actions in the scratch); iq:
+// IQN_Policy's, the only form its two calls have (asvrl_iqn_act_ex: no step-count and no record-copy launch). ar null: a plain call, which alone can hold ended envs (hold_done: env_checks refuses it with ar).
 static int rollout_fallback(const char* who, const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                             const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi, const AsvDqnPolicy* dq,
-                            const AsvSacPolicy* sq, const AsvAutoReset* ar, const AsvEnvLaunch* launch, void* stream) {
+                            const AsvSacPolicy* sq, const AsvAutoReset* ar, const AsvEnvLaunch* launch, void* stream,
+                            const AsvIqnPolicy* iq = nullptr) {
   hipStream_t st = as_stream(stream);
-  const bool closed = pi != nullptr || dq != nullptr || sq != nullptr;
-  const float* pol_obs = dq != nullptr ? dq->obs_in : (sq != nullptr ? sq->obs_in : (pi != nullptr ? pi->obs_in : nullptr));
-  const int64_t* pol_step = dq != nullptr ? dq->step_dev : (sq != nullptr ? sq->step_dev : (pi != nullptr ? pi->step_dev : nullptr));
-  double* pol_actions = dq != nullptr ? dq->actions : (sq != nullptr ? sq->actions : (pi != nullptr ? pi->actions : nullptr));
+  const bool closed = pi != nullptr || dq != nullptr || sq != nullptr || iq != nullptr;
+  const float* pol_obs = iq != nullptr ? iq->obs_in : dq != nullptr ? dq->obs_in : (sq != nullptr ? sq->obs_in : (pi != nullptr ? pi->obs_in : nullptr));
+  const int64_t* pol_step = iq != nullptr ? iq->step_dev : dq != nullptr ? dq->step_dev : (sq != nullptr ? sq->step_dev : (pi != nullptr ? pi->step_dev : nullptr));
+  double* pol_actions = iq != nullptr ? iq->actions : dq != nullptr ? dq->actions : (sq != nullptr ? sq->actions : (pi != nullptr ? pi->actions : nullptr));
   const int E = state->n_envs, R = state->max_robots;
   const size_t NT = static_cast<size_t>(E) * R;
   const size_t noise_row = NT * (static_cast<size_t>(state->max_obs) + R) * 5;
@@ -2397,7 +2429,18 @@ static int rollout_fallback(const char* who, const AsvParams* params, const AsvE
     if (hold_mask != nullptr) c.env_mask = hold_mask;
     const float* obs_t = t == 0 ? obs_first : out->obs;   // the observation the step before (or its reset) wrote
     const double* actions = act;
-    if (closed) {
+    if (iq != nullptr) {
+      // one launch: the act at step *step_dev + t, the step's pairs and the record row under the step's mask
+      const AsvIqnIO io = iqn_act_io(iq, obs_t, NT, pol_step);
+      AsvIqnActEx ex{};
+      ex.cvar = iq->cvar;
+      ex.robots_per_env = R;
+      ex.step_add = t;
+      ex.act_pair = act;
+      ex.rec_row = pol_actions != nullptr ? pol_actions + static_cast<size_t>(t) * 2 * NT : nullptr;
+      ex.env_mask = c.env_mask;
+      rc = asvrl_iqn_act_ex(&iq->w, &iq->head, &io, &ex, stream);
+    } else if (closed) {
       hipLaunchKernelGGL(policy_step_count_kernel, dim3(1), dim3(1), 0, st, pol_step, step, t);
       if (dq != nullptr) {
         const AsvDqnActIO io = dqn_act_io(dq, obs_t, NT, act, step);
@@ -2449,25 +2492,27 @@ static int rollout_fallback(const char* who, const AsvParams* params, const AsvE
   return rc;
 }
 
-// The eight rollout calls: check, plan, zero the counts the window adds to, then the one launch or the fallback.
-// pi, dq or sq: the closed loop under the Actor, DQN_Policy or SAC's sampled actor (ro->actions is null then); ar: the auto-reset (Philox noise only: no recorded rows).
+// The ten rollout calls: check, plan, zero the counts the window adds to, then the one launch or the fallback.
+// pi, dq, sq or iq: the closed loop under the Actor, DQN_Policy, SAC's sampled actor or IQN_Policy (ro->actions is null then); ar: the auto-reset (Philox noise only: no recorded rows).
 static int rollout_call(const char* who, unsigned kind, const AsvParams* params, const AsvEnvState* state,
                         const AsvStepCtl* ctl, const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi,
                         const AsvDqnPolicy* dq, const AsvSacPolicy* sq, const AsvAutoReset* ar,
-                        const AsvEnvLaunch* launch, void* stream) {
-  if (int rc = env_checks(who, kind, params, state, nullptr, nullptr, ctl, out, ro, pi, dq, sq, ar, launch)) return rc;
+                        const AsvEnvLaunch* launch, void* stream, const AsvIqnPolicy* iq = nullptr) {
+  if (int rc = env_checks(who, kind, params, state, nullptr, nullptr, ctl, out, ro, pi, dq, sq, ar, launch, iq)) return rc;
   if (state->n_envs == 0) return 0;
-  EnvPlan P;
-  if (int rc = env_plan(who, state, ctl, launch, pi != nullptr || dq != nullptr || sq != nullptr, ar != nullptr, &P,
-                        sq != nullptr ? sizeof(sactile::SacHeadLds) : 0))
-    return rc;
+  EnvPlan P{};
+  // kIqnPolicy never plans the fused launch: IQN's 150 KB image and 16 waves do not fit beside the env's carve
+  if ((kind & kIqnPolicy) == 0)
+    if (int rc = env_plan(who, state, ctl, launch, pi != nullptr || dq != nullptr || sq != nullptr, ar != nullptr, &P,
+                          sq != nullptr ? sizeof(sactile::SacHeadLds) : 0))
+      return rc;
   hipStream_t st = as_stream(stream);
   if (ro->steps_run != nullptr && hipMemsetAsync(ro->steps_run, 0, sizeof(int32_t) * state->n_envs, st) != hipSuccess)
     return check_launch(who);
   if (ar != nullptr && ar->resets != nullptr &&
       hipMemsetAsync(ar->resets, 0, sizeof(int32_t) * state->n_envs, st) != hipSuccess)
     return check_launch(who);
-  if (!P.fused) return rollout_fallback(who, params, state, ctl, out, ro, pi, dq, sq, ar, launch, stream);
+  if (!P.fused) return rollout_fallback(who, params, state, ctl, out, ro, pi, dq, sq, ar, launch, stream, iq);
   const PairsArgs k{*params, *state, *ctl, *out, ro->actions, ar != nullptr ? nullptr : ro->noise, P.pl.epb, 0};
   if (dq != nullptr && ar != nullptr) return launch_groups(who, P, DqnRolloutArArgs{k, *ro, *dq, *ar, P.ar_off}, st);
   if (dq != nullptr) return launch_groups(who, P, DqnRolloutArgs{k, *ro, *dq}, st);
@@ -2540,6 +2585,22 @@ extern "C" int asvrl_sac_rollout_ar(const AsvParams* params, const AsvEnvState* 
 }
 
 extern "C" int64_t asvrl_sac_policy_struct_size(void) { return sizeof(AsvSacPolicy); }
+
+extern "C" int asvrl_iqn_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                                 const AsvStepOut* out, const AsvRollout* ro, const AsvIqnPolicy* pi,
+                                 const AsvEnvLaunch* launch, void* stream) {
+  return rollout_call("asvrl_iqn_rollout", kRollout | kClosedLoop | kIqnPolicy, params, state, ctl, out, ro, nullptr,
+                      nullptr, nullptr, nullptr, launch, stream, pi);
+}
+
+extern "C" int asvrl_iqn_rollout_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                                    const AsvStepOut* out, const AsvRollout* ro, const AsvIqnPolicy* pi,
+                                    const AsvAutoReset* ar, const AsvEnvLaunch* launch, void* stream) {
+  return rollout_call("asvrl_iqn_rollout_ar", kRollout | kClosedLoop | kAutoReset | kIqnPolicy, params, state, ctl, out,
+                      ro, nullptr, nullptr, nullptr, ar, launch, stream, pi);
+}
+
+extern "C" int64_t asvrl_iqn_policy_struct_size(void) { return sizeof(AsvIqnPolicy); }
 
 extern "C" int64_t asvrl_autoreset_struct_size(void) { return sizeof(AsvAutoReset); }
 

@@ -268,7 +268,8 @@ class DeviceEnvBatch:
     def policy_rollout(self, pack, K, obs_in, *, noise=None, keep=("reward", "done", "info"), hold_done=False,
                        step_dev=None, eps=(1.0, 1.0, 1.0, 0.0, 0.0), policy_seed=0, trainer_deactivate=False, seed=0,
                        counter=0, counter_dev=None, gamma=0.0, env_mask=None, obs=None, obj_cnt=None,
-                       fast_noise=False, launch=None, stream=None, auto_reset=None, deterministic=False):
+                       fast_noise=False, launch=None, stream=None, auto_reset=None, deterministic=False,
+                       cvar=1.0):
         """asvrl_policy_rollout: K closed-loop steps in one launch -- the AC-IQN Actor of `pack` (an MlpPack of
         kind "actor") acts on every robot row and the env steps on its actions, bit for bit the K rounds of
         fused_mlp.actor_act(pack, obs, act64, step, *eps, policy_seed) at step = step_dev + t followed by
@@ -288,12 +289,26 @@ class DeviceEnvBatch:
         asvrl_sac_rollout_ar: the rounds are fused_sac.sac_act(pack, obs, act64, eps_out, step, *eps, policy_seed)
         -- the action noise drawn in the kernel on (global row, step, policy_seed) -- followed by step(act64, ...).
         deterministic=True (a SacActorPack only; ValueError otherwise): the mean action, the rounds'
-        sac_act(..., eps_in=zeros); nothing is drawn for the sample, the epsilon schedule still applies."""
-        from .fused_dqn import DqnPack   # (fused_dqn and fused_sac import nothing from this module)
+        sac_act(..., eps_in=zeros); nothing is drawn for the sample, the epsilon schedule still applies.
+        A fused_iqn.IqnPack (IQN_Policy) goes to asvrl_iqn_rollout / asvrl_iqn_rollout_ar: the rounds are
+        fused_iqn.iqn_act(pack, None, act64, step, *eps, policy_seed, obs=obs, cvar=cvar) -- K = 32 taus per state
+        drawn in the kernel on (global row, step, policy_seed) -- and step(act64, is_continuous=False, ...); "actions"
+        holds (action index, 0.0). The act stays a launch of its own per step (it is not fused into the env kernel),
+        all enqueued by the one call. cvar in (0, 1] (an IqnPack only; ValueError otherwise, and outside the range):
+        act_iqn's risk distortion, every tau times cvar."""
+        from .fused_dqn import DqnPack   # (fused_dqn, fused_sac and fused_iqn import nothing from this module)
+        from .fused_iqn import IqnPack
         from .fused_sac import SacActorPack
         K, NT = int(K), self.n_envs * self.max_robots
-        assert pack.kind == "actor"
+        iqn = isinstance(pack, IqnPack)
+        assert iqn or pack.kind == "actor"
         dqn, sac = isinstance(pack, DqnPack), isinstance(pack, SacActorPack)
+        cvar = float(cvar)
+        if not 0.0 < cvar <= 1.0:
+            raise ValueError("policy_rollout: cvar must be in (0, 1]")
+        if cvar != 1.0 and not iqn:
+            raise ValueError("policy_rollout: cvar is the risk distortion of IQN's quantile fractions (an IqnPack); "
+                             "the other policies have no quantiles to distort")
         if deterministic and not sac:
             raise ValueError("policy_rollout: deterministic=True is the sampled actor's mean action (a SacActorPack); "
                              "the Actor and DQN_Policy have no sample to switch off")
@@ -301,13 +316,17 @@ class DeviceEnvBatch:
         if step_dev is not None:
             assert step_dev.dtype == torch.int64 and step_dev.numel() >= 1
         b = self._rollout_args("policy_rollout", K, {"actions": ((NT, 2), torch.float64, 0)}, noise=noise, keep=keep,
-                               hold_done=hold_done, is_continuous=not dqn, trainer_deactivate=trainer_deactivate,
+                               hold_done=hold_done, is_continuous=not (dqn or iqn), trainer_deactivate=trainer_deactivate,
                                seed=seed, counter=counter, counter_dev=counter_dev, gamma=gamma, env_mask=env_mask,
                                obs=obs, obj_cnt=obj_cnt, fast_noise=fast_noise, launch=launch, auto_reset=auto_reset)
         if b.ar is not None:
             b.ar.obs_in = None
-        pi = _abi.AsvDqnPolicy() if dqn else (_abi.AsvSacPolicy() if sac else _abi.AsvPolicy())
-        pi.w = pack.dw if dqn else (pack.sw if sac else pack.w)
+        if iqn:
+            pi = _abi.AsvIqnPolicy()
+            pi.w, pi.head, pi.cvar = pack.struct, pack.head, cvar
+        else:
+            pi = _abi.AsvDqnPolicy() if dqn else (_abi.AsvSacPolicy() if sac else _abi.AsvPolicy())
+            pi.w = pack.dw if dqn else (pack.sw if sac else pack.w)
         if sac:
             pi.deterministic = int(bool(deterministic))
         pi.obs_in = obs_in.data_ptr()
@@ -316,7 +335,8 @@ class DeviceEnvBatch:
          pi.eps_final) = (float(v) for v in eps)
         pi.seed = int(policy_seed) & 0xFFFFFFFFFFFFFFFF
         pi.actions = b.rec["actions"].data_ptr() if "actions" in b.rec else None
-        name = "asvrl_dqn_rollout" if dqn else ("asvrl_sac_rollout" if sac else "asvrl_policy_rollout")
+        name = ("asvrl_iqn_rollout" if iqn else "asvrl_dqn_rollout" if dqn else
+                "asvrl_sac_rollout" if sac else "asvrl_policy_rollout")
         return self._rollout_call(b, pack.L, name, [C.byref(pi)], stream)
 
     def reset(self, cfg, env_mask=None, seed=0, counter=0, counter_dev=None, stream=None):

@@ -27,6 +27,12 @@ The encoders run inside the trunk kernels' prologue (f32, from the parameters). 
 every robot row is one kernel (encoders, K = 32 quantile samples per state, mean over them,
 argmax, epsilon-greedy on the device step counter).
 
+The closed-loop windows (csrc/asvrl_env.hip, asvrl_iqn_rollout / asvrl_iqn_rollout_ar) take an IqnPack: per step
+they launch the window form of the act pass (asvrl_iqn_act_ex: the same tile with the step offset, the (index, 0.0)
+pair, its masked record row and act_iqn's cvar), then the env step; the act is not fused into the env kernel (its
+150 KB LDS image and 16 waves per CU do not fit beside the env's carve). FusedIQNState.window_pack,
+DeviceEnvBatch.policy_rollout(..., cvar=1.0), DeviceEvaluator.run(..., policy_seed=0, cvar=1.0).
+
 Arithmetic: bf16 MFMA operands with f32 accumulation, f32 master weights / Adam.
 """
 import ctypes as C
@@ -177,20 +183,46 @@ def iqn_train_fused(pack, net, taus, N, q_next, actions, rewards, dones, gamma, 
 
 
 def iqn_act(pack, F, actions64, step_dev, steps_per_count, total, fraction, initial, final, seed, taus=None,
-            stream=None, obs=None):
-    """act_iqn for every row of F (or of the observation rows `obs`) into actions64[:, 0] (f64 action index)."""
+            stream=None, obs=None, cvar=1.0, step_add=0, q_out=None, actions_rec=None, env_mask=None,
+            robots_per_env=1):
+    """act_iqn for every row of F (or of the observation rows `obs`) into actions64[:, 0] (f64 action index).
+    The window form (asvrl_iqn_act_ex, taken only when one of these is set): cvar in (0, 1] multiplies every tau,
+    drawn or given (act_iqn's risk distortion, IQN_model.py:68); step_add is added to the step counter's value;
+    q_out (f32 [rows, >= A]) receives the action values quantiles.mean(dim=1); actions_rec (f64 [rows, 2]) receives
+    (index, 0.0) for the rows of envs with env_mask != 0 (u8, one per robots_per_env rows; None: every row)."""
     io = _io(F, K_ACT, obs=obs, taus=taus, act_out=actions64, ld_act=actions64.stride(0), step_dev=step_dev,
              eps_steps_per_count=float(steps_per_count), eps_total=float(total), eps_fraction=float(fraction),
              eps_initial=float(initial), eps_final=float(final), seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
-    _abi.check(pack.L.asvrl_iqn_act(C.byref(pack.struct), C.byref(pack.head), C.byref(io),
-                                    _abi.stream_ptr(stream)), "asvrl_iqn_act", pack.L)
+    if float(cvar) == 1.0 and int(step_add) == 0 and q_out is None and actions_rec is None and env_mask is None:
+        _abi.check(pack.L.asvrl_iqn_act(C.byref(pack.struct), C.byref(pack.head), C.byref(io),
+                                        _abi.stream_ptr(stream)), "asvrl_iqn_act", pack.L)
+        return
+    ex = _abi.AsvIqnActEx()
+    ex.cvar, ex.robots_per_env, ex.step_add = float(cvar), int(robots_per_env), int(step_add)
+    if q_out is not None:
+        assert q_out.dtype == torch.float32 and q_out.stride(-1) == 1 and q_out.shape[0] == io.B
+        assert q_out.shape[1] >= pack.head.n_actions
+        ex.qmean_out, ex.ld_q = q_out.data_ptr(), q_out.stride(0)
+    if actions_rec is not None:
+        assert actions_rec.dtype == torch.float64 and actions_rec.is_contiguous()
+        assert tuple(actions_rec.shape) == (io.B, 2)
+        ex.rec_row = actions_rec.data_ptr()
+    if env_mask is not None:
+        assert env_mask.dtype == torch.uint8 and env_mask.is_contiguous()
+        assert env_mask.numel() * int(robots_per_env) >= io.B
+        ex.env_mask = env_mask.data_ptr()
+    _abi.check(pack.L.asvrl_iqn_act_ex(C.byref(pack.struct), C.byref(pack.head), C.byref(io), C.byref(ex),
+                                       _abi.stream_ptr(stream)), "asvrl_iqn_act_ex", pack.L)
 
 
 class FusedIQNState:
     """Packs and buffers of the fused IQN update (allocated once, pointer-stable for graphs).
     operands="f32": every kernel from libasvrl_f32.so (the parity build; the optimiser must be a
-    FusedAdam of the same operands)."""
-    actor_pack = policy_pack = None   # act_iqn runs inside its own kernel, not in the closed-loop windows
+    FusedAdam of the same operands). window_pack (the local IqnPack) is what the closed-loop windows and the device
+    evaluation take (DeviceEnvBatch.policy_rollout, DeviceEvaluator.run, VecTrainer._collect_window); policy_pack and
+    actor_pack stay None, so VecTrainer.policy_pack(), collect, greedy_episodes and evaluate still refuse an IQN
+    trainer."""
+    actor_pack = policy_pack = None   # act_iqn runs in its own launch (the windows compose it per step, window_pack)
 
     def __init__(self, net_local, net_target, B, N, operands="bf16", target_in_fused=None):
         dev = net_local.cos_embedding.weight.device
@@ -199,7 +231,7 @@ class FusedIQNState:
         # the target's max inside the fused launch (bf16 build; module default TARGET_IN_FUSED)
         self.target_in_fused = TARGET_IN_FUSED if target_in_fused is None else bool(target_in_fused)
         self.A = net_local.action_size
-        self.local = IqnPack(net_local, operands)
+        self.local = self.window_pack = IqnPack(net_local, operands)
         self.target = IqnPack(net_target, operands)
         self.bufs = TrainBuffers(B, N, dev, operands)
         f = dict(dtype=torch.float32, device=dev)

@@ -10,6 +10,9 @@ buffers) is built. The Fused*State classes share one surface, so neither front e
 FusedSACState also has window_pack, its local actor's SacActorPack: DeviceEnvBatch.policy_rollout, DeviceEvaluator.run
 and VecTrainer._collect_window take it (the sampled head runs inside the env kernel), while its policy_pack and
 actor_pack stay None, so VecTrainer's own policy_pack() / collect / greedy_episodes / evaluate still refuse SAC.
+FusedIQNState has window_pack too, its local IqnPack: the same three take it (per step the window launches the act
+pass, asvrl_iqn_act_ex, and then the env step; policy_rollout and run also take act_iqn's cvar), and the same four
+still refuse IQN.
 """
 from dataclasses import dataclass
 from typing import Callable, Optional

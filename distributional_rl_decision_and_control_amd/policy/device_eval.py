@@ -10,7 +10,8 @@ per-robot bookkeeping in Python. DeviceEvaluator keeps the same episodes in Devi
     a device copy of that state is kept, so every later evaluation restores by copy;
   * an evaluation is the observation pass and then closed-loop windows of `chunk` steps, one launch each
     (DeviceEnvBatch.policy_rollout with hold_done, the greedy Actor of an MlpPack, the greedy DQN_Policy of a
-    DqnPack or SAC's actor of a SacActorPack, sampled as act_sac samples or its mean action), or, teacher-forced, open-loop windows over a caller's action table (DeviceEnvBatch.rollout);
+    DqnPack, SAC's actor of a SacActorPack, sampled as act_sac samples or its mean action, or the greedy IQN_Policy
+    of an IqnPack at a risk level cvar, its act launch and the step enqueued per step by the one call), or, teacher-forced, open-loop windows over a caller's action table (DeviceEnvBatch.rollout);
   * behind every window one asvrl_eval_metrics launch folds the window's records into the evaluation's carried
     state by trainer.py:286-303: discounted return, time, energy, deactivation, and the evaluation's end rule (the
     step limit, ANY collision, or every robot deactivated). Its `alive` output is the next window's env_mask;
@@ -31,6 +32,7 @@ from .. import _abi
 from ..device_env import DeviceEnvBatch
 from ..envs.marinenav.env import MarineNavEnv3, set_batch_params
 from ..fused_dqn import DqnPack
+from ..fused_iqn import IqnPack
 from ..fused_sac import SacActorPack
 
 RECORDS = ("reward", "info", "rs")
@@ -199,11 +201,13 @@ class DeviceEvaluator:
 
     @torch.no_grad()
     def run(self, pack=None, *, actions=None, noise=None, obs_noise=None, seed=0, episode_limit=1000, sync=True,
-            is_continuous=None, policy_seed=0, deterministic=False):
+            is_continuous=None, policy_seed=0, deterministic=False, cvar=1.0):
         """One evaluation of every config. pack: the Actor's MlpPack or DQN's DqnPack, greedy in closed-loop
         windows, or SAC's SacActorPack, which samples its action as act_sac does in evaluation too (group g draws
         under policy_seed + g: rows are batch-local, so two groups share no draws) or, with deterministic=True (a
-        ValueError for any other pack), takes its mean action; or actions: a [T, NT, 2] f64 table per group (a tensor when there is one group, else a list)
+        ValueError for any other pack), takes its mean action, or IQN's IqnPack, greedy over the mean of K = 32
+        quantile samples whose fractions are drawn per act (group g under policy_seed + g, as for SAC) and, with
+        cvar in (0, 1] (a ValueError for any other pack and outside the range), distorted as act_iqn(cvar=) does; or actions: a [T, NT, 2] f64 table per group (a tensor when there is one group, else a list)
         applied open loop, with noise ([T, NT, O + R, 5] f64 per group) or the Philox stream. is_continuous: what
         the table's rows are -- True (also None, the default) thrust commands, False column 0 is the action index;
         with a pack it follows the pack (None) and a value that contradicts it is a ValueError. obs_noise: the observation pass's explicit
@@ -214,11 +218,18 @@ class DeviceEvaluator:
         the end, 1 goal, 2 collision)."""
         if (pack is None) == (actions is None):
             raise ValueError("run takes the Actor's pack or an action table, not both")
-        if pack is not None and pack.kind != "actor":
+        iqn = isinstance(pack, IqnPack)
+        if pack is not None and not iqn and pack.kind != "actor":
             raise ValueError("run: pack must be an MlpPack of kind 'actor'")
-        if pack is not None and is_continuous is not None and bool(is_continuous) == isinstance(pack, DqnPack):
-            raise ValueError("run: is_continuous=%s does not match the pack (a DqnPack picks discrete actions, the "
-                             "Actor continuous ones)" % bool(is_continuous))
+        if (pack is not None and is_continuous is not None
+                and bool(is_continuous) == isinstance(pack, (DqnPack, IqnPack))):
+            raise ValueError("run: is_continuous=%s does not match the pack (a DqnPack or IqnPack picks discrete "
+                             "actions, the Actor continuous ones)" % bool(is_continuous))
+        cvar = float(cvar)
+        if not 0.0 < cvar <= 1.0:
+            raise ValueError("run: cvar must be in (0, 1]")
+        if cvar != 1.0 and not iqn:
+            raise ValueError("run: cvar is the risk distortion of IQN's quantile fractions (an IqnPack)")
         if deterministic and not isinstance(pack, SacActorPack):
             raise ValueError("run: deterministic=True is the mean action of SAC's sampled actor (a SacActorPack)")
         is_continuous = True if is_continuous is None else bool(is_continuous)
@@ -241,7 +252,8 @@ class DeviceEvaluator:
                     grp.step.fill_(t0)
                     b.policy_rollout(pack, k, b.obs, keep=rec, hold_done=True, trainer_deactivate=True,
                                      step_dev=grp.step, env_mask=st["alive"], seed=seed + g, counter=t0,
-                                     fast_noise=True, policy_seed=policy_seed + g, deterministic=deterministic)
+                                     fast_noise=True, policy_seed=policy_seed + g, deterministic=deterministic,
+                                     cvar=cvar)
                 else:
                     nz = noise[g]
                     b.rollout(actions[g][t0:t0 + k], None if nz is None else nz[t0:t0 + k], keep=rec,

@@ -12,8 +12,8 @@ reads only its own keys from it (env.py:75-94). An optional "vectorized" dict in
 (ignored by the reference) makes learn() drive VecTrainer instead: {"n_envs": E, "batch_size": B,
 "num_tau": N, ...} are VecTrainer's keyword arguments. Evaluation, evaluations.npz and the model
 files keep the reference's cadence and format; the trained networks are copied into rl_agent first.
-With "device_eval": true in that dict (AC-IQN, DDPG and DQN) the evaluations run on the device with the batched
-trainer's own actor or Q network (evaluation(batched="device"), policy/device_eval.py).
+With "device_eval": true in that dict (AC-IQN, DDPG, DQN and IQN) the evaluations run on the device with the batched
+trainer's own actor, Q network or quantile network (evaluation(batched="device"), policy/device_eval.py).
 """
 import json
 import os
@@ -170,8 +170,9 @@ class Trainer:
         sched = {k: v for k, v in self.train_env.schedule.items() if k != "vectorized"}
         kw = dict(vec)
         # "device_eval": true evaluates on the device with the batched trainer's own actor (AC-IQN, DDPG) or Q network
-        # (DQN; evaluation(batched="device")) instead of copying the networks out and stepping the Python eval envs
-        device_eval = bool(kw.pop("device_eval", False)) and agent.agent_type in ("AC-IQN", "DQN", "DDPG")
+        # (DQN) or quantile network (IQN; evaluation(batched="device")) instead of copying the networks out and stepping
+        # the Python eval envs
+        device_eval = bool(kw.pop("device_eval", False)) and agent.agent_type in ("AC-IQN", "DQN", "DDPG", "IQN")
         kw.setdefault("graphs", True)
         for key, sk in (("num_robots", "num_robots"), ("num_obs", "num_obstacles"), ("num_cores", "num_cores")):
             if sk in sched:
@@ -321,6 +322,9 @@ class Trainer:
             # the batched trainer's own actor on device-resident eval configs (policy/device_eval.py)
             if tr.agent_type == "DQN":   # DQN_Policy's local images in the same windows
                 res = tr.device_evaluator(self.eval_config, template_env=self.eval_env).run(tr.policy_pack())
+            elif tr.agent_type == "IQN":   # IQN_Policy's local images: the act launch and the step, per step
+                res = tr.device_evaluator(self.eval_config,
+                                          template_env=self.eval_env).run(tr.fused_iqn.window_pack)
             else:
                 res = tr.evaluate(self.eval_config, template_env=self.eval_env)
             obs_d, act_d, traj_d = res["observations"], res["actions"], res["trajectories"]

@@ -125,7 +125,7 @@ class VecMarineNavEnv:
         return rec
 
     def policy_rollout(self, pack, K, hold_done=True, keep=("reward", "done", "info"), eps=(1.0, 1.0, 1.0, 0.0, 0.0),
-                       policy_seed=0, env_mask=None, auto_reset=False, count=True, deterministic=False):
+                       policy_seed=0, env_mask=None, auto_reset=False, count=True, deterministic=False, cvar=1.0):
         """K closed-loop steps in one launch (DeviceEnvBatch.policy_rollout): the AC-IQN Actor of `pack` acts on
         obs_cur and every next observation -- the values of K rounds of fused_mlp.actor_act(pack, obs_cur, actions,
         counter, *eps, policy_seed); step(actions); advance_device(), with the last step's observation in obs_next /
@@ -135,12 +135,16 @@ class VecMarineNavEnv:
         observation at the next step). A fused_dqn.DqnPack drives an env built with is_continuous=False the same
         way (fused_dqn.dqn_act in the Actor's place; "actions" holds (action index, 0.0)). A fused_sac.SacActorPack
         drives a continuous env with fused_sac.sac_act in the Actor's place, its noise drawn in the kernel on
-        (row, step counter, policy_seed); deterministic=True (that pack only) takes the mean action instead."""
+        (row, step counter, policy_seed); deterministic=True (that pack only) takes the mean action instead. A
+        fused_iqn.IqnPack drives an env built with is_continuous=False as a DqnPack does (fused_iqn.iqn_act in the
+        Actor's place, its quantile fractions drawn in the kernel on (row, step counter, policy_seed)); cvar in (0, 1]
+        (that pack only) is act_iqn's risk distortion."""
         from .fused_dqn import DqnPack
-        if isinstance(pack, DqnPack):
+        from .fused_iqn import IqnPack
+        if isinstance(pack, (DqnPack, IqnPack)):
             if self.is_continuous:
-                raise ValueError("policy_rollout: a DqnPack picks discrete actions, this env was built with "
-                                 "is_continuous=True")
+                raise ValueError("policy_rollout: a DqnPack or IqnPack picks discrete actions, this env was built "
+                                 "with is_continuous=True")
         elif not self.is_continuous:
             raise ValueError("policy_rollout: the Actor drives continuous-action envs")
         ar = self._auto_reset(auto_reset, False)
@@ -149,7 +153,7 @@ class VecMarineNavEnv:
                                         eps=eps, policy_seed=policy_seed, trainer_deactivate=True, seed=self.seed,
                                         counter=0, counter_dev=self.counter, gamma=self.gamma, env_mask=env_mask,
                                         obs=self.obs_next, obj_cnt=self.cnt_next, fast_noise=True,
-                                        launch=self._launch(), auto_reset=ar, deterministic=deterministic)
+                                        launch=self._launch(), auto_reset=ar, deterministic=deterministic, cvar=cvar)
         if count:
             self.counter += int(K)
         return rec

@@ -307,7 +307,9 @@ class VecTrainer:
     @torch.no_grad()
     def _collect_window(self, pack, K, snap=None):
         """collect()'s two launches under `pack`: the learner's actor_pack, or a SAC trainer's
-        fused_sac.window_pack, whose ring rows are DDPG's (K calls of rollout(), bit for bit, there too)."""
+        fused_sac.window_pack, whose ring rows are DDPG's (K calls of rollout(), bit for bit, there too), or an IQN
+        trainer's fused_iqn.window_pack: its "actions" record holds (index, 0.0), and the push stores the pair as
+        rollout()'s one-column push stores the index and a zero."""
         K = int(K)
         buf = self._collect_buffers(K)
         buf["obj_cnt"].fill_(-1)   # a row no env took is never pushed

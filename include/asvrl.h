@@ -491,6 +491,26 @@ int asvrl_iqn_train_fused_tq(const AsvCriticWeights* w, const AsvIqnHead* head, 
 /* act_iqn (agent.py:227-256) for every row of F with K = 32 quantile samples per state. */
 int asvrl_iqn_act(const AsvCriticWeights* w, const AsvIqnHead* head, const AsvIqnIO* io, void* stream);
 
+/* The window form of asvrl_iqn_act (new entry points only: the ABI version stays 29). What it adds to the pass: */
+typedef struct AsvIqnActEx {
+  float cvar;              /* in (0, 1]: every tau of the pass, drawn or given, is multiplied by it before the cosine
+                              embedding (calc_cos's taus * cvar, IQN_model.py:68); 1: asvrl_iqn_act's bits */
+  int32_t robots_per_env;  /* >= 1: row b belongs to env b / robots_per_env (env_mask) */
+  int64_t step_add;        /* the tau draw, the epsilon schedule and the exploration draw use *step_dev + step_add */
+  double* act_pair;        /* optional [B][2]: (action index, 0.0), what asvrl_env_step_ex takes with
+                              is_continuous = 0 */
+  double* rec_row;         /* optional [B][2]: the same pair, written only for rows of envs with env_mask != 0 */
+  const uint8_t* env_mask; /* optional [B / robots_per_env]; NULL: every env */
+  float* qmean_out;        /* optional [B][ld_q]: column a < n_actions = mean over the 32 taus of Q(s, tau, a), act_iqn's
+                              quantiles.mean(dim=1); columns >= n_actions are not written */
+  int64_t ld_q;
+} AsvIqnActEx;
+/* io as asvrl_iqn_act's, except that io->act_out may be NULL when ex->act_pair or ex->rec_row is given. */
+int asvrl_iqn_act_ex(const AsvCriticWeights* w, const AsvIqnHead* head, const AsvIqnIO* io, const AsvIqnActEx* ex,
+                     void* stream);
+/* sizeof(AsvIqnActEx) as compiled. */
+int64_t asvrl_iqn_act_ex_struct_size(void);
+
 /* ---------------------------------------------------------------- replay (replay_buffer.py) */
 
 /* ReplayBuffer.add (replay_buffer.py:22-24) for every robot that acted in the last step
@@ -1430,6 +1450,40 @@ int asvrl_sac_rollout_ar(const AsvParams* params, const AsvEnvState* state, cons
                          const AsvAutoReset* ar, const AsvEnvLaunch* launch /* NULL: automatic */, void* stream);
 /* sizeof(AsvSacPolicy) as compiled. */
 int64_t asvrl_sac_policy_struct_size(void);
+
+/* ---------------------------------------------------------------- closed-loop rollout windows for IQN
+ * New entry points only: the ABI version stays 29. */
+
+/* IQN_Policy (act_iqn) driving asvrl_iqn_rollout. */
+typedef struct AsvIqnPolicy {
+  AsvCriticWeights w;             /* asvrl_iqn_pack's trunk images and the f32 encoders */
+  AsvIqnHead head;                /* the padded output head and its bias */
+  const float* obs_in;            /* [NT][ASVRL_OBS_DIM] the observation step 0 acts on (16-byte aligned) */
+  const int64_t* step_dev;        /* tau draw, epsilon schedule and exploration key: step = *step_dev + t (NULL: 0 + t) */
+  double eps_steps_per_count, eps_total, eps_fraction, eps_initial, eps_final;   /* as AsvIqnIO's */
+  uint64_t seed;                  /* Philox key of the tau and exploration draws */
+  double* actions;                /* optional record [K][NT][2]: (action index, 0.0) of every robot slot */
+  float cvar;                     /* in (0, 1]: act_iqn's risk distortion, every tau times cvar (1: risk neutral) */
+  int32_t _pad0;
+} AsvIqnPolicy;
+
+/* The closed loop under IQN_Policy: for t < ro->n_steps, asvrl_iqn_act on every robot row (K = 32 taus per state
+ * drawn in the kernel on (row, *step_dev + t, seed), times cvar; the first arg-max of the mean; the epsilon-greedy
+ * draw) and then the env step on the discrete action -- bit for bit the 2 K launches of asvrl_iqn_act and
+ * asvrl_env_step_ex (and, with the auto-reset, asvrl_env_reset_observe) they replace. The act is NOT fused into the env
+ * kernel (its 150 KB LDS image and its 16 waves per CU do not fit beside the env's carve): every layout runs, per
+ * step, one asvrl_iqn_act_ex launch (step_add = t; it writes the step's action pairs and the record row itself), the
+ * single step, the record launch and, with the auto-reset, the reset launches, all enqueued by this one call with
+ * no host synchronisation. The contract is the two DQN calls' otherwise: ctl->is_continuous must be 0, ro->actions
+ * null; pi->head.n_actions in 1..ASVRL_IQN_MAX_ACTIONS, pi->cvar in (0, 1]. The caller's step counter is only read. */
+int asvrl_iqn_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                      const AsvStepOut* last, const AsvRollout* ro, const AsvIqnPolicy* pi,
+                      const AsvEnvLaunch* launch /* NULL: automatic */, void* stream);
+int asvrl_iqn_rollout_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                         const AsvStepOut* last, const AsvRollout* ro, const AsvIqnPolicy* pi,
+                         const AsvAutoReset* ar, const AsvEnvLaunch* launch /* NULL: automatic */, void* stream);
+/* sizeof(AsvIqnPolicy) as compiled. */
+int64_t asvrl_iqn_policy_struct_size(void);
 
 /* ---------------------------------------------------------------- misc */
 const char* asvrl_last_error(void);

@@ -1,0 +1,189 @@
+"""CPU: the binding of asvrl_iqn_act_ex, asvrl_iqn_rollout and asvrl_iqn_rollout_ar (new entry points, ABI 29).
+sizeof(AsvIqnActEx) and sizeof(AsvIqnPolicy) agree between ctypes and both compiled libraries, and every refusal
+comes back non-zero with its exact text. The checks fail before anything is launched: the pointers below are made-up
+addresses that are never dereferenced."""
+import ctypes as C
+
+import pytest
+
+P = 0x1000   # a made-up, 16-byte aligned address
+NAMES = ("asvrl_iqn_rollout", "asvrl_iqn_rollout_ar")
+IMAGES = ("wc_frag", "w1_frag", "w2_frag", "bc", "b1", "b2", "self_w", "self_b", "obj_w", "obj_b")
+
+
+def _args(**over):
+    """Arguments that pass every check of both rollout calls up to the launch (nothing is launched: every test
+    overrides one of them into a refusal). Overrides are obj__field=value; w__<image> sets a trunk image or an
+    encoder pointer, hd__<name> a member of the head."""
+    from distributional_rl_decision_and_control_amd import _abi
+    from distributional_rl_decision_and_control_amd.device_env import reset_cfg
+    a = dict(params=_abi.params_from(), state=_abi.AsvEnvState(), ctl=_abi.AsvStepCtl(), out=_abi.AsvStepOut(),
+             ro=_abi.AsvRollout(), pi=_abi.AsvIqnPolicy(), ar=_abi.AsvAutoReset())
+    st = a["state"]
+    st.n_envs, st.max_robots, st.max_obs, st.max_cores = 4, 5, 4, 2
+    for n in ("rs", "rflags", "n_robots", "n_obs", "n_cores", "ep_ts", "obstacles", "cores"):
+        setattr(st, n, P)
+    ctl = a["ctl"]
+    ctl.is_continuous, ctl.do_dynamics, ctl.trainer_deactivate, ctl.noise_mode = 0, 1, 1, 2
+    for n in ("obs", "obj_cnt", "reward", "done", "info", "env_done"):
+        setattr(a["out"], n, P)
+    a["ro"].n_steps = 3
+    pi = a["pi"]
+    pi.obs_in, pi.cvar = P, 1.0
+    for n in IMAGES:
+        setattr(pi.w, n, P)
+    pi.head.wo_frag, pi.head.bo, pi.head.n_actions = P, P, 9
+    a["ar"].cfg = reset_cfg(5, 4, 2)
+    for k, v in over.items():
+        obj, field = k.split("__")
+        setattr(a["pi"].w if obj == "w" else (a["pi"].head if obj == "hd" else a[obj]), field, v)
+    return a
+
+
+def _call(L, name, a, null=()):
+    order = ["params", "state", "ctl", "out", "ro", "pi"] + (["ar"] if name.endswith("_ar") else [])
+    return getattr(L, name)(*[None if k in null else C.byref(a[k]) for k in order], None, None)
+
+
+def _refused(L, name, text, null=(), **over):
+    assert _call(L, name, _args(**over), null) != 0, (name, text)
+    assert L.asvrl_last_error().decode() == f"{name}: {text}"
+
+
+@pytest.mark.parametrize("ops", ["bf16", "f32"])
+def test_struct_sizes_and_abi_version(ops):
+    from distributional_rl_decision_and_control_amd import _abi
+    L = _abi.lib(ops)
+    # cvar, robots_per_env, step_add, the four pointers, ld_q
+    assert C.sizeof(_abi.AsvIqnActEx) == 4 + 4 + 8 + 4 * 8 + 8
+    assert L.asvrl_iqn_act_ex_struct_size() == C.sizeof(_abi.AsvIqnActEx)
+    # the trunk, the head, obs_in and step_dev, the five schedule doubles, seed, actions, cvar and its padding
+    assert C.sizeof(_abi.AsvIqnPolicy) == (C.sizeof(_abi.AsvCriticWeights) + C.sizeof(_abi.AsvIqnHead) + 2 * 8 + 5 * 8
+                                           + 8 + 8 + 4 + 4)
+    assert L.asvrl_iqn_policy_struct_size() == C.sizeof(_abi.AsvIqnPolicy)
+    assert L.asvrl_abi_version() == 29 == _abi.ABI_VERSION
+    # no existing struct changed: the sizes of the parent commit
+    assert C.sizeof(_abi.AsvIqnIO) == 224 and C.sizeof(_abi.AsvIqnHead) == 32
+    assert C.sizeof(_abi.AsvCriticWeights) == 16 * 8
+    assert L.asvrl_policy_struct_size() == C.sizeof(_abi.AsvPolicy) == 176
+    assert L.asvrl_dqn_policy_struct_size() == C.sizeof(_abi.AsvDqnPolicy) == 192
+    assert L.asvrl_sac_policy_struct_size() == C.sizeof(_abi.AsvSacPolicy) == 200
+
+
+@pytest.mark.parametrize("ops", ["bf16", "f32"])
+@pytest.mark.parametrize("name", NAMES)
+def test_refusals_of_both_rollout_entry_points(name, ops):
+    from distributional_rl_decision_and_control_amd import _abi
+    L = _abi.lib(ops)
+    for k in ("params", "state", "ctl", "out", "ro"):
+        _refused(L, name, "null argument", null=(k,))
+    _refused(L, name, "null policy", null=("pi",))
+    _refused(L, name, "null obs_in", pi__obs_in=None)
+    _refused(L, name, "is_continuous must be 0 (IQN's actions are indices)", ctl__is_continuous=1)
+    _refused(L, name, "ro->actions must be null (the policy supplies the actions)", ro__actions=P)
+    for img in IMAGES:
+        _refused(L, name, "null IQN image", **{"w__" + img: None})
+    _refused(L, name, "null pi->head.wo_frag", hd__wo_frag=None)
+    _refused(L, name, "null pi->head.bo", hd__bo=None)
+    for n in (0, -1, 33):
+        _refused(L, name, "pi->head.n_actions must be in 1..32", hd__n_actions=n)
+    for cv in (0.0, -0.5, 1.5, float("nan")):
+        _refused(L, name, "pi->cvar must be in (0, 1]", pi__cvar=cv)
+    _refused(L, name, "observation rows must be 16-byte aligned", pi__obs_in=P + 4)
+    _refused(L, name, "observation rows must be 16-byte aligned", out__obs=P + 8)
+    # the rollout's own members, under the new call's name
+    _refused(L, name, "n_steps must be >= 1", ro__n_steps=0)
+    _refused(L, name, "do_dynamics must be 1", ctl__do_dynamics=0)
+    _refused(L, name, "null output", out__reward=None)
+    _refused(L, name, "null state array", state__rs=None)
+    _refused(L, name, "max_robots must be in [1, 256]", state__max_robots=0)
+
+
+@pytest.mark.parametrize("ops", ["bf16", "f32"])
+def test_plain_call_only_refusals(ops):
+    from distributional_rl_decision_and_control_amd import _abi
+    L = _abi.lib(ops)
+    name = "asvrl_iqn_rollout"
+    _refused(L, name, "hold_done needs trainer_deactivate", ro__hold_done=1, ctl__trainer_deactivate=0)
+    _refused(L, name, "noise_mode 0 needs injected noise", ctl__noise_mode=0)
+    _refused(L, name, "hold_done and the env_done record need trainer_deactivate and out->env_done", ro__hold_done=1,
+             out__env_done=None)
+
+
+@pytest.mark.parametrize("ops", ["bf16", "f32"])
+def test_auto_reset_refusals(ops):
+    from distributional_rl_decision_and_control_amd import _abi
+    L = _abi.lib(ops)
+    name = "asvrl_iqn_rollout_ar"
+    _refused(L, name, "null ar (the auto-reset description)", null=("ar",))
+    _refused(L, name, "ro->hold_done cannot be combined with the auto-reset", ro__hold_done=1)
+    _refused(L, name, "noise_mode 0 (recorded noise) cannot cover a sampled reset; Philox noise only (mode 1 or 2)",
+             ctl__noise_mode=0)
+    need = "the auto-reset needs ctl->trainer_deactivate and last->env_done"
+    _refused(L, name, need, out__env_done=None)
+    _refused(L, name, need, ctl__trainer_deactivate=0)
+    _refused(L, name, "observation rows must be 16-byte aligned", ar__obs_prev=P + 4)
+
+
+def _act_args(**over):
+    """Arguments of asvrl_iqn_act_ex that pass every check (B = 0 would return before the launch; the tests
+    override one member into a refusal, so nothing is launched)."""
+    from distributional_rl_decision_and_control_amd import _abi
+    a = dict(w=_abi.AsvCriticWeights(), hd=_abi.AsvIqnHead(), io=_abi.AsvIqnIO(), ex=_abi.AsvIqnActEx())
+    for n in IMAGES:
+        setattr(a["w"], n, P)
+    a["hd"].wo_frag, a["hd"].bo, a["hd"].n_actions = P, P, 9
+    io = a["io"]
+    io.obs, io.ld_obs, io.B, io.N, io.act_out, io.ld_act = P, 40, 185, 32, P, 2
+    io.eps_steps_per_count, io.eps_total, io.eps_fraction = 1.0, 1.0, 1.0
+    ex = a["ex"]
+    ex.cvar, ex.robots_per_env = 1.0, 5
+    for k, v in over.items():
+        obj, field = k.split("__")
+        setattr(a[obj], field, v)
+    return a
+
+
+def _act_refused(L, text, null=(), **over):
+    a = _act_args(**over)
+    rc = L.asvrl_iqn_act_ex(*[None if k in null else C.byref(a[k]) for k in ("w", "hd", "io", "ex")], None)
+    assert rc != 0, text
+    assert L.asvrl_last_error().decode() == text
+
+
+@pytest.mark.parametrize("ops", ["bf16", "f32"])
+def test_refusals_of_the_window_act(ops):
+    from distributional_rl_decision_and_control_amd import _abi
+    L = _abi.lib(ops)
+    for k in ("w", "hd", "io"):
+        _act_refused(L, "asvrl_iqn: null argument", null=(k,))
+    _act_refused(L, "asvrl_iqn_act_ex: null ex", null=("ex",))
+    _act_refused(L, "asvrl_iqn: needs F, or obs with the encoder weights", io__obs=None)
+    _act_refused(L, "asvrl_iqn: needs F, or obs with the encoder weights", w__obj_b=None)
+    _act_refused(L, "asvrl_iqn: ld_obs must cover the packed observation row", io__ld_obs=36)
+    _act_refused(L, "asvrl_iqn: null weight", w__w2_frag=None)
+    _act_refused(L, "asvrl_iqn: bad head", hd__n_actions=33)
+    _act_refused(L, "asvrl_iqn: bad head", hd__bo=None)
+    _act_refused(L, "asvrl_iqn_act_ex: K = 32 quantile samples per state", io__N=8, io__B=184)
+    need = "asvrl_iqn_act_ex: needs act_out with ld_act (or act_pair / rec_row) and the epsilon schedule"
+    _act_refused(L, need, io__act_out=None)
+    _act_refused(L, need, io__ld_act=0)
+    _act_refused(L, need, io__eps_total=0.0)
+    _act_refused(L, need, io__eps_fraction=0.0)
+    for cv in (0.0, -1.0, 1.0001, float("nan")):
+        _act_refused(L, "asvrl_iqn_act_ex: cvar must be in (0, 1]", ex__cvar=cv)
+    _act_refused(L, "asvrl_iqn_act_ex: robots_per_env must be >= 1", ex__robots_per_env=0)
+    _act_refused(L, "asvrl_iqn_act_ex: ld_q must cover n_actions", ex__qmean_out=P, ex__ld_q=8)
+
+
+@pytest.mark.parametrize("ops", ["bf16", "f32"])
+def test_the_existing_act_call_is_unchanged(ops):
+    """asvrl_iqn_act keeps its struct, its checks and their texts: the window form is a call of its own."""
+    from distributional_rl_decision_and_control_amd import _abi
+    L = _abi.lib(ops)
+    for over, text in ((dict(io__N=16, io__B=184), "asvrl_iqn_act: K = 32 quantile samples per state"),
+                       (dict(io__act_out=None), "asvrl_iqn_act: needs act_out, ld_act and the epsilon schedule"),
+                       (dict(hd__n_actions=0), "asvrl_iqn: bad head")):
+        a = _act_args(**over)
+        assert L.asvrl_iqn_act(C.byref(a["w"]), C.byref(a["hd"]), C.byref(a["io"]), None) != 0
+        assert L.asvrl_last_error().decode() == text
