@@ -350,6 +350,17 @@ class AsvRainbowNetIO(C.Structure):
                                                      "dz2a", "dz1v", "dz1a", "dzf")]
 
 
+class AsvRainbowActEx(C.Structure):
+    _fields_ = [("robots_per_env", _I32), ("_pad0", _I32), ("step_add", _I64), ("act_pair", _VP), ("rec_row", _VP),
+                ("env_mask", _VP), ("q_out", _VP), ("ld_q", _I64)]
+
+
+class AsvRainbowPolicy(C.Structure):
+    _fields_ = [("w", AsvRainbowImg), ("support", _VP), ("obs_in", _VP), ("step_dev", _VP),
+                ("eps_steps_per_count", _D), ("eps_total", _D), ("eps_fraction", _D), ("eps_initial", _D),
+                ("eps_final", _D), ("seed", _U64), ("actions", _VP)]
+
+
 EXPORTS = [
     ("asvrl_env_step", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), _VP, _VP, C.POINTER(AsvStepCtl),
                                  C.POINTER(AsvStepOut), _VP]),
@@ -511,6 +522,17 @@ EXPORTS = [
                                        C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvIqnPolicy),
                                        C.POINTER(AsvAutoReset), C.POINTER(AsvEnvLaunch), _VP]),
     ("asvrl_iqn_policy_struct_size", _I64, []),
+    ("asvrl_rainbow_net_act_ex", C.c_int, [C.POINTER(AsvRainbowImg), C.POINTER(AsvRainbowNetIO),
+                                           C.POINTER(AsvRainbowActEx), _VP]),
+    ("asvrl_rainbow_act_ex_struct_size", _I64, []),
+    ("asvrl_rainbow_rollout", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), C.POINTER(AsvStepCtl),
+                                        C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvRainbowPolicy),
+                                        C.POINTER(AsvEnvLaunch), _VP]),
+    ("asvrl_rainbow_rollout_ar", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), C.POINTER(AsvStepCtl),
+                                           C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvRainbowPolicy),
+                                           C.POINTER(AsvAutoReset), C.POINTER(AsvEnvLaunch), _VP]),
+    ("asvrl_rainbow_policy_struct_size", _I64, []),
+    ("asvrl_per_push_window", C.c_int, [C.POINTER(AsvPer), _VP, _VP, _VP, _I32, _VP, _VP, _I32, _VP, _I64, _VP]),
 ]
 
 _libs = {}

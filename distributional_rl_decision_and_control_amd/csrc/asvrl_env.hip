@@ -2013,13 +2013,14 @@ PairLaunch pair_launch(int R, int O, int n_envs, int blk_req, int epb_req, int v
 
 using namespace asvrl;
 
-// ------------------------------------------------------------------ the env step and its ten rollout calls
+// ------------------------------------------------------------------ the env step and its twelve rollout calls
 // One host path. Each call is: env_checks (its arguments), env_plan (the launch shape, and whether the
 // pair-parallel kernel is taken), then launch_groups (that kernel) or, for the rollouts, rollout_fallback (K single
 // steps).
 
 // the groups of checks a call takes beyond the step's own
-enum : unsigned { kRollout = 1, kClosedLoop = 2, kAutoReset = 4, kDqnPolicy = 8, kSacPolicy = 16, kIqnPolicy = 32 };   // (kDqnPolicy, kSacPolicy, kIqnPolicy: with kClosedLoop)
+enum : unsigned { kRollout = 1, kClosedLoop = 2, kAutoReset = 4, kDqnPolicy = 8, kSacPolicy = 16, kIqnPolicy = 32,
+                  kRainbowPolicy = 64 };   // (kDqnPolicy, kSacPolicy, kIqnPolicy, kRainbowPolicy: with kClosedLoop)
 
 static int env_fail(const char* who, const char* what) {
   set_error(std::string(who) + ": " + what);
@@ -2030,17 +2031,20 @@ static int env_fail(const char* who, const char* what) {
     if (!(cond)) return env_fail(who, what);     \
   } while (0)
 
-// The argument checks of the eleven calls, in the order each call reports them (`who` names the call in the error
+// The argument checks of the thirteen calls, in the order each call reports them (`who` names the call in the error
 // text). actions / noise: the single step's; the rollouts carry theirs in ro.
 static int env_checks(const char* who, unsigned kind, const AsvParams* params, const AsvEnvState* state,
                       const double* actions, const double* noise, const AsvStepCtl* ctl, const AsvStepOut* out,
                       const AsvRollout* ro, const AsvPolicy* pi, const AsvDqnPolicy* dq, const AsvSacPolicy* sq,
-                      const AsvAutoReset* ar, const AsvEnvLaunch* launch, const AsvIqnPolicy* iq = nullptr) {
+                      const AsvAutoReset* ar, const AsvEnvLaunch* launch, const AsvIqnPolicy* iq = nullptr,
+                      const AsvRainbowPolicy* rq = nullptr) {
   const bool roll = (kind & kRollout) != 0, closed = (kind & kClosedLoop) != 0, reset = (kind & kAutoReset) != 0;
-  // the closed loop's policy: dq (DQN_Policy), sq (SAC's sampled actor), iq (IQN_Policy), else pi (the Actor)
+  // the closed loop's policy: dq (DQN_Policy), sq (SAC's sampled actor), iq (IQN_Policy), rq (Rainbow_Policy), else
+  // pi (the Actor)
   const bool dqn = (kind & kDqnPolicy) != 0, sac = (kind & kSacPolicy) != 0, iqn = (kind & kIqnPolicy) != 0;
+  const bool rbw = (kind & kRainbowPolicy) != 0;
   const float* pol_obs_in = nullptr;
-  if (closed) pol_obs_in = iqn ? (iq ? iq->obs_in : nullptr) : dqn ? (dq ? dq->obs_in : nullptr) : sac ? (sq ? sq->obs_in : nullptr) : (pi ? pi->obs_in : nullptr);
+  if (closed) pol_obs_in = rbw ? (rq ? rq->obs_in : nullptr) : iqn ? (iq ? iq->obs_in : nullptr) : dqn ? (dq ? dq->obs_in : nullptr) : sac ? (sq ? sq->obs_in : nullptr) : (pi ? pi->obs_in : nullptr);
   ENV_REQUIRE(params && state && ctl && out && (ro || !roll), "null argument");
   if (reset) {   // what the two _ar calls refuse beyond their plain calls' checks
     ENV_REQUIRE(ar != nullptr, "null ar (the auto-reset description)");
@@ -2075,6 +2079,17 @@ static int env_checks(const char* who, unsigned kind, const AsvParams* params, c
     ENV_REQUIRE(iq->head.bo != nullptr, "null pi->head.bo");
     ENV_REQUIRE(iq->head.n_actions >= 1 && iq->head.n_actions <= ASVRL_IQN_MAX_ACTIONS, "pi->head.n_actions must be in 1..32");
     ENV_REQUIRE(iq->cvar > 0.f && iq->cvar <= 1.f, "pi->cvar must be in (0, 1]");
+  } else if (closed && rbw) {   // Rainbow_Policy: asvrl_rainbow_pack's forward images and the support
+    ENV_REQUIRE(ro->actions == nullptr, "ro->actions must be null (the policy supplies the actions)");
+    ENV_REQUIRE(rq != nullptr, "null policy");
+    ENV_REQUIRE(pol_obs_in != nullptr, "null obs_in");
+    ENV_REQUIRE(!ctl->is_continuous, "is_continuous must be 0 (Rainbow's actions are indices)");
+    const AsvRainbowImg& w = rq->w;
+    ENV_REQUIRE(w.enc && w.b_enc && w.v1 && w.a1 && w.v2 && w.a2 && w.vo && w.mo && w.ao && w.b_v1p && w.b_a1p &&
+                    w.b_v2p && w.b_a2p && w.b_vop && w.b_mop && w.b_aop,
+                "null Rainbow image");
+    ENV_REQUIRE(rq->support != nullptr, "null pi->support");
+    ENV_REQUIRE(rq->eps_total > 0.0 && rq->eps_fraction > 0.0, "pi->eps_total and pi->eps_fraction must be > 0");
   } else if (closed) {
     ENV_REQUIRE(ro->actions == nullptr, "ro->actions must be null (the policy supplies the actions)");
     ENV_REQUIRE(dqn ? dq != nullptr : (sac ? sq != nullptr : pi != nullptr), "null policy");
@@ -2365,22 +2380,41 @@ static AsvIqnIO iqn_act_io(const AsvIqnPolicy* iq, const float* x, size_t n, con
   return io;
 }
 
-// The K-launch form of the ten rollout calls (per-robot parameters, layout 2, a carve that does not fit; IQN_Policy always). Per step:
+// act_rainbow's launch over n rows: the window form's outputs are its AsvRainbowActEx's
+static AsvRainbowNetIO rainbow_act_io(const AsvRainbowPolicy* rq, const float* x, size_t n, const int64_t* step) {
+  AsvRainbowNetIO io{};
+  io.x = x;
+  io.ldx = ASVRL_OBS_DIM;
+  io.N = static_cast<int32_t>(n);
+  io.support = rq->support;
+  io.step_dev = step;
+  io.eps_steps_per_count = rq->eps_steps_per_count;
+  io.eps_total = rq->eps_total;
+  io.eps_fraction = rq->eps_fraction;
+  io.eps_initial = rq->eps_initial;
+  io.eps_final = rq->eps_final;
+  io.seed = rq->seed;
+  return io;
+}
+
+// The K-launch form of the twelve rollout calls (per-robot parameters, layout 2, a carve that does not fit; IQN_Policy and
+// Rainbow_Policy always). Per step:
 // the act launch (closed loop), the obs_prev row (auto-reset), the single step and its record launch; then, for the
 // auto-reset, the reset mask and counts and the reset of the ended envs with their observation
 // (asvrl_env_reset_observe, or the two launches where that call does not apply). pi null: the open loop, the actions
 // out of ro; dq instead of pi: DQN_Policy's act launch (asvrl_dqn_act) in the Actor's place; sq: SAC's
 // (asvrl_sac_act, its eps_out and, when deterministic, its zero eps_in behind the actions in the scratch); iq:
-// IQN_Policy's, the only form its two calls have (asvrl_iqn_act_ex: no step-count and no record-copy launch). ar null: a plain call, which alone can hold ended envs (hold_done: env_checks refuses it with ar).
+// IQN_Policy's, the only form its two calls have (asvrl_iqn_act_ex: no step-count and no record-copy launch); rq:
+// Rainbow_Policy's, likewise (asvrl_rainbow_net_act_ex). ar null: a plain call, which alone can hold ended envs (hold_done: env_checks refuses it with ar).
 static int rollout_fallback(const char* who, const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                             const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi, const AsvDqnPolicy* dq,
                             const AsvSacPolicy* sq, const AsvAutoReset* ar, const AsvEnvLaunch* launch, void* stream,
-                            const AsvIqnPolicy* iq = nullptr) {
+                            const AsvIqnPolicy* iq = nullptr, const AsvRainbowPolicy* rq = nullptr) {
   hipStream_t st = as_stream(stream);
-  const bool closed = pi != nullptr || dq != nullptr || sq != nullptr || iq != nullptr;
-  const float* pol_obs = iq != nullptr ? iq->obs_in : dq != nullptr ? dq->obs_in : (sq != nullptr ? sq->obs_in : (pi != nullptr ? pi->obs_in : nullptr));
-  const int64_t* pol_step = iq != nullptr ? iq->step_dev : dq != nullptr ? dq->step_dev : (sq != nullptr ? sq->step_dev : (pi != nullptr ? pi->step_dev : nullptr));
-  double* pol_actions = iq != nullptr ? iq->actions : dq != nullptr ? dq->actions : (sq != nullptr ? sq->actions : (pi != nullptr ? pi->actions : nullptr));
+  const bool closed = pi != nullptr || dq != nullptr || sq != nullptr || iq != nullptr || rq != nullptr;
+  const float* pol_obs = rq != nullptr ? rq->obs_in : iq != nullptr ? iq->obs_in : dq != nullptr ? dq->obs_in : (sq != nullptr ? sq->obs_in : (pi != nullptr ? pi->obs_in : nullptr));
+  const int64_t* pol_step = rq != nullptr ? rq->step_dev : iq != nullptr ? iq->step_dev : dq != nullptr ? dq->step_dev : (sq != nullptr ? sq->step_dev : (pi != nullptr ? pi->step_dev : nullptr));
+  double* pol_actions = rq != nullptr ? rq->actions : iq != nullptr ? iq->actions : dq != nullptr ? dq->actions : (sq != nullptr ? sq->actions : (pi != nullptr ? pi->actions : nullptr));
   const int E = state->n_envs, R = state->max_robots;
   const size_t NT = static_cast<size_t>(E) * R;
   const size_t noise_row = NT * (static_cast<size_t>(state->max_obs) + R) * 5;
@@ -2440,6 +2474,16 @@ static int rollout_fallback(const char* who, const AsvParams* params, const AsvE
       ex.rec_row = pol_actions != nullptr ? pol_actions + static_cast<size_t>(t) * 2 * NT : nullptr;
       ex.env_mask = c.env_mask;
       rc = asvrl_iqn_act_ex(&iq->w, &iq->head, &io, &ex, stream);
+    } else if (rq != nullptr) {
+      // likewise: act_rainbow at step *step_dev + t, the step's pairs and the masked record row in the one launch
+      const AsvRainbowNetIO io = rainbow_act_io(rq, obs_t, NT, pol_step);
+      AsvRainbowActEx ex{};
+      ex.robots_per_env = R;
+      ex.step_add = t;
+      ex.act_pair = act;
+      ex.rec_row = pol_actions != nullptr ? pol_actions + static_cast<size_t>(t) * 2 * NT : nullptr;
+      ex.env_mask = c.env_mask;
+      rc = asvrl_rainbow_net_act_ex(&rq->w, &io, &ex, stream);
     } else if (closed) {
       hipLaunchKernelGGL(policy_step_count_kernel, dim3(1), dim3(1), 0, st, pol_step, step, t);
       if (dq != nullptr) {
@@ -2492,17 +2536,19 @@ static int rollout_fallback(const char* who, const AsvParams* params, const AsvE
   return rc;
 }
 
-// The ten rollout calls: check, plan, zero the counts the window adds to, then the one launch or the fallback.
-// pi, dq, sq or iq: the closed loop under the Actor, DQN_Policy, SAC's sampled actor or IQN_Policy (ro->actions is null then); ar: the auto-reset (Philox noise only: no recorded rows).
+// The twelve rollout calls: check, plan, zero the counts the window adds to, then the one launch or the fallback.
+// pi, dq, sq, iq or rq: the closed loop under the Actor, DQN_Policy, SAC's sampled actor, IQN_Policy or Rainbow_Policy (ro->actions is null then); ar: the auto-reset (Philox noise only: no recorded rows).
 static int rollout_call(const char* who, unsigned kind, const AsvParams* params, const AsvEnvState* state,
                         const AsvStepCtl* ctl, const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi,
                         const AsvDqnPolicy* dq, const AsvSacPolicy* sq, const AsvAutoReset* ar,
-                        const AsvEnvLaunch* launch, void* stream, const AsvIqnPolicy* iq = nullptr) {
-  if (int rc = env_checks(who, kind, params, state, nullptr, nullptr, ctl, out, ro, pi, dq, sq, ar, launch, iq)) return rc;
+                        const AsvEnvLaunch* launch, void* stream, const AsvIqnPolicy* iq = nullptr,
+                        const AsvRainbowPolicy* rq = nullptr) {
+  if (int rc = env_checks(who, kind, params, state, nullptr, nullptr, ctl, out, ro, pi, dq, sq, ar, launch, iq, rq)) return rc;
   if (state->n_envs == 0) return 0;
   EnvPlan P{};
-  // kIqnPolicy never plans the fused launch: IQN's 150 KB image and 16 waves do not fit beside the env's carve
-  if ((kind & kIqnPolicy) == 0)
+  // kIqnPolicy never plans the fused launch: IQN's 150 KB image and 16 waves do not fit beside the env's carve; nor
+  // kRainbowPolicy: its tile is 4 MFMA waves per 32 rows with an LDS layout of its own
+  if ((kind & (kIqnPolicy | kRainbowPolicy)) == 0)
     if (int rc = env_plan(who, state, ctl, launch, pi != nullptr || dq != nullptr || sq != nullptr, ar != nullptr, &P,
                           sq != nullptr ? sizeof(sactile::SacHeadLds) : 0))
       return rc;
@@ -2512,7 +2558,7 @@ static int rollout_call(const char* who, unsigned kind, const AsvParams* params,
   if (ar != nullptr && ar->resets != nullptr &&
       hipMemsetAsync(ar->resets, 0, sizeof(int32_t) * state->n_envs, st) != hipSuccess)
     return check_launch(who);
-  if (!P.fused) return rollout_fallback(who, params, state, ctl, out, ro, pi, dq, sq, ar, launch, stream, iq);
+  if (!P.fused) return rollout_fallback(who, params, state, ctl, out, ro, pi, dq, sq, ar, launch, stream, iq, rq);
   const PairsArgs k{*params, *state, *ctl, *out, ro->actions, ar != nullptr ? nullptr : ro->noise, P.pl.epb, 0};
   if (dq != nullptr && ar != nullptr) return launch_groups(who, P, DqnRolloutArArgs{k, *ro, *dq, *ar, P.ar_off}, st);
   if (dq != nullptr) return launch_groups(who, P, DqnRolloutArgs{k, *ro, *dq}, st);
@@ -2601,6 +2647,22 @@ extern "C" int asvrl_iqn_rollout_ar(const AsvParams* params, const AsvEnvState* 
 }
 
 extern "C" int64_t asvrl_iqn_policy_struct_size(void) { return sizeof(AsvIqnPolicy); }
+
+extern "C" int asvrl_rainbow_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                                     const AsvStepOut* out, const AsvRollout* ro, const AsvRainbowPolicy* pi,
+                                     const AsvEnvLaunch* launch, void* stream) {
+  return rollout_call("asvrl_rainbow_rollout", kRollout | kClosedLoop | kRainbowPolicy, params, state, ctl, out, ro,
+                      nullptr, nullptr, nullptr, nullptr, launch, stream, nullptr, pi);
+}
+
+extern "C" int asvrl_rainbow_rollout_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                                        const AsvStepOut* out, const AsvRollout* ro, const AsvRainbowPolicy* pi,
+                                        const AsvAutoReset* ar, const AsvEnvLaunch* launch, void* stream) {
+  return rollout_call("asvrl_rainbow_rollout_ar", kRollout | kClosedLoop | kAutoReset | kRainbowPolicy, params, state,
+                      ctl, out, ro, nullptr, nullptr, nullptr, ar, launch, stream, nullptr, pi);
+}
+
+extern "C" int64_t asvrl_rainbow_policy_struct_size(void) { return sizeof(AsvRainbowPolicy); }
 
 extern "C" int64_t asvrl_autoreset_struct_size(void) { return sizeof(AsvAutoReset); }
 

@@ -117,10 +117,11 @@ __global__ __launch_bounds__(kTreeThreads) void per_tree_blocks_kernel(float* __
 }
 
 // Work a push / priority update finishes in its last (one-workgroup) launch instead of launches of their own
-// (asvrl_per_push_ex, asvrl_per_update_ex): a device step counter advanced by one, and the mean of the update's
-// values in a fixed order.
+// (asvrl_per_push_ex, asvrl_per_update_ex): a device step counter advanced by one (asvrl_per_push_window: by the
+// window's K), and the mean of the update's values in a fixed order.
 struct TopExtra {
   int64_t* counter;
+  int64_t counter_by = 1;
   const float* mean_in;
   int mean_n;
   float* mean_out;
@@ -148,7 +149,7 @@ __global__ __launch_bounds__(kTopThreads) void per_tree_top_kernel(float* __rest
     if (nx >= C) state[1] = 1;           // full = full or index == 0 after a wrap (:147)
     state[0] = nx % C;
   }
-  if (threadIdx.x == 0 && ex.counter != nullptr) ex.counter[0] += 1;
+  if (threadIdx.x == 0 && ex.counter != nullptr) ex.counter[0] += ex.counter_by;
   if (ex.mean_out != nullptr) {   // thread t sums values t, t + 1024, ... in order, then a fixed pairwise tree
     float v = 0.f;
     for (int i = threadIdx.x; i < ex.mean_n; i += kTopThreads) v += ex.mean_in[i];
@@ -366,9 +367,11 @@ int check_per(const AsvPer* per, const char* what) {
 
 using namespace asvrl;
 
-extern "C" int asvrl_per_push_ex(const AsvPer* per, const float* obs, const int8_t* obj_cnt, const double* actions,
-                                 int32_t action_dim, const double* reward, const uint8_t* done, int32_t n,
-                                 int64_t* step_counter, void* stream) {
+// asvrl_per_push_ex and asvrl_per_push_window: the append of n = m * stride rows, the rebuild and the ring advance,
+// the step counter advanced by counter_by in the last launch
+static int per_push(const AsvPer* per, const float* obs, const int8_t* obj_cnt, const double* actions,
+                    int32_t action_dim, const double* reward, const uint8_t* done, int32_t n, int64_t* step_counter,
+                    int64_t counter_by, void* stream) {
   if (int rc = check_per(per, "asvrl_per_push")) return rc;
   ASVRL_REQUIRE(obs && obj_cnt && actions && reward && done, "asvrl_per_push: null argument");
   ASVRL_REQUIRE(action_dim >= 1, "asvrl_per_push: action_dim >= 1");
@@ -381,7 +384,22 @@ extern "C" int asvrl_per_push_ex(const AsvPer* per, const float* obs, const int8
   if (int rc = check_launch("asvrl_per_push")) return rc;
   TopExtra ex{};
   ex.counter = step_counter;
+  ex.counter_by = counter_by;
   return launch_rebuild(*per, n, st, "asvrl_per_push(tree)", ex);
+}
+
+extern "C" int asvrl_per_push_ex(const AsvPer* per, const float* obs, const int8_t* obj_cnt, const double* actions,
+                                 int32_t action_dim, const double* reward, const uint8_t* done, int32_t n,
+                                 int64_t* step_counter, void* stream) {
+  return per_push(per, obs, obj_cnt, actions, action_dim, reward, done, n, step_counter, 1, stream);
+}
+
+extern "C" int asvrl_per_push_window(const AsvPer* per, const float* obs, const int8_t* obj_cnt,
+                                     const double* actions, int32_t action_dim, const double* reward,
+                                     const uint8_t* done, int32_t n, int64_t* step_counter, int64_t counter_by,
+                                     void* stream) {
+  ASVRL_REQUIRE(counter_by >= 1, "asvrl_per_push_window: counter_by must be >= 1");
+  return per_push(per, obs, obj_cnt, actions, action_dim, reward, done, n, step_counter, counter_by, stream);
 }
 
 extern "C" int asvrl_per_push(const AsvPer* per, const float* obs, const int8_t* obj_cnt, const double* actions,

@@ -19,6 +19,9 @@
 // Modes: ACT     argmax_k Q[k] with epsilon-greedy on the device step counter (act_out, f64)
 //        ARGMAX  argmax_k Q[k] (act_idx; the online net on s_{t+n})
 //        PICK    p[a*] for a* = act_idx[row] (the target net on s_{t+n}, p_out [N][51])
+//        ACT_EX  ACT as the rollout windows launch it (asvrl_rainbow_net_act_ex): step + step_add, always drawn; the
+//                (index, 0.0) pair and its masked record row; Q[k] of every action (q_out). An instantiation of its
+//                own with arguments of its own (RbExArgs), so the three modes above keep their code
 #include "asvrl_common.h"
 #include "asvrl_mfma.h"
 #include "asvrl_lds.h"
@@ -29,11 +32,15 @@ namespace {
 constexpr int kAtoms = 51, kActs = 25, kAP = 64, kEnc = 256, kHid = 128, kObsK = 32;
 constexpr int kSelfF = 56, kObjF = 40, kSelfIn = 7, kObjIn = 5, kObjN = 5;
 constexpr int kNW = 4;
-enum { RB_ACT = 0, RB_ARGMAX = 1, RB_PICK = 2 };
+enum { RB_ACT = 0, RB_ARGMAX = 1, RB_PICK = 2, RB_ACT_EX = 3 };
 
 struct RbArgs {
   AsvRainbowImg w;
   AsvRainbowNetIO io;
+};
+
+struct RbExArgs : RbArgs {   // ACT_EX's kernel argument
+  AsvRainbowActEx ex;
 };
 
 struct RbLds {
@@ -265,8 +272,24 @@ __device__ __forceinline__ float fexp(float x) {
 #endif
 }
 
-template <int MODE>
-__global__ __launch_bounds__(kNW * 64) void rainbow_net_kernel(RbArgs a) {
+// ACT_EX asks for 3 waves per SIMD, ACT's occupancy: its q_out store costs two more VGPRs than ACT's 135 (+ 32 AGPRs),
+// one allocation granule past the 168 that three waves leave each, and the compiler drops to 2 waves unless told;
+// told, it takes the MFMA results in VGPRs (166, no AGPRs, no scratch). 0: no request, the other modes' code as it was.
+// The window at 4096 x 5, K = 64: 62.6-62.8 us per step with the request, 68.4-68.6 without
+// (profiles/rainbow_act_ex_waves_ab.txt; ASVRL_RB_EX_WAVES is the A/B's switch).
+// The f32 parity build makes no request: 196 VGPRs + 32 AGPRs, 2 waves per SIMD, no scratch.
+#ifndef ASVRL_RB_EX_WAVES
+#if ASVRL_OPERAND_F32
+#define ASVRL_RB_EX_WAVES 0
+#else
+#define ASVRL_RB_EX_WAVES 3
+#endif
+#endif
+constexpr int kExWaves = ASVRL_RB_EX_WAVES;
+template <int MODE, class ARGS = RbArgs>
+__global__ __launch_bounds__(kNW * 64) __attribute__((amdgpu_waves_per_eu(MODE == RB_ACT_EX ? kExWaves : 0)))
+void rainbow_net_kernel(ARGS a) {
+  constexpr bool EX = MODE == RB_ACT_EX;
   __shared__ __attribute__((aligned(16))) RbLds L;
   const AsvRainbowNetIO& io = a.io;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = lane >> 5, r = lane & 31;
@@ -328,6 +351,9 @@ __global__ __launch_bounds__(kNW * 64) void rainbow_net_kernel(RbArgs a) {
       se = half_sum(se);
       sz = half_sum(sz);
       const float Q = sz / se;
+      if constexpr (EX) {   // both halves hold Q after half_sum: the h == 0 lane of a valid row stores it
+        if (a.ex.q_out != nullptr && valid && h == 0) a.ex.q_out[static_cast<int64_t>(row) * a.ex.ld_q + k] = Q;
+      }
       if (Q > bq) {   // actions ascend within the wave: ties keep the first
         bq = Q;
         bk = k;
@@ -371,8 +397,9 @@ __global__ __launch_bounds__(kNW * 64) void rainbow_net_kernel(RbArgs a) {
     // epsilon-greedy (agent.py:318-322): greedy iff random() > eps, else a uniform action; eps: the
     // linear schedule of the device step counter (trainer.py:257-264); the draws of rainbow_act_kernel
     double act = static_cast<double>(bk);
-    if (io.step_dev != nullptr) {
-      const uint64_t step = static_cast<uint64_t>(*io.step_dev);
+    if (EX || io.step_dev != nullptr) {
+      uint64_t step = io.step_dev != nullptr ? static_cast<uint64_t>(*io.step_dev) : 0ull;
+      if constexpr (EX) step += static_cast<uint64_t>(a.ex.step_add);
       const double progress = static_cast<double>(step) * io.eps_steps_per_count / io.eps_total;
       const double eps = progress < io.eps_fraction
                              ? io.eps_initial + (progress / io.eps_fraction) * (io.eps_final - io.eps_initial)
@@ -383,7 +410,19 @@ __global__ __launch_bounds__(kNW * 64) void rainbow_net_kernel(RbArgs a) {
       const double c = (static_cast<double>(u.x >> 8) + 1.0) * (1.0 / 16777216.0);   // (0, 1]
       if (!(c > eps)) act = static_cast<double>(u.y % kActs);
     }
-    io.act_out[static_cast<int64_t>(row) * io.ld_act] = act;
+    if constexpr (EX) {   // (row < N here: the rows past N returned above)
+      if (io.act_out != nullptr) io.act_out[static_cast<int64_t>(row) * io.ld_act] = act;
+      if (a.ex.act_pair != nullptr) {
+        a.ex.act_pair[2 * static_cast<int64_t>(row)] = act;
+        a.ex.act_pair[2 * static_cast<int64_t>(row) + 1] = 0.0;
+      }
+      if (a.ex.rec_row != nullptr && (a.ex.env_mask == nullptr || a.ex.env_mask[row / a.ex.robots_per_env] != 0)) {
+        a.ex.rec_row[2 * static_cast<int64_t>(row)] = act;
+        a.ex.rec_row[2 * static_cast<int64_t>(row) + 1] = 0.0;
+      }
+    } else {
+      io.act_out[static_cast<int64_t>(row) * io.ld_act] = act;
+    }
     if (io.act_idx != nullptr) io.act_idx[row] = bk;
   }
 }
@@ -828,6 +867,27 @@ extern "C" int asvrl_rainbow_net_act(const AsvRainbowImg* w, const AsvRainbowNet
   if (io->N <= 0) return 0;
   return launch_net(RB_ACT, w, io, stream);
 }
+
+extern "C" int asvrl_rainbow_net_act_ex(const AsvRainbowImg* w, const AsvRainbowNetIO* io, const AsvRainbowActEx* ex,
+                                        void* stream) {
+  if (int rc = check_img(w, io)) return rc;
+  ASVRL_REQUIRE(ex != nullptr, "asvrl_rainbow_net_act_ex: null ex");
+  ASVRL_REQUIRE((io->act_out || ex->act_pair || ex->rec_row) && (!io->act_out || io->ld_act >= 1) &&
+                    io->eps_total > 0.0 && io->eps_fraction > 0.0,
+                "asvrl_rainbow_net_act_ex: needs act_out with ld_act (or act_pair / rec_row) and the epsilon schedule");
+  ASVRL_REQUIRE(ex->robots_per_env >= 1, "asvrl_rainbow_net_act_ex: robots_per_env must be >= 1");
+  ASVRL_REQUIRE(!ex->q_out || ex->ld_q >= kActs, "asvrl_rainbow_net_act_ex: ld_q must be >= 25");
+  if (io->N <= 0) return 0;
+  RbExArgs a;
+  a.w = *w;
+  a.io = *io;
+  a.ex = *ex;
+  hipLaunchKernelGGL((rainbow_net_kernel<RB_ACT_EX, RbExArgs>), dim3((io->N + 31) / 32), dim3(kNW * 64), 0,
+                     as_stream(stream), a);
+  return check_launch("asvrl_rainbow_net_act_ex");
+}
+
+extern "C" int64_t asvrl_rainbow_act_ex_struct_size(void) { return sizeof(AsvRainbowActEx); }
 
 extern "C" int asvrl_rainbow_net_argmax(const AsvRainbowImg* w, const AsvRainbowNetIO* io, void* stream) {
   if (int rc = check_img(w, io)) return rc;

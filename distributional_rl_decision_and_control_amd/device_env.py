@@ -295,13 +295,20 @@ class DeviceEnvBatch:
         drawn in the kernel on (global row, step, policy_seed) -- and step(act64, is_continuous=False, ...); "actions"
         holds (action index, 0.0). The act stays a launch of its own per step (it is not fused into the env kernel),
         all enqueued by the one call. cvar in (0, 1] (an IqnPack only; ValueError otherwise, and outside the range):
-        act_iqn's risk distortion, every tau times cvar."""
-        from .fused_dqn import DqnPack   # (fused_dqn, fused_sac and fused_iqn import nothing from this module)
+        act_iqn's risk distortion, every tau times cvar.
+        A fused_rainbow.RainbowPack (Rainbow_Policy; kind "rainbow") goes to asvrl_rainbow_rollout /
+        asvrl_rainbow_rollout_ar: the rounds are fused_rainbow.rainbow_act(pack, obs, act64, step, *eps, policy_seed)
+        -- the pack's images as its last refresh() left them, noisy (training mode) or mu only (eval mode) -- and
+        step(act64, is_continuous=False, ...); "actions" holds (action index, 0.0). As for IQN the act is a launch of
+        its own per step (asvrl_rainbow_net_act_ex), all enqueued by the one call; cvar and deterministic stay
+        ValueErrors for it."""
+        from .fused_dqn import DqnPack   # (the fused_* modules import nothing from this module)
         from .fused_iqn import IqnPack
+        from .fused_rainbow import RainbowPack
         from .fused_sac import SacActorPack
         K, NT = int(K), self.n_envs * self.max_robots
-        iqn = isinstance(pack, IqnPack)
-        assert iqn or pack.kind == "actor"
+        iqn, rb = isinstance(pack, IqnPack), isinstance(pack, RainbowPack)
+        assert iqn or rb or pack.kind == "actor"
         dqn, sac = isinstance(pack, DqnPack), isinstance(pack, SacActorPack)
         cvar = float(cvar)
         if not 0.0 < cvar <= 1.0:
@@ -316,7 +323,7 @@ class DeviceEnvBatch:
         if step_dev is not None:
             assert step_dev.dtype == torch.int64 and step_dev.numel() >= 1
         b = self._rollout_args("policy_rollout", K, {"actions": ((NT, 2), torch.float64, 0)}, noise=noise, keep=keep,
-                               hold_done=hold_done, is_continuous=not (dqn or iqn), trainer_deactivate=trainer_deactivate,
+                               hold_done=hold_done, is_continuous=not (dqn or iqn or rb), trainer_deactivate=trainer_deactivate,
                                seed=seed, counter=counter, counter_dev=counter_dev, gamma=gamma, env_mask=env_mask,
                                obs=obs, obj_cnt=obj_cnt, fast_noise=fast_noise, launch=launch, auto_reset=auto_reset)
         if b.ar is not None:
@@ -324,6 +331,9 @@ class DeviceEnvBatch:
         if iqn:
             pi = _abi.AsvIqnPolicy()
             pi.w, pi.head, pi.cvar = pack.struct, pack.head, cvar
+        elif rb:
+            pi = _abi.AsvRainbowPolicy()
+            pi.w, pi.support = pack.struct, pack.support.data_ptr()
         else:
             pi = _abi.AsvDqnPolicy() if dqn else (_abi.AsvSacPolicy() if sac else _abi.AsvPolicy())
             pi.w = pack.dw if dqn else (pack.sw if sac else pack.w)
@@ -335,7 +345,7 @@ class DeviceEnvBatch:
          pi.eps_final) = (float(v) for v in eps)
         pi.seed = int(policy_seed) & 0xFFFFFFFFFFFFFFFF
         pi.actions = b.rec["actions"].data_ptr() if "actions" in b.rec else None
-        name = ("asvrl_iqn_rollout" if iqn else "asvrl_dqn_rollout" if dqn else
+        name = ("asvrl_iqn_rollout" if iqn else "asvrl_rainbow_rollout" if rb else "asvrl_dqn_rollout" if dqn else
                 "asvrl_sac_rollout" if sac else "asvrl_policy_rollout")
         return self._rollout_call(b, pack.L, name, [C.byref(pi)], stream)
 

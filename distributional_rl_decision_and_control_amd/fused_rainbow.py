@@ -25,6 +25,13 @@ the parity build).
 
 The online net's noise is never resampled during training, as in the reference (its reset_noise is
 only called on the target, agent.py:610). The target noise comes from Philox instead of torch.randn.
+
+The closed-loop windows (csrc/asvrl_env.hip, asvrl_rainbow_rollout / asvrl_rainbow_rollout_ar) and the device
+evaluation take a RainbowPack: per step they launch the window form of the act pass (asvrl_rainbow_net_act_ex: the
+same tile with the step offset, the (index, 0.0) pair, its masked record row and the action values), then the env
+step; the act is not fused into the env kernel. Training acts on the noisy weights (FusedRainbow.window_pack, the
+learner's own images); evaluation acts as the reference's policy_local.eval() does, on weight_mu / bias_mu only
+(FusedRainbow.eval_pack: asvrl_rainbow_pack reading the mu tensors directly, no compose launch).
 """
 import ctypes as C
 
@@ -146,11 +153,13 @@ BIAS_SIZES = {"b_enc": 256, "b_v1p": 128, "b_a1p": 128, "b_v2p": 128, "b_a2p": 1
 
 class RainbowNetImage:
     """Fragment images of one Rainbow_Policy for asvrl_rainbow_net_*: the encoders and the composed noisy
-    layers of `noisy` (a NoisyPack of the same net), packed by refresh() (asvrl_rainbow_pack)."""
+    layers of `noisy` (a NoisyPack of the same net), packed by refresh() (asvrl_rainbow_pack). noisy=None: the
+    eval-mode images -- the pack reads each layer's weight_mu / bias_mu in place (NoisyLinear.forward when not
+    training, Rainbow_model.py:47-51), so nothing is composed."""
 
     def __init__(self, net, noisy, operands="bf16", train=False):
         self.L = _abi.lib(operands)
-        dev = noisy.flat.device
+        dev = net.hidden_layer_v.weight_mu.device if noisy is None else noisy.flat.device
         sizes = dict(IMG_SIZES, **(IMGT_SIZES if train else {}))
         self.img = torch.zeros(sum(sizes.values()), dtype=_abi.operand_dtype(operands), device=dev)
         self.bias = torch.zeros(sum(BIAS_SIZES.values()), dtype=torch.float32, device=dev)
@@ -164,7 +173,11 @@ class RainbowNetImage:
             setattr(st, n, self.bias[off:off + k].data_ptr())
             off += k
         self.struct = st
-        W, _ = noisy.weights()
+        if noisy is None:
+            W = {n: (getattr(net, n).weight_mu, getattr(net, n).bias_mu) for n in NOISY}
+            assert all(t.is_contiguous() and t.dtype == torch.float32 for pair in W.values() for t in pair)
+        else:
+            W, _ = noisy.weights()
         se, oe = net.self_encoder[0], net.object_encoder[0]
         src = _abi.AsvRainbowSrc()
         src.self_w, src.self_b, src.obj_w, src.obj_b = (t.data_ptr() for t in (se.weight, se.bias, oe.weight, oe.bias))
@@ -191,9 +204,85 @@ class RainbowNetImage:
         _abi.check(getattr(self.L, fn)(C.byref(self.struct), C.byref(io), _abi.stream_ptr(stream)), fn, self.L)
 
 
+class RainbowPack:
+    """What the closed-loop windows and the device evaluation take for Rainbow (DeviceEnvBatch.policy_rollout,
+    VecMarineNavEnv.policy_rollout, DeviceEvaluator.run, rainbow_act): the library L, the AsvRainbowImg struct and the
+    f32 support. noisy=True: training mode, refresh() composes W = mu + sigma * eps (asvrl_noisy_compose) and packs;
+    noisy=False: eval mode (policy_local.eval()), refresh() packs weight_mu / bias_mu directly -- one launch, no
+    compose. The images are as the last refresh() left them: call it after the parameters change. Build the pack
+    after anything that re-points the parameters (FusedAdam)."""
+    kind = "rainbow"
+
+    def __init__(self, net, operands="bf16", noisy=True, support=None, _share=None):
+        self.net, self.operands, self.noisy = net, operands, bool(noisy)
+        if _share is not None:   # FusedRainbow.window_pack: the learner's own NoisyPack and image, nothing allocated
+            self.noisy_pack, self.image = _share
+        else:
+            self.noisy_pack = NoisyPack(net) if self.noisy else None
+            self.image = RainbowNetImage(net, self.noisy_pack, operands)
+        self.L, self.struct = self.image.L, self.image.struct
+        dev = self.image.img.device
+        if support is None:
+            support = torch.linspace(-1.0, 1.0, ATOMS, device=dev)
+        self.support = support.to(device=dev, dtype=torch.float32).contiguous()
+        assert self.support.numel() == ATOMS
+        if _share is None:
+            self.refresh()
+
+    def refresh(self, stream=None):
+        """The images from the parameters as they are now: compose (noisy only), then asvrl_rainbow_pack."""
+        if self.noisy:
+            self.noisy_pack.compose(stream)
+        self.image.refresh(stream)
+
+
+def rainbow_act(pack, obs, act64, step_dev, steps_per_count, total, fraction, initial, final, seed, q_out=None,
+                step_add=0, env_mask=None, robots_per_env=1, stream=None, act_pair=None, actions_rec=None):
+    """act_rainbow (agent.py:308-324) for every observation row of `obs` (f32 [rows, >= 40]) on the images of
+    `pack` (a RainbowPack, as its last refresh() left them) into act64[:, 0] (f64 action index): asvrl_rainbow_net_act.
+    step_dev: the i64 device step counter of the epsilon schedule and the exploration draw (None: greedy, nothing is
+    drawn). The window form (asvrl_rainbow_net_act_ex, taken only when one of these is set): step_add is added to the
+    step counter's value (and the draw is always made; None counts as 0); q_out (f32 [rows, >= 25]) receives
+    Q[k] = sum_atoms p[k] z; act_pair (f64 [rows, 2]) receives (index, 0.0) on every row, what step() takes with
+    is_continuous=False; actions_rec (f64 [rows, 2]) receives the same pair for the rows of envs with env_mask != 0
+    (u8, one per robots_per_env rows; None: every row). act64 may be None when act_pair or actions_rec is given."""
+    io = pack.image.io(obs, pack.support, act_out=act64.data_ptr() if act64 is not None else None,
+                       ld_act=act64.stride(0) if act64 is not None else 0,
+                       step_dev=step_dev.data_ptr() if step_dev is not None else None,
+                       eps_steps_per_count=float(steps_per_count), eps_total=float(total),
+                       eps_fraction=float(fraction), eps_initial=float(initial), eps_final=float(final),
+                       seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
+    if int(step_add) == 0 and q_out is None and act_pair is None and actions_rec is None and env_mask is None:
+        pack.image.run("asvrl_rainbow_net_act", io, stream)
+        return
+    ex = _abi.AsvRainbowActEx()
+    ex.robots_per_env, ex.step_add = int(robots_per_env), int(step_add)
+    if act_pair is not None:
+        assert act_pair.dtype == torch.float64 and act_pair.is_contiguous() and tuple(act_pair.shape) == (io.N, 2)
+        ex.act_pair = act_pair.data_ptr()
+    if q_out is not None:
+        assert q_out.dtype == torch.float32 and q_out.stride(-1) == 1 and q_out.shape[0] == io.N
+        assert q_out.shape[1] >= ACTIONS
+        ex.q_out, ex.ld_q = q_out.data_ptr(), q_out.stride(0)
+    if actions_rec is not None:
+        assert actions_rec.dtype == torch.float64 and actions_rec.is_contiguous()
+        assert tuple(actions_rec.shape) == (io.N, 2)
+        ex.rec_row = actions_rec.data_ptr()
+    if env_mask is not None:
+        assert env_mask.dtype == torch.uint8 and env_mask.is_contiguous()
+        assert env_mask.numel() * int(robots_per_env) >= io.N
+        ex.env_mask = env_mask.data_ptr()
+    _abi.check(pack.L.asvrl_rainbow_net_act_ex(C.byref(pack.struct), C.byref(io), C.byref(ex),
+                                               _abi.stream_ptr(stream)), "asvrl_rainbow_net_act_ex", pack.L)
+
+
 class FusedRainbow:
-    """Packs and buffers (pointer-stable for graph replay) of the batched Rainbow path."""
-    actor_pack = policy_pack = None   # act_rainbow runs inside its own kernel, not in the closed-loop windows
+    """Packs and buffers (pointer-stable for graph replay) of the batched Rainbow path. window_pack (the training-mode
+    RainbowPack over the learner's own noisy images) is what VecTrainer._collect_window takes; eval_pack (the mu-only
+    images) is what the device evaluation takes (DeviceEvaluator.run, Trainer's "device_eval"). policy_pack and
+    actor_pack stay None, so VecTrainer.policy_pack(), collect, greedy_episodes and evaluate still refuse a Rainbow
+    trainer."""
+    actor_pack = policy_pack = None   # act_rainbow runs in its own launch (the windows compose it per step)
 
     def __init__(self, local, target, B, support, operands="bf16"):
         self.local, self.target, self.B = local, target, B
@@ -219,6 +308,19 @@ class FusedRainbow:
         self.tpack.compose()
         self.img.refresh()
         self.timg.refresh()
+        # the windows' training-mode pack: this learner's own NoisyPack and image (its refresh() is what act() does
+        # first), and the evaluation's mu-only image set
+        self.window_pack = RainbowPack(local, operands, noisy=True, support=self.support, _share=(self.pack, self.img))
+        self._eval_pack = RainbowPack(local, operands, noisy=False, support=self.support)
+
+    @property
+    def eval_pack(self):
+        """The eval-mode RainbowPack of the online net (weight_mu / bias_mu only, as policy_local.eval()). Reading
+        the attribute enqueues its asvrl_rainbow_pack launch on the current stream, so it is current after any number
+        of eager or graph-replayed updates. Not to be read inside a graph capture: the launch would become part of
+        the graph; hold the returned pack instead and call its refresh() where the launch belongs."""
+        self._eval_pack.refresh()
+        return self._eval_pack
 
     def target_changed(self):
         self.tpack.compose()
@@ -243,8 +345,7 @@ class FusedRainbow:
     @torch.no_grad()
     def act(self, obs_rows, actions64, step_dev, steps_per_count, total, fraction, initial, final, seed):
         """act_rainbow for every row (training mode: noisy online weights), epsilon-greedy."""
-        self.pack.compose()
-        self.img.refresh()
+        self.window_pack.refresh()
         io = self.img.io(obs_rows, self.support, act_out=actions64.data_ptr(), ld_act=actions64.stride(0),
                          step_dev=step_dev.data_ptr(), eps_steps_per_count=float(steps_per_count),
                          eps_total=float(total), eps_fraction=float(fraction), eps_initial=float(initial),

@@ -258,11 +258,36 @@ class DevicePER:
         """append() for n = m * stride rows (time-major); rows with obj_cnt < 0 become blank slots.
         step_counter: a device int64 [1] advanced by one in the push's last launch (asvrl_per_push_ex)."""
         n = obs.shape[0]
-        adim = actions.shape[1] if actions.dim() == 2 else 1
+        adim = 1
+        if actions.dim() == 2:   # the row stride, not the width: a column view of wider rows reads its own column
+            assert actions.stride(1) == 1, "action rows must be contiguous"
+            adim = actions.stride(0) if n > 1 else actions.shape[1]
         rc = _abi.lib().asvrl_per_push_ex(C.byref(self._s), _abi.ptr(obs), _abi.ptr(obj_cnt), _abi.ptr(actions),
                                           adim, _abi.ptr(reward), _abi.ptr(done), n, _abi.ptr(step_counter),
                                           _abi.stream_ptr(stream))
         _abi.check(rc, "asvrl_per_push")
+        self.pushed += n
+
+    def push_window(self, buf, K, counter_inc=None, counter_by=None, stream=None):
+        """The push of a whole K-step rollout window in one call (asvrl_per_push_window): the rows, tree, timesteps
+        and ring state of K push() calls on steps t = 0..K-1. buf: a dict or namespace of the window's [K, NT, ...]
+        records obs_prev (the rows the policy acted on), obj_cnt, actions ([K, NT, 2] f64, column 0 read), reward and
+        done, as a rollout with auto_reset keeps them, NT = stride. counter_inc: a device int64 [1] advanced by
+        counter_by (default K) in the push's last launch."""
+        get = buf.get if isinstance(buf, dict) else (lambda k: getattr(buf, k))
+        obs, cnt, actions, reward, done = (get(k) for k in ("obs_prev", "obj_cnt", "actions", "reward", "done"))
+        K = int(K)
+        NT = obs.shape[1]
+        for t in (obs, cnt, actions, reward, done):
+            assert t.is_contiguous() and t.shape[0] == K and t.shape[1] == NT
+        assert obs.dtype == torch.float32 and obs.shape[2] == OBS_DIM and cnt.dtype == torch.int8
+        assert actions.dtype == torch.float64 and actions.dim() == 3 and actions.shape[2] == 2
+        assert reward.dtype == torch.float64 and done.dtype == torch.uint8
+        n = K * NT
+        rc = _abi.lib().asvrl_per_push_window(C.byref(self._s), _abi.ptr(obs), _abi.ptr(cnt), _abi.ptr(actions), 2,
+                                              _abi.ptr(reward), _abi.ptr(done), n, _abi.ptr(counter_inc),
+                                              int(K if counter_by is None else counter_by), _abi.stream_ptr(stream))
+        _abi.check(rc, "asvrl_per_push_window")
         self.pushed += n
 
     def num_elements(self):

@@ -13,6 +13,10 @@ actor_pack stay None, so VecTrainer's own policy_pack() / collect / greedy_episo
 FusedIQNState has window_pack too, its local IqnPack: the same three take it (per step the window launches the act
 pass, asvrl_iqn_act_ex, and then the env step; policy_rollout and run also take act_iqn's cvar), and the same four
 still refuse IQN.
+FusedRainbow has two RainbowPacks: window_pack, the training-mode pack over its own noisy images, is what
+VecTrainer._collect_window takes (the window is pushed into the prioritised replay by DevicePER.push_window), and
+eval_pack, the mu-only images of policy_local.eval(), is what DeviceEvaluator.run and Trainer's "device_eval" take
+(per step asvrl_rainbow_net_act_ex, then the env step). The same four still refuse Rainbow.
 """
 from dataclasses import dataclass
 from typing import Callable, Optional

@@ -11,7 +11,8 @@ per-robot bookkeeping in Python. DeviceEvaluator keeps the same episodes in Devi
   * an evaluation is the observation pass and then closed-loop windows of `chunk` steps, one launch each
     (DeviceEnvBatch.policy_rollout with hold_done, the greedy Actor of an MlpPack, the greedy DQN_Policy of a
     DqnPack, SAC's actor of a SacActorPack, sampled as act_sac samples or its mean action, or the greedy IQN_Policy
-    of an IqnPack at a risk level cvar, its act launch and the step enqueued per step by the one call), or, teacher-forced, open-loop windows over a caller's action table (DeviceEnvBatch.rollout);
+    of an IqnPack at a risk level cvar or the greedy Rainbow_Policy of a RainbowPack (eval mode: mu-only images), the
+    act launch and the step of these two enqueued per step by the one call), or, teacher-forced, open-loop windows over a caller's action table (DeviceEnvBatch.rollout);
   * behind every window one asvrl_eval_metrics launch folds the window's records into the evaluation's carried
     state by trainer.py:286-303: discounted return, time, energy, deactivation, and the evaluation's end rule (the
     step limit, ANY collision, or every robot deactivated). Its `alive` output is the next window's env_mask;
@@ -33,6 +34,7 @@ from ..device_env import DeviceEnvBatch
 from ..envs.marinenav.env import MarineNavEnv3, set_batch_params
 from ..fused_dqn import DqnPack
 from ..fused_iqn import IqnPack
+from ..fused_rainbow import RainbowPack
 from ..fused_sac import SacActorPack
 
 RECORDS = ("reward", "info", "rs")
@@ -207,7 +209,9 @@ class DeviceEvaluator:
         under policy_seed + g: rows are batch-local, so two groups share no draws) or, with deterministic=True (a
         ValueError for any other pack), takes its mean action, or IQN's IqnPack, greedy over the mean of K = 32
         quantile samples whose fractions are drawn per act (group g under policy_seed + g, as for SAC) and, with
-        cvar in (0, 1] (a ValueError for any other pack and outside the range), distorted as act_iqn(cvar=) does; or actions: a [T, NT, 2] f64 table per group (a tensor when there is one group, else a list)
+        cvar in (0, 1] (a ValueError for any other pack and outside the range), distorted as act_iqn(cvar=) does, or
+        Rainbow's RainbowPack, greedy on the images of its last refresh() (FusedRainbow.eval_pack: mu only, as the
+        reference's policy_local.eval(); group g under policy_seed + g as well, though at epsilon 0 nothing is drawn); or actions: a [T, NT, 2] f64 table per group (a tensor when there is one group, else a list)
         applied open loop, with noise ([T, NT, O + R, 5] f64 per group) or the Philox stream. is_continuous: what
         the table's rows are -- True (also None, the default) thrust commands, False column 0 is the action index;
         with a pack it follows the pack (None) and a value that contradicts it is a ValueError. obs_noise: the observation pass's explicit
@@ -219,12 +223,12 @@ class DeviceEvaluator:
         if (pack is None) == (actions is None):
             raise ValueError("run takes the Actor's pack or an action table, not both")
         iqn = isinstance(pack, IqnPack)
-        if pack is not None and not iqn and pack.kind != "actor":
+        if pack is not None and not iqn and not isinstance(pack, RainbowPack) and pack.kind != "actor":
             raise ValueError("run: pack must be an MlpPack of kind 'actor'")
         if (pack is not None and is_continuous is not None
-                and bool(is_continuous) == isinstance(pack, (DqnPack, IqnPack))):
-            raise ValueError("run: is_continuous=%s does not match the pack (a DqnPack or IqnPack picks discrete "
-                             "actions, the Actor continuous ones)" % bool(is_continuous))
+                and bool(is_continuous) == isinstance(pack, (DqnPack, IqnPack, RainbowPack))):
+            raise ValueError("run: is_continuous=%s does not match the pack (a DqnPack, IqnPack or RainbowPack picks "
+                             "discrete actions, the Actor continuous ones)" % bool(is_continuous))
         cvar = float(cvar)
         if not 0.0 < cvar <= 1.0:
             raise ValueError("run: cvar must be in (0, 1]")

@@ -12,8 +12,9 @@ reads only its own keys from it (env.py:75-94). An optional "vectorized" dict in
 (ignored by the reference) makes learn() drive VecTrainer instead: {"n_envs": E, "batch_size": B,
 "num_tau": N, ...} are VecTrainer's keyword arguments. Evaluation, evaluations.npz and the model
 files keep the reference's cadence and format; the trained networks are copied into rl_agent first.
-With "device_eval": true in that dict (AC-IQN, DDPG, DQN and IQN) the evaluations run on the device with the batched
-trainer's own actor, Q network or quantile network (evaluation(batched="device"), policy/device_eval.py).
+With "device_eval": true in that dict (AC-IQN, DDPG, DQN, IQN and Rainbow) the evaluations run on the device with the
+batched trainer's own actor, Q network, quantile network or, for Rainbow, the mu-only (eval-mode) images of its online
+network (evaluation(batched="device"), policy/device_eval.py).
 """
 import json
 import os
@@ -170,9 +171,10 @@ class Trainer:
         sched = {k: v for k, v in self.train_env.schedule.items() if k != "vectorized"}
         kw = dict(vec)
         # "device_eval": true evaluates on the device with the batched trainer's own actor (AC-IQN, DDPG) or Q network
-        # (DQN) or quantile network (IQN; evaluation(batched="device")) instead of copying the networks out and stepping
-        # the Python eval envs
-        device_eval = bool(kw.pop("device_eval", False)) and agent.agent_type in ("AC-IQN", "DQN", "DDPG", "IQN")
+        # (DQN), quantile network (IQN) or eval-mode Rainbow network (evaluation(batched="device")) instead of copying the
+        # networks out and stepping the Python eval envs
+        device_eval = bool(kw.pop("device_eval", False)) and agent.agent_type in ("AC-IQN", "DQN", "DDPG", "IQN",
+                                                                                  "Rainbow")
         kw.setdefault("graphs", True)
         for key, sk in (("num_robots", "num_robots"), ("num_obs", "num_obstacles"), ("num_cores", "num_cores")):
             if sk in sched:
@@ -325,6 +327,9 @@ class Trainer:
             elif tr.agent_type == "IQN":   # IQN_Policy's local images: the act launch and the step, per step
                 res = tr.device_evaluator(self.eval_config,
                                           template_env=self.eval_env).run(tr.fused_iqn.window_pack)
+            elif tr.agent_type == "Rainbow":   # Rainbow_Policy.eval(): the mu-only images, packed on this read
+                res = tr.device_evaluator(self.eval_config,
+                                          template_env=self.eval_env).run(tr.fused_rb.eval_pack)
             else:
                 res = tr.evaluate(self.eval_config, template_env=self.eval_env)
             obs_d, act_d, traj_d = res["observations"], res["actions"], res["trajectories"]

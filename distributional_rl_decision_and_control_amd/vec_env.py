@@ -138,13 +138,15 @@ class VecMarineNavEnv:
         (row, step counter, policy_seed); deterministic=True (that pack only) takes the mean action instead. A
         fused_iqn.IqnPack drives an env built with is_continuous=False as a DqnPack does (fused_iqn.iqn_act in the
         Actor's place, its quantile fractions drawn in the kernel on (row, step counter, policy_seed)); cvar in (0, 1]
-        (that pack only) is act_iqn's risk distortion."""
+        (that pack only) is act_iqn's risk distortion. A fused_rainbow.RainbowPack drives a discrete env the same way
+        (fused_rainbow.rainbow_act in the Actor's place, on the images of the pack's last refresh())."""
         from .fused_dqn import DqnPack
         from .fused_iqn import IqnPack
-        if isinstance(pack, (DqnPack, IqnPack)):
+        from .fused_rainbow import RainbowPack
+        if isinstance(pack, (DqnPack, IqnPack, RainbowPack)):
             if self.is_continuous:
-                raise ValueError("policy_rollout: a DqnPack or IqnPack picks discrete actions, this env was built "
-                                 "with is_continuous=True")
+                raise ValueError("policy_rollout: a DqnPack, IqnPack or RainbowPack picks discrete actions, this env "
+                                 "was built with is_continuous=True")
         elif not self.is_continuous:
             raise ValueError("policy_rollout: the Actor drives continuous-action envs")
         ar = self._auto_reset(auto_reset, False)

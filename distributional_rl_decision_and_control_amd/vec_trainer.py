@@ -199,7 +199,8 @@ class VecTrainer:
         env, the replay and the step counter are not touched. AC-IQN and DDPG only."""
         if self.learner.actor_pack is None:
             raise NotImplementedError("greedy_episodes runs the AC-IQN / DDPG actor; IQN, Rainbow and DQN act inside "
-                                      "their own kernels")
+                                      "their own kernels (the learner's window_pack / eval_pack with "
+                                      "device_evaluator(...).run is the route for IQN and Rainbow)")
         env = self._eval_env()
         alive = torch.ones(self.E, dtype=torch.uint8, device=self.device)
         steps_run = torch.zeros(self.E, dtype=torch.int32, device=self.device)
@@ -225,17 +226,20 @@ class VecTrainer:
         needed; the training env, the replay and the step counter are not touched. AC-IQN and DDPG only."""
         if self.learner.actor_pack is None:
             raise NotImplementedError("evaluate runs the AC-IQN / DDPG actor; IQN, Rainbow and DQN act inside their "
-                                      "own kernels")
+                                      "own kernels (device_evaluator(...).run(policy_pack()) for DQN, "
+                                      "run(fused_iqn.window_pack) for IQN, run(fused_rb.eval_pack) for Rainbow)")
         return self.device_evaluator(configs, chunk, template_env).run(self.learner.actor_pack, **kw)
 
     def policy_pack(self):
         """The pack the closed-loop windows take (DeviceEnvBatch.policy_rollout, DeviceEvaluator.run): the learner's
         own local images -- AC-IQN's or DDPG's actor or DQN's local net. IQN and Rainbow act inside their own
-        kernels."""
+        kernels: the windows take fused_iqn.window_pack, and for Rainbow fused_rb.window_pack (training mode, the noisy
+        images) or fused_rb.eval_pack (evaluation, mu only)."""
         if self.learner.policy_pack is not None:
             return self.learner.policy_pack
         raise NotImplementedError(f"policy_pack: the closed-loop windows run the AC-IQN / DDPG actor or DQN_Policy, not "
-                                  f"{self.agent_type}")
+                                  f"{self.agent_type} (its learner's window_pack, and Rainbow's eval_pack, go to "
+                                  "policy_rollout / DeviceEvaluator.run / _collect_window directly)")
 
     def device_evaluator(self, configs, chunk=64, template_env=None):
         """The DeviceEvaluator of the eval `configs`, built once and cached (one per configs list, chunk and
@@ -301,7 +305,8 @@ class VecTrainer:
         for the host-side step count (env.advance_host() per step) as iteration() does."""
         if self.learner.actor_pack is None or self.per is not None:
             raise NotImplementedError("collect runs the AC-IQN / DDPG actor and pushes into the uniform ring; IQN, "
-                                      "Rainbow and DQN act inside their own kernels")
+                                      "Rainbow and DQN act inside their own kernels (_collect_window takes the "
+                                      "learner's window_pack for SAC, IQN and Rainbow)")
         return self._collect_window(self.learner.actor_pack, K, snap)
 
     @torch.no_grad()
@@ -309,16 +314,25 @@ class VecTrainer:
         """collect()'s two launches under `pack`: the learner's actor_pack, or a SAC trainer's
         fused_sac.window_pack, whose ring rows are DDPG's (K calls of rollout(), bit for bit, there too), or an IQN
         trainer's fused_iqn.window_pack: its "actions" record holds (index, 0.0), and the push stores the pair as
-        rollout()'s one-column push stores the index and a zero."""
+        rollout()'s one-column push stores the index and a zero; or a Rainbow trainer's fused_rb.window_pack: the pack
+        is refreshed once (the compose and pack act() does first: the online noise is never resampled, so K act()
+        calls pack the same images K times), the window runs under the seed and step counter act() gives
+        FusedRainbow.act, and the whole window goes into the prioritised replay in one push (DevicePER.push_window)."""
         K = int(K)
         buf = self._collect_buffers(K)
-        buf["obj_cnt"].fill_(-1)   # a row no env took is never pushed
+        buf["obj_cnt"].fill_(-1)   # a row no env took is never pushed (PER: it becomes a blank slot, as in push())
+        if self.per is not None:
+            pack.refresh()
         keep = {k: buf[k] for k in ("obs", "obs_prev", "obj_cnt", "reward", "done", "actions", "steps_run")}
         rec = self.env.policy_rollout(pack, K, hold_done=False, keep=keep,
                                       eps=(self.E, self.total_timesteps, self.exploration_fraction, self.initial_eps,
                                            self.final_eps), policy_seed=self.seed + 4242,
                                       auto_reset=dict(pushed=buf["pushed"], resets=buf["resets"]), count=False)
-        self.replay.push_window(buf, K, pushed=buf["pushed"], snap=snap, counter_inc=self.env.counter, counter_by=K)
+        if self.per is not None:
+            self.per.push_window(buf, K, counter_inc=self.env.counter, counter_by=K)
+        else:
+            self.replay.push_window(buf, K, pushed=buf["pushed"], snap=snap, counter_inc=self.env.counter,
+                                    counter_by=K)
         self.env.advance_device(True)
         return rec
 

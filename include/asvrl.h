@@ -587,6 +587,13 @@ int asvrl_per_push(const AsvPer* per, const float* obs, const int8_t* obj_cnt, c
 int asvrl_per_push_ex(const AsvPer* per, const float* obs, const int8_t* obj_cnt, const double* actions,
                       int32_t action_dim, const double* reward, const uint8_t* done, int32_t n, int64_t* step_counter,
                       void* stream);
+/* The push of a whole rollout window (new entry point only: the ABI version stays 29): asvrl_per_push_ex on
+ * n = K * stride rows (K time steps, time-major: one thread walks each robot's stream in order, so the ring, the
+ * tree and the per-stream timesteps are those of K single pushes), with step_counter[0] advanced by counter_by
+ * (>= 1; K for a window) in the last launch instead of by one. step_counter may be NULL. */
+int asvrl_per_push_window(const AsvPer* per, const float* obs, const int8_t* obj_cnt, const double* actions,
+                          int32_t action_dim, const double* reward, const uint8_t* done, int32_t n,
+                          int64_t* step_counter, int64_t counter_by, void* stream);
 
 /* ReplayMemory.sample (:157-192): B stratified draws (segment b: uniform in [b*seg, (b+1)*seg) with
  * seg = total / B in f32, the value in f64), SegmentTree.find, the validity rule of :163 (window
@@ -746,6 +753,30 @@ typedef struct AsvRainbowNetIO {
 int asvrl_rainbow_pack(const AsvRainbowSrc* src, const AsvRainbowImgOut* img, void* stream);
 /* act_rainbow (agent.py:308-324) for every row: argmax_k sum softmax(q[k]) z, epsilon-greedy. */
 int asvrl_rainbow_net_act(const AsvRainbowImg* w, const AsvRainbowNetIO* io, void* stream);
+
+/* The window form of asvrl_rainbow_net_act (new entry points only: the ABI version stays 29). What it adds to the
+ * pass: */
+typedef struct AsvRainbowActEx {
+  int32_t robots_per_env;  /* >= 1: row b belongs to env b / robots_per_env (env_mask) */
+  int32_t _pad0;
+  int64_t step_add;        /* the epsilon schedule and the exploration draw use *step_dev + step_add (step_dev NULL:
+                              0 + step_add); unlike asvrl_rainbow_net_act the window form always draws */
+  double* act_pair;        /* optional [N][2]: (action index, 0.0), what asvrl_env_step_ex takes with
+                              is_continuous = 0 */
+  double* rec_row;         /* optional [N][2]: the same pair, written only for rows of envs with env_mask != 0 */
+  const uint8_t* env_mask; /* optional [N / robots_per_env]; NULL: every env */
+  float* q_out;            /* optional [N][ld_q]: column k < 25 = Q[k] = sum_atoms p[k] z, the value act_rainbow takes
+                              the arg-max of (agent.py:320); columns >= 25 are not written */
+  int64_t ld_q;            /* >= 25 */
+} AsvRainbowActEx;
+/* io as asvrl_rainbow_net_act's, except that io->act_out may be NULL when ex->act_pair or ex->rec_row is given. The
+ * images are whatever asvrl_rainbow_pack last packed: composed noisy weights (training mode) or, with the source
+ * pointers at weight_mu / bias_mu, the eval-mode network (policy_local.eval()). With step_add = 0, no mask and no
+ * q_out the action is asvrl_rainbow_net_act's, bit for bit. Rows >= N of the last tile write nothing. */
+int asvrl_rainbow_net_act_ex(const AsvRainbowImg* w, const AsvRainbowNetIO* io, const AsvRainbowActEx* ex,
+                             void* stream);
+/* sizeof(AsvRainbowActEx) as compiled. */
+int64_t asvrl_rainbow_act_ex_struct_size(void);
 /* The double-Q argmax of train_Rainbow (agent.py:605-609): act_idx[row] = argmax_k Q[k]. */
 int asvrl_rainbow_net_argmax(const AsvRainbowImg* w, const AsvRainbowNetIO* io, void* stream);
 /* p(s', a*) of the target net (agent.py:610-612): p_out[row] = softmax(q[act_idx[row]]). */
@@ -1484,6 +1515,39 @@ int asvrl_iqn_rollout_ar(const AsvParams* params, const AsvEnvState* state, cons
                          const AsvAutoReset* ar, const AsvEnvLaunch* launch /* NULL: automatic */, void* stream);
 /* sizeof(AsvIqnPolicy) as compiled. */
 int64_t asvrl_iqn_policy_struct_size(void);
+
+/* ---------------------------------------------------------------- closed-loop rollout windows for Rainbow
+ * New entry points only: the ABI version stays 29. */
+
+/* Rainbow_Policy (act_rainbow) driving asvrl_rainbow_rollout. */
+typedef struct AsvRainbowPolicy {
+  AsvRainbowImg w;                /* asvrl_rainbow_pack's images: noisy (training mode) or mu only (eval mode); the
+                                     transposed images are not read */
+  const float* support;           /* [51] */
+  const float* obs_in;            /* [NT][ASVRL_OBS_DIM] the observation step 0 acts on (16-byte aligned) */
+  const int64_t* step_dev;        /* epsilon schedule and exploration key: step = *step_dev + t (NULL: 0 + t) */
+  double eps_steps_per_count, eps_total, eps_fraction, eps_initial, eps_final;   /* as AsvRainbowNetIO's */
+  uint64_t seed;                  /* Philox key of the exploration draw */
+  double* actions;                /* optional record [K][NT][2]: (action index, 0.0) of every robot slot */
+} AsvRainbowPolicy;
+
+/* The closed loop under Rainbow_Policy: for t < ro->n_steps, asvrl_rainbow_net_act on every robot row (the first
+ * arg-max of Q[k] = sum_atoms p[k] z; the epsilon-greedy draw on (row, *step_dev + t, seed)) and then the env step on
+ * the discrete action -- bit for bit the 2 K launches of asvrl_rainbow_net_act and asvrl_env_step_ex (and, with the
+ * auto-reset, asvrl_env_reset_observe) they replace. As for IQN the act is NOT fused into the env kernel (the env
+ * kernel is one f64 lane per robot-candidate pair with its own LDS layout, the network tile 4 MFMA waves per 32
+ * rows): every layout runs, per step, one asvrl_rainbow_net_act_ex launch (step_add = t; it writes the step's action
+ * pairs and the record row itself), the single step, the record launch and, with the auto-reset, the reset
+ * launches, all enqueued by this one call with no host synchronisation (graph-capturable). The contract is the two
+ * IQN calls' otherwise: ctl->is_continuous must be 0, ro->actions null. The caller's step counter is only read. */
+int asvrl_rainbow_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                          const AsvStepOut* last, const AsvRollout* ro, const AsvRainbowPolicy* pi,
+                          const AsvEnvLaunch* launch /* NULL: automatic */, void* stream);
+int asvrl_rainbow_rollout_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                             const AsvStepOut* last, const AsvRollout* ro, const AsvRainbowPolicy* pi,
+                             const AsvAutoReset* ar, const AsvEnvLaunch* launch /* NULL: automatic */, void* stream);
+/* sizeof(AsvRainbowPolicy) as compiled. */
+int64_t asvrl_rainbow_policy_struct_size(void);
 
 /* ---------------------------------------------------------------- misc */
 const char* asvrl_last_error(void);
