@@ -102,6 +102,33 @@ __global__ __launch_bounds__(kOptThreads) void adam_kernel(float* __restrict__ p
   if (counter != nullptr && blockIdx.x == 0 && threadIdx.x == 0) counter[0] += 1;
 }
 
+// Agent.soft_update (agent.py:643-679) over the flat target / local parameter buffers, with the target's weight
+// images written by the same launch as adam_kernel writes the local ones. The step is predicated on the device
+// learn counter: every thread reads it, so the whole launch either runs or writes nothing.
+__global__ __launch_bounds__(kOptThreads) void target_update_kernel(float* __restrict__ t, const float* __restrict__ l,
+                                                                     int64_t n, float tau, float one_minus_tau,
+                                                                     const int64_t* __restrict__ counter,
+                                                                     int64_t interval, PackTable pk) {
+  if (counter != nullptr && interval > 0 && counter[0] % interval != 0) return;
+  __shared__ AsvPackSeg s_pk[ASVRL_MAX_PACK_SEGS];
+  {   // the pack table into LDS (read per element below)
+    const int* src = reinterpret_cast<const int*>(pk.s);
+    int* dst = reinterpret_cast<int*>(s_pk);
+    constexpr int kWords = static_cast<int>(sizeof(AsvPackSeg)) / 4 * ASVRL_MAX_PACK_SEGS;
+    for (int k = threadIdx.x; k < kWords; k += kOptThreads) dst[k] = src[k];
+  }
+  __syncthreads();
+  const bool copy = tau == 1.f;   // TAU = 1: target <- local, whatever the target held (1 l + 0 t is NaN for t = inf)
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kOptThreads + threadIdx.x; i < n;
+       i += static_cast<int64_t>(gridDim.x) * kOptThreads) {
+    const float li = l[i];
+    // tau * l + (1 - tau) * t as torch evaluates it: both products rounded to f32, then the sum (never an FMA)
+    const float ti = copy ? li : __fadd_rn(__fmul_rn(tau, li), __fmul_rn(one_minus_tau, t[i]));
+    t[i] = ti;
+    pack_param_lds(s_pk, pk.n, i, ti);
+  }
+}
+
 }  // namespace
 }  // namespace asvrl
 
@@ -164,6 +191,36 @@ extern "C" int asvrl_adam_step_pack(float* params, float* grads, float* exp_avg,
                      grads, exp_avg, exp_avg_sq, n, norm_parts, nparts, step, lr, beta1, beta2, eps, max_norm,
                      norm_out, t, counter);
   return check_launch("asvrl_adam_step_pack");
+}
+
+extern "C" int asvrl_target_update_pack(float* target, const float* local, int64_t n, float tau, float one_minus_tau,
+                                        const int64_t* counter, int64_t interval, const AsvPackSeg* segs, int32_t nseg,
+                                        void* stream) {
+  ASVRL_REQUIRE(target != nullptr, "asvrl_target_update_pack: target is null");
+  ASVRL_REQUIRE(local != nullptr, "asvrl_target_update_pack: local is null");
+  ASVRL_REQUIRE(n >= 0, "asvrl_target_update_pack: n is negative");
+  ASVRL_REQUIRE(nseg >= 0 && nseg <= ASVRL_MAX_PACK_SEGS,
+                "asvrl_target_update_pack: nseg outside 0.." + std::to_string(ASVRL_MAX_PACK_SEGS));
+  ASVRL_REQUIRE(nseg == 0 || segs != nullptr, "asvrl_target_update_pack: segs is null with nseg > 0");
+  ASVRL_REQUIRE(interval >= 0, "asvrl_target_update_pack: interval is negative");
+  ASVRL_REQUIRE(tau > 0.f && tau <= 1.f, "asvrl_target_update_pack: tau outside (0, 1]");
+  PackTable t{};
+  for (int k = 0; k < nseg; ++k) {
+    const AsvPackSeg& g = segs[k];
+    ASVRL_REQUIRE(g.image && g.rows >= 1 && g.cols >= 1 && g.nrep >= 1 && g.flat_off >= 0 &&
+                      g.flat_off + static_cast<int64_t>(g.rows) * g.cols <= n,
+                  "asvrl_target_update_pack: segs[" + std::to_string(k) + "] outside the parameters [0, n)");
+    ASVRL_REQUIRE(g.f32 || (g.K % 16 == 0 && g.K >= 16),
+                  "asvrl_target_update_pack: segs[" + std::to_string(k) + "] image K must be a multiple of 16");
+    t.s[k] = g;
+  }
+  t.n = nseg;
+  if (n == 0) return 0;
+  int64_t nb = (n + kAdamPer * kOptThreads - 1) / (kAdamPer * kOptThreads);
+  nb = nb < 1 ? 1 : (nb > 1024 ? 1024 : nb);
+  hipLaunchKernelGGL(target_update_kernel, dim3(static_cast<unsigned>(nb)), dim3(kOptThreads), 0, as_stream(stream),
+                     target, local, n, tau, one_minus_tau, counter, interval, t);
+  return check_launch("asvrl_target_update_pack");
 }
 
 // 2: bf16 MFMA operands, weight images and saved activations (libasvrl.so); 4: f32 (libasvrl_f32.so)

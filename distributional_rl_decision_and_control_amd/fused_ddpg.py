@@ -37,6 +37,7 @@ from .fused_critic import PartialArena
 from .fused_mlp import (ENC, HID, OBSK, ActorBuffers, ActorGrads, MlpPack, actor_act, actor_backward, actor_forward,
                         actor_train_forward)
 from .fused_update import _actor_step, _reduce_and_step, learn_prologue
+from .learner import target_step
 
 OBS = 40
 
@@ -134,6 +135,11 @@ class FusedDDPGState:
         """Re-pack the target networks after a hard/soft update (eager, outside graphs)."""
         self.target.refresh()
         self.target_actor.refresh()
+
+    def target_step(self, tr):
+        """The device-side target update behind a learn step (VecTrainer target_update="device"): blend and
+        re-pack of the target actor and the target critic, one launch each, predicated on tr's learn counter."""
+        target_step(tr, (self.target_actor, self.target))
 
     def refresh_local(self):
         """Re-pack the local networks after their parameters were loaded (eager, outside graphs)."""

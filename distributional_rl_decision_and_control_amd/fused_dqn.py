@@ -29,6 +29,7 @@ from . import _abi
 from .fused_critic import PartialArena
 from .fused_mlp import ENC, HID, OBSK, MlpPack
 from .fused_update import _reduce_and_step
+from .learner import target_step
 
 OBS = 40
 QPAD = _abi.DQN_MAX_ACTIONS
@@ -132,6 +133,11 @@ class FusedDQNState:
     def target_changed(self):
         """Re-pack the target network after a hard/soft update (eager, outside graphs)."""
         self.target.refresh()
+
+    def target_step(self, tr):
+        """The device-side target update behind a learn step (VecTrainer target_update="device"): blend and
+        re-pack of the target network in one launch, predicated on tr's learn counter."""
+        target_step(tr, (self.target,))
 
     def refresh_local(self):
         """Re-pack the local network after its parameters were loaded (eager, outside graphs)."""

@@ -42,6 +42,7 @@ import torch
 from . import _abi
 from .fused_critic import CriticPack, PartialArena, TrainBuffers, fused_groups, fused_train_supported
 from .fused_update import ENC_IN_KERNEL, _reduce_and_step
+from .learner import target_step
 
 OBS = 40
 K_ACT = 32
@@ -247,6 +248,11 @@ class FusedIQNState:
     def target_changed(self):
         """Re-pack the target network after a hard/soft update (eager, outside graphs)."""
         self.target.refresh()
+
+    def target_step(self, tr):
+        """The device-side target update behind a learn step (VecTrainer target_update="device"): blend and
+        re-pack of the target network in one launch, predicated on tr's learn counter."""
+        target_step(tr, (self.target,))
 
     def refresh_local(self):
         """Re-pack the local network after its parameters were loaded (eager, outside graphs)."""

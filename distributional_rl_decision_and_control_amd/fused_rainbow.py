@@ -326,6 +326,14 @@ class FusedRainbow:
         self.tpack.compose()
         self.timg.refresh()
 
+    def target_step(self, tr):
+        """The device-side target update behind a learn step (VecTrainer target_update="device"): the blend of
+        the target's f32 masters alone, predicated on tr's learn counter. No image is written here: update()
+        composes the target's noisy weights from the masters (tpack.reset / compose) and packs its images
+        (timg.refresh) at every step before it reads them, so they are never older than the masters."""
+        from .learner import target_step
+        target_step(tr, (None,))
+
     def refresh_local(self):
         self.pack.compose()
         self.img.refresh()

@@ -41,6 +41,7 @@ from .fused_critic import PartialArena
 from .fused_ddpg import DdpgCriticPack
 from .fused_mlp import ENC, HID, OBSK, MlpPack
 from .fused_update import _reduce_and_step
+from .learner import target_step
 
 OBS = 40
 ALPHA = 0.078   # agent.py:95, fixed
@@ -192,6 +193,11 @@ class FusedSACState:
         for p in self.target:
             p.refresh()
         self.target_actor.refresh()
+
+    def target_step(self, tr):
+        """The device-side target update behind a learn step (VecTrainer target_update="device"): blend and
+        re-pack of the target actor and both target critics, one launch each, predicated on tr's learn counter."""
+        target_step(tr, (self.target_actor, self.target[0], self.target[1]))
 
     def refresh_local(self):
         """Re-pack the local networks after their parameters were loaded (eager, outside graphs)."""

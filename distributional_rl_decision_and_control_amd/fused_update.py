@@ -42,7 +42,7 @@ from .fused_critic import CriticPack, PartialArena, critic_actor_grad, critic_fo
 from .fused_mlp import (ActorBuffers, ActorGrads, MlpPack, actor_act, actor_backward, actor_forward,
                         actor_train_forward)
 from .fused_mlp import actor_grads as actor_grads_launch
-from .learner import FusedAdam, clip_and_step
+from .learner import FusedAdam, clip_and_step, target_step
 
 OBS = 40
 # the encoders' gradients formed inside the fused critic launch (ABI 16: 0.333 -> 0.323 ms per AC-IQN
@@ -102,6 +102,11 @@ class FusedACIQNState:
         """Re-pack the target networks after a hard/soft update (eager, outside graphs)."""
         self.target_trunk.refresh()
         self.target_actor.refresh()
+
+    def target_step(self, tr):
+        """The device-side target update behind a learn step (VecTrainer target_update="device"): blend and
+        re-pack of the target actor and the target critic, one launch each, predicated on tr's learn counter."""
+        target_step(tr, (self.target_actor, self.target_trunk))
 
     def refresh_local(self):
         """Re-pack the local networks after their parameters were loaded (eager, outside graphs)."""

@@ -86,7 +86,81 @@ def _clip(params, max_norm):
     return torch.nn.utils.clip_grad_norm_(params, max_norm)
 
 
-class FusedAdam:
+class _FlatPack:
+    """pack_seg over `flat` (one f32 buffer the parameters are views of) and `n`: what a pack class's
+    adam_segments(opt) needs of `opt`, shared by FusedAdam (the local networks) and FlatParams (the targets)."""
+
+    def pack_seg(self, w, image, K=0, chained=False, transposed=False, f32=False, row0=0, col0=0, nrep=1, rep_row=0,
+                 rep_col=0):
+        """An AsvPackSeg sending parameter w (one of this buffer's, re-pointed into `flat`) into a weight image
+        at every step (asvrl_adam_step_pack, asvrl_target_update_pack)."""
+        off = (w.data_ptr() - self.flat.data_ptr()) // 4
+        assert 0 <= off and off + w.numel() <= self.n and w.is_contiguous()
+        g = _abi.AsvPackSeg()
+        g.flat_off, g.image = off, image.data_ptr()
+        g.rows, g.cols = (w.shape[0], w.shape[1]) if w.dim() == 2 else (w.shape[0], 1)
+        g.K, g.chained, g.transposed, g.f32 = K, int(chained), int(transposed), int(f32)
+        g.row0, g.col0, g.nrep, g.rep_row, g.rep_col = row0, col0, nrep, rep_row, rep_col
+        return g
+
+
+class FlatParams(_FlatPack):
+    """A target network's parameters re-pointed at one flat f32 buffer, as FusedAdam re-points the local ones, so
+    Agent.soft_update (agent.py:643-679) is one launch per network: asvrl_target_update_pack blends the whole buffer
+    with the local optimiser's and writes the target's weight images through the pack's segment table.
+
+    Every parameter is taken, whatever its requires_grad (the targets have it switched off): order and offsets then
+    equal those of the FusedAdam over the same network's local copy. Construct it before anything caches parameter
+    pointers (CriticPack, NoisyPack), as FusedAdam."""
+
+    def __init__(self, params, operands="bf16"):
+        self.L = _abi.lib(operands)
+        self.params = list(params)
+        dev = self.params[0].device
+        self.n = sum(p.numel() for p in self.params)
+        self.flat = torch.empty(self.n, dtype=torch.float32, device=dev)
+        off = 0
+        with torch.no_grad():
+            for p in self.params:
+                k = p.numel()
+                self.flat[off:off + k].copy_(p.reshape(-1))
+                p.data = self.flat[off:off + k].view_as(p)
+                off += k
+        self._segs = {}
+
+    def update_from(self, local, tau, pack=None, counter=None, interval=0, stream=None):
+        """target <- tau * local + (1 - tau) * target in one launch on the current stream, the images of `pack`
+        (the target's pack: its adam_segments over this buffer; None: no images) written with it. local: the
+        FusedAdam (or flat f32 tensor) of the local network. counter / interval: the launch writes nothing unless
+        counter[0] % interval == 0 (an int64 device scalar, read only); counter None: unconditional."""
+        src = local.flat if hasattr(local, "flat") else local
+        assert src.dtype == torch.float32 and src.numel() == self.n and src.is_contiguous(), "local / target layouts"
+        key = id(pack)
+        if key not in self._segs:
+            segs = list(pack.adam_segments(self)) if pack is not None else []
+            assert pack is None or pack.L is self.L, "target buffer and pack of different builds"
+            self._segs[key] = ((_abi.AsvPackSeg * max(1, len(segs)))(*segs), len(segs), pack)
+        arr, nseg, _ = self._segs[key]
+        tau = float(tau)
+        # float(tau) and float(1.0 - tau), the subtraction in double: torch's own scalars for TAU * l + (1.0 - TAU) * t
+        rc = self.L.asvrl_target_update_pack(_abi.ptr(self.flat), _abi.ptr(src), self.n, tau, 1.0 - tau,
+                                             _abi.ptr(counter), int(interval) if counter is not None else 0, arr, nseg,
+                                             _abi.stream_ptr(stream))
+        _abi.check(rc, "asvrl_target_update_pack", self.L)
+
+
+def target_step(tr, packs):
+    """The shared body of every Fused*State.target_step(tr): one asvrl_target_update_pack per target network of
+    `tr` (a VecTrainer with target_update="device": tr._target_flat and tr.local_opts() in learners.policy_modules
+    order) with that network's target pack from `packs` (same order; None: the blend alone), predicated on
+    tr.learn_counter % tr.target_update_interval == 0."""
+    flats, opts = tr._target_flat, tr.local_opts()
+    assert flats is not None and len(flats) == len(opts) == len(packs)
+    for flat, opt, pack in zip(flats, opts, packs):
+        flat.update_from(opt, tr.tau, pack, counter=tr.learn_counter, interval=tr.target_update_interval)
+
+
+class FusedAdam(_FlatPack):
     """clip_grad_norm_(params, max_norm) + optim.Adam(params, lr).step() (agent.py:75-76,98,
     415-416) as the two launches of asvrl_adam_clip over flat buffers.
 
@@ -129,19 +203,6 @@ class FusedAdam:
             _abi.ptr(self.norm), _abi.ptr(self.work), _abi.stream_ptr(None))
         _abi.check(rc, "asvrl_adam_clip", self.L)
         return self.norm[0]
-
-    def pack_seg(self, w, image, K=0, chained=False, transposed=False, f32=False, row0=0, col0=0, nrep=1, rep_row=0,
-                 rep_col=0):
-        """An AsvPackSeg sending parameter w (one of this optimiser's, re-pointed into its flat buffer)
-        into a weight image at every step (asvrl_adam_step_pack)."""
-        off = (w.data_ptr() - self.flat.data_ptr()) // 4
-        assert 0 <= off and off + w.numel() <= self.n and w.is_contiguous()
-        g = _abi.AsvPackSeg()
-        g.flat_off, g.image = off, image.data_ptr()
-        g.rows, g.cols = (w.shape[0], w.shape[1]) if w.dim() == 2 else (w.shape[0], 1)
-        g.K, g.chained, g.transposed, g.f32 = K, int(chained), int(transposed), int(f32)
-        g.row0, g.col0, g.nrep, g.rep_row, g.rep_col = row0, col0, nrep, rep_row, rep_col
-        return g
 
     def step_synced(self, pack=None, counter=None, stream=None):
         """Clip + Adam over gradients already reduced in place (the data-parallel path, after GradSync's

@@ -5,6 +5,10 @@ buffers) is built. The Fused*State classes share one surface, so neither front e
     act(obs, actions, step, E, total, fraction, initial, final, seed)      the batched epsilon-greedy act kernel
     learn(tr, state, guard, actor_wait, target_wait, actor_done)           VecTrainer's sample + update
     target_changed() / refresh_local()                                     re-pack the target / local weight images
+    target_step(tr)                                                        VecTrainer target_update="device": one
+                                                                           asvrl_target_update_pack per target network
+                                                                           (blend + re-pack, predicated on the device
+                                                                           learn counter; Rainbow: the blend alone)
     policy_pack, actor_pack                                                 what the closed-loop windows take, or None
 
 FusedSACState also has window_pack, its local actor's SacActorPack: DeviceEnvBatch.policy_rollout, DeviceEvaluator.run

@@ -185,6 +185,10 @@ class Trainer:
         # (trainer.py:175-192: one B=64 learn step per UPDATE_EVERY timesteps)
         kw.setdefault("learning_starts", max(int(kw.get("batch_size", 4096)), int(self.learning_starts)))
         kw.setdefault("target_update_interval", max(1, int(self.target_update_interval) // int(self.UPDATE_EVERY)))
+        # soft_update's TAU (agent.py:643-679): rl_agent's own, so Agent(TAU=0.005) trains with Polyak averaging on
+        # the batched loop too (1.0, Agent's default: the hard update). "target_update": "device" in the block moves
+        # the update into the learn step's launches (VecTrainer)
+        kw.setdefault("tau", agent.TAU)
         tr = VecTrainer(agent_type=agent.agent_type, seed=getattr(self.train_env, "seed", 0), device=agent.device,
                         total_timesteps=total_timesteps, schedule=sched, gamma=agent.GAMMA, lr=agent.LR,
                         exploration_fraction=self.exploration_fraction, initial_eps=self.initial_eps,

@@ -10,12 +10,15 @@ One iteration (= one `step` of bench.py):
   5. learn: sample B transitions (asvrl_replay_sample) and one distributional update
      (AC-IQN and DDPG: two dependent optimizer steps, critic then actor; SAC: three, both critics then the
      actor; IQN, Rainbow and DQN: one)
-  6. hard target update every `target_update_interval` learn steps (agent.py:643-679, TAU=1)
+  6. target update every `target_update_interval` learn steps (agent.py:643-679): the hard copy (tau = 1, the
+     default) or the Polyak blend (tau < 1), issued by the host between iterations (target_update="host") or as
+     launches of the learn step predicated on the device learn counter (target_update="device")
 
 Cadence in the batched setting: one learn step of batch B per iteration (after
 `learning_starts` transitions) replaces the reference's one B=64 step per 4 single-env
 timesteps; target updates count learn steps (2500 = 10000 timesteps / UPDATE_EVERY 4).
-With `graphs=True` steps 1-5 are captured once into a HIP graph and replayed.
+With `graphs=True` steps 1-5 are captured once into a HIP graph and replayed; with target_update="device" step 6
+is captured with them.
 """
 import time
 
@@ -23,7 +26,7 @@ import torch
 
 from . import streams
 from .learn_ops import DevicePER, DeviceReplay
-from .learner import FusedAdam
+from .learner import FlatParams, FusedAdam
 from .learners import LEARNERS, policy_modules, policy_parameters
 from .vec_env import VecMarineNavEnv
 
@@ -37,9 +40,19 @@ class VecTrainer:
                  learning_starts=None, target_update_interval=2500, total_timesteps=6_000_000,
                  exploration_fraction=0.25, initial_eps=0.6, final_eps=0.05, seed=0,
                  device="cuda", sync=None, graphs=False, schedule=None, net_seed=100, overlap=True, unroll=1,
-                 chain=None, operands="bf16", target_after_env=False, push_after_actor=None):
+                 chain=None, operands="bf16", target_after_env=False, push_after_actor=None, tau=1.0,
+                 target_update="host"):
         """Every learner (learners.LEARNERS) runs on the hand-written kernels with FusedAdam; operands="f32" takes
-        them from the f32-operand parity build (libasvrl_f32.so). Shapes the kernels do not take raise ValueError."""
+        them from the f32-operand parity build (libasvrl_f32.so). Shapes the kernels do not take raise ValueError.
+        tau: soft_update's TAU, 0 < tau <= 1 (1: the hard copy). target_update: "host" -- the update is issued by
+        iteration() every target_update_interval host-counted learn steps, between graph replays; "device" -- every
+        learn step ends with one asvrl_target_update_pack launch per target network, which fires when the device
+        learn counter is a multiple of target_update_interval (captured with the rest of the iteration)."""
+        if not 0.0 < float(tau) <= 1.0:
+            raise ValueError(f"tau must be in (0, 1], not {tau!r}")
+        if target_update not in ("host", "device"):
+            raise ValueError(f"target_update must be 'host' or 'device', not {target_update!r}")
+        self.tau, self.target_update = float(tau), target_update
         if agent_type not in LEARNERS:
             raise NotImplementedError(f"VecTrainer agent_type {agent_type!r} (AC-IQN, IQN, Rainbow, DQN, DDPG and SAC "
                                       "are batched)")
@@ -86,6 +99,12 @@ class VecTrainer:
         else:
             self.opt = FusedAdam(self.local.parameters(), lr=lr, operands=operands)
             self.grads = self.opt.grads
+        # target_update="device": each target network in one flat buffer of its local optimiser's order (before the
+        # packs, for the same reason); None otherwise -- the targets stay as they were built
+        self._target_flat = None
+        if target_update == "device":
+            self._target_flat = [FlatParams(m.parameters(), operands) for m in policy_modules(self.target)]
+            assert [f.n for f in self._target_flat] == [o.n for o in self.local_opts()]
         self.action_dim = spec.action_dim
         self.n_step = 3 if spec.per else None
         self.support = torch.linspace(-1.0, 1.0, 51, device=self.device) if spec.per else None
@@ -336,16 +355,43 @@ class VecTrainer:
         self.env.advance_device(True)
         return rec
 
-    def learn(self, state=None, guard=0, actor_wait=None, target_wait=None, actor_done=None):
+    def learn(self, state=None, guard=0, actor_wait=None, target_wait=None, actor_done=None, target_step=True):
         """One learn step of batch B: sample (uniform ring, or the prioritised tree for Rainbow) and the
         agent's fused update. state / guard: the ring snapshot to sample against and the newest entries to
-        skip (the overlapped schedule); actor_wait: an event to wait for before the actor's weights change."""
-        return self.learner.learn(self, state, guard, actor_wait, target_wait, actor_done)
+        skip (the overlapped schedule); actor_wait: an event to wait for before the actor's weights change.
+        With target_update="device" the target step follows the learner's last launch (target_step=False: the
+        caller enqueues it itself, _target_step())."""
+        out = self.learner.learn(self, state, guard, actor_wait, target_wait, actor_done)
+        if target_step:
+            self._target_step()
+        return out
+
+    def local_opts(self):
+        """The local networks' optimisers in policy_modules order."""
+        if not LEARNERS[self.agent_type].actor_critic:
+            return [self.opt]
+        return [self.actor_opt] + (list(self.critic_opts) if LEARNERS[self.agent_type].twin else [self.critic_opt])
+
+    def _target_step(self):
+        """target_update="device": the target update of the learn step just enqueued, on the current stream. The
+        learner's last launch has incremented the learn counter, so the launches fire when it is a multiple of
+        target_update_interval and write nothing otherwise."""
+        if self._target_flat is not None:
+            self.learner.target_step(self)
 
     def hard_update(self):
         """soft_update with TAU = 1.0 (agent.py:643-679): target <- local."""
         with torch.no_grad():
             torch._foreach_copy_(policy_parameters(self.target), policy_parameters(self.local))
+            self.learner.target_changed()   # eager, outside any captured graph
+
+    def soft_update(self):
+        """soft_update (agent.py:643-679) with this trainer's tau, in Agent.soft_update's own expression per
+        parameter: target <- tau * local + (1 - tau) * target, then the target's weight images re-packed."""
+        tau = self.tau
+        with torch.no_grad():
+            for t, l in zip(policy_parameters(self.target), policy_parameters(self.local)):
+                t.copy_(tau * l + (1.0 - tau) * t)
             self.learner.target_changed()   # eager, outside any captured graph
 
     @torch.no_grad()
@@ -414,8 +460,11 @@ class VecTrainer:
         self.iterations += 1
         if do_learn:
             self.learn_steps += 1
-            if self.learn_steps % self.target_update_interval == 0:
-                self.hard_update()
+            if self._target_flat is None and self.learn_steps % self.target_update_interval == 0:
+                if self.tau == 1.0:
+                    self.hard_update()
+                else:
+                    self.soft_update()
         self.last_losses = out
         return out
 
@@ -478,8 +527,11 @@ class VecTrainer:
             if k > 0:
                 main.wait_event(ev_snap[k - 1])
             out = self.learn(state=self.ring_snap2[(k - 1) % 2], guard=self.E * self.R, actor_wait=ev_act[k],
-                             target_wait=ev_env[k] if tae else None, actor_done=ev_actor[k] if paa else None)
+                             target_wait=ev_env[k] if tae else None, actor_done=ev_actor[k] if paa else None,
+                             target_step=False)
             ev_learn[k].record(main)
+            # behind the event the next act waits for: nothing on the rollout stream reads a target
+            self._target_step()
             if paa:
                 with torch.cuda.stream(s_roll):
                     s_roll.wait_event(ev_actor[k])

@@ -826,6 +826,22 @@ int asvrl_adam_step_pack(float* params, float* grads, float* exp_avg, float* exp
                          float* norm_out, const double* norm_parts, int32_t nparts, const AsvPackSeg* segs,
                          int32_t nseg, int64_t* counter, void* stream);
 
+/* Agent.soft_update (agent.py:643-679) on the device: target[i] <- tau * local[i] + (1 - tau) * target[i] over two
+ * flat f32 buffers of n elements in the same order, and every new target[i] into the target's weight images through
+ * the segment table, as asvrl_adam_step_pack does for the local ones (same segments, same values as the pack
+ * launches). One launch, capturable. tau in (0, 1] and one_minus_tau are given as float(tau) and
+ * float(1.0 - tau), the subtraction in double: the blend is fadd(fmul(tau, l), fmul(one_minus_tau, t)), two rounded
+ * products and a rounded sum, never an FMA, which is bit for bit what torch gives for
+ * TAU * l.data + (1.0 - TAU) * t.data. tau == 1 copies local[i] (a hard update: a non-finite target value does not
+ * survive as NaN). counter (optional, i64 device scalar, read only) with interval > 0: the launch writes nothing
+ * unless counter[0] % interval == 0; counter NULL or interval 0: unconditional. n == 0 returns 0. Errors (before
+ * any launch, asvrl_last_error names the argument): target or local NULL, n < 0, nseg outside
+ * 0..ASVRL_MAX_PACK_SEGS, segs NULL with nseg > 0, a segment outside [0, n), an image K that is not a multiple of
+ * 16, interval < 0, tau outside (0, 1]. */
+int asvrl_target_update_pack(float* target, const float* local, int64_t n, float tau, float one_minus_tau,
+                             const int64_t* counter, int64_t interval, const AsvPackSeg* segs, int32_t nseg,
+                             void* stream);
+
 /* ---------------------------------------------------------------- Linear weight gradients */
 
 /* grad_weight / grad_bias of an nn.Linear from bf16 activations over R rows (the backward's
