@@ -1,7 +1,7 @@
 // asvrl_dqn_tile.h -- DQN_Policy's head on the one-wave Actor tile (asvrl_actor_tile.h, trunk_chain): the Q values
 // of a 32-row tile, their first arg-max, and the epsilon-greedy choice of the batched act (agent.py:271-287).
-// Shared by asvrl_dqn.hip (dqn_act_kernel, dqn_fwd_kernel) and asvrl_env.hip (env_dqn_rollout_kernel, the DQN act
-// in front of every env step): the same MFMAs in the same order and the same Philox key, so a row's action does
+// Shared by asvrl_dqn.hip (dqn_act_kernel, dqn_fwd_kernel) and asvrl_env.hip (env_policy_rollout_kernel<kPolDqn>, the DQN
+// act in front of every env step): the same MFMAs in the same order and the same Philox key, so a row's action does
 // not depend on which kernel computed it.
 #pragma once
 #include "asvrl_actor_tile.h"

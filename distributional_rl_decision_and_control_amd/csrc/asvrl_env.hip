@@ -679,14 +679,14 @@ __host__ __device__ constexpr size_t autoreset_lds(int blk, int epb) {
 // 32-row tiles w, w + waves, ...; it reads the rows of an LDS copy of the observation (PI->obs_in before step 0,
 // then what the phases of the step before wrote: they write it beside their global outputs) and leaves the f64
 // action pairs in LDS, where phase 1 takes the lane's action instead of from A->actions.
-// POL = kPolDqn (env_dqn_rollout_kernel): the same closed loop under DQN_Policy -- the Actor's trunk staged the same
+// POL = kPolDqn (the same kernel template): the same closed loop under DQN_Policy -- the Actor's trunk staged the same
 // way, the 25-wide head's fragments and bias read from L2 (asvrl_dqn_tile.h: dqn_act_kernel's functions), the first
 // arg-max and the epsilon-greedy index left as the pair (index, 0.0), which phase 1 takes as a discrete action.
-// POL = kPolSac (env_sac_rollout_kernel): the closed loop under SAC's sampled actor -- the trunk staged the same way,
+// POL = kPolSac (likewise): the closed loop under SAC's sampled actor -- the trunk staged the same way,
 // the f32 head (2 KB) staged beside it in HL before the staging's barrier, then sac_act_kernel's statements
 // (asvrl_sac_tile.h): the two normals of (global row, step) in the act stream, or none when PI->deterministic, the
 // head without its log-probability, and atile::explore into the f64 action pair.
-// AR (asvrl_env_rollout_ar / asvrl_policy_rollout_ar, with ROLL): episodes restart inside the window. After the
+// AR (the _ar calls, with ROLL): episodes restart inside the window. After the
 // phases of step t the workgroup votes on "an env of mine ended in this step"; if so its waves reset the ended envs
 // (reset_env, one wave per env, the waves taking them in turn, each in its own ResetLds behind the carve and the
 // policy rows), the robot lanes of those envs reload what the rollout keeps over the steps (state, goal, phi, ret,
@@ -1490,154 +1490,81 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(NM == 1 ?
                              A->group0 + xcd_group(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x)), smem);
 }
 
-// K open-loop steps in one launch (asvrl_env_rollout): env_pairs_kernel's workgroup-to-group mapping and LDS
+// The rollout windows: K steps in one launch, one kernel instantiation per policy x auto-reset (x block x noise
+// mode). Their one argument: the step's, the window's, then the policy's struct (closed loop), then the auto-reset's
+// and where its LDS starts in the dynamic carve (AR). A member a kernel does not take is an empty struct that
+// occupies nothing, so each instantiation's kernarg segment holds exactly the members it reads, in this order.
+struct NoPolicy {};   // the open loop: the actions out of ro
+template <int> struct Absent {};
+template <class Pol, bool AR>
+struct WindowArgs {
+  PairsArgs k;   // noise: row 0 of the rollout's; actions: row 0 of the rollout's (open loop), null (closed loop)
+  AsvRollout ro;
+  [[no_unique_address]] std::conditional_t<std::is_same_v<Pol, NoPolicy>, Absent<0>, Pol> pi;
+  [[no_unique_address]] std::conditional_t<AR, AsvAutoReset, Absent<1>> ar;
+  [[no_unique_address]] std::conditional_t<AR, int, Absent<2>> ar_off;
+};
+static_assert(sizeof(WindowArgs<NoPolicy, false>) == sizeof(PairsArgs) + sizeof(AsvRollout) &&
+                  sizeof(WindowArgs<AsvPolicy, false>) == sizeof(WindowArgs<NoPolicy, false>) + sizeof(AsvPolicy) &&
+                  sizeof(WindowArgs<NoPolicy, true>) == sizeof(WindowArgs<NoPolicy, false>) + sizeof(AsvAutoReset) + 8,
+              "absent members take no room in the kernarg segment");
+
+// K open-loop steps (asvrl_env_rollout, asvrl_env_rollout_ar): env_pairs_kernel's workgroup-to-group mapping and LDS
 // carve, the step loop inside the workgroup (env_pairs_block<ROLL>). An env group needs nothing from another
 // group, so no step waits on the rest of the grid. Two waves per SIMD by registers: the resident state rides
 // through the pair phases, and the training shape (4096 envs x 5 robots: 512 workgroups of 4 waves on 1024
 // SIMDs) has no more than two waves per SIMD to place.
+// AR: the auto-reset in the step loop (env_pairs_block<AR>), with the waves' ResetLds and the per-env reset flags at
+// ar_off of the dynamic LDS, behind everything the plain kernel carves. Philox noise only: no NM = 0 instantiation.
 #ifndef ASVRL_ENV_ROLLOUT_WPE
 #define ASVRL_ENV_ROLLOUT_WPE 2
 #endif
-struct RolloutArgs {
-  PairsArgs k;   // actions / noise: row 0 of the rollout's
-  AsvRollout ro;
-};
-template <int BLOCK, int NM>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(NM == 1 ? 1 : ASVRL_ENV_ROLLOUT_WPE))) void env_rollout_kernel(RolloutArgs) {
+template <int BLOCK, int NM, bool AR>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(NM == 1 ? 1 : ASVRL_ENV_ROLLOUT_WPE))) void env_rollout_kernel(WindowArgs<NoPolicy, AR>) {
+  static_assert(!AR || NM != 0, "the auto-reset is Philox noise only");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const KArg<RolloutArgs> RA = kargs<RolloutArgs>();
-  env_pairs_block<BLOCK, NM, true, true>(
-      &RA->k, RA->k.epb, RA->k.group0 + xcd_group(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x)), smem,
-      &RA->ro);
+  const KArg<WindowArgs<NoPolicy, AR>> RA = kargs<WindowArgs<NoPolicy, AR>>();
+  const int epb = RA->k.epb, bid = RA->k.group0 + xcd_group(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x));
+  if constexpr (AR)
+    env_pairs_block<BLOCK, NM, true, true, kPolNone, true>(&RA->k, epb, bid, smem, &RA->ro, nullptr, nullptr,
+                                                           &RA->ar, smem + RA->ar_off);
+  else
+    env_pairs_block<BLOCK, NM, true, true>(&RA->k, epb, bid, smem, &RA->ro);
 }
 
-// K closed-loop steps in one launch (asvrl_policy_rollout): env_rollout_kernel with the AC-IQN Actor in front of
-// every step (env_pairs_block<POL>). The Actor's weight images (bf16: 112 KB, 115 KB with the f32 biases and the
-// output layer) sit in LDS beside the pair carve, the workgroup's observation rows (160 B per robot) and action
-// pairs (16 B per robot), so one workgroup owns a CU: one wave per SIMD and the whole register file.
+// K closed-loop steps (asvrl_policy_rollout, asvrl_dqn_rollout, asvrl_sac_rollout and their _ar forms):
+// env_rollout_kernel with the policy POL in front of every step (env_pairs_block<POL>). The trunk's weight images
+// (bf16: 112 KB, 115 KB with the f32 biases and the output layer) sit in the static ActorLds beside the pair carve,
+// the workgroup's observation rows (160 B per robot) and action pairs (16 B per robot), so one workgroup owns a CU:
+// one wave per SIMD and the whole register file. kPolDqn: the head's 8 KB image and its bias stay in L2. kPolSac:
+// the f32 head beside the trunk (SacHeadLds, 2064 B: 512 weights every lane reads per tile, so they sit in LDS, not
+// L2); no other policy's kernel declares it.
 #ifndef ASVRL_ENV_POLICY_WPE
 #define ASVRL_ENV_POLICY_WPE 1, 1
 #endif
-struct PolicyArgs {
-  PairsArgs k;   // actions null; noise: row 0 of the rollout's
-  AsvRollout ro;
-  AsvPolicy pi;
-};
-template <int BLOCK, int NM>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(ASVRL_ENV_POLICY_WPE))) void env_policy_rollout_kernel(PolicyArgs) {
+template <int BLOCK, int NM, int POL, bool AR>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(ASVRL_ENV_POLICY_WPE))) void env_policy_rollout_kernel(WindowArgs<typename PolicyOf<POL>::type, AR>) {
+  static_assert(POL != kPolNone, "the open loop is env_rollout_kernel");
+  static_assert(!AR || NM != 0, "the auto-reset is Philox noise only");
+  using Args = WindowArgs<typename PolicyOf<POL>::type, AR>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ __attribute__((aligned(16))) atile::ActorLds AL;
-  const KArg<PolicyArgs> PA = kargs<PolicyArgs>();
-  env_pairs_block<BLOCK, NM, true, true, kPolActor>(
-      &PA->k, PA->k.epb, PA->k.group0 + xcd_group(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x)), smem,
-      &PA->ro, &PA->pi, &AL);
+  sactile::SacHeadLds* head = nullptr;
+  if constexpr (POL == kPolSac) {
+    __shared__ __attribute__((aligned(16))) sactile::SacHeadLds HL;
+    head = &HL;
+  }
+  const KArg<Args> PA = kargs<Args>();
+  const int epb = PA->k.epb, bid = PA->k.group0 + xcd_group(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x));
+  if constexpr (AR)
+    env_pairs_block<BLOCK, NM, true, true, POL, true>(&PA->k, epb, bid, smem, &PA->ro, &PA->pi, &AL, &PA->ar,
+                                                      smem + PA->ar_off, head);
+  else
+    env_pairs_block<BLOCK, NM, true, true, POL>(&PA->k, epb, bid, smem, &PA->ro, &PA->pi, &AL, nullptr, nullptr,
+                                                head);
 }
 
-// The two rollouts with the auto-reset in the step loop (asvrl_env_rollout_ar / asvrl_policy_rollout_ar): new
-// instantiations (env_pairs_block<AR>) with the waves' ResetLds and the per-env reset flags at ar_off of the dynamic
-// LDS, behind everything the plain kernels carve. Philox noise only.
-struct RolloutArArgs {
-  PairsArgs k;
-  AsvRollout ro;
-  AsvAutoReset ar;
-  int ar_off;
-};
-template <int BLOCK, int NM>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(NM == 1 ? 1 : ASVRL_ENV_ROLLOUT_WPE))) void env_rollout_ar_kernel(RolloutArArgs) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const KArg<RolloutArArgs> RA = kargs<RolloutArArgs>();
-  env_pairs_block<BLOCK, NM, true, true, kPolNone, true>(
-      &RA->k, RA->k.epb, RA->k.group0 + xcd_group(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x)), smem,
-      &RA->ro, nullptr, nullptr, &RA->ar, smem + RA->ar_off);
-}
-struct PolicyArArgs {
-  PairsArgs k;
-  AsvRollout ro;
-  AsvPolicy pi;
-  AsvAutoReset ar;
-  int ar_off;
-};
-template <int BLOCK, int NM>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(ASVRL_ENV_POLICY_WPE))) void env_policy_rollout_ar_kernel(PolicyArArgs) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ __attribute__((aligned(16))) atile::ActorLds AL;
-  const KArg<PolicyArArgs> PA = kargs<PolicyArArgs>();
-  env_pairs_block<BLOCK, NM, true, true, kPolActor, true>(
-      &PA->k, PA->k.epb, PA->k.group0 + xcd_group(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x)), smem,
-      &PA->ro, &PA->pi, &AL, &PA->ar, smem + PA->ar_off);
-}
-
-// The closed loop under DQN_Policy (asvrl_dqn_rollout / asvrl_dqn_rollout_ar): env_policy_rollout_kernel and
-// env_policy_rollout_ar_kernel with env_pairs_block<kPolDqn> -- the same static ActorLds (the trunk's images; the
-// head's 8 KB image and its bias stay in L2), the same dynamic carve, one workgroup per CU.
-struct DqnRolloutArgs {
-  PairsArgs k;   // actions null; noise: row 0 of the rollout's
-  AsvRollout ro;
-  AsvDqnPolicy pi;
-};
-template <int BLOCK, int NM>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(ASVRL_ENV_POLICY_WPE))) void env_dqn_rollout_kernel(DqnRolloutArgs) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ __attribute__((aligned(16))) atile::ActorLds AL;
-  const KArg<DqnRolloutArgs> PA = kargs<DqnRolloutArgs>();
-  env_pairs_block<BLOCK, NM, true, true, kPolDqn>(
-      &PA->k, PA->k.epb, PA->k.group0 + xcd_group(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x)), smem,
-      &PA->ro, &PA->pi, &AL);
-}
-struct DqnRolloutArArgs {
-  PairsArgs k;
-  AsvRollout ro;
-  AsvDqnPolicy pi;
-  AsvAutoReset ar;
-  int ar_off;
-};
-template <int BLOCK, int NM>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(ASVRL_ENV_POLICY_WPE))) void env_dqn_rollout_ar_kernel(DqnRolloutArArgs) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ __attribute__((aligned(16))) atile::ActorLds AL;
-  const KArg<DqnRolloutArArgs> PA = kargs<DqnRolloutArArgs>();
-  env_pairs_block<BLOCK, NM, true, true, kPolDqn, true>(
-      &PA->k, PA->k.epb, PA->k.group0 + xcd_group(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x)), smem,
-      &PA->ro, &PA->pi, &AL, &PA->ar, smem + PA->ar_off);
-}
-
-// The closed loop under SAC's sampled actor (asvrl_sac_rollout / asvrl_sac_rollout_ar): the two kernels above with
-// env_pairs_block<kPolSac> -- the same static ActorLds and, beside it, the f32 head (SacHeadLds, 2064 B: 512 weights
-// every lane reads per tile, so they sit in LDS, not L2), the same dynamic carve, one workgroup per CU.
-struct SacRolloutArgs {
-  PairsArgs k;   // actions null; noise: row 0 of the rollout's
-  AsvRollout ro;
-  AsvSacPolicy pi;
-};
-template <int BLOCK, int NM>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(ASVRL_ENV_POLICY_WPE))) void env_sac_rollout_kernel(SacRolloutArgs) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ __attribute__((aligned(16))) atile::ActorLds AL;
-  __shared__ __attribute__((aligned(16))) sactile::SacHeadLds HL;
-  const KArg<SacRolloutArgs> PA = kargs<SacRolloutArgs>();
-  env_pairs_block<BLOCK, NM, true, true, kPolSac>(
-      &PA->k, PA->k.epb, PA->k.group0 + xcd_group(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x)), smem,
-      &PA->ro, &PA->pi, &AL, nullptr, nullptr, &HL);
-}
-struct SacRolloutArArgs {
-  PairsArgs k;
-  AsvRollout ro;
-  AsvSacPolicy pi;
-  AsvAutoReset ar;
-  int ar_off;
-};
-template <int BLOCK, int NM>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(ASVRL_ENV_POLICY_WPE))) void env_sac_rollout_ar_kernel(SacRolloutArArgs) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ __attribute__((aligned(16))) atile::ActorLds AL;
-  __shared__ __attribute__((aligned(16))) sactile::SacHeadLds HL;
-  const KArg<SacRolloutArArgs> PA = kargs<SacRolloutArArgs>();
-  env_pairs_block<BLOCK, NM, true, true, kPolSac, true>(
-      &PA->k, PA->k.epb, PA->k.group0 + xcd_group(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x)), smem,
-      &PA->ro, &PA->pi, &AL, &PA->ar, smem + PA->ar_off, &HL);
-}
-
-// The K-launch fallback of the two calls. In front of step t: row t of obs_prev, the observation (src) the stepping
+// The K-launch fallback of the _ar calls. In front of step t: row t of obs_prev, the observation (src) the stepping
 // envs' rows hold ...
 __global__ __launch_bounds__(kBlock) void autoreset_obs_prev_kernel(const float* __restrict__ src, float* __restrict__ row,
                                                                     const uint8_t* __restrict__ mask, int n_envs, int R) {
@@ -2013,14 +1940,11 @@ PairLaunch pair_launch(int R, int O, int n_envs, int blk_req, int epb_req, int v
 
 using namespace asvrl;
 
-// ------------------------------------------------------------------ the env step and its twelve rollout calls
+// ------------------------------------------------------------------ the env step and its rollout calls
 // One host path. Each call is: env_checks (its arguments), env_plan (the launch shape, and whether the
 // pair-parallel kernel is taken), then launch_groups (that kernel) or, for the rollouts, rollout_fallback (K single
-// steps).
-
-// the groups of checks a call takes beyond the step's own
-enum : unsigned { kRollout = 1, kClosedLoop = 2, kAutoReset = 4, kDqnPolicy = 8, kSacPolicy = 16, kIqnPolicy = 32,
-                  kRainbowPolicy = 64 };   // (kDqnPolicy, kSacPolicy, kIqnPolicy, kRainbowPolicy: with kClosedLoop)
+// steps). A rollout call is one instantiation of rollout_call per policy x auto-reset: the policy is the type of its
+// one policy pointer (NoPolicy: the open loop), and what differs between policies is PolicyTraits below.
 
 static int env_fail(const char* who, const char* what) {
   set_error(std::string(who) + ": " + what);
@@ -2031,22 +1955,194 @@ static int env_fail(const char* who, const char* what) {
     if (!(cond)) return env_fail(who, what);     \
   } while (0)
 
-// The argument checks of the thirteen calls, in the order each call reports them (`who` names the call in the error
-// text). actions / noise: the single step's; the rollouts carry theirs in ro.
-static int env_checks(const char* who, unsigned kind, const AsvParams* params, const AsvEnvState* state,
+// One step of the K-launch fallback's act launch: n observation rows x, the f64 action pairs into act, the launch's
+// step count read from *step + step_add. rec_row / env_mask: row t of the kept actions and the step's env mask, for
+// the policies whose act launch writes the record itself. eps_out / eps_zero: SAC's scratch (PolicyTraits::eps_rows).
+struct ActStep {
+  const float* x;
+  size_t n;
+  double* act;
+  const int64_t* step;
+  int step_add, robots_per_env;
+  double* rec_row;
+  const uint8_t* env_mask;
+  float* eps_out;
+  const float* eps_zero;
+};
+// the rows, the step count and the policy's epsilon schedule and seed into any act launch's IO struct
+template <class IO, class Pol>
+static void act_schedule(IO& io, const Pol* pi, const int64_t* step) {
+  io.step_dev = step;
+  io.eps_steps_per_count = pi->eps_steps_per_count;
+  io.eps_total = pi->eps_total;
+  io.eps_fraction = pi->eps_fraction;
+  io.eps_initial = pi->eps_initial;
+  io.eps_final = pi->eps_final;
+  io.seed = pi->seed;
+}
+static int mlp_images(const char* who, const AsvMlpWeights& w, const char* what) {
+  ENV_REQUIRE(w.enc_frag && w.b_enc && w.w1_frag && w.w2_frag && w.b1 && w.b2 && w.wout && w.bout, what);
+  return 0;
+}
+
+// What differs per policy, all of it:
+//   kWindow      a fused window kernel exists (env_plan may take it); false: the fallback is the call's only form
+//   kPol         that kernel's env_pairs_block<POL>
+//   kHeadBytes   static LDS beside the Actor's images in it
+//   kActRecords  the fallback's act launch adds step_add itself and writes the record row under the step's mask;
+//                false: policy_step_count_kernel in front of it and policy_actions_kernel behind it
+//   eps_rows     the fallback's extra scratch, in [n][2] f32 arrays
+//   checks       is_continuous and the images, in the order the call reports them
+//   act          the fallback's act launch
+struct PolicyDefaults {
+  static constexpr bool kWindow = true, kActRecords = false;
+  static constexpr int kPol = kPolNone;
+  static constexpr size_t kHeadBytes = 0;
+  template <class Pol> static int eps_rows(const Pol*) { return 0; }
+};
+template <class Pol> struct PolicyTraits;
+template <> struct PolicyTraits<NoPolicy> : PolicyDefaults {};
+constexpr const NoPolicy* kOpenLoop = nullptr;   // the policy argument of the step and the open-loop calls
+
+template <> struct PolicyTraits<AsvPolicy> : PolicyDefaults {   // the AC-IQN Actor
+  static constexpr int kPol = kPolActor;
+  static int checks(const char* who, const AsvStepCtl* ctl, const AsvPolicy* pi) {
+    ENV_REQUIRE(ctl->is_continuous, "is_continuous must be 1 (the Actor is the continuous agent)");
+    return mlp_images(who, pi->w, "null actor image");
+  }
+  static int act(const AsvPolicy* pi, const ActStep& s, void* stream) {
+    AsvMlpIO io{};
+    io.x = s.x;
+    io.ldx = ASVRL_OBS_DIM;
+    io.n = static_cast<int32_t>(s.n);
+    io.a_out64 = s.act;
+    act_schedule(io, pi, s.step);
+    return asvrl_actor_forward(&pi->w, &io, atile::MLP_ACT, stream);
+  }
+};
+
+template <> struct PolicyTraits<AsvDqnPolicy> : PolicyDefaults {   // DQN_Policy: the (index, 0.0) pairs into act
+  static constexpr int kPol = kPolDqn;
+  static int checks(const char* who, const AsvStepCtl* ctl, const AsvDqnPolicy* pi) {
+    ENV_REQUIRE(!ctl->is_continuous, "is_continuous must be 0 (DQN's actions are indices)");
+    if (int rc = mlp_images(who, pi->w.trunk, "null DQN image")) return rc;
+    ENV_REQUIRE(pi->w.head_frag != nullptr, "null pi->w.head_frag");
+    // >= 2: the tile's staging reads the first two output rows (the Actor's whole output layer)
+    ENV_REQUIRE(pi->w.n_actions >= 2 && pi->w.n_actions <= ASVRL_DQN_MAX_ACTIONS, "pi->w.n_actions must be in 2..32");
+    return 0;
+  }
+  static int act(const AsvDqnPolicy* pi, const ActStep& s, void* stream) {
+    AsvDqnActIO io{};
+    io.x = s.x;
+    io.ldx = ASVRL_OBS_DIM;
+    io.n = static_cast<int32_t>(s.n);
+    io.act_out = s.act;
+    io.ld_act = 2;
+    act_schedule(io, pi, s.step);
+    return asvrl_dqn_act(&pi->w, &io, stream);
+  }
+};
+
+// SAC's sampled actor: eps_in null draws the noise in the kernel, an all-zero eps_in (deterministic) is the mean
+// action; eps_out is the kernel's own record of the eps it used
+template <> struct PolicyTraits<AsvSacPolicy> : PolicyDefaults {
+  static constexpr int kPol = kPolSac;
+  static constexpr size_t kHeadBytes = sizeof(sactile::SacHeadLds);
+  static int eps_rows(const AsvSacPolicy* pi) { return pi->deterministic != 0 ? 2 : 1; }
+  static int checks(const char* who, const AsvStepCtl* ctl, const AsvSacPolicy* pi) {
+    ENV_REQUIRE(ctl->is_continuous, "is_continuous must be 1 (SAC's actions are continuous)");
+    if (int rc = mlp_images(who, pi->w.trunk, "null SAC actor image")) return rc;
+    ENV_REQUIRE(pi->w.head != nullptr, "null pi->w.head");
+    ENV_REQUIRE(pi->w.bhead != nullptr, "null pi->w.bhead");
+    return 0;
+  }
+  static int act(const AsvSacPolicy* pi, const ActStep& s, void* stream) {
+    AsvSacActIO io{};
+    io.x = s.x;
+    io.ldx = ASVRL_OBS_DIM;
+    io.n = static_cast<int32_t>(s.n);
+    io.a_out64 = s.act;
+    io.eps_in = s.eps_zero;
+    io.eps_out = s.eps_out;
+    act_schedule(io, pi, s.step);
+    return asvrl_sac_act(&pi->w, &io, stream);
+  }
+};
+
+// IQN_Policy: the critic trunk's images (no MLP trunk), the padded head, the risk level. No window kernel: IQN's
+// 150 KB image and 16 waves do not fit beside the env's carve. act_iqn with K = 32 taus per state, drawn in the kernel.
+template <> struct PolicyTraits<AsvIqnPolicy> : PolicyDefaults {
+  static constexpr bool kWindow = false, kActRecords = true;
+  static int checks(const char* who, const AsvStepCtl* ctl, const AsvIqnPolicy* pi) {
+    ENV_REQUIRE(!ctl->is_continuous, "is_continuous must be 0 (IQN's actions are indices)");
+    const AsvCriticWeights& w = pi->w;
+    ENV_REQUIRE(w.wc_frag && w.w1_frag && w.w2_frag && w.bc && w.b1 && w.b2 && w.self_w && w.self_b && w.obj_w && w.obj_b,
+                "null IQN image");
+    ENV_REQUIRE(pi->head.wo_frag != nullptr, "null pi->head.wo_frag");
+    ENV_REQUIRE(pi->head.bo != nullptr, "null pi->head.bo");
+    ENV_REQUIRE(pi->head.n_actions >= 1 && pi->head.n_actions <= ASVRL_IQN_MAX_ACTIONS, "pi->head.n_actions must be in 1..32");
+    ENV_REQUIRE(pi->cvar > 0.f && pi->cvar <= 1.f, "pi->cvar must be in (0, 1]");
+    return 0;
+  }
+  static int act(const AsvIqnPolicy* pi, const ActStep& s, void* stream) {
+    AsvIqnIO io{};
+    io.obs = s.x;
+    io.ld_obs = ASVRL_OBS_DIM;
+    io.B = static_cast<int32_t>(s.n);
+    io.N = 32;
+    act_schedule(io, pi, s.step);
+    AsvIqnActEx ex{};
+    ex.cvar = pi->cvar;
+    ex.robots_per_env = s.robots_per_env;
+    ex.step_add = s.step_add;
+    ex.act_pair = s.act;
+    ex.rec_row = s.rec_row;
+    ex.env_mask = s.env_mask;
+    return asvrl_iqn_act_ex(&pi->w, &pi->head, &io, &ex, stream);
+  }
+};
+
+// Rainbow_Policy: asvrl_rainbow_pack's forward images and the support. No window kernel: its tile is 4 MFMA waves per
+// 32 rows with an LDS layout of its own.
+template <> struct PolicyTraits<AsvRainbowPolicy> : PolicyDefaults {
+  static constexpr bool kWindow = false, kActRecords = true;
+  static int checks(const char* who, const AsvStepCtl* ctl, const AsvRainbowPolicy* pi) {
+    ENV_REQUIRE(!ctl->is_continuous, "is_continuous must be 0 (Rainbow's actions are indices)");
+    const AsvRainbowImg& w = pi->w;
+    ENV_REQUIRE(w.enc && w.b_enc && w.v1 && w.a1 && w.v2 && w.a2 && w.vo && w.mo && w.ao && w.b_v1p && w.b_a1p &&
+                    w.b_v2p && w.b_a2p && w.b_vop && w.b_mop && w.b_aop,
+                "null Rainbow image");
+    ENV_REQUIRE(pi->support != nullptr, "null pi->support");
+    ENV_REQUIRE(pi->eps_total > 0.0 && pi->eps_fraction > 0.0, "pi->eps_total and pi->eps_fraction must be > 0");
+    return 0;
+  }
+  static int act(const AsvRainbowPolicy* pi, const ActStep& s, void* stream) {
+    AsvRainbowNetIO io{};
+    io.x = s.x;
+    io.ldx = ASVRL_OBS_DIM;
+    io.N = static_cast<int32_t>(s.n);
+    io.support = pi->support;
+    act_schedule(io, pi, s.step);
+    AsvRainbowActEx ex{};
+    ex.robots_per_env = s.robots_per_env;
+    ex.step_add = s.step_add;
+    ex.act_pair = s.act;
+    ex.rec_row = s.rec_row;
+    ex.env_mask = s.env_mask;
+    return asvrl_rainbow_net_act_ex(&pi->w, &io, &ex, stream);
+  }
+};
+
+// The argument checks of the step and the rollout calls, in the order each call reports them (`who` names the call
+// in the error text). roll: a rollout, which carries its actions / noise in ro (the single step's are the arguments
+// here); reset: an _ar call, whatever ar points to. Pol other than NoPolicy: the closed loop under *pi.
+template <class Pol>
+static int env_checks(const char* who, bool roll, bool reset, const AsvParams* params, const AsvEnvState* state,
                       const double* actions, const double* noise, const AsvStepCtl* ctl, const AsvStepOut* out,
-                      const AsvRollout* ro, const AsvPolicy* pi, const AsvDqnPolicy* dq, const AsvSacPolicy* sq,
-                      const AsvAutoReset* ar, const AsvEnvLaunch* launch, const AsvIqnPolicy* iq = nullptr,
-                      const AsvRainbowPolicy* rq = nullptr) {
-  const bool roll = (kind & kRollout) != 0, closed = (kind & kClosedLoop) != 0, reset = (kind & kAutoReset) != 0;
-  // the closed loop's policy: dq (DQN_Policy), sq (SAC's sampled actor), iq (IQN_Policy), rq (Rainbow_Policy), else
-  // pi (the Actor)
-  const bool dqn = (kind & kDqnPolicy) != 0, sac = (kind & kSacPolicy) != 0, iqn = (kind & kIqnPolicy) != 0;
-  const bool rbw = (kind & kRainbowPolicy) != 0;
-  const float* pol_obs_in = nullptr;
-  if (closed) pol_obs_in = rbw ? (rq ? rq->obs_in : nullptr) : iqn ? (iq ? iq->obs_in : nullptr) : dqn ? (dq ? dq->obs_in : nullptr) : sac ? (sq ? sq->obs_in : nullptr) : (pi ? pi->obs_in : nullptr);
+                      const AsvRollout* ro, const Pol* pi, const AsvAutoReset* ar, const AsvEnvLaunch* launch) {
+  constexpr bool closed = !std::is_same_v<Pol, NoPolicy>;
   ENV_REQUIRE(params && state && ctl && out && (ro || !roll), "null argument");
-  if (reset) {   // what the two _ar calls refuse beyond their plain calls' checks
+  if (reset) {   // what the _ar calls refuse beyond their plain calls' checks
     ENV_REQUIRE(ar != nullptr, "null ar (the auto-reset description)");
     ENV_REQUIRE(!ro->hold_done, "ro->hold_done cannot be combined with the auto-reset");
     ENV_REQUIRE(ctl->trainer_deactivate && out->env_done != nullptr,
@@ -2067,51 +2163,11 @@ static int env_checks(const char* who, unsigned kind, const AsvParams* params, c
     ENV_REQUIRE(ro->n_steps >= 1, "n_steps must be >= 1");
     if (!closed) ENV_REQUIRE(ro->actions != nullptr, "null actions");
   }
-  if (closed && iqn) {   // IQN_Policy: the critic trunk's images (no MLP trunk), the padded head, the risk level
+  if constexpr (closed) {
     ENV_REQUIRE(ro->actions == nullptr, "ro->actions must be null (the policy supplies the actions)");
-    ENV_REQUIRE(iq != nullptr, "null policy");
-    ENV_REQUIRE(pol_obs_in != nullptr, "null obs_in");
-    ENV_REQUIRE(!ctl->is_continuous, "is_continuous must be 0 (IQN's actions are indices)");
-    const AsvCriticWeights& w = iq->w;
-    ENV_REQUIRE(w.wc_frag && w.w1_frag && w.w2_frag && w.bc && w.b1 && w.b2 && w.self_w && w.self_b && w.obj_w && w.obj_b,
-                "null IQN image");
-    ENV_REQUIRE(iq->head.wo_frag != nullptr, "null pi->head.wo_frag");
-    ENV_REQUIRE(iq->head.bo != nullptr, "null pi->head.bo");
-    ENV_REQUIRE(iq->head.n_actions >= 1 && iq->head.n_actions <= ASVRL_IQN_MAX_ACTIONS, "pi->head.n_actions must be in 1..32");
-    ENV_REQUIRE(iq->cvar > 0.f && iq->cvar <= 1.f, "pi->cvar must be in (0, 1]");
-  } else if (closed && rbw) {   // Rainbow_Policy: asvrl_rainbow_pack's forward images and the support
-    ENV_REQUIRE(ro->actions == nullptr, "ro->actions must be null (the policy supplies the actions)");
-    ENV_REQUIRE(rq != nullptr, "null policy");
-    ENV_REQUIRE(pol_obs_in != nullptr, "null obs_in");
-    ENV_REQUIRE(!ctl->is_continuous, "is_continuous must be 0 (Rainbow's actions are indices)");
-    const AsvRainbowImg& w = rq->w;
-    ENV_REQUIRE(w.enc && w.b_enc && w.v1 && w.a1 && w.v2 && w.a2 && w.vo && w.mo && w.ao && w.b_v1p && w.b_a1p &&
-                    w.b_v2p && w.b_a2p && w.b_vop && w.b_mop && w.b_aop,
-                "null Rainbow image");
-    ENV_REQUIRE(rq->support != nullptr, "null pi->support");
-    ENV_REQUIRE(rq->eps_total > 0.0 && rq->eps_fraction > 0.0, "pi->eps_total and pi->eps_fraction must be > 0");
-  } else if (closed) {
-    ENV_REQUIRE(ro->actions == nullptr, "ro->actions must be null (the policy supplies the actions)");
-    ENV_REQUIRE(dqn ? dq != nullptr : (sac ? sq != nullptr : pi != nullptr), "null policy");
-    ENV_REQUIRE(pol_obs_in != nullptr, "null obs_in");
-    if (dqn)
-      ENV_REQUIRE(!ctl->is_continuous, "is_continuous must be 0 (DQN's actions are indices)");
-    else if (sac)
-      ENV_REQUIRE(ctl->is_continuous, "is_continuous must be 1 (SAC's actions are continuous)");
-    else
-      ENV_REQUIRE(ctl->is_continuous, "is_continuous must be 1 (the Actor is the continuous agent)");
-    const AsvMlpWeights& w = dqn ? dq->w.trunk : (sac ? sq->w.trunk : pi->w);
-    ENV_REQUIRE(w.enc_frag && w.b_enc && w.w1_frag && w.w2_frag && w.b1 && w.b2 && w.wout && w.bout,
-                dqn ? "null DQN image" : (sac ? "null SAC actor image" : "null actor image"));
-    if (sac) {
-      ENV_REQUIRE(sq->w.head != nullptr, "null pi->w.head");
-      ENV_REQUIRE(sq->w.bhead != nullptr, "null pi->w.bhead");
-    }
-    if (dqn) {
-      ENV_REQUIRE(dq->w.head_frag != nullptr, "null pi->w.head_frag");
-      // >= 2: the tile's staging reads the first two output rows (the Actor's whole output layer)
-      ENV_REQUIRE(dq->w.n_actions >= 2 && dq->w.n_actions <= ASVRL_DQN_MAX_ACTIONS, "pi->w.n_actions must be in 2..32");
-    }
+    ENV_REQUIRE(pi != nullptr, "null policy");
+    ENV_REQUIRE(pi->obs_in != nullptr, "null obs_in");
+    if (int rc = PolicyTraits<Pol>::checks(who, ctl, pi)) return rc;
   }
   if (roll) {
     ENV_REQUIRE(ctl->do_dynamics, "do_dynamics must be 1");
@@ -2138,8 +2194,8 @@ static int env_checks(const char* who, unsigned kind, const AsvParams* params, c
                 "block must be 0, 64, 128 or 256");
     ENV_REQUIRE(launch->envs_per_block >= 0 && launch->max_groups >= 0, "negative envs_per_block / max_groups");
   }
-  if (closed)
-    ENV_REQUIRE(reinterpret_cast<uintptr_t>(pol_obs_in) % 16 == 0 &&
+  if constexpr (closed)
+    ENV_REQUIRE(reinterpret_cast<uintptr_t>(pi->obs_in) % 16 == 0 &&
                     reinterpret_cast<uintptr_t>(out->obs) % 16 == 0 &&
                     (!reset || reinterpret_cast<uintptr_t>(ar->obs_prev) % 16 == 0),
                 "observation rows must be 16-byte aligned");
@@ -2236,19 +2292,16 @@ static int env_plan(const char* who, const AsvEnvState* state, const AsvStepCtl*
   return 0;
 }
 
-// The kernel family of an argument struct, and the PairsArgs in it. The auto-reset kernels exist for Philox noise only.
+// The kernel of an argument struct, and the PairsArgs in it. The auto-reset windows exist for Philox noise only.
 template <int B, int NM> static auto kernel_of(const PairsArgs&) { return &env_pairs_kernel<B, NM>; }
-template <int B, int NM> static auto kernel_of(const RolloutArgs&) { return &env_rollout_kernel<B, NM>; }
-template <int B, int NM> static auto kernel_of(const PolicyArgs&) { return &env_policy_rollout_kernel<B, NM>; }
-template <int B, int NM> static auto kernel_of(const RolloutArArgs&) { return &env_rollout_ar_kernel<B, NM>; }
-template <int B, int NM> static auto kernel_of(const PolicyArArgs&) { return &env_policy_rollout_ar_kernel<B, NM>; }
-template <int B, int NM> static auto kernel_of(const DqnRolloutArgs&) { return &env_dqn_rollout_kernel<B, NM>; }
-template <int B, int NM> static auto kernel_of(const DqnRolloutArArgs&) { return &env_dqn_rollout_ar_kernel<B, NM>; }
-template <int B, int NM> static auto kernel_of(const SacRolloutArgs&) { return &env_sac_rollout_kernel<B, NM>; }
-template <int B, int NM> static auto kernel_of(const SacRolloutArArgs&) { return &env_sac_rollout_ar_kernel<B, NM>; }
-template <class Args>
-constexpr bool kPhiloxOnly = std::is_same<Args, RolloutArArgs>::value || std::is_same<Args, PolicyArArgs>::value ||
-                             std::is_same<Args, DqnRolloutArArgs>::value || std::is_same<Args, SacRolloutArArgs>::value;
+template <int B, int NM, class Pol, bool AR> static auto kernel_of(const WindowArgs<Pol, AR>&) {
+  if constexpr (std::is_same_v<Pol, NoPolicy>)
+    return &env_rollout_kernel<B, NM, AR>;
+  else
+    return &env_policy_rollout_kernel<B, NM, PolicyTraits<Pol>::kPol, AR>;
+}
+template <class Args> constexpr bool kPhiloxOnly = false;
+template <class Pol> constexpr bool kPhiloxOnly<WindowArgs<Pol, true>> = true;
 static PairsArgs& pairs_of(PairsArgs& a) { return a; }
 template <class Args> static PairsArgs& pairs_of(Args& a) { return a.k; }
 
@@ -2259,8 +2312,8 @@ static auto kernel_for_noise(int nm, const Args& a) -> void (*)(Args) {
   }
   return nm == 1 ? kernel_of<B, 1>(a) : kernel_of<B, 2>(a);
 }
-// The pair-parallel launch of any of the nine kernels: P.groups workgroups in launches of at most P.chunk, each
-// told its first group.
+// The pair-parallel launch of the step's kernel or a window's: P.groups workgroups in launches of at most P.chunk,
+// each told its first group.
 template <class Args>
 static int launch_groups(const char* who, const EnvPlan& P, Args a, hipStream_t st) {
   void (*const kern)(Args) = P.pl.blk == 64    ? kernel_for_noise<64>(P.nm, a)
@@ -2277,7 +2330,7 @@ extern "C" int asvrl_env_step_ex(const AsvParams* params, const AsvEnvState* sta
                                  const double* noise, const AsvStepCtl* ctl, const AsvStepOut* out,
                                  const AsvEnvLaunch* launch, void* stream) {
   const char* who = "asvrl_env_step";
-  if (int rc = env_checks(who, 0, params, state, actions, noise, ctl, out, nullptr, nullptr, nullptr, nullptr, nullptr,
+  if (int rc = env_checks(who, false, false, params, state, actions, noise, ctl, out, nullptr, kOpenLoop, nullptr,
                           launch))
     return rc;
   if (state->n_envs == 0) return 0;
@@ -2306,128 +2359,33 @@ extern "C" int asvrl_env_step(const AsvParams* params, const AsvEnvState* state,
   return asvrl_env_step_ex(params, state, actions, noise, ctl, out, nullptr, stream);
 }
 
-// the Actor's act launch over n rows x: the actions into act, the step count read from step
-static AsvMlpIO act_io(const AsvPolicy* pi, const float* x, size_t n, double* act, const int64_t* step) {
-  AsvMlpIO io{};
-  io.x = x;
-  io.ldx = ASVRL_OBS_DIM;
-  io.n = static_cast<int32_t>(n);
-  io.a_out64 = act;
-  io.step_dev = step;
-  io.eps_steps_per_count = pi->eps_steps_per_count;
-  io.eps_total = pi->eps_total;
-  io.eps_fraction = pi->eps_fraction;
-  io.eps_initial = pi->eps_initial;
-  io.eps_final = pi->eps_final;
-  io.seed = pi->seed;
-  return io;
-}
-
-// DQN_Policy's act launch over n rows x: the (index, 0.0) pairs into act
-static AsvDqnActIO dqn_act_io(const AsvDqnPolicy* dq, const float* x, size_t n, double* act, const int64_t* step) {
-  AsvDqnActIO io{};
-  io.x = x;
-  io.ldx = ASVRL_OBS_DIM;
-  io.n = static_cast<int32_t>(n);
-  io.act_out = act;
-  io.ld_act = 2;
-  io.step_dev = step;
-  io.eps_steps_per_count = dq->eps_steps_per_count;
-  io.eps_total = dq->eps_total;
-  io.eps_fraction = dq->eps_fraction;
-  io.eps_initial = dq->eps_initial;
-  io.eps_final = dq->eps_final;
-  io.seed = dq->seed;
-  return io;
-}
-
-// the sampled actor's act launch over n rows x: eps_in null draws the noise in the kernel, an all-zero eps_in is
-// the mean action; eps_out is the kernel's own record of the eps it used
-static AsvSacActIO sac_act_io(const AsvSacPolicy* sq, const float* x, size_t n, double* act, const float* eps_in,
-                              float* eps_out, const int64_t* step) {
-  AsvSacActIO io{};
-  io.x = x;
-  io.ldx = ASVRL_OBS_DIM;
-  io.n = static_cast<int32_t>(n);
-  io.a_out64 = act;
-  io.eps_in = eps_in;
-  io.eps_out = eps_out;
-  io.step_dev = step;
-  io.eps_steps_per_count = sq->eps_steps_per_count;
-  io.eps_total = sq->eps_total;
-  io.eps_fraction = sq->eps_fraction;
-  io.eps_initial = sq->eps_initial;
-  io.eps_final = sq->eps_final;
-  io.seed = sq->seed;
-  return io;
-}
-
-// act_iqn's launch over n rows x (K = 32 taus per state, drawn in the kernel): the window form's outputs are its
-// AsvIqnActEx's
-static AsvIqnIO iqn_act_io(const AsvIqnPolicy* iq, const float* x, size_t n, const int64_t* step) {
-  AsvIqnIO io{};
-  io.obs = x;
-  io.ld_obs = ASVRL_OBS_DIM;
-  io.B = static_cast<int32_t>(n);
-  io.N = 32;
-  io.step_dev = step;
-  io.eps_steps_per_count = iq->eps_steps_per_count;
-  io.eps_total = iq->eps_total;
-  io.eps_fraction = iq->eps_fraction;
-  io.eps_initial = iq->eps_initial;
-  io.eps_final = iq->eps_final;
-  io.seed = iq->seed;
-  return io;
-}
-
-// act_rainbow's launch over n rows: the window form's outputs are its AsvRainbowActEx's
-static AsvRainbowNetIO rainbow_act_io(const AsvRainbowPolicy* rq, const float* x, size_t n, const int64_t* step) {
-  AsvRainbowNetIO io{};
-  io.x = x;
-  io.ldx = ASVRL_OBS_DIM;
-  io.N = static_cast<int32_t>(n);
-  io.support = rq->support;
-  io.step_dev = step;
-  io.eps_steps_per_count = rq->eps_steps_per_count;
-  io.eps_total = rq->eps_total;
-  io.eps_fraction = rq->eps_fraction;
-  io.eps_initial = rq->eps_initial;
-  io.eps_final = rq->eps_final;
-  io.seed = rq->seed;
-  return io;
-}
-
-// The K-launch form of the twelve rollout calls (per-robot parameters, layout 2, a carve that does not fit; IQN_Policy and
-// Rainbow_Policy always). Per step:
-// the act launch (closed loop), the obs_prev row (auto-reset), the single step and its record launch; then, for the
-// auto-reset, the reset mask and counts and the reset of the ended envs with their observation
-// (asvrl_env_reset_observe, or the two launches where that call does not apply). pi null: the open loop, the actions
-// out of ro; dq instead of pi: DQN_Policy's act launch (asvrl_dqn_act) in the Actor's place; sq: SAC's
-// (asvrl_sac_act, its eps_out and, when deterministic, its zero eps_in behind the actions in the scratch); iq:
-// IQN_Policy's, the only form its two calls have (asvrl_iqn_act_ex: no step-count and no record-copy launch); rq:
-// Rainbow_Policy's, likewise (asvrl_rainbow_net_act_ex). ar null: a plain call, which alone can hold ended envs (hold_done: env_checks refuses it with ar).
+// The K-launch form of the rollout calls (per-robot parameters, layout 2, a carve that does not fit; always, for a
+// policy without a window kernel). Per step: the act launch (closed loop: PolicyTraits<Pol>::act, between the
+// step-count and the record-copy launch unless it does both itself), the obs_prev row (auto-reset), the single step
+// and its record launch; then, for the auto-reset, the reset mask and counts and the reset of the ended envs with
+// their observation (asvrl_env_reset_observe, or the two launches where that call does not apply). NoPolicy: the open
+// loop, the actions out of ro. ar null: a plain call, which alone can hold ended envs (hold_done: env_checks refuses
+// it with ar).
+template <class Pol>
 static int rollout_fallback(const char* who, const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
-                            const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi, const AsvDqnPolicy* dq,
-                            const AsvSacPolicy* sq, const AsvAutoReset* ar, const AsvEnvLaunch* launch, void* stream,
-                            const AsvIqnPolicy* iq = nullptr, const AsvRainbowPolicy* rq = nullptr) {
+                            const AsvStepOut* out, const AsvRollout* ro, const Pol* pi, const AsvAutoReset* ar,
+                            const AsvEnvLaunch* launch, void* stream) {
+  using T = PolicyTraits<Pol>;
+  constexpr bool closed = !std::is_same_v<Pol, NoPolicy>;
   hipStream_t st = as_stream(stream);
-  const bool closed = pi != nullptr || dq != nullptr || sq != nullptr || iq != nullptr || rq != nullptr;
-  const float* pol_obs = rq != nullptr ? rq->obs_in : iq != nullptr ? iq->obs_in : dq != nullptr ? dq->obs_in : (sq != nullptr ? sq->obs_in : (pi != nullptr ? pi->obs_in : nullptr));
-  const int64_t* pol_step = rq != nullptr ? rq->step_dev : iq != nullptr ? iq->step_dev : dq != nullptr ? dq->step_dev : (sq != nullptr ? sq->step_dev : (pi != nullptr ? pi->step_dev : nullptr));
-  double* pol_actions = rq != nullptr ? rq->actions : iq != nullptr ? iq->actions : dq != nullptr ? dq->actions : (sq != nullptr ? sq->actions : (pi != nullptr ? pi->actions : nullptr));
   const int E = state->n_envs, R = state->max_robots;
   const size_t NT = static_cast<size_t>(E) * R;
   const size_t noise_row = NT * (static_cast<size_t>(state->max_obs) + R) * 5;
   const unsigned egrid = (static_cast<unsigned>(E) + kBlock - 1) / kBlock;
   const unsigned agrid = (static_cast<unsigned>(NT) + kBlock - 1) / kBlock;
   const unsigned qgrid = (static_cast<unsigned>(NT) * (ASVRL_OBS_DIM / 4) + kBlock - 1) / kBlock;
-  // stream-ordered scratch: the actions [NT][2] f64 and the act launch's step count (closed loop), then the reset
-  // mask [E] (auto-reset); hold_done's mask [E] is an allocation of its own
-  // (SAC: eps_out [NT][2] f32 and, when deterministic, the zero eps_in [NT][2] f32 behind the step count)
+  // stream-ordered scratch: the actions [NT][2] f64 and the act launch's step count (closed loop), then the policy's
+  // eps arrays [NT][2] f32 (SAC: eps_out and, when deterministic, the zero eps_in), then the reset mask [E]
+  // (auto-reset); hold_done's mask [E] is an allocation of its own
   const size_t pol_bytes = closed ? sizeof(double) * 2 * NT + sizeof(int64_t) : 0;
-  const size_t eps_bytes = sq != nullptr ? sizeof(float) * 2 * NT : 0;
-  const bool zero_eps = sq != nullptr && sq->deterministic != 0;
-  const size_t act_bytes = pol_bytes + eps_bytes * (zero_eps ? 2 : 1);
+  const size_t eps_bytes = sizeof(float) * 2 * NT;
+  const int eps_rows = T::eps_rows(pi);
+  const size_t act_bytes = pol_bytes + eps_bytes * eps_rows;
   const size_t scratch_bytes = act_bytes + (ar != nullptr ? E : 0);
   unsigned char* scratch = nullptr;
   if (scratch_bytes != 0 && hipMallocAsync(reinterpret_cast<void**>(&scratch), scratch_bytes, st) != hipSuccess)
@@ -2435,8 +2393,8 @@ static int rollout_fallback(const char* who, const AsvParams* params, const AsvE
   double* act = reinterpret_cast<double*>(scratch);
   int64_t* step = closed ? reinterpret_cast<int64_t*>(act + 2 * NT) : nullptr;
   uint8_t* rmask = ar != nullptr ? scratch + act_bytes : nullptr;
-  float* eps_out = sq != nullptr ? reinterpret_cast<float*>(scratch + pol_bytes) : nullptr;
-  float* eps_zero = zero_eps ? eps_out + 2 * NT : nullptr;
+  float* eps_out = eps_rows >= 1 ? reinterpret_cast<float*>(scratch + pol_bytes) : nullptr;
+  float* eps_zero = eps_rows >= 2 ? eps_out + 2 * NT : nullptr;
   int rc = 0;
   if (eps_zero != nullptr && hipMemsetAsync(eps_zero, 0, eps_bytes, st) != hipSuccess) rc = check_launch(who);
   uint8_t* hold_mask = nullptr;
@@ -2456,49 +2414,25 @@ static int rollout_fallback(const char* who, const AsvParams* params, const AsvE
   AsvStepOut oo = *out;   // the observation pass's outputs: no episode bookkeeping
   oo.env_done = nullptr;
   oo.stats = nullptr;
-  const float* obs_first = closed ? pol_obs : (ar != nullptr ? ar->obs_in : nullptr);
+  const float* obs_first = ar != nullptr ? ar->obs_in : nullptr;
+  if constexpr (closed) obs_first = pi->obs_in;
   for (int t = 0; t < ro->n_steps && rc == 0; ++t) {
     AsvStepCtl c = *ctl;
     c.counter = ctl->counter + static_cast<uint64_t>(t);
     if (hold_mask != nullptr) c.env_mask = hold_mask;
     const float* obs_t = t == 0 ? obs_first : out->obs;   // the observation the step before (or its reset) wrote
     const double* actions = act;
-    if (iq != nullptr) {
-      // one launch: the act at step *step_dev + t, the step's pairs and the record row under the step's mask
-      const AsvIqnIO io = iqn_act_io(iq, obs_t, NT, pol_step);
-      AsvIqnActEx ex{};
-      ex.cvar = iq->cvar;
-      ex.robots_per_env = R;
-      ex.step_add = t;
-      ex.act_pair = act;
-      ex.rec_row = pol_actions != nullptr ? pol_actions + static_cast<size_t>(t) * 2 * NT : nullptr;
-      ex.env_mask = c.env_mask;
-      rc = asvrl_iqn_act_ex(&iq->w, &iq->head, &io, &ex, stream);
-    } else if (rq != nullptr) {
-      // likewise: act_rainbow at step *step_dev + t, the step's pairs and the masked record row in the one launch
-      const AsvRainbowNetIO io = rainbow_act_io(rq, obs_t, NT, pol_step);
-      AsvRainbowActEx ex{};
-      ex.robots_per_env = R;
-      ex.step_add = t;
-      ex.act_pair = act;
-      ex.rec_row = pol_actions != nullptr ? pol_actions + static_cast<size_t>(t) * 2 * NT : nullptr;
-      ex.env_mask = c.env_mask;
-      rc = asvrl_rainbow_net_act_ex(&rq->w, &io, &ex, stream);
-    } else if (closed) {
-      hipLaunchKernelGGL(policy_step_count_kernel, dim3(1), dim3(1), 0, st, pol_step, step, t);
-      if (dq != nullptr) {
-        const AsvDqnActIO io = dqn_act_io(dq, obs_t, NT, act, step);
-        rc = asvrl_dqn_act(&dq->w, &io, stream);
-      } else if (sq != nullptr) {
-        const AsvSacActIO io = sac_act_io(sq, obs_t, NT, act, eps_zero, eps_out, step);
-        rc = asvrl_sac_act(&sq->w, &io, stream);
+    if constexpr (closed) {
+      double* rec_row = pi->actions != nullptr ? pi->actions + static_cast<size_t>(t) * 2 * NT : nullptr;
+      if constexpr (T::kActRecords) {
+        // one launch: the act at step *step_dev + t, the step's pairs and the record row under the step's mask
+        rc = T::act(pi, ActStep{obs_t, NT, act, pi->step_dev, t, R, rec_row, c.env_mask, eps_out, eps_zero}, stream);
       } else {
-        const AsvMlpIO io = act_io(pi, obs_t, NT, act, step);
-        rc = asvrl_actor_forward(&pi->w, &io, atile::MLP_ACT, stream);
+        hipLaunchKernelGGL(policy_step_count_kernel, dim3(1), dim3(1), 0, st, pi->step_dev, step, t);
+        rc = T::act(pi, ActStep{obs_t, NT, act, step, 0, R, nullptr, nullptr, eps_out, eps_zero}, stream);
+        if (rc == 0 && rec_row != nullptr)
+          hipLaunchKernelGGL(policy_actions_kernel, dim3(agrid), dim3(kBlock), 0, st, act, rec_row, c.env_mask, E, R);
       }
-      if (rc == 0 && pol_actions != nullptr)
-        hipLaunchKernelGGL(policy_actions_kernel, dim3(agrid), dim3(kBlock), 0, st, act,
-                           pol_actions + static_cast<size_t>(t) * 2 * NT, c.env_mask, E, R);
     } else {
       actions = ro->actions + static_cast<size_t>(t) * 2 * NT;
     }
@@ -2536,52 +2470,51 @@ static int rollout_fallback(const char* who, const AsvParams* params, const AsvE
   return rc;
 }
 
-// The twelve rollout calls: check, plan, zero the counts the window adds to, then the one launch or the fallback.
-// pi, dq, sq, iq or rq: the closed loop under the Actor, DQN_Policy, SAC's sampled actor, IQN_Policy or Rainbow_Policy (ro->actions is null then); ar: the auto-reset (Philox noise only: no recorded rows).
-static int rollout_call(const char* who, unsigned kind, const AsvParams* params, const AsvEnvState* state,
-                        const AsvStepCtl* ctl, const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi,
-                        const AsvDqnPolicy* dq, const AsvSacPolicy* sq, const AsvAutoReset* ar,
-                        const AsvEnvLaunch* launch, void* stream, const AsvIqnPolicy* iq = nullptr,
-                        const AsvRainbowPolicy* rq = nullptr) {
-  if (int rc = env_checks(who, kind, params, state, nullptr, nullptr, ctl, out, ro, pi, dq, sq, ar, launch, iq, rq)) return rc;
+// A rollout call: check, plan, zero the counts the window adds to, then the one launch or the fallback. AR: an _ar
+// call, the auto-reset described by ar (Philox noise only: no recorded rows); a plain call passes ar null. Pol other
+// than NoPolicy: the closed loop under *pi (ro->actions is null then).
+template <bool AR, class Pol>
+static int rollout_call(const char* who, const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                        const AsvStepOut* out, const AsvRollout* ro, const Pol* pi, const AsvAutoReset* ar,
+                        const AsvEnvLaunch* launch, void* stream) {
+  using T = PolicyTraits<Pol>;
+  if (int rc = env_checks(who, true, AR, params, state, nullptr, nullptr, ctl, out, ro, pi, ar, launch)) return rc;
   if (state->n_envs == 0) return 0;
   EnvPlan P{};
-  // kIqnPolicy never plans the fused launch: IQN's 150 KB image and 16 waves do not fit beside the env's carve; nor
-  // kRainbowPolicy: its tile is 4 MFMA waves per 32 rows with an LDS layout of its own
-  if ((kind & (kIqnPolicy | kRainbowPolicy)) == 0)
-    if (int rc = env_plan(who, state, ctl, launch, pi != nullptr || dq != nullptr || sq != nullptr, ar != nullptr, &P,
-                          sq != nullptr ? sizeof(sactile::SacHeadLds) : 0))
-      return rc;
+  if constexpr (T::kWindow) {
+    if (int rc = env_plan(who, state, ctl, launch, !std::is_same_v<Pol, NoPolicy>, AR, &P, T::kHeadBytes)) return rc;
+  }
   hipStream_t st = as_stream(stream);
   if (ro->steps_run != nullptr && hipMemsetAsync(ro->steps_run, 0, sizeof(int32_t) * state->n_envs, st) != hipSuccess)
     return check_launch(who);
-  if (ar != nullptr && ar->resets != nullptr &&
+  if (AR && ar->resets != nullptr &&
       hipMemsetAsync(ar->resets, 0, sizeof(int32_t) * state->n_envs, st) != hipSuccess)
     return check_launch(who);
-  if (!P.fused) return rollout_fallback(who, params, state, ctl, out, ro, pi, dq, sq, ar, launch, stream, iq, rq);
-  const PairsArgs k{*params, *state, *ctl, *out, ro->actions, ar != nullptr ? nullptr : ro->noise, P.pl.epb, 0};
-  if (dq != nullptr && ar != nullptr) return launch_groups(who, P, DqnRolloutArArgs{k, *ro, *dq, *ar, P.ar_off}, st);
-  if (dq != nullptr) return launch_groups(who, P, DqnRolloutArgs{k, *ro, *dq}, st);
-  if (sq != nullptr && ar != nullptr) return launch_groups(who, P, SacRolloutArArgs{k, *ro, *sq, *ar, P.ar_off}, st);
-  if (sq != nullptr) return launch_groups(who, P, SacRolloutArgs{k, *ro, *sq}, st);
-  if (pi != nullptr && ar != nullptr) return launch_groups(who, P, PolicyArArgs{k, *ro, *pi, *ar, P.ar_off}, st);
-  if (ar != nullptr) return launch_groups(who, P, RolloutArArgs{k, *ro, *ar, P.ar_off}, st);
-  if (pi != nullptr) return launch_groups(who, P, PolicyArgs{k, *ro, *pi}, st);
-  return launch_groups(who, P, RolloutArgs{k, *ro}, st);
+  if constexpr (T::kWindow) {
+    if (P.fused) {
+      WindowArgs<Pol, AR> a{
+          PairsArgs{*params, *state, *ctl, *out, ro->actions, AR ? nullptr : ro->noise, P.pl.epb, 0}, *ro};
+      if constexpr (!std::is_same_v<Pol, NoPolicy>) a.pi = *pi;
+      if constexpr (AR) {
+        a.ar = *ar;
+        a.ar_off = P.ar_off;
+      }
+      return launch_groups(who, P, a, st);
+    }
+  }
+  return rollout_fallback(who, params, state, ctl, out, ro, pi, ar, launch, stream);
 }
 
 extern "C" int asvrl_env_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                  const AsvStepOut* out, const AsvRollout* ro, const AsvEnvLaunch* launch,
                                  void* stream) {
-  return rollout_call("asvrl_env_rollout", kRollout, params, state, ctl, out, ro, nullptr, nullptr, nullptr, nullptr,
-                      launch, stream);
+  return rollout_call<false>("asvrl_env_rollout", params, state, ctl, out, ro, kOpenLoop, nullptr, launch, stream);
 }
 
 extern "C" int asvrl_policy_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                     const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi,
                                     const AsvEnvLaunch* launch, void* stream) {
-  return rollout_call("asvrl_policy_rollout", kRollout | kClosedLoop, params, state, ctl, out, ro, pi, nullptr, nullptr,
-                      nullptr, launch, stream);
+  return rollout_call<false>("asvrl_policy_rollout", params, state, ctl, out, ro, pi, nullptr, launch, stream);
 }
 
 extern "C" int64_t asvrl_policy_struct_size(void) { return sizeof(AsvPolicy); }
@@ -2589,29 +2522,25 @@ extern "C" int64_t asvrl_policy_struct_size(void) { return sizeof(AsvPolicy); }
 extern "C" int asvrl_env_rollout_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                     const AsvStepOut* out, const AsvRollout* ro, const AsvAutoReset* ar,
                                     const AsvEnvLaunch* launch, void* stream) {
-  return rollout_call("asvrl_env_rollout_ar", kRollout | kAutoReset, params, state, ctl, out, ro, nullptr, nullptr, nullptr,
-                      ar, launch, stream);
+  return rollout_call<true>("asvrl_env_rollout_ar", params, state, ctl, out, ro, kOpenLoop, ar, launch, stream);
 }
 
 extern "C" int asvrl_policy_rollout_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                        const AsvStepOut* out, const AsvRollout* ro, const AsvPolicy* pi,
                                        const AsvAutoReset* ar, const AsvEnvLaunch* launch, void* stream) {
-  return rollout_call("asvrl_policy_rollout_ar", kRollout | kClosedLoop | kAutoReset, params, state, ctl, out, ro, pi,
-                      nullptr, nullptr, ar, launch, stream);
+  return rollout_call<true>("asvrl_policy_rollout_ar", params, state, ctl, out, ro, pi, ar, launch, stream);
 }
 
 extern "C" int asvrl_dqn_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                  const AsvStepOut* out, const AsvRollout* ro, const AsvDqnPolicy* pi,
                                  const AsvEnvLaunch* launch, void* stream) {
-  return rollout_call("asvrl_dqn_rollout", kRollout | kClosedLoop | kDqnPolicy, params, state, ctl, out, ro, nullptr, pi,
-                      nullptr, nullptr, launch, stream);
+  return rollout_call<false>("asvrl_dqn_rollout", params, state, ctl, out, ro, pi, nullptr, launch, stream);
 }
 
 extern "C" int asvrl_dqn_rollout_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                     const AsvStepOut* out, const AsvRollout* ro, const AsvDqnPolicy* pi,
                                     const AsvAutoReset* ar, const AsvEnvLaunch* launch, void* stream) {
-  return rollout_call("asvrl_dqn_rollout_ar", kRollout | kClosedLoop | kAutoReset | kDqnPolicy, params, state, ctl, out,
-                      ro, nullptr, pi, nullptr, ar, launch, stream);
+  return rollout_call<true>("asvrl_dqn_rollout_ar", params, state, ctl, out, ro, pi, ar, launch, stream);
 }
 
 extern "C" int64_t asvrl_dqn_policy_struct_size(void) { return sizeof(AsvDqnPolicy); }
@@ -2619,15 +2548,13 @@ extern "C" int64_t asvrl_dqn_policy_struct_size(void) { return sizeof(AsvDqnPoli
 extern "C" int asvrl_sac_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                  const AsvStepOut* out, const AsvRollout* ro, const AsvSacPolicy* pi,
                                  const AsvEnvLaunch* launch, void* stream) {
-  return rollout_call("asvrl_sac_rollout", kRollout | kClosedLoop | kSacPolicy, params, state, ctl, out, ro, nullptr,
-                      nullptr, pi, nullptr, launch, stream);
+  return rollout_call<false>("asvrl_sac_rollout", params, state, ctl, out, ro, pi, nullptr, launch, stream);
 }
 
 extern "C" int asvrl_sac_rollout_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                     const AsvStepOut* out, const AsvRollout* ro, const AsvSacPolicy* pi,
                                     const AsvAutoReset* ar, const AsvEnvLaunch* launch, void* stream) {
-  return rollout_call("asvrl_sac_rollout_ar", kRollout | kClosedLoop | kAutoReset | kSacPolicy, params, state, ctl, out,
-                      ro, nullptr, nullptr, pi, ar, launch, stream);
+  return rollout_call<true>("asvrl_sac_rollout_ar", params, state, ctl, out, ro, pi, ar, launch, stream);
 }
 
 extern "C" int64_t asvrl_sac_policy_struct_size(void) { return sizeof(AsvSacPolicy); }
@@ -2635,15 +2562,13 @@ extern "C" int64_t asvrl_sac_policy_struct_size(void) { return sizeof(AsvSacPoli
 extern "C" int asvrl_iqn_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                  const AsvStepOut* out, const AsvRollout* ro, const AsvIqnPolicy* pi,
                                  const AsvEnvLaunch* launch, void* stream) {
-  return rollout_call("asvrl_iqn_rollout", kRollout | kClosedLoop | kIqnPolicy, params, state, ctl, out, ro, nullptr,
-                      nullptr, nullptr, nullptr, launch, stream, pi);
+  return rollout_call<false>("asvrl_iqn_rollout", params, state, ctl, out, ro, pi, nullptr, launch, stream);
 }
 
 extern "C" int asvrl_iqn_rollout_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                     const AsvStepOut* out, const AsvRollout* ro, const AsvIqnPolicy* pi,
                                     const AsvAutoReset* ar, const AsvEnvLaunch* launch, void* stream) {
-  return rollout_call("asvrl_iqn_rollout_ar", kRollout | kClosedLoop | kAutoReset | kIqnPolicy, params, state, ctl, out,
-                      ro, nullptr, nullptr, nullptr, ar, launch, stream, pi);
+  return rollout_call<true>("asvrl_iqn_rollout_ar", params, state, ctl, out, ro, pi, ar, launch, stream);
 }
 
 extern "C" int64_t asvrl_iqn_policy_struct_size(void) { return sizeof(AsvIqnPolicy); }
@@ -2651,15 +2576,13 @@ extern "C" int64_t asvrl_iqn_policy_struct_size(void) { return sizeof(AsvIqnPoli
 extern "C" int asvrl_rainbow_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                      const AsvStepOut* out, const AsvRollout* ro, const AsvRainbowPolicy* pi,
                                      const AsvEnvLaunch* launch, void* stream) {
-  return rollout_call("asvrl_rainbow_rollout", kRollout | kClosedLoop | kRainbowPolicy, params, state, ctl, out, ro,
-                      nullptr, nullptr, nullptr, nullptr, launch, stream, nullptr, pi);
+  return rollout_call<false>("asvrl_rainbow_rollout", params, state, ctl, out, ro, pi, nullptr, launch, stream);
 }
 
 extern "C" int asvrl_rainbow_rollout_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                         const AsvStepOut* out, const AsvRollout* ro, const AsvRainbowPolicy* pi,
                                         const AsvAutoReset* ar, const AsvEnvLaunch* launch, void* stream) {
-  return rollout_call("asvrl_rainbow_rollout_ar", kRollout | kClosedLoop | kAutoReset | kRainbowPolicy, params, state,
-                      ctl, out, ro, nullptr, nullptr, nullptr, ar, launch, stream, nullptr, pi);
+  return rollout_call<true>("asvrl_rainbow_rollout_ar", params, state, ctl, out, ro, pi, ar, launch, stream);
 }
 
 extern "C" int64_t asvrl_rainbow_policy_struct_size(void) { return sizeof(AsvRainbowPolicy); }

@@ -1,8 +1,8 @@
 // asvrl_sac_tile.h -- SAC_model.Actor's head on the one-wave Actor tile (asvrl_actor_tile.h, trunk_chain): the f32
 // head beside ActorLds, the Philox + Box-Muller noise of a row, and the reparameterised sample with its atan squash
 // and log-probability (SAC_model.py:183-199).
-// Shared by asvrl_sac.hip (sac_act_kernel, sac_actor_fwd_kernel) and asvrl_env.hip (env_sac_rollout_kernel, the SAC
-// act in front of every env step): the same dot products in the same order and the same Philox key, so a row's
+// Shared by asvrl_sac.hip (sac_act_kernel, sac_actor_fwd_kernel) and asvrl_env.hip (env_policy_rollout_kernel<kPolSac>, the
+// SAC act in front of every env step): the same dot products in the same order and the same Philox key, so a row's
 // action does not depend on which kernel computed it.
 #pragma once
 #include "asvrl_actor_tile.h"

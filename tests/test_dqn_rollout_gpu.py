@@ -1,5 +1,5 @@
 """GPU: the closed-loop rollout windows under DQN_Policy (asvrl_dqn_rollout / asvrl_dqn_rollout_ar,
-env_dqn_rollout_kernel / env_dqn_rollout_ar_kernel) against the composed loop of the calls they replace, bit for
+env_policy_rollout_kernel's kPolDqn instantiations) against the composed loop of the calls they replace, bit for
 bit: for t < K, fused_dqn.dqn_act on the current observation at step counter STEP0 + t, the single env step with
 is_continuous=False at noise counter C0 + t on those indices and, with the auto-reset, reset_observe on
 env_done & mask at (RC + t, OC + t). Every record of every step (the actions among them; obs_prev, pushed and resets

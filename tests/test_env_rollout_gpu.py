@@ -1,4 +1,4 @@
-"""GPU: the fused K-step env rollout (asvrl_env_rollout, env_rollout_kernel) against
+"""GPU: the fused K-step env rollout (asvrl_env_rollout, env_rollout_kernel without AR) against
 
   * the K-call loop of single steps it replaces, bit for bit (records of every step, final state and outputs),
     over shapes with partial groups, 1 / 12 / 30 robots and vortex cores, both Philox precisions, three launch

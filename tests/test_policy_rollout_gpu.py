@@ -1,5 +1,5 @@
-"""GPU: the closed-loop policy rollout (asvrl_policy_rollout, env_policy_rollout_kernel) against the composed loop of
-the existing calls it replaces, bit for bit: for t < K, fused_mlp.actor_act on the current observation at step
+"""GPU: the closed-loop policy rollout (asvrl_policy_rollout, env_policy_rollout_kernel<kPolActor>) against the composed
+loop of the existing calls it replaces, bit for bit: for t < K, fused_mlp.actor_act on the current observation at step
 counter s + t, then the single env step at noise counter c + t on those actions. Every record of every step
 (the actions included), the steps every env took and the final state and outputs are compared with atol = rtol =
 0 (the stats' return sum, an atomic sum, within 1e-12 as in the open-loop test), over shapes with partial groups,

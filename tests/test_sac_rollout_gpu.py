@@ -1,5 +1,5 @@
 """GPU: the closed-loop rollout windows under SAC's sampled actor (asvrl_sac_rollout / asvrl_sac_rollout_ar,
-env_sac_rollout_kernel / env_sac_rollout_ar_kernel) against the composed loop of the calls they replace, bit for bit:
+env_policy_rollout_kernel's kPolSac instantiations) against the composed loop of the calls they replace, bit for bit:
 for t < K, fused_sac.sac_act on the current observation at step counter STEP0 + t (the noise drawn in the kernel on
 (row, step, seed); an all-zero eps_in for deterministic=True), the single env step at noise counter C0 + t on those
 actions and, with the auto-reset, reset_observe on env_done & mask at (RC + t, OC + t). Every record of every step
