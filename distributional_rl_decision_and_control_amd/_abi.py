@@ -108,6 +108,20 @@ class AsvCriticParts(C.Structure):
 
 # (name, restype, argtypes) of every exported entry point, mirroring include/asvrl.h
 _VP, _I32, _I64, _U64, _F, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_double
+# the epsilon-greedy schedule every act-IO and policy struct carries: the device step counter, the linear schedule
+# (steps per count, total, fraction, initial, final) and the seed of the exploration draw
+_SCHEDULE = [("step_dev", _VP), ("eps_steps_per_count", _D), ("eps_total", _D), ("eps_fraction", _D),
+             ("eps_initial", _D), ("eps_final", _D), ("seed", _U64)]
+
+
+def fill_schedule(s, step_dev, eps, seed):
+    """The _SCHEDULE members of any struct that has them (csrc/asvrl_env.hip's act_schedule reads them back):
+    step_dev an i64 device tensor or None (NULL: step 0), eps the five doubles in order, seed masked to 64 bits."""
+    s.step_dev = step_dev.data_ptr() if step_dev is not None else None
+    s.eps_steps_per_count, s.eps_total, s.eps_fraction, s.eps_initial, s.eps_final = (float(v) for v in eps)
+    s.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
 class AsvCriticIO(C.Structure):
     _fields_ = [("F", _VP), ("G", _VP), ("obs", _VP), ("ld_obs", _I64), ("act", _VP), ("ld_act", _I64), ("xb", _VP),
                 ("taus", _VP), ("B", _I32), ("N", _I32), ("Np", _I32), ("kappa", C.c_float),
@@ -129,9 +143,7 @@ class AsvIqnIO(C.Structure):
                 ("Np", _I32), ("kappa", C.c_float), ("q_next", _VP), ("actions", _VP), ("rewards", _VP),
                 ("dones", _VP), ("ld_rd", _I64),
                 ("gamma", C.c_float), ("q", _VP), ("row_loss", _VP), ("dzF", _VP), ("dz_out", _VP),
-                ("tile_loss", _VP), ("loss_scale", C.c_float), ("act_out", _VP), ("ld_act", _I64),
-                ("step_dev", _VP), ("eps_steps_per_count", _D), ("eps_total", _D), ("eps_fraction", _D),
-                ("eps_initial", _D), ("eps_final", _D), ("seed", _U64)]
+                ("tile_loss", _VP), ("loss_scale", C.c_float), ("act_out", _VP), ("ld_act", _I64)] + _SCHEDULE
 
 
 class AsvIqnActEx(C.Structure):
@@ -140,9 +152,8 @@ class AsvIqnActEx(C.Structure):
 
 
 class AsvIqnPolicy(C.Structure):
-    _fields_ = [("w", AsvCriticWeights), ("head", AsvIqnHead), ("obs_in", _VP), ("step_dev", _VP),
-                ("eps_steps_per_count", _D), ("eps_total", _D), ("eps_fraction", _D), ("eps_initial", _D),
-                ("eps_final", _D), ("seed", _U64), ("actions", _VP), ("cvar", C.c_float), ("_pad0", _I32)]
+    _fields_ = [("w", AsvCriticWeights), ("head", AsvIqnHead), ("obs_in", _VP)] + _SCHEDULE + \
+               [("actions", _VP), ("cvar", C.c_float), ("_pad0", _I32)]
 
 
 MAX_SUM_SEGS = 24
@@ -192,15 +203,12 @@ class AsvMlpWeights(C.Structure):
 class AsvMlpIO(C.Structure):
     _fields_ = [("x", _VP), ("ldx", _I64), ("act", _VP), ("lda", _I64), ("n", _I32), ("F", _VP), ("G", _VP),
                 ("xb", _VP), ("a_out", _VP), ("ld_aout", _I64), ("a_out64", _VP), ("pre", _VP), ("h0", _VP),
-                ("h1", _VP), ("h2", _VP), ("dA", _VP), ("dout", _VP), ("dz2", _VP), ("dz1", _VP), ("dz0", _VP),
-                ("step_dev", _VP), ("eps_steps_per_count", _D), ("eps_total", _D), ("eps_fraction", _D),
-                ("eps_initial", _D), ("eps_final", _D), ("seed", _U64)]
+                ("h1", _VP), ("h2", _VP), ("dA", _VP), ("dout", _VP), ("dz2", _VP), ("dz1", _VP), ("dz0", _VP)] + \
+        _SCHEDULE
 
 
 class AsvPolicy(C.Structure):
-    _fields_ = [("w", AsvMlpWeights), ("obs_in", _VP), ("step_dev", _VP), ("eps_steps_per_count", _D),
-                ("eps_total", _D), ("eps_fraction", _D), ("eps_initial", _D), ("eps_final", _D), ("seed", _U64),
-                ("actions", _VP)]
+    _fields_ = [("w", AsvMlpWeights), ("obs_in", _VP)] + _SCHEDULE + [("actions", _VP)]
 
 
 class AsvAutoReset(C.Structure):
@@ -223,14 +231,11 @@ class AsvDqnWeights(C.Structure):
 
 class AsvDqnActIO(C.Structure):
     _fields_ = [("x", _VP), ("ldx", _I64), ("n", _I32), ("_pad0", _I32), ("act_out", _VP), ("ld_act", _I64),
-                ("q_out", _VP), ("step_dev", _VP), ("eps_steps_per_count", _D), ("eps_total", _D),
-                ("eps_fraction", _D), ("eps_initial", _D), ("eps_final", _D), ("seed", _U64)]
+                ("q_out", _VP)] + _SCHEDULE
 
 
 class AsvDqnPolicy(C.Structure):
-    _fields_ = [("w", AsvDqnWeights), ("obs_in", _VP), ("step_dev", _VP), ("eps_steps_per_count", _D),
-                ("eps_total", _D), ("eps_fraction", _D), ("eps_initial", _D), ("eps_final", _D), ("seed", _U64),
-                ("actions", _VP)]
+    _fields_ = [("w", AsvDqnWeights), ("obs_in", _VP)] + _SCHEDULE + [("actions", _VP)]
 
 
 DQN_GRAD_ARRAYS = ("xb", "h0", "h1", "h2", "q_sel", "q_next", "dz_out", "dz2", "dz1", "dz0", "tile_loss")
@@ -263,14 +268,12 @@ class AsvSacActorWeights(C.Structure):
 
 class AsvSacActIO(C.Structure):
     _fields_ = [("x", _VP), ("ldx", _I64), ("n", _I32), ("_pad0", _I32), ("a_out64", _VP), ("eps_in", _VP),
-                ("eps_out", _VP), ("step_dev", _VP), ("eps_steps_per_count", _D), ("eps_total", _D),
-                ("eps_fraction", _D), ("eps_initial", _D), ("eps_final", _D), ("seed", _U64)]
+                ("eps_out", _VP)] + _SCHEDULE
 
 
 class AsvSacPolicy(C.Structure):
-    _fields_ = [("w", AsvSacActorWeights), ("obs_in", _VP), ("step_dev", _VP), ("eps_steps_per_count", _D),
-                ("eps_total", _D), ("eps_fraction", _D), ("eps_initial", _D), ("eps_final", _D), ("seed", _U64),
-                ("actions", _VP), ("deterministic", _I32), ("_pad0", _I32)]
+    _fields_ = [("w", AsvSacActorWeights), ("obs_in", _VP)] + _SCHEDULE + \
+               [("actions", _VP), ("deterministic", _I32), ("_pad0", _I32)]
 
 
 SAC_ACTOR_ARRAYS = ("xb", "h0", "h1", "h2", "mu", "ls", "sigma", "z", "a", "eps", "logp", "na", "logp_next",
@@ -320,11 +323,9 @@ class AsvNoisySegs(C.Structure):
 class AsvRainbowHeadIO(C.Structure):
     _fields_ = [("v", _VP), ("ldv", _I64), ("a", _VP), ("lda", _I64), ("N", _I32), ("atoms", _I32),
                 ("actions_n", _I32), ("_pad0", _I32), ("support", _VP), ("act_out", _VP), ("ld_act", _I64),
-                ("act_idx", _VP), ("step_dev", _VP), ("eps_steps_per_count", _D), ("eps_total", _D),
-                ("eps_fraction", _D), ("eps_initial", _D), ("eps_final", _D), ("seed", _U64), ("p_out", _VP),
-                ("actions", _VP), ("weights", _VP), ("ld_rd", _I64), ("m", _VP), ("loss", _VP), ("dv", _VP),
-                ("da", _VP), ("grad_scale", C.c_float), ("_pad1", _I32)]
-
+                ("act_idx", _VP)] + _SCHEDULE + \
+               [("p_out", _VP), ("actions", _VP), ("weights", _VP), ("ld_rd", _I64), ("m", _VP), ("loss", _VP),
+                ("dv", _VP), ("da", _VP), ("grad_scale", C.c_float), ("_pad1", _I32)]
 
 
 class AsvRainbowSrc(C.Structure):
@@ -343,11 +344,11 @@ class AsvRainbowImg(C.Structure):   # also AsvRainbowImgOut (same layout)
 
 class AsvRainbowNetIO(C.Structure):
     _fields_ = [("x", _VP), ("ldx", _I64), ("N", _I32), ("_pad0", _I32), ("support", _VP), ("act_out", _VP),
-                ("ld_act", _I64), ("act_idx", _VP), ("step_dev", _VP), ("eps_steps_per_count", _D), ("eps_total", _D),
-                ("eps_fraction", _D), ("eps_initial", _D), ("eps_final", _D), ("seed", _U64), ("p_out", _VP),
-                ("actions", _VP), ("weights", _VP), ("ld_rd", _I64), ("m", _VP), ("grad_scale", _F), ("_pad1", _I32),
-                ("loss", _VP)] + [(n, _VP) for n in ("xb", "f", "hv1", "ha1", "hv2", "ha2", "dzv", "dza", "dz2v",
-                                                     "dz2a", "dz1v", "dz1a", "dzf")]
+                ("ld_act", _I64), ("act_idx", _VP)] + _SCHEDULE + \
+               [("p_out", _VP), ("actions", _VP), ("weights", _VP), ("ld_rd", _I64), ("m", _VP), ("grad_scale", _F),
+                ("_pad1", _I32), ("loss", _VP)] + \
+               [(n, _VP) for n in ("xb", "f", "hv1", "ha1", "hv2", "ha2", "dzv", "dza", "dz2v", "dz2a", "dz1v", "dz1a",
+                                   "dzf")]
 
 
 class AsvRainbowActEx(C.Structure):
@@ -356,9 +357,22 @@ class AsvRainbowActEx(C.Structure):
 
 
 class AsvRainbowPolicy(C.Structure):
-    _fields_ = [("w", AsvRainbowImg), ("support", _VP), ("obs_in", _VP), ("step_dev", _VP),
-                ("eps_steps_per_count", _D), ("eps_total", _D), ("eps_fraction", _D), ("eps_initial", _D),
-                ("eps_final", _D), ("seed", _U64), ("actions", _VP)]
+    _fields_ = [("w", AsvRainbowImg), ("support", _VP), ("obs_in", _VP)] + _SCHEDULE + [("actions", _VP)]
+
+
+# the closed-loop rollouts: policy -> (entry point, its policy struct); each entry point also has an _ar form with
+# the AsvAutoReset behind the policy. The pack classes take their `rollout` / `policy_struct` from here
+ROLLOUTS = {"actor": ("asvrl_policy_rollout", AsvPolicy), "dqn": ("asvrl_dqn_rollout", AsvDqnPolicy),
+            "sac": ("asvrl_sac_rollout", AsvSacPolicy), "iqn": ("asvrl_iqn_rollout", AsvIqnPolicy),
+            "rainbow": ("asvrl_rainbow_rollout", AsvRainbowPolicy)}
+
+
+def _rollout_exports():
+    head = [C.POINTER(t) for t in (AsvParams, AsvEnvState, AsvStepCtl, AsvStepOut, AsvRollout)]
+    tail = [C.POINTER(AsvEnvLaunch), _VP]
+    for name, policy in ROLLOUTS.values():
+        yield name, C.c_int, head + [C.POINTER(policy)] + tail
+        yield name + "_ar", C.c_int, head + [C.POINTER(policy), C.POINTER(AsvAutoReset)] + tail
 
 
 EXPORTS = [
@@ -459,16 +473,11 @@ EXPORTS = [
     ("asvrl_operand_bytes", C.c_int32, []),
     ("asvrl_struct_sizes", None, [C.c_void_p]),
     ("asvrl_rollout_struct_size", _I64, []),
-    ("asvrl_policy_rollout", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), C.POINTER(AsvStepCtl),
-                                       C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvPolicy),
-                                       C.POINTER(AsvEnvLaunch), _VP]),
+    *_rollout_exports(),
     ("asvrl_policy_struct_size", _I64, []),
     ("asvrl_env_rollout_ar", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), C.POINTER(AsvStepCtl),
                                        C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvAutoReset),
                                        C.POINTER(AsvEnvLaunch), _VP]),
-    ("asvrl_policy_rollout_ar", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), C.POINTER(AsvStepCtl),
-                                          C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvPolicy),
-                                          C.POINTER(AsvAutoReset), C.POINTER(AsvEnvLaunch), _VP]),
     ("asvrl_autoreset_struct_size", _I64, []),
     ("asvrl_replay_push_window", C.c_int, [_VP, _VP, _VP, _VP, _I32, _I64, _VP, _VP, _I32, _I32, _VP, _VP, _I64, _VP,
                                            _VP, _VP, _VP, _I64, _VP]),
@@ -480,12 +489,6 @@ EXPORTS = [
     ("asvrl_dqn_weights_struct_size", _I64, []),
     ("asvrl_dqn_act_struct_size", _I64, []),
     ("asvrl_dqn_grad_struct_size", _I64, []),
-    ("asvrl_dqn_rollout", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), C.POINTER(AsvStepCtl),
-                                    C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvDqnPolicy),
-                                    C.POINTER(AsvEnvLaunch), _VP]),
-    ("asvrl_dqn_rollout_ar", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), C.POINTER(AsvStepCtl),
-                                       C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvDqnPolicy),
-                                       C.POINTER(AsvAutoReset), C.POINTER(AsvEnvLaunch), _VP]),
     ("asvrl_dqn_policy_struct_size", _I64, []),
     ("asvrl_ddpg_grad", C.c_int, [C.POINTER(AsvDdpgWeights), C.POINTER(AsvDdpgWeights), C.POINTER(AsvDdpgGradIO),
                                   _VP]),
@@ -506,32 +509,14 @@ EXPORTS = [
     ("asvrl_sac_actor_struct_size", _I64, []),
     ("asvrl_sac_grad_struct_size", _I64, []),
     ("asvrl_sac_actor_grad_struct_size", _I64, []),
-    ("asvrl_sac_rollout", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), C.POINTER(AsvStepCtl),
-                                    C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvSacPolicy),
-                                    C.POINTER(AsvEnvLaunch), _VP]),
-    ("asvrl_sac_rollout_ar", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), C.POINTER(AsvStepCtl),
-                                       C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvSacPolicy),
-                                       C.POINTER(AsvAutoReset), C.POINTER(AsvEnvLaunch), _VP]),
     ("asvrl_sac_policy_struct_size", _I64, []),
     ("asvrl_iqn_act_ex", C.c_int, [C.POINTER(AsvCriticWeights), C.POINTER(AsvIqnHead), C.POINTER(AsvIqnIO),
                                    C.POINTER(AsvIqnActEx), _VP]),
     ("asvrl_iqn_act_ex_struct_size", _I64, []),
-    ("asvrl_iqn_rollout", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), C.POINTER(AsvStepCtl),
-                                    C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvIqnPolicy),
-                                    C.POINTER(AsvEnvLaunch), _VP]),
-    ("asvrl_iqn_rollout_ar", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), C.POINTER(AsvStepCtl),
-                                       C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvIqnPolicy),
-                                       C.POINTER(AsvAutoReset), C.POINTER(AsvEnvLaunch), _VP]),
     ("asvrl_iqn_policy_struct_size", _I64, []),
     ("asvrl_rainbow_net_act_ex", C.c_int, [C.POINTER(AsvRainbowImg), C.POINTER(AsvRainbowNetIO),
                                            C.POINTER(AsvRainbowActEx), _VP]),
     ("asvrl_rainbow_act_ex_struct_size", _I64, []),
-    ("asvrl_rainbow_rollout", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), C.POINTER(AsvStepCtl),
-                                        C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvRainbowPolicy),
-                                        C.POINTER(AsvEnvLaunch), _VP]),
-    ("asvrl_rainbow_rollout_ar", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvEnvState), C.POINTER(AsvStepCtl),
-                                           C.POINTER(AsvStepOut), C.POINTER(AsvRollout), C.POINTER(AsvRainbowPolicy),
-                                           C.POINTER(AsvAutoReset), C.POINTER(AsvEnvLaunch), _VP]),
     ("asvrl_rainbow_policy_struct_size", _I64, []),
     ("asvrl_per_push_window", C.c_int, [C.POINTER(AsvPer), _VP, _VP, _VP, _I32, _VP, _VP, _I32, _VP, _I64, _VP]),
 ]

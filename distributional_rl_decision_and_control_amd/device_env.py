@@ -270,84 +270,37 @@ class DeviceEnvBatch:
                        counter=0, counter_dev=None, gamma=0.0, env_mask=None, obs=None, obj_cnt=None,
                        fast_noise=False, launch=None, stream=None, auto_reset=None, deterministic=False,
                        cvar=1.0):
-        """asvrl_policy_rollout: K closed-loop steps in one launch -- the AC-IQN Actor of `pack` (an MlpPack of
-        kind "actor") acts on every robot row and the env steps on its actions, bit for bit the K rounds of
-        fused_mlp.actor_act(pack, obs, act64, step, *eps, policy_seed) at step = step_dev + t followed by
-        step(act64, counter=counter + t), where round 0 acts on obs_in (f32 [E*R, 40]; may be the tensor the step
-        writes) and round t > 0 on the observation of round t - 1. eps: (steps_per_count, total, fraction, initial,
-        final) of the linear epsilon schedule (the default is greedy); step_dev: i64 device step counter (None: 0),
-        only read. keep, noise, hold_done and the remaining arguments are rollout()'s; keep also takes "actions":
-        f64 [K, E*R, 2], the action every robot slot of a stepping env was given (rows of steps an env did not
-        take stay 0). The call goes to pack.L, so an f32 pack runs the f32-operand build. No host sync; with every
-        record passed in by the caller (and steps_run) the call can be graph-captured.
-        auto_reset (asvrl_policy_rollout_ar): as rollout()'s; the Actor acts on a reset env's reset observation at the
-        next step, and "obs_prev" records the rows it acted on at every step (obs_in comes from this call's own).
-        A fused_dqn.DqnPack (DQN_Policy; also an MlpPack of kind "actor") goes to asvrl_dqn_rollout /
-        asvrl_dqn_rollout_ar instead: the rounds are fused_dqn.dqn_act(pack, obs, act64, step, *eps, policy_seed)
-        and step(act64, is_continuous=False, ...), and "actions" holds (action index, 0.0).
-        A fused_sac.SacActorPack (SAC's sampled actor; also an MlpPack of kind "actor") goes to asvrl_sac_rollout /
-        asvrl_sac_rollout_ar: the rounds are fused_sac.sac_act(pack, obs, act64, eps_out, step, *eps, policy_seed)
-        -- the action noise drawn in the kernel on (global row, step, policy_seed) -- followed by step(act64, ...).
-        deterministic=True (a SacActorPack only; ValueError otherwise): the mean action, the rounds'
-        sac_act(..., eps_in=zeros); nothing is drawn for the sample, the epsilon schedule still applies.
-        A fused_iqn.IqnPack (IQN_Policy) goes to asvrl_iqn_rollout / asvrl_iqn_rollout_ar: the rounds are
-        fused_iqn.iqn_act(pack, None, act64, step, *eps, policy_seed, obs=obs, cvar=cvar) -- K = 32 taus per state
-        drawn in the kernel on (global row, step, policy_seed) -- and step(act64, is_continuous=False, ...); "actions"
-        holds (action index, 0.0). The act stays a launch of its own per step (it is not fused into the env kernel),
-        all enqueued by the one call. cvar in (0, 1] (an IqnPack only; ValueError otherwise, and outside the range):
-        act_iqn's risk distortion, every tau times cvar.
-        A fused_rainbow.RainbowPack (Rainbow_Policy; kind "rainbow") goes to asvrl_rainbow_rollout /
-        asvrl_rainbow_rollout_ar: the rounds are fused_rainbow.rainbow_act(pack, obs, act64, step, *eps, policy_seed)
-        -- the pack's images as its last refresh() left them, noisy (training mode) or mu only (eval mode) -- and
-        step(act64, is_continuous=False, ...); "actions" holds (action index, 0.0). As for IQN the act is a launch of
-        its own per step (asvrl_rainbow_net_act_ex), all enqueued by the one call; cvar and deterministic stay
-        ValueErrors for it."""
-        from .fused_dqn import DqnPack   # (the fused_* modules import nothing from this module)
-        from .fused_iqn import IqnPack
-        from .fused_rainbow import RainbowPack
-        from .fused_sac import SacActorPack
+        """K closed-loop steps in one launch: the policy of `pack` acts on every robot row and the env steps on its
+        actions, bit for bit K rounds of the pack's own act call at step = step_dev + t followed by
+        step(act64, is_continuous=pack.continuous, counter=counter + t), where round 0 acts on obs_in (f32 [E*R, 40];
+        may be the tensor the step writes) and round t > 0 on the observation of round t - 1. pack: an MlpPack of kind
+        "actor", a DqnPack, SacActorPack, IqnPack or RainbowPack -- anything with the window-policy surface MlpPack
+        describes; each class says what its rounds are and which of cvar / deterministic it takes (a ValueError for
+        the others, and for cvar outside (0, 1]). The call is pack.rollout of pack.L (its _ar form under auto_reset),
+        so an f32 pack runs the f32-operand build. eps: (steps_per_count, total, fraction, initial, final) of the
+        linear epsilon schedule (the default is greedy); step_dev: i64 device step counter (None: 0), only read. keep,
+        noise, hold_done and the remaining arguments are rollout()'s; keep also takes "actions": f64 [K, E*R, 2], the
+        action every robot slot of a stepping env was given (rows of steps an env did not take stay 0). No host sync;
+        with every record passed in by the caller (and steps_run) the call can be graph-captured.
+        auto_reset: as rollout()'s; the policy acts on a reset env's reset observation at the next step, and
+        "obs_prev" records the rows it acted on at every step (obs_in comes from this call's own)."""
         K, NT = int(K), self.n_envs * self.max_robots
-        iqn, rb = isinstance(pack, IqnPack), isinstance(pack, RainbowPack)
-        assert iqn or rb or pack.kind == "actor"
-        dqn, sac = isinstance(pack, DqnPack), isinstance(pack, SacActorPack)
-        cvar = float(cvar)
-        if not 0.0 < cvar <= 1.0:
-            raise ValueError("policy_rollout: cvar must be in (0, 1]")
-        if cvar != 1.0 and not iqn:
-            raise ValueError("policy_rollout: cvar is the risk distortion of IQN's quantile fractions (an IqnPack); "
-                             "the other policies have no quantiles to distort")
-        if deterministic and not sac:
-            raise ValueError("policy_rollout: deterministic=True is the sampled actor's mean action (a SacActorPack); "
-                             "the Actor and DQN_Policy have no sample to switch off")
+        assert pack.is_policy
+        cvar = policy_options("policy_rollout", pack, cvar, deterministic)
         assert obs_in.dtype == torch.float32 and obs_in.is_contiguous() and tuple(obs_in.shape) == (NT, OBS_DIM)
         if step_dev is not None:
             assert step_dev.dtype == torch.int64 and step_dev.numel() >= 1
         b = self._rollout_args("policy_rollout", K, {"actions": ((NT, 2), torch.float64, 0)}, noise=noise, keep=keep,
-                               hold_done=hold_done, is_continuous=not (dqn or iqn or rb), trainer_deactivate=trainer_deactivate,
+                               hold_done=hold_done, is_continuous=pack.continuous, trainer_deactivate=trainer_deactivate,
                                seed=seed, counter=counter, counter_dev=counter_dev, gamma=gamma, env_mask=env_mask,
                                obs=obs, obj_cnt=obj_cnt, fast_noise=fast_noise, launch=launch, auto_reset=auto_reset)
         if b.ar is not None:
             b.ar.obs_in = None
-        if iqn:
-            pi = _abi.AsvIqnPolicy()
-            pi.w, pi.head, pi.cvar = pack.struct, pack.head, cvar
-        elif rb:
-            pi = _abi.AsvRainbowPolicy()
-            pi.w, pi.support = pack.struct, pack.support.data_ptr()
-        else:
-            pi = _abi.AsvDqnPolicy() if dqn else (_abi.AsvSacPolicy() if sac else _abi.AsvPolicy())
-            pi.w = pack.dw if dqn else (pack.sw if sac else pack.w)
-        if sac:
-            pi.deterministic = int(bool(deterministic))
+        pi = pack.policy(cvar=cvar, deterministic=deterministic)
         pi.obs_in = obs_in.data_ptr()
-        pi.step_dev = step_dev.data_ptr() if step_dev is not None else None
-        (pi.eps_steps_per_count, pi.eps_total, pi.eps_fraction, pi.eps_initial,
-         pi.eps_final) = (float(v) for v in eps)
-        pi.seed = int(policy_seed) & 0xFFFFFFFFFFFFFFFF
+        _abi.fill_schedule(pi, step_dev, eps, policy_seed)
         pi.actions = b.rec["actions"].data_ptr() if "actions" in b.rec else None
-        name = ("asvrl_iqn_rollout" if iqn else "asvrl_rainbow_rollout" if rb else "asvrl_dqn_rollout" if dqn else
-                "asvrl_sac_rollout" if sac else "asvrl_policy_rollout")
-        return self._rollout_call(b, pack.L, name, [C.byref(pi)], stream)
+        return self._rollout_call(b, pack.L, pack.rollout, [C.byref(pi)], stream)
 
     def reset(self, cfg, env_mask=None, seed=0, counter=0, counter_dev=None, stream=None):
         st = self.state_struct()
@@ -379,6 +332,22 @@ class DeviceEnvBatch:
                                                 _abi.ptr(counter_dev), C.byref(ctl), C.byref(out),
                                                 _abi.stream_ptr(stream))
         _abi.check(rc, "asvrl_env_reset_observe")
+
+
+def policy_options(who, pack, cvar, deterministic):
+    """The refusals of the per-policy options every front end of the closed-loop windows shares (`who`: its name):
+    cvar must lie in (0, 1] and differ from 1 only for a pack that takes it, deterministic needs one that takes it.
+    pack may be None (DeviceEvaluator.run's action table). Returns cvar as a float."""
+    cvar = float(cvar)
+    if not 0.0 < cvar <= 1.0:
+        raise ValueError(f"{who}: cvar must be in (0, 1]")
+    if cvar != 1.0 and not getattr(pack, "takes_cvar", False):
+        raise ValueError(f"{who}: cvar is the risk distortion of IQN's quantile fractions (an IqnPack); "
+                         "the other policies have no quantiles to distort")
+    if deterministic and not getattr(pack, "takes_deterministic", False):
+        raise ValueError(f"{who}: deterministic=True is the sampled actor's mean action (a SacActorPack); "
+                         "the Actor and DQN_Policy have no sample to switch off")
+    return cvar
 
 
 def reset_cfg(num_robots=5, num_obs=4, num_cores=0, min_start_goal_dis=40.0, width=55.0, height=55.0,

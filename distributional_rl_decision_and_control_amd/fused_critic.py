@@ -310,6 +310,17 @@ def linear_wgrad_vec(dq, x, dw, db, work, accumulate=False, stream=None):
     _abi.check(rc, "asvrl_linear_wgrad_vec")
 
 
+def arena_floats(L, B, layers, vecs=0, small=False):
+    """The floats a PartialArena needs for one update over B rows: the MFMA partials of `layers` ((M, K) each),
+    `vecs` 128-wide vector layers (a one-scalar output row) and, small=True, the 128 x 2 action encoder; every region
+    rounded to _take()'s 64 floats, plus one spare round."""
+    need = sum((int(L.asvrl_linear_wgrad_groups(B, M, K)) * (M * K + M) + 63) // 64 * 64 for M, K in layers)
+    need += vecs * ((int(L.asvrl_linear_wgrad_vec_groups(B)) * (128 + 1) + 63) // 64 * 64)
+    if small:
+        need += ((B + 31) // 32 * (128 * 2 + 128) + 63) // 64 * 64
+    return need + 64
+
+
 class PartialArena:
     """Weight-gradient partials of several layers, reduced together by ONE asvrl_partial_sums
     launch (instead of one reduction launch per layer). Regions are handed out in call order

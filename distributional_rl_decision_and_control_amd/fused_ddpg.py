@@ -33,9 +33,9 @@ import ctypes as C
 import torch
 
 from . import _abi
-from .fused_critic import PartialArena
+from .fused_critic import PartialArena, arena_floats
 from .fused_mlp import (ENC, HID, OBSK, ActorBuffers, ActorGrads, MlpPack, actor_act, actor_backward, actor_forward,
-                        actor_train_forward)
+                        actor_train_forward, default_net)
 from .fused_update import _actor_step, _reduce_and_step, learn_prologue
 from .learner import target_step
 
@@ -45,13 +45,8 @@ OBS = 40
 def supported(policy, B):
     """The shapes the kernels take: the default network dims, 2 actions and a batch that is a positive multiple
     of 32."""
-    c, a = policy.critic, policy.actor
-    return (B >= 32 and B % 32 == 0 and c.concat_feature_dimension == 256 and c.hidden_dimension == 128
-            and c.self_dimension == 7 and c.object_dimension == 5 and c.max_object_num == 5
-            and c.self_feature_dimension == 56 and c.object_feature_dimension == 40 and c.action_dimension == 2
-            and a.concat_feature_dimension == 256 and a.hidden_dimension == 128 and a.self_dimension == 7
-            and a.object_dimension == 5 and a.max_object_num == 5 and a.self_feature_dimension == 56
-            and a.object_feature_dimension == 40 and a.action_dimension == 2)
+    return B >= 32 and B % 32 == 0 and all(default_net(n) and n.action_dimension == 2
+                                           for n in (policy.critic, policy.actor))
 
 
 class DdpgCriticPack(MlpPack):
@@ -106,8 +101,8 @@ class FusedDDPGState:
         self.B, self.device, self.operands = B, dev, operands
         self.local = DdpgCriticPack(policy_local.critic, operands)
         self.target = DdpgCriticPack(policy_target.critic, operands)
-        self.actor = self.actor_pack = self.policy_pack = MlpPack(policy_local.actor, "actor", operands,
-                                                                  double=double_actor)
+        self.actor = MlpPack(policy_local.actor, "actor", operands, double=double_actor)
+        self.actor_pack = self.policy_pack = self.window_pack = self.eval_pack = self.actor
         self.target_actor = MlpPack(policy_target.actor, "actor", operands)
         self.abufs = ActorBuffers(B, dev, operands)
         self.agrads = ActorGrads(B, dev, operands)
@@ -124,12 +119,8 @@ class FusedDDPGState:
         self.q_pi = torch.zeros(B, **f)
         self.tile_loss = torch.zeros(2, B // 32, **f)   # critic, actor
         self.losses = torch.zeros(2, **f)
-        L = self.local.L
-        need = sum((int(L.asvrl_linear_wgrad_groups(B, M, K)) * (M * K + M) + 63) // 64 * 64
-                   for M, K in ((HID, HID), (HID, ENC), (ENC, OBSK)))
-        need += (int(L.asvrl_linear_wgrad_vec_groups(B)) * (HID + 1) + 63) // 64 * 64
-        need += ((B + 31) // 32 * (HID * 2 + HID) + 63) // 64 * 64
-        self.arena = PartialArena(need + 64, dev, operands)
+        layers = ((HID, HID), (HID, ENC), (ENC, OBSK))
+        self.arena = PartialArena(arena_floats(self.local.L, B, layers, vecs=1, small=True), dev, operands)
 
     def target_changed(self):
         """Re-pack the target networks after a hard/soft update (eager, outside graphs)."""

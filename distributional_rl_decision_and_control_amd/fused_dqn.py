@@ -26,8 +26,8 @@ import ctypes as C
 import torch
 
 from . import _abi
-from .fused_critic import PartialArena
-from .fused_mlp import ENC, HID, OBSK, MlpPack
+from .fused_critic import PartialArena, arena_floats
+from .fused_mlp import ENC, HID, OBSK, MlpPack, default_net
 from .fused_update import _reduce_and_step
 from .learner import target_step
 
@@ -39,17 +39,21 @@ ACTIONS = 25
 def supported(net, B):
     """The shapes the kernels take: the default network (vec_trainer.DEFAULT_NET) with 25 actions and a batch
     that is a positive multiple of 32."""
-    return (B >= 32 and B % 32 == 0 and net.action_size == ACTIONS
-            and net.concat_feature_dimension == 256 and net.hidden_dimension == 128
-            and net.self_dimension == 7 and net.object_dimension == 5 and net.max_object_num == 5
-            and net.self_feature_dimension == 56 and net.object_feature_dimension == 40)
+    return B >= 32 and B % 32 == 0 and net.action_size == ACTIONS and default_net(net)
 
 
 class DqnPack(MlpPack):
     """Packed images of one DQN_Policy: the Actor's set (MlpPack kind "actor": encoder image, hidden layers and
     their transposes) plus the output layer padded to 32 rows (`head`, rows 25.. zero). refresh() re-packs from
     the f32 parameters in one call; adam_segments(opt) lets FusedAdam's step write the images itself.
-    double=True: two image sets as MlpPack(double=True)."""
+    double=True: two image sets as MlpPack(double=True).
+
+    As a window policy (MlpPack; asvrl_dqn_rollout): the rounds are dqn_act(pack, obs, act64, step, *eps, policy_seed)
+    and step(act64, is_continuous=False, ...), the act inside the env kernel; the "actions" record holds
+    (action index, 0.0)."""
+    rollout, policy_struct = _abi.ROLLOUTS["dqn"]
+    continuous = False
+    _policy_w = "dw"
 
     def __init__(self, net, operands="bf16", double=False):
         self._dqn_segs = {}
@@ -96,9 +100,7 @@ def dqn_act(pack, obs, actions64, step_dev, steps_per_count, total, fraction, in
         assert q_out.dtype == torch.float32 and q_out.is_contiguous() and tuple(q_out.shape) == (obs.shape[0],
                                                                                                  pack.net.action_size)
         io.q_out = q_out.data_ptr()
-    io.step_dev = step_dev.data_ptr() if step_dev is not None else None
-    io.eps_steps_per_count, io.eps_total, io.eps_fraction = float(steps_per_count), float(total), float(fraction)
-    io.eps_initial, io.eps_final, io.seed = float(initial), float(final), int(seed) & 0xFFFFFFFFFFFFFFFF
+    _abi.fill_schedule(io, step_dev, (steps_per_count, total, fraction, initial, final), seed)
     _abi.check(pack.L.asvrl_dqn_act(C.byref(pack.dw), C.byref(io), _abi.stream_ptr(stream)), "asvrl_dqn_act", pack.L)
 
 
@@ -112,7 +114,8 @@ class FusedDQNState:
             raise ValueError(f"DQN learner kernels: B={B} (a positive multiple of 32), the default network, 25 actions")
         dev = net_local.output_layer.weight.device
         self.B, self.device, self.operands = B, dev, operands
-        self.local = self.policy_pack = DqnPack(net_local, operands)   # the closed-loop windows run the Q network
+        # the closed-loop windows and the device evaluation run the Q network
+        self.local = self.policy_pack = self.window_pack = self.eval_pack = DqnPack(net_local, operands)
         self.actor_pack = None
         self.target = DqnPack(net_target, operands)
         bf = dict(dtype=_abi.operand_dtype(operands), device=dev)
@@ -125,10 +128,8 @@ class FusedDQNState:
         self.q_sel, self.q_next = torch.zeros(B, **f), torch.zeros(B, **f)
         self.tile_loss = torch.zeros(B // 32, **f)
         self.loss = torch.zeros(1, **f)
-        L = self.local.L
-        need = sum((int(L.asvrl_linear_wgrad_groups(B, M, K)) * (M * K + M) + 63) // 64 * 64
-                   for M, K in ((QPAD, HID), (HID, HID), (HID, ENC), (ENC, OBSK)))
-        self.arena = PartialArena(need + 64, dev, operands)
+        layers = ((QPAD, HID), (HID, HID), (HID, ENC), (ENC, OBSK))
+        self.arena = PartialArena(arena_floats(self.local.L, B, layers), dev, operands)
 
     def target_changed(self):
         """Re-pack the target network after a hard/soft update (eager, outside graphs)."""

@@ -41,6 +41,7 @@ import torch
 
 from . import _abi
 from .fused_critic import CriticPack, PartialArena, TrainBuffers, fused_groups, fused_train_supported
+from .fused_mlp import default_net
 from .fused_update import ENC_IN_KERNEL, _reduce_and_step
 from .learner import target_step
 
@@ -61,16 +62,24 @@ TARGET_IN_FUSED = False
 
 
 def supported(net, B, N):
-    return (net.concat_feature_dimension == 256 and net.hidden_dimension == 128 and net.n == 64
-            and 1 <= net.action_size <= _abi.IQN_MAX_ACTIONS and N in (8, 16, 32) and (B * N) % 32 == 0
-            and net.self_dimension == 7 and net.object_dimension == 5 and net.max_object_num == 5
-            and net.self_feature_dimension == 56 and net.object_feature_dimension == 40)
+    return (default_net(net) and net.n == 64 and 1 <= net.action_size <= _abi.IQN_MAX_ACTIONS and N in (8, 16, 32)
+            and (B * N) % 32 == 0)
 
 
 class IqnPack(CriticPack):
     """bf16 images of one IQN_Policy: the trunk (CriticPack's five) and the padded output head,
     one refresh launch; the observation encoders are read in f32 by the kernels themselves.
-    operands="f32": the f32 images of libasvrl_f32.so (the parity build)."""
+    operands="f32": the f32 images of libasvrl_f32.so (the parity build).
+
+    As a window policy (the surface MlpPack describes; asvrl_iqn_rollout): the rounds are iqn_act(pack, None, act64,
+    step, *eps, policy_seed, obs=obs, cvar=cvar) -- K = 32 taus per state drawn in the kernel on (global row, step,
+    policy_seed) -- and step(act64, is_continuous=False, ...); "actions" holds (action index, 0.0). The act stays a
+    launch of its own per step (it is not fused into the env kernel), all enqueued by the one call. cvar in (0, 1]
+    (this pack only): act_iqn's risk distortion, every tau times cvar."""
+    rollout, policy_struct = _abi.ROLLOUTS["iqn"]
+    continuous = False
+    takes_cvar, takes_deterministic = True, False
+    is_policy = True
 
     def __init__(self, net, operands="bf16"):
         dev = net.cos_embedding.weight.device
@@ -81,6 +90,11 @@ class IqnPack(CriticPack):
         hd.n_actions = net.action_size
         self.head = hd
         super().__init__(net, operands)
+
+    def policy(self, cvar=1.0, deterministic=False):
+        pi = self.policy_struct()
+        pi.w, pi.head, pi.cvar = self.struct, self.head, float(cvar)
+        return pi
 
     def adam_segments(self, opt):
         """The trunk images and the head's leading rows (the padding rows stay zero)."""
@@ -105,8 +119,7 @@ def _io(F, N, obs=None, xb=None, **kw):
         assert obs.dtype == torch.float32 and obs.stride(-1) == 1
         io.obs, io.ld_obs = obs.data_ptr(), obs.stride(0)
     io.xb = xb.data_ptr() if xb is not None else None
-    for k in ("Np", "kappa", "gamma", "ld_rd", "loss_scale", "ld_act", "eps_steps_per_count", "eps_total",
-              "eps_fraction", "eps_initial", "eps_final", "seed"):
+    for k in ("Np", "kappa", "gamma", "ld_rd", "loss_scale", "ld_act"):
         if k in kw:
             setattr(io, k, kw.pop(k))
     for k, v in kw.items():
@@ -191,9 +204,8 @@ def iqn_act(pack, F, actions64, step_dev, steps_per_count, total, fraction, init
     drawn or given (act_iqn's risk distortion, IQN_model.py:68); step_add is added to the step counter's value;
     q_out (f32 [rows, >= A]) receives the action values quantiles.mean(dim=1); actions_rec (f64 [rows, 2]) receives
     (index, 0.0) for the rows of envs with env_mask != 0 (u8, one per robots_per_env rows; None: every row)."""
-    io = _io(F, K_ACT, obs=obs, taus=taus, act_out=actions64, ld_act=actions64.stride(0), step_dev=step_dev,
-             eps_steps_per_count=float(steps_per_count), eps_total=float(total), eps_fraction=float(fraction),
-             eps_initial=float(initial), eps_final=float(final), seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
+    io = _io(F, K_ACT, obs=obs, taus=taus, act_out=actions64, ld_act=actions64.stride(0))
+    _abi.fill_schedule(io, step_dev, (steps_per_count, total, fraction, initial, final), seed)
     if float(cvar) == 1.0 and int(step_add) == 0 and q_out is None and actions_rec is None and env_mask is None:
         _abi.check(pack.L.asvrl_iqn_act(C.byref(pack.struct), C.byref(pack.head), C.byref(io),
                                         _abi.stream_ptr(stream)), "asvrl_iqn_act", pack.L)
@@ -219,10 +231,8 @@ def iqn_act(pack, F, actions64, step_dev, steps_per_count, total, fraction, init
 class FusedIQNState:
     """Packs and buffers of the fused IQN update (allocated once, pointer-stable for graphs).
     operands="f32": every kernel from libasvrl_f32.so (the parity build; the optimiser must be a
-    FusedAdam of the same operands). window_pack (the local IqnPack) is what the closed-loop windows and the device
-    evaluation take (DeviceEnvBatch.policy_rollout, DeviceEvaluator.run, VecTrainer._collect_window); policy_pack and
-    actor_pack stay None, so VecTrainer.policy_pack(), collect, greedy_episodes and evaluate still refuse an IQN
-    trainer."""
+    FusedAdam of the same operands). window_pack and eval_pack are the local IqnPack; policy_pack and actor_pack stay
+    None, so VecTrainer.policy_pack(), collect, greedy_episodes and evaluate still refuse an IQN trainer."""
     actor_pack = policy_pack = None   # act_iqn runs in its own launch (the windows compose it per step, window_pack)
 
     def __init__(self, net_local, net_target, B, N, operands="bf16", target_in_fused=None):
@@ -232,7 +242,7 @@ class FusedIQNState:
         # the target's max inside the fused launch (bf16 build; module default TARGET_IN_FUSED)
         self.target_in_fused = TARGET_IN_FUSED if target_in_fused is None else bool(target_in_fused)
         self.A = net_local.action_size
-        self.local = self.window_pack = IqnPack(net_local, operands)
+        self.local = self.window_pack = self.eval_pack = IqnPack(net_local, operands)
         self.target = IqnPack(net_target, operands)
         self.bufs = TrainBuffers(B, N, dev, operands)
         f = dict(dtype=torch.float32, device=dev)

@@ -20,6 +20,14 @@ MAX_OBJ = 5   # object-encoder copies in the encoder image (max_object_num)
 MODE_ACT, MODE_FWD, MODE_TRAIN = 1, 2, 3
 
 
+def default_net(n):
+    """The network dimensions every kernel is built for (vec_trainer.DEFAULT_NET): encoders 7 -> 56 and
+    5 x (5 -> 40), 256 concatenated features, 128 hidden. Each learner's supported() adds what is its own."""
+    return (n.concat_feature_dimension == ENC and n.hidden_dimension == HID and n.self_dimension == 7
+            and n.object_dimension == 5 and n.max_object_num == MAX_OBJ and n.self_feature_dimension == 56
+            and n.object_feature_dimension == 40)
+
+
 def _p(t):
     return t.data_ptr() if t is not None else None
 
@@ -32,12 +40,24 @@ class MlpPack:
     double=True (an Actor in the batched loop): two image sets, with f32 copies of the biases and the output
     layer in each. Launches read set `parity` (self.w); the optimiser step writes the other one
     (adam_segments) and flip() makes it current -- so the rollout's act kernel, which reads the current set,
-    never races the step that rewrites the weights (no cross-stream wait before the optimiser)."""
+    never races the step that rewrites the weights (no cross-stream wait before the optimiser).
+
+    A pack of kind "actor" is a window policy: what DeviceEnvBatch.policy_rollout, VecMarineNavEnv.policy_rollout and
+    DeviceEvaluator.run take. They read `rollout` / `policy_struct` (the entry point, also in its _ar form, and its
+    policy struct: one row of _abi.ROLLOUTS), `continuous` (thrust commands or an action index), `takes_cvar` /
+    `takes_deterministic` (the per-policy options it accepts), `is_policy`, policy() and L, and nothing else. This
+    one is the AC-IQN Actor (asvrl_policy_rollout): the window's rounds are actor_act(pack, obs, act64, step, *eps,
+    policy_seed) and step(act64, ...), the act inside the env kernel."""
+    rollout, policy_struct = _abi.ROLLOUTS["actor"]
+    continuous = True
+    takes_cvar = takes_deterministic = False
+    _policy_w = "w"   # the current set's weights struct that policy() hands to the window
 
     def __init__(self, net, kind, operands="bf16", double=False):
         assert kind in ("actor", "critic", "encoders")
         assert not double or kind == "actor"
         self.net, self.kind = net, kind
+        self.is_policy = kind == "actor"   # a critic's or the bare encoders' images drive no window
         self.operands = operands
         self.L = _abi.lib(operands)
         self.double = double
@@ -92,6 +112,14 @@ class MlpPack:
         """The set the last optimiser step wrote becomes current (double packs; host-side, at enqueue)."""
         if self.double:
             self.parity ^= 1
+
+    def policy(self, cvar=1.0, deterministic=False):
+        """The policy struct of a window over the current image set, its weights and the policy's own members
+        filled (the caller adds obs_in, the schedule and the actions record). Host-side only: nothing is allocated
+        or launched, so it is safe at enqueue time and inside a graph capture."""
+        pi = self.policy_struct()
+        pi.w = self.sets[self.parity][self._policy_w]
+        return pi
 
     def src(self):
         n = self.net
@@ -186,9 +214,7 @@ def actor_act(pack, x, actions64, step_dev, steps_per_count, total, fraction, in
     io = _abi.AsvMlpIO()
     io.x, io.ldx, io.n = x.data_ptr(), ldx, x.shape[0]
     io.a_out64 = actions64.data_ptr()
-    io.step_dev = step_dev.data_ptr()
-    io.eps_steps_per_count, io.eps_total, io.eps_fraction = float(steps_per_count), float(total), float(fraction)
-    io.eps_initial, io.eps_final, io.seed = float(initial), float(final), int(seed) & 0xFFFFFFFFFFFFFFFF
+    _abi.fill_schedule(io, step_dev, (steps_per_count, total, fraction, initial, final), seed)
     _abi.check(pack.L.asvrl_actor_forward(C.byref(pack.w), C.byref(io), MODE_ACT, _abi.stream_ptr(stream)),
                "asvrl_actor_forward(act)", pack.L)
 

@@ -39,6 +39,7 @@ import torch
 
 from . import _abi
 from .fused_critic import PartialArena
+from .fused_mlp import default_net
 from .learn_ops import c51_project
 
 NOISY = ("hidden_layer_v", "hidden_layer_v_2", "output_layer_v", "hidden_layer_a", "hidden_layer_a_2",
@@ -49,10 +50,7 @@ ATOMS, ACTIONS = 51, 25
 def supported(net, B):
     """The Rainbow kernels' network shape (Rainbow_Policy defaults: 256 concatenated features, 128 hidden,
     25 actions x 51 atoms, encoders 7 -> 56 and 5 x (5 -> 40)) and a batch of whole 32-row tiles."""
-    return (net.concat_feature_dimension == 256 and net.hidden_dimension == 128 and net.action_size == ACTIONS
-            and net.atoms == ATOMS and net.self_dimension == 7 and net.object_dimension == 5
-            and net.max_object_num == 5 and net.self_feature_dimension == 56 and net.object_feature_dimension == 40
-            and B > 0 and B % 32 == 0)
+    return default_net(net) and net.action_size == ACTIONS and net.atoms == ATOMS and B > 0 and B % 32 == 0
 
 
 class NoisyPack:
@@ -210,8 +208,17 @@ class RainbowPack:
     f32 support. noisy=True: training mode, refresh() composes W = mu + sigma * eps (asvrl_noisy_compose) and packs;
     noisy=False: eval mode (policy_local.eval()), refresh() packs weight_mu / bias_mu directly -- one launch, no
     compose. The images are as the last refresh() left them: call it after the parameters change. Build the pack
-    after anything that re-points the parameters (FusedAdam)."""
+    after anything that re-points the parameters (FusedAdam).
+
+    As a window policy (the surface MlpPack describes; asvrl_rainbow_rollout): the rounds are rainbow_act(pack, obs,
+    act64, step, *eps, policy_seed) on the images of the last refresh(), noisy or mu only, and step(act64,
+    is_continuous=False, ...); "actions" holds (action index, 0.0). As for IQN the act is a launch of its own per
+    step (asvrl_rainbow_net_act_ex), all enqueued by the one call."""
     kind = "rainbow"
+    rollout, policy_struct = _abi.ROLLOUTS["rainbow"]
+    continuous = False
+    takes_cvar = takes_deterministic = False
+    is_policy = True
 
     def __init__(self, net, operands="bf16", noisy=True, support=None, _share=None):
         self.net, self.operands, self.noisy = net, operands, bool(noisy)
@@ -228,6 +235,11 @@ class RainbowPack:
         assert self.support.numel() == ATOMS
         if _share is None:
             self.refresh()
+
+    def policy(self, cvar=1.0, deterministic=False):
+        pi = self.policy_struct()
+        pi.w, pi.support = self.struct, self.support.data_ptr()
+        return pi
 
     def refresh(self, stream=None):
         """The images from the parameters as they are now: compose (noisy only), then asvrl_rainbow_pack."""
@@ -247,11 +259,8 @@ def rainbow_act(pack, obs, act64, step_dev, steps_per_count, total, fraction, in
     is_continuous=False; actions_rec (f64 [rows, 2]) receives the same pair for the rows of envs with env_mask != 0
     (u8, one per robots_per_env rows; None: every row). act64 may be None when act_pair or actions_rec is given."""
     io = pack.image.io(obs, pack.support, act_out=act64.data_ptr() if act64 is not None else None,
-                       ld_act=act64.stride(0) if act64 is not None else 0,
-                       step_dev=step_dev.data_ptr() if step_dev is not None else None,
-                       eps_steps_per_count=float(steps_per_count), eps_total=float(total),
-                       eps_fraction=float(fraction), eps_initial=float(initial), eps_final=float(final),
-                       seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
+                       ld_act=act64.stride(0) if act64 is not None else 0)
+    _abi.fill_schedule(io, step_dev, (steps_per_count, total, fraction, initial, final), seed)
     if int(step_add) == 0 and q_out is None and act_pair is None and actions_rec is None and env_mask is None:
         pack.image.run("asvrl_rainbow_net_act", io, stream)
         return
@@ -354,11 +363,8 @@ class FusedRainbow:
     def act(self, obs_rows, actions64, step_dev, steps_per_count, total, fraction, initial, final, seed):
         """act_rainbow for every row (training mode: noisy online weights), epsilon-greedy."""
         self.window_pack.refresh()
-        io = self.img.io(obs_rows, self.support, act_out=actions64.data_ptr(), ld_act=actions64.stride(0),
-                         step_dev=step_dev.data_ptr(), eps_steps_per_count=float(steps_per_count),
-                         eps_total=float(total), eps_fraction=float(fraction), eps_initial=float(initial),
-                         eps_final=float(final), seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
-        self.img.run("asvrl_rainbow_net_act", io)
+        rainbow_act(self.window_pack, obs_rows, actions64, step_dev, steps_per_count, total, fraction, initial, final,
+                    seed)
 
     def update(self, opt, grads, rows, gamma=0.99, n=3, vmin=-1.0, vmax=1.0, sync=None, max_norm=0.5, seed=0,
                counter_dev=None, compose=True, reset_target=True):

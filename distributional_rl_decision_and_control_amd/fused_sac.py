@@ -37,9 +37,9 @@ import ctypes as C
 import torch
 
 from . import _abi
-from .fused_critic import PartialArena
+from .fused_critic import PartialArena, arena_floats
 from .fused_ddpg import DdpgCriticPack
-from .fused_mlp import ENC, HID, OBSK, MlpPack
+from .fused_mlp import ENC, HID, OBSK, MlpPack, default_net
 from .fused_update import _reduce_and_step
 from .learner import target_step
 
@@ -48,17 +48,11 @@ ALPHA = 0.078   # agent.py:95, fixed
 CRITIC_ARRAYS = ("xb", "h0", "h1", "p", "h2", "q", "q_next", "dq", "dz2", "dz1", "dzG", "dz0")
 
 
-def _net_ok(n):
-    return (n.concat_feature_dimension == 256 and n.hidden_dimension == 128 and n.self_dimension == 7
-            and n.object_dimension == 5 and n.max_object_num == 5 and n.self_feature_dimension == 56
-            and n.object_feature_dimension == 40 and n.action_dimension == 2)
-
-
 def supported(policy, B):
     """The shapes the kernels take: the default network dims, 2 actions and a batch that is a positive multiple
     of 32."""
-    return (B >= 32 and B % 32 == 0 and _net_ok(policy.actor) and _net_ok(policy.critic_1)
-            and _net_ok(policy.critic_2))
+    return B >= 32 and B % 32 == 0 and all(default_net(n) and n.action_dimension == 2
+                                           for n in (policy.actor, policy.critic_1, policy.critic_2))
 
 
 class SacActorPack(MlpPack):
@@ -66,10 +60,23 @@ class SacActorPack(MlpPack):
     f32 copies of the hidden biases, and the f32 head -- `head` [4][128] (output_layer_mu.weight, then
     output_layer_log_std.weight) and `bhead` [4]. adam_segments(opt) lets FusedAdam's step write all of it, as
     DdpgCriticPack does for `wo` / `bo`. double=True (the batched loop): two sets, the step writing the one the act
-    kernel does not read (MlpPack)."""
+    kernel does not read (MlpPack).
+
+    As a window policy (MlpPack; asvrl_sac_rollout): the rounds are sac_act(pack, obs, act64, eps_out, step, *eps,
+    policy_seed) -- the action noise drawn in the kernel on (global row, step, policy_seed) -- and step(act64, ...),
+    the act inside the env kernel. deterministic=True (this pack only): the mean action, the rounds'
+    sac_act(..., eps_in=zeros); nothing is drawn for the sample, the epsilon schedule still applies."""
+    rollout, policy_struct = _abi.ROLLOUTS["sac"]
+    takes_deterministic = True
+    _policy_w = "sw"
 
     def __init__(self, net, operands="bf16", double=False):
         super().__init__(net, "actor", operands, double)
+
+    def policy(self, cvar=1.0, deterministic=False):
+        pi = super().policy()
+        pi.deterministic = int(bool(deterministic))
+        return pi
 
     @staticmethod
     def _make_set(net, kind, operands, copies):
@@ -139,21 +146,12 @@ class _CriticBufs:
         self.q, self.q_next, self.dq = torch.zeros(B, **f), torch.zeros(B, **f), torch.zeros(B, **f)
 
 
-def _arena_floats(L, B, layers, vecs, small=False):
-    need = sum((int(L.asvrl_linear_wgrad_groups(B, M, K)) * (M * K + M) + 63) // 64 * 64 for M, K in layers)
-    need += vecs * ((int(L.asvrl_linear_wgrad_vec_groups(B)) * (HID + 1) + 63) // 64 * 64)
-    if small:
-        need += ((B + 31) // 32 * (HID * 2 + HID) + 63) // 64 * 64
-    return need + 64
-
-
 class FusedSACState:
     """Packs and buffers of the fused SAC update (allocated once, pointer-stable for graph replay).
     operands="f32": every kernel from libasvrl_f32.so (the parity build; the optimisers must be FusedAdam of the
-    same operands). double_actor (the batched loop): two actor image sets, as FusedDDPGState. window_pack (the local
-    actor's SacActorPack) is what the closed-loop windows and the device evaluation take
-    (DeviceEnvBatch.policy_rollout, DeviceEvaluator.run, VecTrainer._collect_window); policy_pack and actor_pack stay
-    None, so VecTrainer.policy_pack(), collect, greedy_episodes and evaluate still refuse a SAC trainer."""
+    same operands). double_actor (the batched loop): two actor image sets, as FusedDDPGState. window_pack and
+    eval_pack are the local actor's SacActorPack; policy_pack and actor_pack stay None, so VecTrainer.policy_pack(),
+    collect, greedy_episodes and evaluate still refuse a SAC trainer."""
 
     policy_pack = actor_pack = None
 
@@ -165,7 +163,8 @@ class FusedSACState:
         self.local = [DdpgCriticPack(policy_local.critic_1, operands), DdpgCriticPack(policy_local.critic_2, operands)]
         self.target = [DdpgCriticPack(policy_target.critic_1, operands),
                        DdpgCriticPack(policy_target.critic_2, operands)]
-        self.actor = self.window_pack = SacActorPack(policy_local.actor, operands, double=double_actor)
+        self.actor = self.window_pack = self.eval_pack = SacActorPack(policy_local.actor, operands,
+                                                                      double=double_actor)
         self.target_actor = SacActorPack(policy_target.actor, operands)
         self.L = self.actor.L
         bf = dict(dtype=_abi.operand_dtype(operands), device=dev)
@@ -185,8 +184,8 @@ class FusedSACState:
         self.act_eps = None   # act()'s eps_out, sized at the first call
         layers = ((HID, HID), (HID, ENC), (ENC, OBSK))
         # one arena per network: each reduction forms that network's own squared gradient norm
-        self.carena = [PartialArena(_arena_floats(self.L, B, layers, 1, small=True), dev, operands) for _ in range(2)]
-        self.aarena = PartialArena(_arena_floats(self.L, B, layers, 4), dev, operands)
+        self.carena = [PartialArena(arena_floats(self.L, B, layers, 1, small=True), dev, operands) for _ in range(2)]
+        self.aarena = PartialArena(arena_floats(self.L, B, layers, 4), dev, operands)
 
     def target_changed(self):
         """Re-pack the target networks after a hard/soft update (eager, outside graphs)."""
@@ -231,9 +230,7 @@ def sac_act(pack, x, actions64, eps_out, step_dev, steps_per_count, total, fract
     io.x, io.ldx, io.n = x.data_ptr(), x.stride(0), x.shape[0]
     io.a_out64, io.eps_out = actions64.data_ptr(), eps_out.data_ptr()
     io.eps_in = eps_in.data_ptr() if eps_in is not None else None
-    io.step_dev = step_dev.data_ptr() if step_dev is not None else None
-    io.eps_steps_per_count, io.eps_total, io.eps_fraction = float(steps_per_count), float(total), float(fraction)
-    io.eps_initial, io.eps_final, io.seed = float(initial), float(final), int(seed) & 0xFFFFFFFFFFFFFFFF
+    _abi.fill_schedule(io, step_dev, (steps_per_count, total, fraction, initial, final), seed)
     _abi.check(pack.L.asvrl_sac_act(C.byref(pack.sw), C.byref(io), _abi.stream_ptr(stream)), "asvrl_sac_act", pack.L)
 
 

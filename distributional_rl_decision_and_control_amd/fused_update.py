@@ -40,7 +40,7 @@ import torch
 from . import _abi
 from .fused_critic import CriticPack, PartialArena, critic_actor_grad, critic_forward, critic_train_fused
 from .fused_mlp import (ActorBuffers, ActorGrads, MlpPack, actor_act, actor_backward, actor_forward,
-                        actor_train_forward)
+                        actor_train_forward, default_net)
 from .fused_mlp import actor_grads as actor_grads_launch
 from .learner import FusedAdam, clip_and_step, target_step
 
@@ -60,11 +60,8 @@ TARGET_IN_FUSED = True
 
 def supported(policy, B, N):
     c, a = policy.critic, policy.actor
-    return (c.concat_feature_dimension == 256 and c.hidden_dimension == 128 and c.n == 64 and N in (8, 16, 32)
-            and (B * N) % 32 == 0 and B % 32 == 0 and c.self_dimension == 7 and c.object_dimension == 5
-            and c.max_object_num == 5 and c.self_feature_dimension == 56 and c.object_feature_dimension == 40
-            and a.hidden_dimension == 128 and a.concat_feature_dimension == 256 and a.action_dimension == 2
-            and c.action_dimension == 2)
+    return (default_net(c) and default_net(a) and c.n == 64 and N in (8, 16, 32) and (B * N) % 32 == 0
+            and B % 32 == 0 and a.action_dimension == 2 and c.action_dimension == 2)
 
 
 class FusedACIQNState:
@@ -81,8 +78,8 @@ class FusedACIQNState:
         self.target_trunk = CriticPack(policy_target.critic, operands)
         # double_actor (the batched loop): two actor image sets, the optimiser writing the one the act kernel
         # does not read (MlpPack)
-        self.actor = self.actor_pack = self.policy_pack = MlpPack(policy_local.actor, "actor", operands,
-                                                                  double=double_actor)
+        self.actor = MlpPack(policy_local.actor, "actor", operands, double=double_actor)
+        self.actor_pack = self.policy_pack = self.window_pack = self.eval_pack = self.actor
         self.target_actor = MlpPack(policy_target.actor, "actor", operands)
         self.abufs = ActorBuffers(B, dev, operands)
         self.agrads = ActorGrads(B, dev, operands)

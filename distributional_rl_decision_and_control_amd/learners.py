@@ -9,18 +9,14 @@ buffers) is built. The Fused*State classes share one surface, so neither front e
                                                                            asvrl_target_update_pack per target network
                                                                            (blend + re-pack, predicated on the device
                                                                            learn counter; Rainbow: the blend alone)
-    policy_pack, actor_pack                                                 what the closed-loop windows take, or None
-
-FusedSACState also has window_pack, its local actor's SacActorPack: DeviceEnvBatch.policy_rollout, DeviceEvaluator.run
-and VecTrainer._collect_window take it (the sampled head runs inside the env kernel), while its policy_pack and
-actor_pack stay None, so VecTrainer's own policy_pack() / collect / greedy_episodes / evaluate still refuse SAC.
-FusedIQNState has window_pack too, its local IqnPack: the same three take it (per step the window launches the act
-pass, asvrl_iqn_act_ex, and then the env step; policy_rollout and run also take act_iqn's cvar), and the same four
-still refuse IQN.
-FusedRainbow has two RainbowPacks: window_pack, the training-mode pack over its own noisy images, is what
-VecTrainer._collect_window takes (the window is pushed into the prioritised replay by DevicePER.push_window), and
-eval_pack, the mu-only images of policy_local.eval(), is what DeviceEvaluator.run and Trainer's "device_eval" take
-(per step asvrl_rainbow_net_act_ex, then the env step). The same four still refuse Rainbow.
+    window_pack                                                            the training-mode pack of the closed-loop
+                                                                           windows (VecTrainer._collect_window)
+    eval_pack                                                              what DeviceEvaluator.run takes (Rainbow: the
+                                                                           mu-only images, re-packed on every read;
+                                                                           every other learner: window_pack itself)
+    policy_pack, actor_pack                                                what VecTrainer.policy_pack() and collect /
+                                                                           greedy_episodes / evaluate go by: None
+                                                                           where they refuse the agent type
 """
 from dataclasses import dataclass
 from typing import Callable, Optional

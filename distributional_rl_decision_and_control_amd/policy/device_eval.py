@@ -30,12 +30,8 @@ import numpy as np
 import torch
 
 from .. import _abi
-from ..device_env import DeviceEnvBatch
+from ..device_env import DeviceEnvBatch, policy_options
 from ..envs.marinenav.env import MarineNavEnv3, set_batch_params
-from ..fused_dqn import DqnPack
-from ..fused_iqn import IqnPack
-from ..fused_rainbow import RainbowPack
-from ..fused_sac import SacActorPack
 
 RECORDS = ("reward", "info", "rs")
 OBS_COUNTER = 0x80000000   # the observation pass's Philox counter (VecMarineNavEnv.reset's); step t draws at t
@@ -222,20 +218,12 @@ class DeviceEvaluator:
         the end, 1 goal, 2 collision)."""
         if (pack is None) == (actions is None):
             raise ValueError("run takes the Actor's pack or an action table, not both")
-        iqn = isinstance(pack, IqnPack)
-        if pack is not None and not iqn and not isinstance(pack, RainbowPack) and pack.kind != "actor":
+        if pack is not None and not pack.is_policy:
             raise ValueError("run: pack must be an MlpPack of kind 'actor'")
-        if (pack is not None and is_continuous is not None
-                and bool(is_continuous) == isinstance(pack, (DqnPack, IqnPack, RainbowPack))):
+        if pack is not None and is_continuous is not None and bool(is_continuous) != pack.continuous:
             raise ValueError("run: is_continuous=%s does not match the pack (a DqnPack, IqnPack or RainbowPack picks "
                              "discrete actions, the Actor continuous ones)" % bool(is_continuous))
-        cvar = float(cvar)
-        if not 0.0 < cvar <= 1.0:
-            raise ValueError("run: cvar must be in (0, 1]")
-        if cvar != 1.0 and not iqn:
-            raise ValueError("run: cvar is the risk distortion of IQN's quantile fractions (an IqnPack)")
-        if deterministic and not isinstance(pack, SacActorPack):
-            raise ValueError("run: deterministic=True is the mean action of SAC's sampled actor (a SacActorPack)")
+        cvar = policy_options("run", pack, cvar, deterministic)
         is_continuous = True if is_continuous is None else bool(is_continuous)
         episode_limit = int(episode_limit)
         actions = self._per_group(actions, "actions")

@@ -325,17 +325,9 @@ class Trainer:
             if tr is None:
                 raise RuntimeError("evaluation(batched='device') runs on learn_vectorized's VecTrainer")
             print(f"Evaluating episodes 0-{len(self.eval_config) - 1} (on the device)")
-            # the batched trainer's own actor on device-resident eval configs (policy/device_eval.py)
-            if tr.agent_type == "DQN":   # DQN_Policy's local images in the same windows
-                res = tr.device_evaluator(self.eval_config, template_env=self.eval_env).run(tr.policy_pack())
-            elif tr.agent_type == "IQN":   # IQN_Policy's local images: the act launch and the step, per step
-                res = tr.device_evaluator(self.eval_config,
-                                          template_env=self.eval_env).run(tr.fused_iqn.window_pack)
-            elif tr.agent_type == "Rainbow":   # Rainbow_Policy.eval(): the mu-only images, packed on this read
-                res = tr.device_evaluator(self.eval_config,
-                                          template_env=self.eval_env).run(tr.fused_rb.eval_pack)
-            else:
-                res = tr.evaluate(self.eval_config, template_env=self.eval_env)
+            # the batched trainer's own local images on device-resident eval configs (policy/device_eval.py);
+            # Rainbow's eval_pack is Rainbow_Policy.eval(): the mu-only images, packed on this read
+            res = tr.device_evaluator(self.eval_config, template_env=self.eval_env).run(tr.learner.eval_pack)
             obs_d, act_d, traj_d = res["observations"], res["actions"], res["trajectories"]
             rew_d, succ_d, time_d, en_d, rel_d = (res["rewards"], res["successes"], res["times"], res["energies"],
                                                   res["relations"])

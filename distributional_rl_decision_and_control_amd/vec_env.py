@@ -126,24 +126,15 @@ class VecMarineNavEnv:
 
     def policy_rollout(self, pack, K, hold_done=True, keep=("reward", "done", "info"), eps=(1.0, 1.0, 1.0, 0.0, 0.0),
                        policy_seed=0, env_mask=None, auto_reset=False, count=True, deterministic=False, cvar=1.0):
-        """K closed-loop steps in one launch (DeviceEnvBatch.policy_rollout): the AC-IQN Actor of `pack` acts on
-        obs_cur and every next observation -- the values of K rounds of fused_mlp.actor_act(pack, obs_cur, actions,
-        counter, *eps, policy_seed); step(actions); advance_device(), with the last step's observation in obs_next /
-        cnt_next and the step counter advanced by K on the device. eps: the linear epsilon schedule over the step
-        counter (the default is greedy). The contract is otherwise rollout()'s. Returns the kept per-step records
-        (keep also takes "actions"). auto_reset, count: as rollout()'s (the Actor acts on a reset env's reset
-        observation at the next step). A fused_dqn.DqnPack drives an env built with is_continuous=False the same
-        way (fused_dqn.dqn_act in the Actor's place; "actions" holds (action index, 0.0)). A fused_sac.SacActorPack
-        drives a continuous env with fused_sac.sac_act in the Actor's place, its noise drawn in the kernel on
-        (row, step counter, policy_seed); deterministic=True (that pack only) takes the mean action instead. A
-        fused_iqn.IqnPack drives an env built with is_continuous=False as a DqnPack does (fused_iqn.iqn_act in the
-        Actor's place, its quantile fractions drawn in the kernel on (row, step counter, policy_seed)); cvar in (0, 1]
-        (that pack only) is act_iqn's risk distortion. A fused_rainbow.RainbowPack drives a discrete env the same way
-        (fused_rainbow.rainbow_act in the Actor's place, on the images of the pack's last refresh())."""
-        from .fused_dqn import DqnPack
-        from .fused_iqn import IqnPack
-        from .fused_rainbow import RainbowPack
-        if isinstance(pack, (DqnPack, IqnPack, RainbowPack)):
+        """K closed-loop steps in one launch (DeviceEnvBatch.policy_rollout): the policy of `pack` acts on obs_cur and
+        every next observation -- the values of K rounds of the pack's act call on (obs_cur, actions, counter, *eps,
+        policy_seed); step(actions); advance_device(), with the last step's observation in obs_next / cnt_next and
+        the step counter advanced by K on the device. eps: the linear epsilon schedule over the step counter (the
+        default is greedy). The contract is otherwise rollout()'s. Returns the kept per-step records (keep also takes
+        "actions"). auto_reset, count: as rollout()'s (the policy acts on a reset env's reset observation at the next
+        step). pack.continuous must match how this env was built; deterministic and cvar are the pack's own options
+        (see the pack classes)."""
+        if not pack.continuous:
             if self.is_continuous:
                 raise ValueError("policy_rollout: a DqnPack, IqnPack or RainbowPack picks discrete actions, this env "
                                  "was built with is_continuous=True")

@@ -47,6 +47,23 @@ def test_surface(agent_type):
             assert tr.learner.actor_pack is None and tr.policy_pack() is tr.fused_dqn.local
         else:
             assert tr.learner.actor_pack is tr.policy_pack() is tr.learner.actor
+    # one name per purpose: what _collect_window takes and what DeviceEvaluator.run takes
+    if agent_type == "Rainbow":
+        assert tr.learner.window_pack.noisy and tr.learner.window_pack.image is tr.fused_rb.img
+        assert not tr.learner.eval_pack.noisy and tr.learner.eval_pack is not tr.learner.window_pack
+    else:
+        want = {"AC-IQN": lambda: tr.fused2.actor, "DDPG": lambda: tr.fused_ddpg.actor,
+                "DQN": lambda: tr.fused_dqn.local, "IQN": lambda: tr.fused_iqn.local}[agent_type]()
+        assert tr.learner.window_pack is want and tr.learner.eval_pack is want
+
+
+def test_sac_window_and_eval_packs():
+    """The sixth batched agent type: both names are the local actor's pack, and the refusals stay."""
+    tr = _trainer("SAC")
+    assert tr.learner is tr.fused_sac and tr.learner.window_pack is tr.learner.eval_pack is tr.fused_sac.actor
+    assert tr.learner.policy_pack is None and tr.learner.actor_pack is None
+    with pytest.raises(NotImplementedError):
+        tr.policy_pack()
 
 
 @pytest.mark.parametrize("agent_type", TYPES)
