@@ -222,6 +222,15 @@ class AsvEvalMetrics(C.Structure):
                                    "alive", "deact", "outcome", "ret", "time", "energy")]
 
 
+class AsvNoiseStreams(C.Structure):
+    _fields_ = [("n_envs", _I32), ("max_robots", _I32), ("max_obs", _I32), ("_pad0", _I32)] + \
+               [(n, _VP) for n in ("n_robots", "n_obs", "rflags", "env_mask", "robot_params", "key", "pos", "has_gauss",
+                                   "gauss", "noise_out", "draws_n", "draws_sum", "draws_sq")]
+
+
+RS_KEY_WORDS = 624   # MT19937 words of a numpy RandomState stream
+
+
 DQN_MAX_ACTIONS = 32
 
 
@@ -483,6 +492,9 @@ EXPORTS = [
                                            _VP, _VP, _VP, _I64, _VP]),
     ("asvrl_eval_metrics", C.c_int, [C.POINTER(AsvEvalMetrics), _VP]),
     ("asvrl_eval_metrics_struct_size", _I64, []),
+    ("asvrl_noise_streams", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvNoiseStreams), _VP]),
+    ("asvrl_noise_streams_host", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvNoiseStreams), _VP]),
+    ("asvrl_noise_streams_struct_size", _I64, []),
     ("asvrl_dqn_pack", C.c_int, [C.POINTER(AsvMlpSrc), _VP, C.POINTER(AsvDqnWeights), _VP]),
     ("asvrl_dqn_act", C.c_int, [C.POINTER(AsvDqnWeights), C.POINTER(AsvDqnActIO), _VP]),
     ("asvrl_dqn_grad", C.c_int, [C.POINTER(AsvDqnWeights), C.POINTER(AsvDqnWeights), C.POINTER(AsvDqnGradIO), _VP]),

@@ -19,12 +19,13 @@ SOURCES = [os.path.join(HERE, "csrc", f) for f in ("asvrl_env.hip", "asvrl_learn
                                                              "asvrl_optim.hip", "asvrl_wgrad.hip", "asvrl_mlp.hip",
                                                              "asvrl_per.hip", "asvrl_rainbow.hip", "asvrl_rainbow_net.hip",
                                                              "asvrl_eval.hip", "asvrl_dqn.hip", "asvrl_ddpg.hip",
-                                                             "asvrl_sac.hip")]
+                                                             "asvrl_sac.hip", "asvrl_noise.hip")]
 HEADERS = [os.path.join(HERE, "csrc", "asvrl_common.h"), os.path.join(HERE, "csrc", "asvrl_mfma.h"),
            os.path.join(HERE, "csrc", "asvrl_lds.h"), os.path.join(HERE, "csrc", "asvrl_vonmises_k1.h"),
            os.path.join(HERE, "csrc", "asvrl_critic_tile.h"), os.path.join(HERE, "csrc", "asvrl_actor_tile.h"),
            os.path.join(HERE, "csrc", "asvrl_dqn_tile.h"), os.path.join(HERE, "csrc", "asvrl_ddpg_tile.h"),
-           os.path.join(HERE, "csrc", "asvrl_sac_tile.h"), os.path.join(ROOT, "include", "asvrl.h")]
+           os.path.join(HERE, "csrc", "asvrl_sac_tile.h"), os.path.join(HERE, "csrc", "asvrl_rs_stream.h"),
+           os.path.join(ROOT, "include", "asvrl.h")]
 OUT = os.path.join(HERE, "lib", "libasvrl.so")
 OUT_F32 = os.path.join(HERE, "lib", "libasvrl_f32.so")
 VARIANTS = {OUT: [], OUT_F32: ["-DASVRL_OPERAND_F32=1"]}

@@ -18,11 +18,16 @@ per-robot bookkeeping in Python. DeviceEvaluator keeps the same episodes in Devi
     step limit, ANY collision, or every robot deactivated). Its `alive` output is the next window's env_mask;
   * one copy at the end brings the per-robot sums, outcomes and lengths to the host.
 
-Perception noise in the closed loop is the rollout's Philox stream (seed, env, robot, step; f32 draws), not each
-robot's numpy RandomState, and SAC's action noise is Philox + Box-Muller on (row, step, policy_seed + group), not
-torch's generator: the results agree with evaluate_configs in distribution, and exactly under teacher
-forcing with the noise given (tests/test_device_eval_gpu.py). Observation, action and trajectory histories are not
-kept.
+Perception noise has two modes. perception="philox" (the default): the rollout's Philox stream (seed, env, robot,
+step; f32 draws), not each robot's numpy RandomState; the results agree with evaluate_configs in distribution, and
+exactly under teacher forcing with the noise given (tests/test_device_eval_gpu.py). perception="numpy": every robot's
+own numpy.random.RandomState(seed) stream continued on the device (noise_streams.NoiseStreams, asvrl_noise_streams):
+one launch in front of every step draws the step's rows for the robots that are still active, and the windows are one
+step long, because which robots draw depends on the deactivations of the step before. The episodes are then the ones
+the reference, Trainer.evaluation and evaluate_configs produce for the same configs and actions
+(tests/test_eval60_reference_noise_gpu.py). In both modes SAC's action noise is Philox + Box-Muller on (row, step,
+policy_seed + group), not torch's generator, and IQN's quantile fractions and the exploration draw are Philox too.
+Observation, action and trajectory histories are not kept.
 """
 import ctypes as C
 
@@ -32,8 +37,10 @@ import torch
 from .. import _abi
 from ..device_env import DeviceEnvBatch, policy_options
 from ..envs.marinenav.env import MarineNavEnv3, set_batch_params
+from ..noise_streams import NoiseStreams
 
 RECORDS = ("reward", "info", "rs")
+PERCEPTIONS = ("philox", "numpy")
 OBS_COUNTER = 0x80000000   # the observation pass's Philox counter (VecMarineNavEnv.reset's); step t draws at t
 
 
@@ -69,6 +76,14 @@ def new_metrics_state(E, R, device):
     return dict(length=torch.zeros(E, dtype=torch.int32, device=device), ended=torch.zeros(E, **u8),
                 alive=torch.ones(E, **u8), deact=torch.zeros(NT, **u8), outcome=torch.zeros(NT, **u8),
                 ret=torch.zeros(NT, **f64), time=torch.zeros(NT, **f64), energy=torch.zeros(NT, **f64))
+
+
+def _check_perception(who, perception, *noises):
+    if perception not in PERCEPTIONS:
+        raise ValueError(f"{who}: perception must be one of {PERCEPTIONS}, not {perception!r}")
+    if perception == "numpy" and any(n is not None for n in noises):
+        raise ValueError(f"{who}: perception='numpy' draws the noise from the robots' RandomState streams; "
+                         "explicit noise (noise= / obs_noise=) goes with perception='philox'")
 
 
 class _Group:
@@ -108,6 +123,19 @@ class _Group:
         self.state = new_metrics_state(E, R, device)
         self.step = torch.zeros(1, dtype=torch.int64, device=device)
         self._rec = {}
+        self._streams = None
+
+    def streams(self):
+        """Every robot row's RandomState(rob.perception.seed) stream as the robot's Perception held it before
+        reset_with_eval_config's observation pass (built on first use, restored by observe)."""
+        if self._streams is None:
+            R = self.batch.max_robots
+            seeds = [None] * (self.batch.n_envs * R)
+            for e, env in enumerate(self.envs):
+                for i, rob in enumerate(env.robots):
+                    seeds[e * R + i] = rob.perception.seed
+            self._streams = NoiseStreams(seeds, device=self.batch.device)
+        return self._streams
 
     def restore(self):
         b = self.batch
@@ -187,19 +215,28 @@ class DeviceEvaluator:
             raise ValueError(f"{what}: {len(x)} tensors for {len(self.groups)} parameter groups")
         return list(x)
 
-    def observe(self, noise=None, seed=0):
+    def observe(self, noise=None, seed=0, perception="philox"):
         """Restore the initial state, zero the carried metrics and run the observation pass (the do_dynamics = 0
         step of VecMarineNavEnv.reset) into every batch's obs / obs64 / obj_cnt. noise: explicit draws per group
-        ([NT, O + R, 5] f64) instead of the Philox stream."""
+        ([NT, O + R, 5] f64) instead of the Philox stream. perception="numpy": the pass's rows come from the robots'
+        RandomState streams, restored to their seeds first (noise must be None); the streams then stand where each
+        robot's Perception stands after reset_with_eval_config, and their draw counters are zeroed behind the pass."""
+        _check_perception("observe", perception, noise)
         noise = self._per_group(noise, "observe noise")
         for g, grp in enumerate(self.groups):
             grp.restore()
+            if perception == "numpy":
+                ns = grp.streams()
+                ns.restore()
+                grp.batch.step(None, do_dynamics=False, noise=ns.fill(grp.batch))
+                ns.zero_counters()
+                continue
             grp.batch.step(None, do_dynamics=False, noise=noise[g], seed=seed + g, counter=OBS_COUNTER,
                            fast_noise=True)
 
     @torch.no_grad()
     def run(self, pack=None, *, actions=None, noise=None, obs_noise=None, seed=0, episode_limit=1000, sync=True,
-            is_continuous=None, policy_seed=0, deterministic=False, cvar=1.0):
+            is_continuous=None, policy_seed=0, deterministic=False, cvar=1.0, perception="philox"):
         """One evaluation of every config. pack: the Actor's MlpPack or DQN's DqnPack, greedy in closed-loop
         windows, or SAC's SacActorPack, which samples its action as act_sac does in evaluation too (group g draws
         under policy_seed + g: rows are batch-local, so two groups share no draws) or, with deterministic=True (a
@@ -215,7 +252,16 @@ class DeviceEvaluator:
         ceil((episode_limit + 1) / chunk) windows without a host wait. Returns evaluate_configs' per-config lists
         (rewards, successes, times, energies, lengths; observations / actions / trajectories / relations empty per
         robot) and the per-robot arrays robot_rewards, robot_times, robot_energies, robot_outcomes (0 running at
-        the end, 1 goal, 2 collision)."""
+        the end, 1 goal, 2 collision).
+        perception: "philox" (the default: the noise described above) or "numpy": the perception noise of the
+        observation pass and of every step is drawn from each robot's own RandomState(rob.perception.seed) stream, as
+        the reference, Trainer.evaluation and evaluate_configs draw it. Every step is then one asvrl_noise_streams
+        launch under env_mask = alive, a window of length 1 on its rows and asvrl_eval_metrics with K = 1 (`chunk`
+        only sets how many steps lie between two host waits of sync=True). seed does not enter the perception noise;
+        noise= or obs_noise= with it, and any other value of perception, is a ValueError. policy_seed, IQN's tau
+        draws, SAC's action noise and the exploration draw stay Philox in both modes. The result then also carries
+        draws_n, draws_sum and draws_sq: per config, an array per robot of the count, sum and sum of squares of its
+        step draws in draw order (the observation pass's are not counted); in the Philox mode the three are None."""
         if (pack is None) == (actions is None):
             raise ValueError("run takes the Actor's pack or an action table, not both")
         if pack is not None and not pack.is_policy:
@@ -224,6 +270,7 @@ class DeviceEvaluator:
             raise ValueError("run: is_continuous=%s does not match the pack (a DqnPack, IqnPack or RainbowPack picks "
                              "discrete actions, the Actor continuous ones)" % bool(is_continuous))
         cvar = policy_options("run", pack, cvar, deterministic)
+        _check_perception("run", perception, noise, obs_noise)
         is_continuous = True if is_continuous is None else bool(is_continuous)
         episode_limit = int(episode_limit)
         actions = self._per_group(actions, "actions")
@@ -233,34 +280,40 @@ class DeviceEvaluator:
             T = min(int(a.shape[0]) for a in actions)
             total = min(total, T)
         L = pack.L if pack is not None else _abi.lib()
-        self.observe(obs_noise, seed)
+        self.observe(obs_noise, seed, perception)
+        numpy_noise = perception == "numpy"
         t0 = self.windows = 0
         while t0 < total:
-            k = min(self.chunk, total - t0)
+            k = 1 if numpy_noise else min(self.chunk, total - t0)
             for g, grp in enumerate(self.groups):
                 b, st = grp.batch, grp.state
                 rec = grp.records(k)
+                if numpy_noise:   # this step's rows from the streams of the robots still active
+                    noise[g] = grp.streams().fill(b, env_mask=st["alive"])[None]
                 if pack is not None:
                     grp.step.fill_(t0)
-                    b.policy_rollout(pack, k, b.obs, keep=rec, hold_done=True, trainer_deactivate=True,
+                    b.policy_rollout(pack, k, b.obs, noise=noise[g] if numpy_noise else None, keep=rec,
+                                     hold_done=True, trainer_deactivate=True,
                                      step_dev=grp.step, env_mask=st["alive"], seed=seed + g, counter=t0,
                                      fast_noise=True, policy_seed=policy_seed + g, deterministic=deterministic,
                                      cvar=cvar)
                 else:
                     nz = noise[g]
-                    b.rollout(actions[g][t0:t0 + k], None if nz is None else nz[t0:t0 + k], keep=rec,
+                    b.rollout(actions[g][t0:t0 + k], nz if nz is None or numpy_noise else nz[t0:t0 + k], keep=rec,
                               hold_done=True, is_continuous=is_continuous, trainer_deactivate=True,
                               env_mask=st["alive"], seed=seed + g, counter=t0, fast_noise=True)
                 eval_metrics(L, k, b.n_envs, b.max_robots, rec, b.n_robots, grp.dt, grp.N, grp.pc, st, self.gamma,
                              episode_limit)
             t0 += k
             self.windows += 1
+            if numpy_noise and t0 % self.chunk and t0 < total:
+                continue   # one-step windows: the host waits every `chunk` steps
             if sync and not any(bool(grp.state["alive"].any().item()) for grp in self.groups):
                 break   # one host wait per window
         self.steps = t0
-        return self._result(check_ended=pack is None and total < episode_limit + 1)
+        return self._result(check_ended=pack is None and total < episode_limit + 1, draws=numpy_noise)
 
-    def _result(self, check_ended=False):
+    def _result(self, check_ended=False, draws=False):
         # one copy: every group's lengths, ended flags, outcomes and sums in one f64 tensor
         parts = []
         for grp in self.groups:
@@ -272,7 +325,15 @@ class DeviceEvaluator:
         out = dict(observations=[None] * n, actions=[None] * n, trajectories=[None] * n, rewards=[None] * n,
                    successes=[None] * n, times=[None] * n, energies=[None] * n, relations=[None] * n,
                    lengths=[None] * n, robot_rewards=[None] * n, robot_times=[None] * n, robot_energies=[None] * n,
-                   robot_outcomes=[None] * n)
+                   robot_outcomes=[None] * n, draws_n=None, draws_sum=None, draws_sq=None)
+        if draws:
+            for name in ("draws_n", "draws_sum", "draws_sq"):
+                out[name] = [None] * n
+            for grp in self.groups:
+                R = grp.batch.max_robots
+                for name, a in zip(("draws_n", "draws_sum", "draws_sq"), grp.streams().counters()):
+                    for le, c in enumerate(grp.members):
+                        out[name][c] = a[le * R:le * R + self.n_robots[c]].copy()
         at = 0
         for grp in self.groups:
             E, R = grp.batch.n_envs, grp.batch.max_robots

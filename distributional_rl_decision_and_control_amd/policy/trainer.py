@@ -14,7 +14,8 @@ reads only its own keys from it (env.py:75-94). An optional "vectorized" dict in
 files keep the reference's cadence and format; the trained networks are copied into rl_agent first.
 With "device_eval": true in that dict (AC-IQN, DDPG, DQN, IQN and Rainbow) the evaluations run on the device with the
 batched trainer's own actor, Q network, quantile network or, for Rainbow, the mu-only (eval-mode) images of its online
-network (evaluation(batched="device"), policy/device_eval.py).
+network (evaluation(batched="device"), policy/device_eval.py). "device_eval": {"perception": "numpy"} does the same
+with the perception noise drawn from every robot's own RandomState stream, as the other evaluation paths draw it.
 """
 import json
 import os
@@ -172,9 +173,19 @@ class Trainer:
         kw = dict(vec)
         # "device_eval": true evaluates on the device with the batched trainer's own actor (AC-IQN, DDPG) or Q network
         # (DQN), quantile network (IQN) or eval-mode Rainbow network (evaluation(batched="device")) instead of copying the
-        # networks out and stepping the Python eval envs
-        device_eval = bool(kw.pop("device_eval", False)) and agent.agent_type in ("AC-IQN", "DQN", "DDPG", "IQN",
-                                                                                  "Rainbow")
+        # networks out and stepping the Python eval envs. A dict in its place switches it on with options:
+        # {"perception": "numpy"} draws the perception noise from the robots' own RandomState streams, as the other
+        # two evaluation paths do (DeviceEvaluator.run's perception)
+        opts = kw.pop("device_eval", False)
+        if isinstance(opts, dict):
+            if set(opts) - {"perception"}:
+                raise ValueError(f"device_eval: unknown option(s) {sorted(set(opts) - {'perception'})}; it takes "
+                                 "\"perception\"")
+            self._device_eval_kw = dict(opts)
+            opts = True
+        else:
+            self._device_eval_kw = {}
+        device_eval = bool(opts) and agent.agent_type in ("AC-IQN", "DQN", "DDPG", "IQN", "Rainbow")
         kw.setdefault("graphs", True)
         for key, sk in (("num_robots", "num_robots"), ("num_obs", "num_obstacles"), ("num_cores", "num_cores")):
             if sk in sched:
@@ -327,7 +338,8 @@ class Trainer:
             print(f"Evaluating episodes 0-{len(self.eval_config) - 1} (on the device)")
             # the batched trainer's own local images on device-resident eval configs (policy/device_eval.py);
             # Rainbow's eval_pack is Rainbow_Policy.eval(): the mu-only images, packed on this read
-            res = tr.device_evaluator(self.eval_config, template_env=self.eval_env).run(tr.learner.eval_pack)
+            res = tr.device_evaluator(self.eval_config, template_env=self.eval_env).run(
+                tr.learner.eval_pack, **getattr(self, "_device_eval_kw", {}))
             obs_d, act_d, traj_d = res["observations"], res["actions"], res["trajectories"]
             rew_d, succ_d, time_d, en_d, rel_d = (res["rewards"], res["successes"], res["times"], res["energies"],
                                                   res["relations"])

@@ -1192,6 +1192,55 @@ int asvrl_eval_metrics(const AsvEvalMetrics* m, void* stream);
 /* sizeof(AsvEvalMetrics) as compiled. */
 int64_t asvrl_eval_metrics_struct_size(void);
 
+/* ---------------------------------------------------------------- the reference's perception-noise streams */
+
+/* One env step's perception noise drawn from every robot's own numpy.random.RandomState stream (wamv.py:5-40,
+ * drawn at :466-468 and :493-495), continued on the device: the rows asvrl_env_step / asvrl_env_rollout take as
+ * explicit noise (noise mode 0), [NT][O + R][5] f64 with NT = n_envs * max_robots, O = max_obs, R = max_robots.
+ *
+ * A stream is numpy's get_state() tuple: key (624 MT19937 words), pos (0..624), has_gauss and the cached gauss.
+ * Robot i of env e (row e * R + i) draws iff env_mask[e] != 0 (a NULL mask: every env), i < n_robots[e] and
+ * rflags[row] does not carry ASVRL_FLAG_DEACTIVATED; a robot that does not draw keeps its stream bit for bit and
+ * gets a zero row. One that draws takes five values -- normal(0, pos_std) twice, normal(0, vel_std) twice,
+ * vonmises(0, r_kappa), as Perception.draw_candidate_noise -- for every obstacle k < n_obs[e] into slot k and then
+ * for every robot j < n_robots[e], j != i, not deactivated, into slot O + j (MarineNavEnv3._pack's order); every
+ * other slot of the row is zero. pos_std, vel_std and r_kappa are those of the AsvParams argument, or of
+ * robot_params[row] when the table is given (AsvEnvState.robot_params). The draws are numpy's word for word:
+ * MT19937 words and every accept / reject decision of the normal's polar method exactly; the values through the
+ * device's log / sqrt / cos / acos / fmod (asvrl_noise_streams) or the host's (asvrl_noise_streams_host).
+ * draws_n / draws_sum / draws_sq (all three or none) accumulate the count, sum and sum of squares of the values
+ * drawn, in draw order. One launch, one wave per robot row, no atomics. */
+typedef struct AsvNoiseStreams {
+  int32_t n_envs;      /* E >= 1 */
+  int32_t max_robots;  /* R in 1..256 */
+  int32_t max_obs;     /* O >= 0; (O + R) * 40 bytes of LDS per workgroup must fit (O + R <= 1024) */
+  int32_t _pad0;
+  /* the batch (read only) */
+  const int32_t* n_robots;      /* [E] */
+  const int32_t* n_obs;         /* [E] */
+  const uint8_t* rflags;        /* [NT] */
+  const uint8_t* env_mask;      /* [E] or NULL */
+  const AsvParams* robot_params; /* [NT] or NULL: every robot AsvParams' pos_std / vel_std / r_kappa */
+  /* the streams (read and written) */
+  uint32_t* key;        /* [NT][624] */
+  int32_t*  pos;        /* [NT] */
+  int32_t*  has_gauss;  /* [NT] */
+  double*   gauss;      /* [NT] */
+  /* written */
+  double*   noise_out;  /* [NT][O + R][5] */
+  /* accumulated (all NULL: not counted) */
+  int64_t*  draws_n;    /* [NT] */
+  double*   draws_sum;  /* [NT] */
+  double*   draws_sq;   /* [NT] */
+} AsvNoiseStreams;
+
+int asvrl_noise_streams(const AsvParams* p, const AsvNoiseStreams* ns, void* stream);
+/* The same call on HOST pointers, run on the CPU by the same draw functions (csrc/asvrl_rs_stream.h): it needs no
+ * GPU, and pins the algorithm to numpy bit for bit where the host's libm is numpy's. `stream` is ignored. */
+int asvrl_noise_streams_host(const AsvParams* p, const AsvNoiseStreams* ns, void* stream);
+/* sizeof(AsvNoiseStreams) as compiled. */
+int64_t asvrl_noise_streams_struct_size(void);
+
 /* ---------------------------------------------------------------- DQN (agent.py:271-287, 518-545)
  * DQN_Policy (DQN_model.py) has the Actor's trunk layer for layer (both observation encoders, hidden_layer,
  * hidden_layer_2) and a 128 -> A output layer (A = 25) without a squash. Its images are the Actor's
