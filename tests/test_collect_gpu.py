@@ -5,13 +5,13 @@ import numpy as np
 import pytest
 import torch
 
+import window_cases as wc
+from window_cases import ENV_ARRAYS
+
 pytestmark = pytest.mark.gpu
 
 E = 37
-
-
-def _same(got, ref, what):
-    torch.testing.assert_close(got, ref, rtol=0, atol=0, equal_nan=True, msg=lambda m: f"{what}: {m}")
+LIMIT = 5   # the episode limit, set before the first step: every env ends several times
 
 
 def _synthetic(K, n, seed=3):
@@ -54,7 +54,7 @@ def test_push_window_matches_single_pushes(given):
     total = int(counts.sum().item())
     assert rings[0][1].tolist() == [(head0 + total) % CAP, min(2000 + total, CAP)] and head0 + total > CAP
     for got, ref, what in zip(rings[1], rings[0], ("ring", "{head, size}", "snap", "counter")):
-        _same(got, ref, what)
+        wc.same(got, ref, what)
     # a second window on the same replay: the scratch is left ready
     rp = DeviceReplay(CAP)
     rp.push_window(rec, K)
@@ -64,36 +64,11 @@ def test_push_window_matches_single_pushes(given):
         DeviceReplay(K * n - 1).push_window(rec, K)
 
 
-def _trainer(**kw):
-    from distributional_rl_decision_and_control_amd.vec_trainer import VecTrainer
-    tr = VecTrainer(n_envs=E, agent_type="AC-IQN", batch_size=64, buffer_size=4096, graphs=False, seed=3, **kw)
-    tr.env.batch.params.episode_limit = 5   # before the first step: every env ends several times
-    return tr
-
-
-ENV_ARRAYS = ("rs", "rflags", "n_robots", "n_obs", "n_cores", "ep_ts", "obstacles", "cores", "obs", "obj_cnt", "reward",
-              "done", "info", "env_done")
-
-
-def _compare(a, b, what):
-    _same(a.replay.ring, b.replay.ring, f"{what}: ring")
-    _same(a.replay.state, b.replay.state, f"{what}: ring state")
-    _same(a.env.counter, b.env.counter, f"{what}: env.counter")
-    _same(a.env.obs_cur, b.env.obs_cur, f"{what}: obs_cur")
-    _same(a.env.cnt_cur, b.env.cnt_cur, f"{what}: cnt_cur")
-    for n in ENV_ARRAYS:
-        _same(getattr(a.env.batch, n), getattr(b.env.batch, n), f"{what}: {n}")
-    sa, sb = a.env.episode_stats(), b.env.episode_stats()
-    for k in ("robot_episodes", "env_episodes", "success", "collision", "timeout"):
-        assert sa[k] == sb[k], (what, k, sa[k], sb[k])
-    assert abs(sa["mean_return"] - sb["mean_return"]) <= 1e-12 * max(1.0, abs(sb["mean_return"]))
-
-
 def test_collect_matches_rollouts():
     """collect(13) twice against rollout() 26 times: the ring (which wraps), its state, the counter, the current
     observation, every env array, the episode statistics, and a learn() afterwards."""
     K = 13
-    ref, tr = _trainer(), _trainer()
+    ref, tr = wc.trainer("AC-IQN", LIMIT, E), wc.trainer("AC-IQN", LIMIT, E)
     for _ in range(2 * K):
         ref.rollout()
     resets = 0
@@ -105,14 +80,8 @@ def test_collect_matches_rollouts():
     assert ref.env.episode_stats()["env_episodes"] == resets
     pushed = 2 * K * E * tr.R   # an upper bound; the ring of 4096 rows must have wrapped
     assert ref.replay.size() == 4096 and pushed > 4096
-    _compare(tr, ref, "collect(13) x 2")
-    la, lb = tr.learn(), ref.learn()
-    torch.cuda.synchronize()
-    for x, y in zip(la, lb):
-        if torch.is_tensor(x):
-            _same(x, y, "loss after the windows")
-        else:
-            assert x == y
+    wc.compare_trainers(tr, ref, "collect(13) x 2", host_counters=False)
+    wc.same_learn(tr, ref, "loss after the windows")
 
 
 def test_collect_other_agents():
@@ -123,7 +92,7 @@ def test_collect_other_agents():
 
 def test_collect_graph_capture():
     """collect(4) captured in a graph and replayed equals the eager call."""
-    ref, tr = _trainer(), _trainer()
+    ref, tr = wc.trainer("AC-IQN", LIMIT, E), wc.trainer("AC-IQN", LIMIT, E)
     for t in (ref, tr):
         t.env.swap = False   # a captured window finds the same observation buffers at every replay
     for _ in range(2):
@@ -144,5 +113,5 @@ def test_collect_graph_capture():
         dst.copy_(src)
     g.replay()
     torch.cuda.synchronize()
-    _compare(tr, ref, "captured collect(4)")
+    wc.compare_trainers(tr, ref, "captured collect(4)", host_counters=False)
     assert np.isfinite(tr.env.episode_stats()["mean_return"])

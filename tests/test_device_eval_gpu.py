@@ -14,69 +14,38 @@ Trainer.evaluation(batched="device")) on a handful of the shipped schedule's eva
 
 Tolerances: integers and flags exact; f64 sums 1e-12 relative (pow and summation order over at most 64 terms of
 2.3e-16 each), the return relative to max(1, sum |term|)."""
-import copy
-import functools
-import json
-import math
+import dataclasses
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import device_eval_cases as dev
+import window_cases as wc
+from device_eval_cases import GAMMA
+
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "eval60_ref.npz")
-PICK = (0, 10, 20, 30, 40, 55)   # 3, 4, 5 robots without buoys; 5 robots with 2, 3 and 4 buoys
-GAMMA = 0.99
-RSUM = 5.59                      # two WAM-V radii (2 * 0.5 * sqrt(5^2 + 2.5^2)), metres
+
+def _trained_actor():
+    """The Actor with the 'trained' weights of tests/golden/eval60_ref.npz."""
+    z = np.load(dev.GOLDEN)
+    actor = wc.CASES["actor"].net()
+    prefix = "trained/net/"
+    actor.load_state_dict({k[len(prefix):]: torch.from_numpy(z[k]) for k in z.files if k.startswith(prefix)})
+    return actor
 
 
-@functools.lru_cache(maxsize=None)
-def _golden():
-    z = np.load(GOLDEN)
-    configs = json.loads(str(z["trained/configs"]))
-    sd = {k[len("trained/net/"):]: torch.from_numpy(z[k]) for k in z.files if k.startswith("trained/net/")}
-    return configs, sd
-
-
-def _configs():
-    configs, _ = _golden()
-    out = [copy.deepcopy(configs[i]) for i in PICK]
-    assert [c["env"]["num_robots"] for c in out] == [3, 4, 5, 5, 5, 5]
-    assert [len(c["env"]["obstacles"]["r"]) for c in out] == [0, 0, 0, 2, 3, 4]
-    return out
-
-
-@functools.lru_cache(maxsize=None)
-def _pack(operands):
-    from distributional_rl_decision_and_control_amd.fused_mlp import MlpPack
-    from distributional_rl_decision_and_control_amd.policy.AC_IQN_model import AC_IQN_Policy
-    from distributional_rl_decision_and_control_amd.vec_trainer import DEFAULT_NET
-    pol = AC_IQN_Policy(**DEFAULT_NET, value_ranges_of_action=[[-1, 1], [-1, 1]], device="cuda", seed=100)
-    pol.actor.load_state_dict(_golden()[1])
-    return MlpPack(pol.actor, "actor", operands)
-
-
-def _zero_host_noise(monkeypatch):
-    from distributional_rl_decision_and_control_amd.envs.marinenav.vehicles import wamv
-    monkeypatch.setattr(wamv.Perception, "draw_candidate_noise", lambda self: (0.0, 0.0, 0.0, 0.0, 0.0))
-
-
-def _close(got, ref, scale=None, what=""):
-    got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
-    scale = np.abs(ref) if scale is None else np.asarray(scale, dtype=np.float64)
-    err = np.abs(got - ref) / np.maximum(scale, 1e-300)
-    print(f"{what}: max relative error {err.max():.2e}")
-    assert (np.abs(got - ref) <= 1e-12 * scale).all(), (what, got, ref)
+CASE = dataclasses.replace(wc.CASES["actor"], net=_trained_actor)
 
 
 # ------------------------------------------------------------------ loader
 def test_loader_initial_state_and_observations(monkeypatch):
     from distributional_rl_decision_and_control_amd import _abi
     from distributional_rl_decision_and_control_amd.policy.device_eval import DeviceEvaluator
-    _zero_host_noise(monkeypatch)
-    ev = DeviceEvaluator(_configs(), chunk=5)
+    dev.zero_host_noise(monkeypatch)
+    ev = DeviceEvaluator(dev.configs(False), chunk=5)
     assert len(ev.groups) == 1   # the shipped schedule's configs share their env-level parameters
     grp = ev.groups[0]
     b = grp.batch
@@ -112,59 +81,12 @@ def test_loader_initial_state_and_observations(monkeypatch):
 
 
 # ------------------------------------------------------------------ teacher-forced against evaluate_configs
-def _place(cfg, i, start, goal=None, theta=None, thrust=None):
-    rb = cfg["robots"]
-    rb["start"][i] = [float(start[0]), float(start[1])]
-    rb["goal"][i] = [float(v) for v in (goal if goal is not None else start)]
-    if theta is not None:
-        rb["init_theta"][i] = float(theta)
-    if thrust is not None:
-        rb["init_left_thrust"][i] = rb["init_right_thrust"][i] = float(thrust)
-    rb["init_velocity_r"][i] = [0.0, 0.0, 0.0]
-
-
-def _edited_configs():
-    """Every episode ends early and certainly. Returns (configs, the (config, robot) rows held at full thrust)."""
-    cfgs = _configs()
-    full = []
-    # 0 (3 robots): one on its goal, two facing each other 12 m apart at full thrust: a collision a few steps later
-    _place(cfgs[0], 0, (5, 5))
-    _place(cfgs[0], 1, (20, 30), goal=(50, 50), theta=0.0, thrust=1000.0)
-    _place(cfgs[0], 2, (32, 30), goal=(5, 50), theta=math.pi, thrust=1000.0)
-    full += [(0, 1), (0, 2)]
-    # 1 (4 robots): two robots 3 m apart (closer than their radii's sum): a collision at the first step
-    assert RSUM > 3.0
-    _place(cfgs[1], 0, (20, 20), goal=(50, 20))
-    _place(cfgs[1], 1, (23, 20), goal=(5, 20))
-    _place(cfgs[1], 2, (5, 50), goal=(50, 50))
-    _place(cfgs[1], 3, (50, 50), goal=(5, 50))
-    # 2 (5 robots): four on their goals, the fifth 3.5 m in front of its goal at full thrust: all reach their goals
-    for i, xy in enumerate(((5, 5), (50, 5), (5, 50), (50, 50))):
-        _place(cfgs[2], i, xy)
-    _place(cfgs[2], 4, (25, 25), goal=(28.5, 25), theta=0.0, thrust=1000.0)
-    full += [(2, 4)]
-    # 3 (5 robots, 2 buoys): one on its goal, two 3 m apart: a collision at the first step, after no goal step
-    _place(cfgs[3], 0, cfgs[3]["robots"]["start"][0])
-    s = cfgs[3]["robots"]["start"][1]
-    _place(cfgs[3], 2, (s[0] + 3.0, s[1]), goal=cfgs[3]["robots"]["goal"][2])
-    # 4 (5 robots, 3 buoys): as 2, on the config's own starts (the robots are placed clear of each other)
-    for i in range(4):
-        _place(cfgs[4], i, cfgs[4]["robots"]["start"][i])
-    s = cfgs[4]["robots"]["start"][4]
-    _place(cfgs[4], 4, s, goal=(s[0] + 3.5, s[1]), theta=0.0, thrust=1000.0)
-    full += [(4, 4)]
-    # 5 (5 robots, 4 buoys): two 3 m apart
-    s = cfgs[5]["robots"]["start"][0]
-    _place(cfgs[5], 1, (s[0], s[1] + 3.0), goal=cfgs[5]["robots"]["goal"][1])
-    return cfgs, full
-
-
 def test_teacher_forced_against_evaluate_configs(monkeypatch):
     from distributional_rl_decision_and_control_amd.agent import Agent
     from distributional_rl_decision_and_control_amd.policy.batched_eval import evaluate_configs
     from distributional_rl_decision_and_control_amd.policy.device_eval import DeviceEvaluator
-    _zero_host_noise(monkeypatch)
-    cfgs, full = _edited_configs()
+    dev.zero_host_noise(monkeypatch)
+    cfgs, full = dev.edited_configs()
     T, R = 64, 5
     ev = DeviceEvaluator(cfgs, chunk=5, gamma=GAMMA)
     assert len(ev.groups) == 1 and ev.groups[0].members == list(range(len(cfgs)))
@@ -180,14 +102,7 @@ def test_teacher_forced_against_evaluate_configs(monkeypatch):
     ref = evaluate_configs(agent, cfgs, policy=teacher)
     got = ev.run(actions=torch.from_numpy(table).cuda(), noise=ev.zero_noise(T), obs_noise=ev.zero_noise(),
                  episode_limit=1000)
-    print("host lengths", ref["lengths"], "successes", ref["successes"])
-    print("device lengths", got["lengths"], "outcomes", [o.tolist() for o in got["robot_outcomes"]])
-    assert got["lengths"] == ref["lengths"]
-    assert got["successes"] == ref["successes"]
-    for name in ("times", "energies"):
-        _close(got[name], ref[name], what=name)
-    # the return's terms change sign: the bar is relative to max(1, sum |term|); max(1, |return|) is no larger
-    _close(got["rewards"], ref["rewards"], scale=np.maximum(1.0, np.abs(ref["rewards"])), what="rewards")
+    dev.check_teacher_forced(got, ref)
     for name in ("observations", "actions", "trajectories", "relations"):
         assert [len(v) for v in got[name]] == ev.n_robots and all(h == [] for v in got[name] for h in v)
     # the inputs cover what they were built for (a condition on the inputs, not a tolerance)
@@ -202,103 +117,25 @@ def test_teacher_forced_against_evaluate_configs(monkeypatch):
 
 
 # ------------------------------------------------------------------ closed loop against the composed loop
-def _bookkeep(st, n_robots, R, reward, info, tl, tr, dt, N, pc, stepping, limit):
-    """trainer.py:286-303 for one step of every env in `stepping` (numpy, in place)."""
-    from distributional_rl_decision_and_control_amd import _abi
-    for e in np.nonzero(stepping)[0]:
-        if st["ended"][e]:
-            continue
-        collided = False
-        for i in range(n_robots[e]):
-            r = e * R + i
-            if st["deact"][r]:
-                continue
-            term = GAMMA ** int(st["length"][e]) * reward[r]
-            st["ret"][r] += term
-            st["abs"][r] += abs(term)
-            st["time"][r] += dt[r] * N[r]
-            st["energy"][r] += pc[r] * np.abs(tl[r]) * dt[r] * N[r] + pc[r] * np.abs(tr[r]) * dt[r] * N[r]
-            if info[r] in (_abi.INFO_COLLISION, _abi.INFO_REACH_GOAL):
-                st["deact"][r] = 1
-                st["outcome"][r] = 2 if info[r] == _abi.INFO_COLLISION else 1
-                collided |= info[r] == _abi.INFO_COLLISION
-        end = st["length"][e] >= limit or collided or bool(st["deact"][e * R:e * R + n_robots[e]].all())
-        st["length"][e] += 1
-        st["ended"][e] = end
-
-
-def _composed(ev, pack, limit, chunk, seed):
-    """The evaluation as single launches on the evaluator's own batch: actor_act + step at the Philox keys run()
-    uses, an env leaving at a window's start once the bookkeeping ended it and inside a window once the step's
-    env_done held it."""
-    from distributional_rl_decision_and_control_amd import _abi
-    from distributional_rl_decision_and_control_amd.fused_mlp import actor_act
-    grp = ev.groups[0]
-    b = grp.batch
-    E, R = b.n_envs, b.max_robots
-    NT = E * R
-    ev.observe(seed=seed)
-    n_robots = b.n_robots.cpu().numpy()
-    dt, N, pc = (t.cpu().numpy() for t in (grp.dt, grp.N, grp.pc))
-    st = dict(length=np.zeros(E, np.int64), ended=np.zeros(E, bool), deact=np.zeros(NT, np.uint8),
-              outcome=np.zeros(NT, np.uint8), ret=np.zeros(NT), time=np.zeros(NT), energy=np.zeros(NT),
-              abs=np.zeros(NT))
-    act64 = torch.zeros((NT, 2), dtype=torch.float64, device="cuda")
-    step = torch.zeros(1, dtype=torch.int64, device="cuda")
-    mask = None
-    for t in range(limit + 1):
-        if t % chunk == 0:
-            mask = torch.from_numpy((~st["ended"]).astype(np.uint8)).cuda()
-        step.fill_(t)
-        actor_act(pack, b.obs, act64, step, 1.0, 1.0, 1.0, 0.0, 0.0, 0)
-        b.step(act64, trainer_deactivate=True, seed=seed, counter=t, fast_noise=True, env_mask=mask)
-        rs = b.rs.cpu().numpy()
-        _bookkeep(st, n_robots, R, b.reward.cpu().numpy(), b.info.cpu().numpy(), rs[_abi.F_TL], rs[_abi.F_TR], dt, N,
-                  pc, mask.cpu().numpy() != 0, limit)
-        mask = mask * (b.env_done == 0).to(torch.uint8)
-    return st
-
-
 @pytest.mark.parametrize("operands", ["bf16", "f32"])
 def test_closed_loop_matches_single_launches(operands):
     from distributional_rl_decision_and_control_amd.policy.device_eval import DeviceEvaluator
     LIMIT, CHUNK, SEED = 22, 5, 17
-    pack = _pack(operands)
-    ev = DeviceEvaluator(_configs(), chunk=CHUNK, gamma=GAMMA)
-    got = ev.run(pack, seed=SEED, episode_limit=LIMIT)
-    assert ev.windows <= math.ceil((LIMIT + 1) / CHUNK) and ev.steps <= LIMIT + 1
-    again = ev.run(pack, seed=SEED, episode_limit=LIMIT)          # restored by copy: the same bits
-    nosync = ev.run(pack, seed=SEED, episode_limit=LIMIT, sync=False)
-    assert ev.windows == math.ceil((LIMIT + 1) / CHUNK) and ev.steps == LIMIT + 1
-    for other, what in ((again, "second run"), (nosync, "sync=False")):
-        assert other["lengths"] == got["lengths"] and other["successes"] == got["successes"], what
-        for name in ("rewards", "times", "energies"):
-            assert np.array(other[name]).tobytes() == np.array(got[name]).tobytes(), (what, name)
-        for name in ("robot_rewards", "robot_times", "robot_energies", "robot_outcomes"):
-            assert all(a.tobytes() == c.tobytes() for a, c in zip(other[name], got[name])), (what, name)
-    st = _composed(ev, pack, LIMIT, CHUNK, SEED)
-    R = ev.groups[0].batch.max_robots
+    pack = wc.pack(CASE, operands)
+    ev = DeviceEvaluator(dev.configs(False), chunk=CHUNK, gamma=GAMMA)
+    got = dev.run_thrice(ev, pack, LIMIT, CHUNK, seed=SEED)
+    ev.observe(seed=SEED)
+    st, _ = dev.composed(ev, 0, CASE, pack, LIMIT, CHUNK, SEED, 0)
     print(operands, "lengths", got["lengths"], "outcomes", [o.tolist() for o in got["robot_outcomes"]])
-    assert got["lengths"] == st["length"].tolist()
     assert LIMIT + 1 in got["lengths"], "at least one env times out at 23 steps"
-    assert st["ended"].all()
-    for c, k in enumerate(ev.n_robots):
-        sl = slice(c * R, c * R + k)
-        assert got["robot_outcomes"][c].tolist() == st["outcome"][sl].tolist()
-        assert got["successes"][c] == bool((st["outcome"][sl] == 1).all())
-        _close(got["robot_times"][c], st["time"][sl], what=f"config {c} times")
-        _close(got["robot_energies"][c], st["energy"][sl], what=f"config {c} energies")
-        _close(got["robot_rewards"][c], st["ret"][sl], scale=np.maximum(1.0, st["abs"][sl]), what=f"config {c} returns")
-        assert got["rewards"][c] == np.mean(got["robot_rewards"][c])
-        assert got["times"][c] == np.mean(got["robot_times"][c])
-        assert got["energies"][c] == np.mean(got["robot_energies"][c])
+    dev.check_group(ev, got, 0, st)
 
 
 # ------------------------------------------------------------------ VecTrainer.evaluate
 def test_vec_trainer_evaluate():
     from distributional_rl_decision_and_control_amd.policy.device_eval import DeviceEvaluator
     from distributional_rl_decision_and_control_amd.vec_trainer import VecTrainer
-    cfgs = _configs()
+    cfgs = dev.configs(False)
     tr = VecTrainer(n_envs=37, batch_size=64, buffer_size=4096, graphs=False, seed=3, gamma=GAMMA)
     for _ in range(2):
         tr.iteration()

@@ -14,35 +14,19 @@ configs tests/test_device_eval_gpu.py uses (tests/golden/eval60_ref.npz: 3, 4 an
 Tolerances as in tests/test_device_eval_gpu.py: integers and flags exact; f64 sums 1e-12 relative (pow and summation
 order over at most 64 terms of 2.3e-16 each), the return relative to max(1, sum |term|). The weights are a seeded
 DQN_Policy (Agent(seed=100, agent_type="DQN"))."""
-import copy
+import dataclasses
 import functools
-import json
-import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
+import device_eval_cases as dev
+import window_cases as wc
+from device_eval_cases import GAMMA
+from window_cases import A
+
 pytestmark = pytest.mark.gpu
-
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "eval60_ref.npz")
-PICK = (0, 10, 20, 30, 40, 55)   # 3, 4, 5 robots without buoys; 5 robots with 2, 3 and 4 buoys
-GAMMA = 0.99
-RSUM = 5.59                      # two WAM-V radii (2 * 0.5 * sqrt(5^2 + 2.5^2)), metres
-A = 25
-
-
-@functools.lru_cache(maxsize=None)
-def _all_configs():
-    return json.loads(str(np.load(GOLDEN)["trained/configs"]))
-
-
-def _configs():
-    out = [copy.deepcopy(_all_configs()[i]) for i in PICK]
-    assert [c["env"]["num_robots"] for c in out] == [3, 4, 5, 5, 5, 5]
-    assert [len(c["env"]["obstacles"]["r"]) for c in out] == [0, 0, 0, 2, 3, 4]
-    return out
 
 
 @functools.lru_cache(maxsize=None)
@@ -51,192 +35,44 @@ def _agent():
     return Agent(seed=100, agent_type="DQN")
 
 
-@functools.lru_cache(maxsize=None)
-def _pack(operands):
-    from distributional_rl_decision_and_control_amd.fused_dqn import DqnPack
-    return DqnPack(_agent().policy_local, operands)
-
-
-def _zero_host_noise(monkeypatch):
-    from distributional_rl_decision_and_control_amd.envs.marinenav.vehicles import wamv
-    monkeypatch.setattr(wamv.Perception, "draw_candidate_noise", lambda self: (0.0, 0.0, 0.0, 0.0, 0.0))
-
-
-def _close(got, ref, scale=None, what=""):
-    got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
-    scale = np.abs(ref) if scale is None else np.asarray(scale, dtype=np.float64)
-    err = np.abs(got - ref) / np.maximum(scale, 1e-300)
-    print(f"{what}: max relative error {err.max():.2e}")
-    assert (np.abs(got - ref) <= 1e-12 * scale).all(), (what, got, ref)
+CASE = dataclasses.replace(wc.CASES["dqn"], net=lambda: _agent().policy_local)
 
 
 # ------------------------------------------------------------------ closed loop against the composed loop
-def _bookkeep(st, n_robots, R, reward, info, tl, tr, dt, N, pc, stepping, limit):
-    """trainer.py:286-303 for one step of every env in `stepping` (numpy, in place)."""
-    from distributional_rl_decision_and_control_amd import _abi
-    for e in np.nonzero(stepping)[0]:
-        if st["ended"][e]:
-            continue
-        collided = False
-        for i in range(n_robots[e]):
-            r = e * R + i
-            if st["deact"][r]:
-                continue
-            term = GAMMA ** int(st["length"][e]) * reward[r]
-            st["ret"][r] += term
-            st["abs"][r] += abs(term)
-            st["time"][r] += dt[r] * N[r]
-            st["energy"][r] += pc[r] * np.abs(tl[r]) * dt[r] * N[r] + pc[r] * np.abs(tr[r]) * dt[r] * N[r]
-            if info[r] in (_abi.INFO_COLLISION, _abi.INFO_REACH_GOAL):
-                st["deact"][r] = 1
-                st["outcome"][r] = 2 if info[r] == _abi.INFO_COLLISION else 1
-                collided |= info[r] == _abi.INFO_COLLISION
-        end = st["length"][e] >= limit or collided or bool(st["deact"][e * R:e * R + n_robots[e]].all())
-        st["length"][e] += 1
-        st["ended"][e] = end
-
-
-def _composed(ev, pack, limit, chunk, seed):
-    """The evaluation as single launches on the evaluator's own batch: greedy dqn_act + the discrete step at the
-    Philox keys run() uses, an env leaving at a window's start once the bookkeeping ended it and inside a window
-    once the step's env_done held it. Also returns every action index the loop took."""
-    from distributional_rl_decision_and_control_amd import _abi
-    from distributional_rl_decision_and_control_amd.fused_dqn import dqn_act
-    grp = ev.groups[0]
-    b = grp.batch
-    E, R = b.n_envs, b.max_robots
-    NT = E * R
-    ev.observe(seed=seed)
-    n_robots = b.n_robots.cpu().numpy()
-    dt, N, pc = (t.cpu().numpy() for t in (grp.dt, grp.N, grp.pc))
-    st = dict(length=np.zeros(E, np.int64), ended=np.zeros(E, bool), deact=np.zeros(NT, np.uint8),
-              outcome=np.zeros(NT, np.uint8), ret=np.zeros(NT), time=np.zeros(NT), energy=np.zeros(NT),
-              abs=np.zeros(NT))
-    act64 = torch.zeros((NT, 2), dtype=torch.float64, device="cuda")
-    step = torch.zeros(1, dtype=torch.int64, device="cuda")
-    mask = None
-    taken = []
-    for t in range(limit + 1):
-        if t % chunk == 0:
-            mask = torch.from_numpy((~st["ended"]).astype(np.uint8)).cuda()
-        step.fill_(t)
-        dqn_act(pack, b.obs, act64, step, 1.0, 1.0, 1.0, 0.0, 0.0, 0)
-        taken.append(act64[:, 0].cpu().numpy().copy())
-        b.step(act64, is_continuous=False, trainer_deactivate=True, seed=seed, counter=t, fast_noise=True,
-               env_mask=mask)
-        rs = b.rs.cpu().numpy()
-        _bookkeep(st, n_robots, R, b.reward.cpu().numpy(), b.info.cpu().numpy(), rs[_abi.F_TL], rs[_abi.F_TR], dt, N,
-                  pc, mask.cpu().numpy() != 0, limit)
-        mask = mask * (b.env_done == 0).to(torch.uint8)
-    return st, np.stack(taken)
-
-
 @pytest.mark.parametrize("operands", ["bf16", "f32"])
 def test_closed_loop_matches_single_launches(operands):
     from distributional_rl_decision_and_control_amd.policy.device_eval import DeviceEvaluator
     LIMIT, CHUNK, SEED = 22, 5, 17
-    pack = _pack(operands)
-    ev = DeviceEvaluator(_configs(), chunk=CHUNK, gamma=GAMMA)
-    got = ev.run(pack, seed=SEED, episode_limit=LIMIT)
-    assert ev.windows <= math.ceil((LIMIT + 1) / CHUNK) and ev.steps <= LIMIT + 1
-    again = ev.run(pack, seed=SEED, episode_limit=LIMIT)          # restored by copy: the same bits
-    nosync = ev.run(pack, seed=SEED, episode_limit=LIMIT, sync=False)
-    assert ev.windows == math.ceil((LIMIT + 1) / CHUNK) and ev.steps == LIMIT + 1
-    for other, what in ((again, "second run"), (nosync, "sync=False")):
-        assert other["lengths"] == got["lengths"] and other["successes"] == got["successes"], what
-        for name in ("rewards", "times", "energies"):
-            assert np.array(other[name]).tobytes() == np.array(got[name]).tobytes(), (what, name)
-        for name in ("robot_rewards", "robot_times", "robot_energies", "robot_outcomes"):
-            assert all(a.tobytes() == c.tobytes() for a, c in zip(other[name], got[name])), (what, name)
-    st, taken = _composed(ev, pack, LIMIT, CHUNK, SEED)
-    R = ev.groups[0].batch.max_robots
+    pack = wc.pack(CASE, operands)
+    ev = DeviceEvaluator(dev.configs(False), chunk=CHUNK, gamma=GAMMA)
+    got = dev.run_thrice(ev, pack, LIMIT, CHUNK, seed=SEED)
+    ev.observe(seed=SEED)
+    st, taken = dev.composed(ev, 0, CASE, pack, LIMIT, CHUNK, SEED, 0)
+    taken = taken[..., 0]   # every action index the loop took
     print(operands, "lengths", got["lengths"], "outcomes", [o.tolist() for o in got["robot_outcomes"]])
-    assert got["lengths"] == st["length"].tolist()
-    assert st["ended"].all()
     # the inputs cover what they were built for: the windows chain, and the greedy policy is not one constant index
     assert max(got["lengths"]) > CHUNK, "some episode must run past the first window"
     assert ((taken >= 0) & (taken < A) & (taken == np.round(taken))).all() and len(np.unique(taken)) >= 3
-    for c, k in enumerate(ev.n_robots):
-        sl = slice(c * R, c * R + k)
-        assert got["robot_outcomes"][c].tolist() == st["outcome"][sl].tolist()
-        assert got["successes"][c] == bool((st["outcome"][sl] == 1).all())
-        _close(got["robot_times"][c], st["time"][sl], what=f"config {c} times")
-        _close(got["robot_energies"][c], st["energy"][sl], what=f"config {c} energies")
-        _close(got["robot_rewards"][c], st["ret"][sl], scale=np.maximum(1.0, st["abs"][sl]), what=f"config {c} returns")
-        assert got["rewards"][c] == np.mean(got["robot_rewards"][c])
-        assert got["times"][c] == np.mean(got["robot_times"][c])
-        assert got["energies"][c] == np.mean(got["robot_energies"][c])
+    dev.check_group(ev, got, 0, st)
 
 
 def test_pack_and_flag_must_match():
     from distributional_rl_decision_and_control_amd.policy.device_eval import DeviceEvaluator
-    ev = DeviceEvaluator(_configs()[:1], chunk=5, gamma=GAMMA)
+    ev = DeviceEvaluator(dev.configs(False)[:1], chunk=5, gamma=GAMMA)
     with pytest.raises(ValueError, match="is_continuous"):
-        ev.run(_pack("bf16"), is_continuous=True)
-    from distributional_rl_decision_and_control_amd.fused_mlp import MlpPack
-    from distributional_rl_decision_and_control_amd.policy.AC_IQN_model import AC_IQN_Policy
-    from distributional_rl_decision_and_control_amd.vec_trainer import DEFAULT_NET
-    pol = AC_IQN_Policy(**DEFAULT_NET, value_ranges_of_action=[[-1, 1], [-1, 1]], device="cuda", seed=100)
+        ev.run(wc.pack(CASE, "bf16"), is_continuous=True)
     with pytest.raises(ValueError, match="is_continuous"):
-        ev.run(MlpPack(pol.actor, "actor"), is_continuous=False)
+        ev.run(wc.pack(wc.CASES["actor"]), is_continuous=False)
 
 
 # ------------------------------------------------------------------ teacher-forced against evaluate_configs
-def _place(cfg, i, start, goal=None, theta=None, thrust=None):
-    rb = cfg["robots"]
-    rb["start"][i] = [float(start[0]), float(start[1])]
-    rb["goal"][i] = [float(v) for v in (goal if goal is not None else start)]
-    if theta is not None:
-        rb["init_theta"][i] = float(theta)
-    if thrust is not None:
-        rb["init_left_thrust"][i] = rb["init_right_thrust"][i] = float(thrust)
-    rb["init_velocity_r"][i] = [0.0, 0.0, 0.0]
-
-
-def _edited_configs():
-    """Every episode ends early and certainly (the edits of tests/test_device_eval_gpu.py). Returns (configs, the
-    (config, robot) rows held at full thrust)."""
-    cfgs = _configs()
-    full = []
-    # 0 (3 robots): one on its goal, two facing each other 12 m apart at full thrust: a collision a few steps later
-    _place(cfgs[0], 0, (5, 5))
-    _place(cfgs[0], 1, (20, 30), goal=(50, 50), theta=0.0, thrust=1000.0)
-    _place(cfgs[0], 2, (32, 30), goal=(5, 50), theta=math.pi, thrust=1000.0)
-    full += [(0, 1), (0, 2)]
-    # 1 (4 robots): two robots 3 m apart (closer than their radii's sum): a collision at the first step
-    assert RSUM > 3.0
-    _place(cfgs[1], 0, (20, 20), goal=(50, 20))
-    _place(cfgs[1], 1, (23, 20), goal=(5, 20))
-    _place(cfgs[1], 2, (5, 50), goal=(50, 50))
-    _place(cfgs[1], 3, (50, 50), goal=(5, 50))
-    # 2 (5 robots): four on their goals, the fifth 3.5 m in front of its goal at full thrust: all reach their goals
-    for i, xy in enumerate(((5, 5), (50, 5), (5, 50), (50, 50))):
-        _place(cfgs[2], i, xy)
-    _place(cfgs[2], 4, (25, 25), goal=(28.5, 25), theta=0.0, thrust=1000.0)
-    full += [(2, 4)]
-    # 3 (5 robots, 2 buoys): one on its goal, two 3 m apart: a collision at the first step
-    _place(cfgs[3], 0, cfgs[3]["robots"]["start"][0])
-    s = cfgs[3]["robots"]["start"][1]
-    _place(cfgs[3], 2, (s[0] + 3.0, s[1]), goal=cfgs[3]["robots"]["goal"][2])
-    # 4 (5 robots, 3 buoys): as 2, on the config's own starts (the robots are placed clear of each other)
-    for i in range(4):
-        _place(cfgs[4], i, cfgs[4]["robots"]["start"][i])
-    s = cfgs[4]["robots"]["start"][4]
-    _place(cfgs[4], 4, s, goal=(s[0] + 3.5, s[1]), theta=0.0, thrust=1000.0)
-    full += [(4, 4)]
-    # 5 (5 robots, 4 buoys): two 3 m apart
-    s = cfgs[5]["robots"]["start"][0]
-    _place(cfgs[5], 1, (s[0], s[1] + 3.0), goal=cfgs[5]["robots"]["goal"][1])
-    return cfgs, full
-
-
 def test_teacher_forced_index_table_against_evaluate_configs(monkeypatch):
     """Column 0 of the table is the action index (column 1 is ignored by the discrete step): the host loop is
     given the same indices. Index 24 adds the largest thrust change to both thrusters: full thrust stays full."""
     from distributional_rl_decision_and_control_amd.policy.batched_eval import evaluate_configs
     from distributional_rl_decision_and_control_amd.policy.device_eval import DeviceEvaluator
-    _zero_host_noise(monkeypatch)
-    cfgs, full = _edited_configs()
+    dev.zero_host_noise(monkeypatch)
+    cfgs, full = dev.edited_configs()
     T, R = 64, 5
     ev = DeviceEvaluator(cfgs, chunk=5, gamma=GAMMA)
     assert len(ev.groups) == 1 and ev.groups[0].members == list(range(len(cfgs)))
@@ -253,14 +89,7 @@ def test_teacher_forced_index_table_against_evaluate_configs(monkeypatch):
     ref = evaluate_configs(agent, cfgs, policy=teacher)
     got = ev.run(actions=torch.from_numpy(table).cuda(), noise=ev.zero_noise(T), obs_noise=ev.zero_noise(),
                  episode_limit=1000, is_continuous=False)
-    print("host lengths", ref["lengths"], "successes", ref["successes"])
-    print("device lengths", got["lengths"], "outcomes", [o.tolist() for o in got["robot_outcomes"]])
-    assert got["lengths"] == ref["lengths"]
-    assert got["successes"] == ref["successes"]
-    for name in ("times", "energies"):
-        _close(got[name], ref[name], what=name)
-    # the return's terms change sign: the bar is relative to max(1, sum |term|); max(1, |return|) is no larger
-    _close(got["rewards"], ref["rewards"], scale=np.maximum(1.0, np.abs(ref["rewards"])), what="rewards")
+    dev.check_teacher_forced(got, ref)
     # the inputs cover what they were built for (a condition on the inputs, not a tolerance)
     assert max(ref["lengths"]) < T
     out = got["robot_outcomes"]
@@ -277,7 +106,7 @@ def test_teacher_forced_index_table_against_evaluate_configs(monkeypatch):
 def test_vec_trainer_policy_pack_and_device_evaluator():
     from distributional_rl_decision_and_control_amd.policy.device_eval import DeviceEvaluator
     from distributional_rl_decision_and_control_amd.vec_trainer import VecTrainer
-    cfgs = _configs()
+    cfgs = dev.configs(False)
     tr = VecTrainer(n_envs=37, agent_type="DQN", batch_size=64, buffer_size=4096, graphs=False, seed=3, gamma=GAMMA)
     for _ in range(2):
         tr.iteration()
@@ -307,28 +136,4 @@ def test_vec_trainer_policy_pack_and_device_evaluator():
 
 # ------------------------------------------------------------------ Trainer
 def test_trainer_device_eval_dqn(tmp_path, monkeypatch):
-    from distributional_rl_decision_and_control_amd.agent import Agent
-    from distributional_rl_decision_and_control_amd.envs.marinenav.env import MarineNavEnv3
-    from distributional_rl_decision_and_control_amd.policy import batched_eval
-    from distributional_rl_decision_and_control_amd.policy.trainer import Trainer
-
-    def refuse(*a, **k):
-        raise AssertionError("evaluate_configs was called: the evaluation left the device")
-    monkeypatch.setattr(batched_eval, "evaluate_configs", refuse)
-    E = 64
-    sched = {"timesteps": [0], "num_robots": [3], "num_cores": [0], "num_obstacles": [2], "min_start_goal_dis": [30.0],
-             "vectorized": {"n_envs": E, "batch_size": 64, "buffer_size": 8192, "graphs": False, "device_eval": True}}
-    eval_sched = {"num_episodes": [1], "num_robots": [3], "num_cores": [0], "num_obstacles": [2],
-                  "min_start_goal_dis": [30.0]}
-    torch.manual_seed(0)
-    trainer = Trainer(MarineNavEnv3(seed=1, schedule=sched), MarineNavEnv3(seed=253, is_eval_env=True), eval_sched,
-                      Agent(seed=100, agent_type="DQN"), learning_starts=100)
-    vt = trainer.learn(total_timesteps=E * 8, eval_freq=E * 4, eval_log_path=str(tmp_path), verbose=False)
-    assert vt is trainer.vec_trainer and vt.agent_type == "DQN"
-    n = len(trainer.eval_timesteps)
-    assert n >= 2 and trainer.eval_timesteps[-1] == E * 8
-    assert len(trainer.eval_rewards) == n and all(np.isfinite(r).all() for r in trainer.eval_rewards)
-    assert all(isinstance(s, bool) for s in trainer.eval_successes[-1])
-    assert all(t > 0 for t in trainer.eval_times[-1])
-    ev = np.load(os.path.join(str(tmp_path), "evaluations.npz"), allow_pickle=True)   # our own file
-    assert list(ev["timesteps"]) == trainer.eval_timesteps and ev["rewards"].shape == (n, 1)
+    dev.check_trainer_device_eval(tmp_path, monkeypatch, "DQN", 8)

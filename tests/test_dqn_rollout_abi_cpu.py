@@ -6,47 +6,12 @@ import ctypes as C
 
 import pytest
 
-P = 0x1000   # a made-up, 16-byte aligned address
-NAMES = ("asvrl_dqn_rollout", "asvrl_dqn_rollout_ar")
-IMAGES = ("enc_frag", "b_enc", "w1_frag", "w2_frag", "b1", "b2", "wout", "bout")
+import rollout_abi_cases
+from rollout_abi_cases import P
 
-
-def _args(**over):
-    """Arguments that pass every check of both calls up to the launch (nothing is launched: every test overrides
-    one of them into a refusal). Overrides are obj__field=value; w__<image> sets a trunk image."""
-    from distributional_rl_decision_and_control_amd import _abi
-    from distributional_rl_decision_and_control_amd.device_env import reset_cfg
-    a = dict(params=_abi.params_from(), state=_abi.AsvEnvState(), ctl=_abi.AsvStepCtl(), out=_abi.AsvStepOut(),
-             ro=_abi.AsvRollout(), pi=_abi.AsvDqnPolicy(), ar=_abi.AsvAutoReset())
-    st = a["state"]
-    st.n_envs, st.max_robots, st.max_obs, st.max_cores = 4, 5, 4, 2
-    for n in ("rs", "rflags", "n_robots", "n_obs", "n_cores", "ep_ts", "obstacles", "cores"):
-        setattr(st, n, P)
-    ctl = a["ctl"]
-    ctl.is_continuous, ctl.do_dynamics, ctl.trainer_deactivate, ctl.noise_mode = 0, 1, 1, 2
-    for n in ("obs", "obj_cnt", "reward", "done", "info", "env_done"):
-        setattr(a["out"], n, P)
-    a["ro"].n_steps = 3
-    pi = a["pi"]
-    pi.obs_in = P
-    for n in IMAGES:
-        setattr(pi.w.trunk, n, P)
-    pi.w.head_frag, pi.w.n_actions = P, 25
-    a["ar"].cfg = reset_cfg(5, 4, 2)
-    for k, v in over.items():
-        obj, field = k.split("__")
-        setattr(a["pi"].w.trunk if obj == "w" else a[obj], field, v)
-    return a
-
-
-def _call(L, name, a, null=()):
-    order = ["params", "state", "ctl", "out", "ro", "pi"] + (["ar"] if name.endswith("_ar") else [])
-    return getattr(L, name)(*[None if k in null else C.byref(a[k]) for k in order], None, None)
-
-
-def _refused(L, name, text, null=(), **over):
-    assert _call(L, name, _args(**over), null) != 0, (name, text)
-    assert L.asvrl_last_error().decode() == f"{name}: {text}"
+RO = rollout_abi_cases.Rollout("dqn")
+NAMES, IMAGES = RO.names, RO.images
+_refused = RO.refused
 
 
 @pytest.mark.parametrize("ops", ["bf16", "f32"])
@@ -72,14 +37,9 @@ def test_refusals_of_both_entry_points(name, ops):
     _refused(L, name, "ro->actions must be null (the policy supplies the actions)", ro__actions=P)
     for img in IMAGES:
         _refused(L, name, "null DQN image", **{"w__" + img: None})
-    a = _args()
-    a["pi"].w.head_frag = None
-    assert _call(L, name, a) != 0 and L.asvrl_last_error().decode() == f"{name}: null pi->w.head_frag"
+    _refused(L, name, "null pi->w.head_frag", dw__head_frag=None)
     for n_actions in (1, 33, 0, -3):
-        a = _args()
-        a["pi"].w.n_actions = n_actions
-        assert _call(L, name, a) != 0
-        assert L.asvrl_last_error().decode() == f"{name}: pi->w.n_actions must be in 2..32", n_actions
+        _refused(L, name, "pi->w.n_actions must be in 2..32", dw__n_actions=n_actions)
     _refused(L, name, "observation rows must be 16-byte aligned", pi__obs_in=P + 4)
     _refused(L, name, "observation rows must be 16-byte aligned", out__obs=P + 8)
     # the rollout's own members, under the new call's name
@@ -117,14 +77,5 @@ def test_auto_reset_refusals(ops):
 def test_the_actor_calls_keep_refusing_a_discrete_env():
     """The dispatch is explicit: the Actor's entry points still want is_continuous = 1."""
     from distributional_rl_decision_and_control_amd import _abi
-    L = _abi.lib()
-    a = _args()
-    pol = _abi.AsvPolicy()
-    pol.obs_in = P
-    for n in IMAGES:
-        setattr(pol.w, n, P)
-    rc = L.asvrl_policy_rollout(C.byref(a["params"]), C.byref(a["state"]), C.byref(a["ctl"]), C.byref(a["out"]),
-                                C.byref(a["ro"]), C.byref(pol), None, None)
-    assert rc != 0
-    assert L.asvrl_last_error().decode() == ("asvrl_policy_rollout: is_continuous must be 1 (the Actor is the "
-                                             "continuous agent)")
+    rollout_abi_cases.Rollout("actor").refused(_abi.lib(), "asvrl_policy_rollout", "is_continuous must be 1 (the Actor "
+                                               "is the continuous agent)", ctl__is_continuous=0)

@@ -6,48 +6,12 @@ import ctypes as C
 
 import pytest
 
-P = 0x1000   # a made-up, 16-byte aligned address
-NAMES = ("asvrl_iqn_rollout", "asvrl_iqn_rollout_ar")
-IMAGES = ("wc_frag", "w1_frag", "w2_frag", "bc", "b1", "b2", "self_w", "self_b", "obj_w", "obj_b")
+import rollout_abi_cases
+from rollout_abi_cases import P
 
-
-def _args(**over):
-    """Arguments that pass every check of both rollout calls up to the launch (nothing is launched: every test
-    overrides one of them into a refusal). Overrides are obj__field=value; w__<image> sets a trunk image or an
-    encoder pointer, hd__<name> a member of the head."""
-    from distributional_rl_decision_and_control_amd import _abi
-    from distributional_rl_decision_and_control_amd.device_env import reset_cfg
-    a = dict(params=_abi.params_from(), state=_abi.AsvEnvState(), ctl=_abi.AsvStepCtl(), out=_abi.AsvStepOut(),
-             ro=_abi.AsvRollout(), pi=_abi.AsvIqnPolicy(), ar=_abi.AsvAutoReset())
-    st = a["state"]
-    st.n_envs, st.max_robots, st.max_obs, st.max_cores = 4, 5, 4, 2
-    for n in ("rs", "rflags", "n_robots", "n_obs", "n_cores", "ep_ts", "obstacles", "cores"):
-        setattr(st, n, P)
-    ctl = a["ctl"]
-    ctl.is_continuous, ctl.do_dynamics, ctl.trainer_deactivate, ctl.noise_mode = 0, 1, 1, 2
-    for n in ("obs", "obj_cnt", "reward", "done", "info", "env_done"):
-        setattr(a["out"], n, P)
-    a["ro"].n_steps = 3
-    pi = a["pi"]
-    pi.obs_in, pi.cvar = P, 1.0
-    for n in IMAGES:
-        setattr(pi.w, n, P)
-    pi.head.wo_frag, pi.head.bo, pi.head.n_actions = P, P, 9
-    a["ar"].cfg = reset_cfg(5, 4, 2)
-    for k, v in over.items():
-        obj, field = k.split("__")
-        setattr(a["pi"].w if obj == "w" else (a["pi"].head if obj == "hd" else a[obj]), field, v)
-    return a
-
-
-def _call(L, name, a, null=()):
-    order = ["params", "state", "ctl", "out", "ro", "pi"] + (["ar"] if name.endswith("_ar") else [])
-    return getattr(L, name)(*[None if k in null else C.byref(a[k]) for k in order], None, None)
-
-
-def _refused(L, name, text, null=(), **over):
-    assert _call(L, name, _args(**over), null) != 0, (name, text)
-    assert L.asvrl_last_error().decode() == f"{name}: {text}"
+RO = rollout_abi_cases.Rollout("iqn")
+NAMES, IMAGES = RO.names, RO.images
+_refused = RO.refused
 
 
 @pytest.mark.parametrize("ops", ["bf16", "f32"])
@@ -125,30 +89,8 @@ def test_auto_reset_refusals(ops):
     _refused(L, name, "observation rows must be 16-byte aligned", ar__obs_prev=P + 4)
 
 
-def _act_args(**over):
-    """Arguments of asvrl_iqn_act_ex that pass every check (B = 0 would return before the launch; the tests
-    override one member into a refusal, so nothing is launched)."""
-    from distributional_rl_decision_and_control_amd import _abi
-    a = dict(w=_abi.AsvCriticWeights(), hd=_abi.AsvIqnHead(), io=_abi.AsvIqnIO(), ex=_abi.AsvIqnActEx())
-    for n in IMAGES:
-        setattr(a["w"], n, P)
-    a["hd"].wo_frag, a["hd"].bo, a["hd"].n_actions = P, P, 9
-    io = a["io"]
-    io.obs, io.ld_obs, io.B, io.N, io.act_out, io.ld_act = P, 40, 185, 32, P, 2
-    io.eps_steps_per_count, io.eps_total, io.eps_fraction = 1.0, 1.0, 1.0
-    ex = a["ex"]
-    ex.cvar, ex.robots_per_env = 1.0, 5
-    for k, v in over.items():
-        obj, field = k.split("__")
-        setattr(a[obj], field, v)
-    return a
-
-
-def _act_refused(L, text, null=(), **over):
-    a = _act_args(**over)
-    rc = L.asvrl_iqn_act_ex(*[None if k in null else C.byref(a[k]) for k in ("w", "hd", "io", "ex")], None)
-    assert rc != 0, text
-    assert L.asvrl_last_error().decode() == text
+ACT = rollout_abi_cases.WindowAct("iqn")
+_act_refused = ACT.refused
 
 
 @pytest.mark.parametrize("ops", ["bf16", "f32"])
@@ -184,6 +126,4 @@ def test_the_existing_act_call_is_unchanged(ops):
     for over, text in ((dict(io__N=16, io__B=184), "asvrl_iqn_act: K = 32 quantile samples per state"),
                        (dict(io__act_out=None), "asvrl_iqn_act: needs act_out, ld_act and the epsilon schedule"),
                        (dict(hd__n_actions=0), "asvrl_iqn: bad head")):
-        a = _act_args(**over)
-        assert L.asvrl_iqn_act(C.byref(a["w"]), C.byref(a["hd"]), C.byref(a["io"]), None) != 0
-        assert L.asvrl_last_error().decode() == text
+        ACT.plain_refused(L, text, **over)

@@ -6,192 +6,40 @@ with the auto-reset, reset_observe on env_done & mask at (RC + t, OC + t). Every
 among them; obs_prev, pushed and resets with the auto-reset), the steps every env took and every final array are
 compared with atol = rtol = 0 (the stats' return sum, an atomic sum, within 1e-12 as in the predecessors' tests).
 E = 37 envs: at 5 robots 185 act tiles, a partial last 16-wave workgroup. The weights are a seeded IQN_Policy."""
-import functools
+import dataclasses
 
 import numpy as np
 import pytest
 import torch
 
+import window_cases as wc
+from window_cases import EPS_HALF, EPS_ZERO, POLICY_SEED
+
 pytestmark = pytest.mark.gpu
 
 E = 37
-A = 25
-GAMMA = 0.99
 KMAX = 13
-STEP0 = 7          # the policy's step counter at the window's start
-POLICY_SEED = 4242
-C0, RC, OC = 1, 0x40000000, 0x80000000
-RECORDS = ("reward", "done", "info", "env_done", "obs", "obj_cnt", "rs", "actions")
-AR_RECORDS = RECORDS + ("obs_prev",)
-FINALS = ("rs", "rflags", "n_robots", "n_obs", "n_cores", "ep_ts", "obstacles", "cores", "obs", "obs64", "obj_cnt",
-          "reward", "done", "info", "env_done")   # + stats
-EPS_HALF = (1.0, 1.0, 1.0, 0.5, 0.5)    # past the exploration fraction from step 1 on: epsilon = 0.5
-EPS_ZERO = (1.0, 1.0, 1.0, 0.0, 0.0)    # greedy
 SHAPES = [(1, 0, 0), (5, 4, 2)]
 
 
-def _same(got, ref, what):
-    torch.testing.assert_close(got, ref, rtol=0, atol=0, equal_nan=True, msg=lambda m: f"{what}: {m}")
+
+def _count_greedy(extra, case, b, pack, act64, step, on_r, eps, options):
+    """Once a round at epsilon 0.5: the same rows, step and taus at epsilon 0 give the greedy action; counts the acting
+    rows whose action is that arg-max of the act pass's own action values."""
+    if eps is EPS_HALF:
+        greedy64 = torch.zeros_like(act64)
+        case.act(pack, b.obs, greedy64, step, EPS_ZERO, POLICY_SEED, **options)
+        extra["greedy_rows"] = extra.get("greedy_rows", 0) + int((act64[on_r, 0] == greedy64[on_r, 0]).sum())
+        extra["acting_rows"] = extra.get("acting_rows", 0) + int(on_r.sum())
 
 
-@functools.lru_cache(maxsize=None)
-def _net():
-    from distributional_rl_decision_and_control_amd.policy.IQN_model import IQN_Policy
-    from distributional_rl_decision_and_control_amd.vec_trainer import DEFAULT_NET
-    return IQN_Policy(**DEFAULT_NET, action_size=A, device="cuda", seed=100).to("cuda")
+CASE = dataclasses.replace(wc.CASES["iqn"], n_envs=E, kmax=KMAX, hook=_count_greedy)
 
-
-@functools.lru_cache(maxsize=None)
-def _pack(operands="bf16"):
-    """The seeded IQN_Policy's packed images."""
-    from distributional_rl_decision_and_control_amd.fused_iqn import IqnPack
-    return IqnPack(_net(), operands)
-
-
-def _cfg(R, O, C):
-    from distributional_rl_decision_and_control_amd.device_env import reset_cfg
-    return reset_cfg(R, O, C, 20.0, width=55.0, height=55.0)
-
-
-def _batch(R, O, C, fast=True, ending=False, robot_params=False):
-    """A device-reset batch with its reset observation in b.obs; the same call gives the same batch. ending: every
-    env ends inside a 13-step window at a step that depends on the env (episode_limit 5, ep_ts preset to e % 9)."""
-    from distributional_rl_decision_and_control_amd import _abi
-    from distributional_rl_decision_and_control_amd.device_env import DeviceEnvBatch
-    b = DeviceEnvBatch(E, R, O, C, obs64=True, params=_abi.params_from(episode_limit=5) if ending else None)
-    if robot_params:
-        b.set_robot_params([b.params] * (E * R))
-    b.reset(_cfg(R, O, C), seed=11)
-    b.step(None, do_dynamics=False, seed=11, counter=0, fast_noise=fast)
-    if ending:
-        b.ep_ts.copy_(torch.arange(E, dtype=torch.int32, device="cuda") % 9)
-    return b
-
-
-def _finals(b):
-    return {k: getattr(b, k).clone() for k in FINALS + ("stats",)}
-
-
-def _specs(b):
-    spec = b._record_specs()
-    NT = b.n_envs * b.max_robots
-    spec["actions"] = ((NT, 2), torch.float64, 0)
-    spec["obs_prev"] = ((NT, 40), torch.float32, 0)
-    return spec
-
-
-def _loop(b, pack, K, eps, cfg=None, hold=False, launch=None, env_mask=None, fast=True, two_launch=False, cvar=1.0,
-          step0=STEP0, c0=C0):
-    """The composed reference: K rounds of iqn_act on b.obs (which the step rewrites in place) with the step tensor
-    at step0 + t and b.step(is_continuous=False) at counter c0 + t; hold: the mask drops an env after its env_done;
-    cfg (the auto-reset): reset_observe(env_done & mask) behind every step. cvar = 1 goes through asvrl_iqn_act.
-    Returns a dict of the records as policy_rollout() lays them out (rows of steps an env did not take at the
-    pre-fill), steps_run, pushed [K], the resets and finals after every step, and the share of acting rows whose
-    action is the arg-max of the act pass's own action values (greedy_share)."""
-    from distributional_rl_decision_and_control_amd.fused_iqn import iqn_act
-    ar = cfg is not None
-    spec = _specs(b)
-    names = AR_RECORDS if ar else RECORDS
-    rec = {n: torch.full((K,) + spec[n][0], spec[n][2], dtype=spec[n][1], device="cuda") for n in names}
-    R = b.max_robots
-    mask = env_mask.clone() if env_mask is not None else (torch.ones(E, dtype=torch.uint8, device="cuda") if hold else None)
-    slot = torch.arange(E * R, device="cuda") % R
-    act64 = torch.zeros((E * R, 2), dtype=torch.float64, device="cuda")
-    greedy64 = torch.zeros((E * R, 2), dtype=torch.float64, device="cuda")
-    step = torch.full((1,), step0, dtype=torch.int64, device="cuda")
-    steps_run = torch.zeros(E, dtype=torch.int32, device="cuda")
-    pushed = torch.zeros(K, dtype=torch.int32, device="cuda")
-    resets = torch.zeros(E, dtype=torch.int32, device="cuda")
-    finals, resets_after = [], []
-    greedy_rows = acting_rows = 0
-    for t in range(K):
-        on_e = (mask != 0) if mask is not None else torch.ones(E, dtype=torch.bool, device="cuda")
-        on_r = on_e.repeat_interleave(R)
-        if ar:
-            rec["obs_prev"][t][on_r] = b.obs[on_r]
-        iqn_act(pack, None, act64, step, *eps, POLICY_SEED, obs=b.obs, cvar=cvar)
-        if eps is EPS_HALF:   # the same rows, step and taus at epsilon 0: the greedy action
-            iqn_act(pack, None, greedy64, step, *EPS_ZERO, POLICY_SEED, obs=b.obs, cvar=cvar)
-            greedy_rows += int((act64[on_r, 0] == greedy64[on_r, 0]).sum())
-            acting_rows += int(on_r.sum())
-        step += 1
-        rs_r = on_r & (slot < b.n_robots.repeat_interleave(R)) if ar else on_r
-        b.step(act64, is_continuous=False, seed=11, counter=c0 + t, trainer_deactivate=True, gamma=GAMMA,
-               env_mask=mask, launch=launch, fast_noise=fast)
-        for n in RECORDS:
-            src = act64 if n == "actions" else getattr(b, n)
-            if n == "rs":
-                rec[n][t][:, rs_r] = src[:, rs_r]
-            else:
-                sel = on_e if n == "env_done" else on_r
-                rec[n][t][sel] = src[sel]
-        steps_run += on_e.int()
-        if hold:
-            mask = mask * (b.env_done == 0).to(torch.uint8)
-        if ar:
-            pushed[t] = int((b.obj_cnt[on_r] >= 0).sum())
-            m = (b.env_done * on_e.to(torch.uint8)).contiguous()
-            resets += m.int()
-            if two_launch:
-                b.reset(cfg, m, seed=11, counter=RC + (c0 - C0) + t)
-                b.step(None, do_dynamics=False, seed=11, counter=OC + (c0 - C0) + t, fast_noise=fast, env_mask=m)
-            else:
-                b.reset_observe(cfg, m, seed=11, counter=RC + (c0 - C0) + t, obs_counter=OC + (c0 - C0) + t,
-                                obs=b.obs, obj_cnt=b.obj_cnt, fast_noise=fast)
-        finals.append(_finals(b))
-        resets_after.append(resets.clone())
-    share = greedy_rows / acting_rows if acting_rows else None
-    return dict(rec=rec, steps_run=steps_run, pushed=pushed, resets_after=resets_after, finals=finals,
-                greedy_share=share)
-
-
-def _run(b, pack, K, eps, cfg=None, step0=STEP0, c0=C0, **kw):
-    step = torch.full((1,), step0, dtype=torch.int64, device="cuda")
-    ar = dict(cfg=cfg, reset_counter=RC + (c0 - C0), obs_counter=OC + (c0 - C0)) if cfg is not None else None
-    got = b.policy_rollout(pack, K, b.obs, keep=AR_RECORDS if cfg is not None else RECORDS, step_dev=step, eps=eps,
-                           policy_seed=POLICY_SEED, trainer_deactivate=True, seed=11, counter=c0, gamma=GAMMA,
-                           auto_reset=ar, **kw)
-    assert int(step.item()) == step0, "the caller's step counter is only read"
-    return got
-
-
-def _check(b, got, ref, K, what, steps=None, t0=0):
-    """The window's K steps against rounds t0 .. t0 + K - 1 of the reference."""
-    ar = "obs_prev" in ref["rec"]
-    for n in (AR_RECORDS if ar else RECORDS):
-        _same(getattr(got, n), ref["rec"][n][t0:t0 + K], f"{what}: record {n}")
-    if ar:
-        _same(got.pushed, ref["pushed"][t0:t0 + K], f"{what}: pushed")
-        before = ref["resets_after"][t0 - 1] if t0 else torch.zeros_like(ref["resets_after"][0])
-        _same(got.resets, ref["resets_after"][t0 + K - 1] - before, f"{what}: resets")
-    _same(got.steps_run, steps if steps is not None else torch.full((E,), K, dtype=torch.int32, device="cuda"),
-          f"{what}: steps_run")
-    final = ref["finals"][t0 + K - 1]
-    for n in FINALS:
-        _same(getattr(b, n), final[n], f"{what}: final {n}")
-    s, r = b.stats.cpu().numpy(), final["stats"].cpu().numpy()
-    assert np.array_equal(s[1:], r[1:]), f"{what}: stats counts {s} vs {r}"
-    assert abs(s[0] - r[0]) <= 1e-12 * max(1.0, abs(r[0])), f"{what}: stats return sum {s[0]} vs {r[0]}"
-
-
-def _assert_indices(actions, what):
-    """Every recorded action is an exact integer in 0..A-1 with column 1 equal to 0.0."""
-    a0 = actions[..., 0]
-    assert bool(((a0 >= 0) & (a0 <= A - 1) & (a0 == a0.round())).all()), f"{what}: action indices"
-    assert bool((actions[..., 1] == 0.0).all()), f"{what}: column 1"
-
-
-@functools.lru_cache(maxsize=None)
-def _reference(R, O, C, fast, eps, operands="bf16", ar=False, cvar=1.0):
-    """One 13-round loop per case: its first K rounds are the reference of a K-step window."""
-    return _loop(_batch(R, O, C, fast, ending=ar), _pack(operands), KMAX, eps, cfg=_cfg(R, O, C) if ar else None,
-                 fast=fast, cvar=cvar)
-
-
-def _assert_not_vacuous(ref, eps, R):
-    _assert_indices(ref["rec"]["actions"], "reference")
+def _assert_greedy_share(ref, eps, R):
+    wc.assert_indices(ref["rec"]["actions"], "reference")
     if eps is EPS_HALF and R > 1:   # (one robot per env: 37 rows a step)
-        assert 0.25 <= ref["greedy_share"] <= 0.75, ref["greedy_share"]
+        share = ref["greedy_rows"] / ref["acting_rows"]
+        assert 0.25 <= share <= 0.75, share
 
 
 @pytest.mark.parametrize("eps", [EPS_HALF, EPS_ZERO], ids=["eps0.5", "greedy"])
@@ -201,53 +49,53 @@ def test_iqn_rollout_matches_composed_loop(R, O, C, fast, eps):
     """K = 1, 2 and 13 at the automatic step shape; K = 13 also at a forced one-wave pair shape, at max_groups = 3
     and at layout 2 (the sweep step): the IQN window composes the same launches under every layout."""
     from distributional_rl_decision_and_control_amd import _abi
-    ref = _reference(R, O, C, fast, eps)
-    _assert_not_vacuous(ref, eps, R)
+    ref = wc.reference(CASE, R, O, C, fast, eps)
+    _assert_greedy_share(ref, eps, R)
     shapes = [(K, None) for K in (1, 2, 13)]
     shapes += [(13, (_abi.ENV_LAYOUT_PAIRS, 64, max(1, 64 // R))), (13, (0, 0, 0, 3)), (13, (2, 0, 0))]
     for K, launch in shapes:
-        b = _batch(R, O, C, fast)
-        got = _run(b, _pack(), K, eps, fast_noise=fast, launch=launch)
-        _check(b, got, ref, K, f"R={R} O={O} K={K} launch={launch}")
-        _assert_indices(got.actions, f"R={R} K={K}")
+        b = wc.batch(CASE, R, O, C, fast)
+        got = wc.run_window(b, wc.pack(CASE), K, eps, fast_noise=fast, launch=launch)
+        wc.check(b, got, ref, K, f"R={R} O={O} K={K} launch={launch}")
+        wc.assert_indices(got.actions, f"R={R} K={K}")
 
 
 def test_iqn_rollout_f32_build():
     """IqnPack(operands="f32") runs the f32-operand library against that library's own composed loop."""
     R, O, C = 5, 4, 2
     for eps in (EPS_HALF, EPS_ZERO):
-        ref = _reference(R, O, C, True, eps, "f32")
-        _assert_not_vacuous(ref, eps, R)
+        ref = wc.reference(CASE, R, O, C, True, eps, "f32")
+        _assert_greedy_share(ref, eps, R)
         for K in (2, 13):
-            b = _batch(R, O, C, True)
-            got = _run(b, _pack("f32"), K, eps, fast_noise=True)
-            _check(b, got, ref, K, f"f32 eps={eps} K={K}")
+            b = wc.batch(CASE, R, O, C, True)
+            got = wc.run_window(b, wc.pack(CASE, "f32"), K, eps, fast_noise=True)
+            wc.check(b, got, ref, K, f"f32 eps={eps} K={K}")
 
 
 @pytest.mark.parametrize("ops", ["bf16", "f32"])
 def test_iqn_rollout_cvar(ops):
     """cvar = 0.25 is the composed loop at 0.25 and not the window at cvar = 1."""
     R, O, C = 5, 4, 2
-    ref = _reference(R, O, C, True, EPS_HALF, ops, cvar=0.25)
-    _assert_not_vacuous(ref, EPS_HALF, R)
-    b = _batch(R, O, C, True)
-    got = _run(b, _pack(ops), KMAX, EPS_HALF, fast_noise=True, cvar=0.25)
-    _check(b, got, ref, KMAX, f"{ops} cvar=0.25")
-    neutral = _reference(R, O, C, True, EPS_HALF, ops)["rec"]["actions"]
+    ref = wc.reference(CASE, R, O, C, True, EPS_HALF, ops, cvar=0.25)
+    _assert_greedy_share(ref, EPS_HALF, R)
+    b = wc.batch(CASE, R, O, C, True)
+    got = wc.run_window(b, wc.pack(CASE, ops), KMAX, EPS_HALF, fast_noise=True, cvar=0.25)
+    wc.check(b, got, ref, KMAX, f"{ops} cvar=0.25")
+    neutral = wc.reference(CASE, R, O, C, True, EPS_HALF, ops)["rec"]["actions"]
     changed = float((got.actions[0, :, 0] != neutral[0, :, 0]).float().mean())   # step 0: the same observations
     assert changed > 0.0, "cvar = 0.25 must act differently from cvar = 1"
-    assert not torch.equal(got.reward, _reference(R, O, C, True, EPS_HALF, ops)["rec"]["reward"])
+    assert not torch.equal(got.reward, wc.reference(CASE, R, O, C, True, EPS_HALF, ops)["rec"]["reward"])
 
 
 def test_iqn_rollout_split_6_plus_7_is_13():
     """Two windows, 6 steps and then 7 with the step counter and the noise counter advanced by 6, are the 13."""
     R, O, C = 5, 4, 2
-    ref = _reference(R, O, C, True, EPS_HALF)
-    b = _batch(R, O, C, True)
-    first = _run(b, _pack(), 6, EPS_HALF, fast_noise=True)
-    _check(b, first, ref, 6, "first 6")
-    second = _run(b, _pack(), 7, EPS_HALF, fast_noise=True, step0=STEP0 + 6, c0=C0 + 6)
-    _check(b, second, ref, 7, "then 7", t0=6)
+    ref = wc.reference(CASE, R, O, C, True, EPS_HALF)
+    b = wc.batch(CASE, R, O, C, True)
+    first = wc.run_window(b, wc.pack(CASE), 6, EPS_HALF, fast_noise=True)
+    wc.check(b, first, ref, 6, "first 6")
+    second = wc.run_window(b, wc.pack(CASE), 7, EPS_HALF, fast_noise=True, t0=6)
+    wc.check(b, second, ref, 7, "then 7", t0=6)
 
 
 @pytest.mark.parametrize("masked", [False, True])
@@ -255,15 +103,12 @@ def test_iqn_rollout_hold_done(masked):
     """hold_done is the chain of rounds whose env_mask drops an env after its env_done; `masked`: on top of a
     caller's mask that leaves every fourth env (and a whole act workgroup's envs) out. An env that is off takes no
     action: its rows of the actions record keep their pre-fill."""
-    mask = None
-    if masked:
-        mask = torch.ones(E, dtype=torch.uint8, device="cuda")
-        mask[::4] = 0
-        mask[8:16] = 0
-    ref = _loop(_batch(5, 4, 0, ending=True), _pack(), KMAX, EPS_HALF, hold=True, env_mask=mask)
-    b = _batch(5, 4, 0, ending=True)
-    got = _run(b, _pack(), KMAX, EPS_HALF, hold_done=True, fast_noise=True, env_mask=mask)
-    _check(b, got, ref, KMAX, f"hold masked={masked}", steps=ref["steps_run"])
+    mask = wc.quarter_mask(E) if masked else None
+    ref = wc.composed_loop(CASE, wc.batch(CASE, 5, 4, 0, ending=True), wc.pack(CASE), KMAX, EPS_HALF, hold=True,
+                           env_mask=mask)
+    b = wc.batch(CASE, 5, 4, 0, ending=True)
+    got = wc.run_window(b, wc.pack(CASE), KMAX, EPS_HALF, hold_done=True, fast_noise=True, env_mask=mask)
+    wc.check(b, got, ref, KMAX, f"hold masked={masked}", steps=ref["steps_run"])
     on = np.ones(E, bool) if mask is None else mask.cpu().numpy() != 0
     expect = np.where(on, np.maximum(1, 5 - np.arange(E) % 9 + 1), 0)   # the end step is known
     assert np.array_equal(got.steps_run.cpu().numpy(), expect)
@@ -276,10 +121,10 @@ def test_iqn_rollout_env_mask():
     mask = torch.ones(E, dtype=torch.uint8, device="cuda")
     mask[1::3] = 0
     K = 5
-    ref = _loop(_batch(5, 4, 2), _pack(), K, EPS_HALF, env_mask=mask)
-    b = _batch(5, 4, 2)
-    got = _run(b, _pack(), K, EPS_HALF, fast_noise=True, env_mask=mask)
-    _check(b, got, ref, K, "env_mask", steps=ref["steps_run"])
+    ref = wc.composed_loop(CASE, wc.batch(CASE, 5, 4, 2), wc.pack(CASE), K, EPS_HALF, env_mask=mask)
+    b = wc.batch(CASE, 5, 4, 2)
+    got = wc.run_window(b, wc.pack(CASE), K, EPS_HALF, fast_noise=True, env_mask=mask)
+    wc.check(b, got, ref, K, "env_mask", steps=ref["steps_run"])
     off_r = (mask == 0).repeat_interleave(5)
     assert not bool(got.actions[:, off_r].any())
 
@@ -287,11 +132,11 @@ def test_iqn_rollout_env_mask():
 def test_iqn_rollout_per_robot_parameters():
     """Per-robot parameters (the sweep step): the same records and finals."""
     K = 3
-    ref = _loop(_batch(5, 4, 2, robot_params=True), _pack(), K, EPS_HALF)
-    b = _batch(5, 4, 2, robot_params=True)
-    got = _run(b, _pack(), K, EPS_HALF, fast_noise=True)
-    _check(b, got, ref, K, "robot_params")
-    _assert_indices(got.actions, "robot_params")
+    ref = wc.composed_loop(CASE, wc.batch(CASE, 5, 4, 2, robot_params=True), wc.pack(CASE), K, EPS_HALF)
+    b = wc.batch(CASE, 5, 4, 2, robot_params=True)
+    got = wc.run_window(b, wc.pack(CASE), K, EPS_HALF, fast_noise=True)
+    wc.check(b, got, ref, K, "robot_params")
+    wc.assert_indices(got.actions, "robot_params")
 
 
 @pytest.mark.parametrize("eps", [EPS_HALF, EPS_ZERO], ids=["eps0.5", "greedy"])
@@ -299,84 +144,56 @@ def test_iqn_rollout_auto_reset(eps):
     """episode_limit 5 and ep_ts preset to e % 9: every env ends at least twice in 13 steps; obs_prev, pushed and
     resets are compared with the records, in one window of 13 and in windows of 6 and 7."""
     R, O, C = 5, 4, 2
-    ref = _reference(R, O, C, True, eps, ar=True)
-    _assert_not_vacuous(ref, eps, R)
+    ref = wc.reference(CASE, R, O, C, True, eps, ar=True)
+    _assert_greedy_share(ref, eps, R)
     assert ref["resets_after"][-1].min().item() >= 2, "every env must end at least twice"
     assert int(ref["pushed"].min().item()) > 0
     for launch in (None, (2, 0, 0)):
-        b = _batch(R, O, C, ending=True)
-        got = _run(b, _pack(), KMAX, eps, cfg=_cfg(R, O, C), fast_noise=True, launch=launch)
-        _check(b, got, ref, KMAX, f"auto-reset eps={eps} launch={launch}")
-        _assert_indices(got.actions, "auto-reset")
-    b = _batch(R, O, C, ending=True)
-    first = _run(b, _pack(), 6, eps, cfg=_cfg(R, O, C), fast_noise=True)
-    _check(b, first, ref, 6, "auto-reset first 6")
-    second = _run(b, _pack(), 7, eps, cfg=_cfg(R, O, C), fast_noise=True, step0=STEP0 + 6, c0=C0 + 6)
-    _check(b, second, ref, 7, "auto-reset then 7", t0=6)
+        b = wc.batch(CASE, R, O, C, ending=True)
+        got = wc.run_window(b, wc.pack(CASE), KMAX, eps, cfg=wc.cfg(CASE, R, O, C), fast_noise=True, launch=launch)
+        wc.check(b, got, ref, KMAX, f"auto-reset eps={eps} launch={launch}")
+        wc.assert_indices(got.actions, "auto-reset")
+    b = wc.batch(CASE, R, O, C, ending=True)
+    first = wc.run_window(b, wc.pack(CASE), 6, eps, cfg=wc.cfg(CASE, R, O, C), fast_noise=True)
+    wc.check(b, first, ref, 6, "auto-reset first 6")
+    second = wc.run_window(b, wc.pack(CASE), 7, eps, cfg=wc.cfg(CASE, R, O, C), fast_noise=True, t0=6)
+    wc.check(b, second, ref, 7, "auto-reset then 7", t0=6)
 
 
 def test_iqn_rollout_auto_reset_per_robot_parameters():
     """Per-robot parameters: the two reset launches behind every step."""
     R, O, C, K = 5, 4, 2, 7
-    cfg = _cfg(R, O, C)
-    ref = _loop(_batch(R, O, C, ending=True, robot_params=True), _pack(), K, EPS_HALF, cfg=cfg, two_launch=True)
+    cfg = wc.cfg(CASE, R, O, C)
+    ref = wc.composed_loop(CASE, wc.batch(CASE, R, O, C, ending=True, robot_params=True), wc.pack(CASE), K, EPS_HALF,
+                           cfg=cfg, two_launch=True)
     assert ref["resets_after"][-1].sum().item() > 0
-    b = _batch(R, O, C, ending=True, robot_params=True)
-    got = _run(b, _pack(), K, EPS_HALF, cfg=cfg, fast_noise=True)
-    _check(b, got, ref, K, "auto-reset robot_params")
+    b = wc.batch(CASE, R, O, C, ending=True, robot_params=True)
+    got = wc.run_window(b, wc.pack(CASE), K, EPS_HALF, cfg=cfg, fast_noise=True)
+    wc.check(b, got, ref, K, "auto-reset robot_params")
 
 
 def test_policy_rollout_value_errors():
-    from distributional_rl_decision_and_control_amd.fused_dqn import DqnPack
-    from distributional_rl_decision_and_control_amd.policy.DQN_model import DQN_Policy
-    from distributional_rl_decision_and_control_amd.vec_trainer import DEFAULT_NET
-    b = _batch(5, 4, 2)
+    b = wc.batch(CASE, 5, 4, 2)
     for cvar in (0.0, -0.25, 1.5):
         with pytest.raises(ValueError, match="cvar"):
-            b.policy_rollout(_pack(), 2, b.obs, cvar=cvar)
-    dqn = DqnPack(DQN_Policy(**DEFAULT_NET, action_size=A, device="cuda", seed=100).to("cuda"))
+            b.policy_rollout(wc.pack(CASE), 2, b.obs, cvar=cvar)
     with pytest.raises(ValueError, match="cvar"):
-        b.policy_rollout(dqn, 2, b.obs, cvar=0.5)
+        b.policy_rollout(wc.pack(wc.CASES["dqn"]), 2, b.obs, cvar=0.5)
     with pytest.raises(ValueError, match="deterministic"):
-        b.policy_rollout(_pack(), 2, b.obs, deterministic=True)
+        b.policy_rollout(wc.pack(CASE), 2, b.obs, deterministic=True)
 
 
 # ------------------------------------------------------------------ VecMarineNavEnv.policy_rollout
-def _vec(is_continuous):
-    from distributional_rl_decision_and_control_amd.vec_env import VecMarineNavEnv
-    env = VecMarineNavEnv(E, num_robots=5, num_obs=4, min_start_goal_dis=20.0, seed=5, is_continuous=is_continuous)
-    env.reset()
-    return env
-
-
 @pytest.mark.parametrize("cvar", [1.0, 0.25])
 def test_vec_env_takes_an_iqn_pack_on_a_discrete_env(cvar):
-    from distributional_rl_decision_and_control_amd.fused_iqn import iqn_act
-    K = 4
-    pack = _pack()
-    twin = _vec(False)
-    act64 = torch.zeros((E * 5, 2), dtype=torch.float64, device="cuda")
-    for t in range(K):
-        iqn_act(pack, None, act64, twin.counter, *EPS_HALF, POLICY_SEED, obs=twin.obs_cur, cvar=cvar)
-        twin.step(act64)
-        twin.advance_device()
-    env = _vec(False)
-    rec = env.policy_rollout(pack, K, hold_done=False, keep=("reward", "actions"), eps=EPS_HALF,
-                             policy_seed=POLICY_SEED, cvar=cvar)
-    assert rec.reward.shape == (K, E * 5) and rec.actions.shape == (K, E * 5, 2)
-    _assert_indices(rec.actions, "vec env")
-    _same(env.obs_next, twin.obs_next, "obs_next")
-    _same(env.counter, twin.counter, "counter")
-    for n in ("rs", "rflags", "ep_ts", "reward", "done", "info", "env_done"):
-        _same(getattr(env.batch, n), getattr(twin.batch, n), n)
-    _same(rec.actions[-1], act64, "last actions record")
+    wc.check_vec_env(CASE, wc.pack(CASE), 4, assert_actions=wc.assert_indices, cvar=cvar)
 
 
 def test_vec_env_pack_and_env_must_match():
     with pytest.raises(ValueError, match="IqnPack.*is_continuous=True"):
-        _vec(True).policy_rollout(_pack(), 2)
+        wc.vec_env(CASE, True).policy_rollout(wc.pack(CASE), 2)
     with pytest.raises(ValueError, match="cvar"):
-        _vec(False).policy_rollout(_pack(), 2, cvar=2.0)
+        wc.vec_env(CASE, False).policy_rollout(wc.pack(CASE), 2, cvar=2.0)
 
 
 # ------------------------------------------------------------------ graph capture
@@ -384,43 +201,4 @@ def test_iqn_rollout_graph_capture():
     """One call with caller-supplied records captured in a graph on a single stream and replayed from the restored
     state gives the eager call's records: the per-step launches and the call's stream-ordered scratch are captured
     as they are enqueued."""
-    R, O, C, K = 5, 4, 2, 5
-    pack = _pack()
-    b = _batch(R, O, C)
-    state = {n: getattr(b, n).clone() for n in ("rs", "rflags", "ep_ts", "obs", "stats")}
-    spec = _specs(b)
-
-    def records():
-        rec = {n: torch.full((K,) + spec[n][0], spec[n][2], dtype=spec[n][1], device="cuda") for n in RECORDS}
-        rec["steps_run"] = torch.zeros(E, dtype=torch.int32, device="cuda")
-        return rec
-
-    step = torch.full((1,), STEP0, dtype=torch.int64, device="cuda")
-
-    def call(rec):
-        b.policy_rollout(pack, K, b.obs, keep=rec, step_dev=step, eps=EPS_HALF, policy_seed=POLICY_SEED,
-                         trainer_deactivate=True, seed=11, counter=C0, gamma=GAMMA, fast_noise=True, cvar=0.5)
-
-    eager = records()
-    call(eager)
-    torch.cuda.synchronize()
-    finals = _finals(b)
-    _assert_indices(eager["actions"], "eager")
-    assert bool((eager["steps_run"] == K).all())
-
-    def restore():
-        for n, t in state.items():
-            getattr(b, n).copy_(t)
-
-    restore()
-    rec = records()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        call(rec)
-    restore()   # capturing ran nothing: the records are still at their pre-fill
-    g.replay()
-    torch.cuda.synchronize()
-    for n in RECORDS + ("steps_run",):
-        _same(rec[n], eager[n], f"replayed record {n}")
-    for n in FINALS:
-        _same(getattr(b, n), finals[n], f"replayed final {n}")
+    wc.check_graph_capture(CASE, wc.batch(CASE, 5, 4, 2), wc.pack(CASE), 5, assert_actions=wc.assert_indices, cvar=0.5)

@@ -8,47 +8,21 @@ the same loss, gradient norm and priorities. episode_limit 3: every env restarts
 import pytest
 import torch
 
+import window_cases as wc
+from window_cases import PER_ARRAYS
+
 pytestmark = pytest.mark.gpu
 
 E, K = 37, 5
-ENV_ARRAYS = ("rs", "rflags", "n_robots", "n_obs", "n_cores", "ep_ts", "obstacles", "cores", "obs", "obj_cnt", "reward",
-              "done", "info", "env_done")
-PER_ARRAYS = ("rows", "tree", "state", "t", "maxp", "dirty")
-
-
-def _same(got, ref, what):
-    torch.testing.assert_close(got, ref, rtol=0, atol=0, equal_nan=True, msg=lambda m: f"{what}: {m}")
-
-
-def _trainer():
-    from distributional_rl_decision_and_control_amd.vec_trainer import VecTrainer
-    tr = VecTrainer(agent_type="Rainbow", n_envs=E, batch_size=64, buffer_size=37 * 5 * 40, graphs=False, seed=3)
-    tr.env.batch.params.episode_limit = 3   # before the first step: every env ends inside a window of 5
-    return tr
-
-
-def _compare(a, b, what):
-    for n in PER_ARRAYS:
-        _same(getattr(a.per, n), getattr(b.per, n), f"{what}: per.{n}")
-    assert a.per.pushed == b.per.pushed, (what, a.per.pushed, b.per.pushed)
-    _same(a.env.counter, b.env.counter, f"{what}: env.counter")
-    _same(a.learn_counter, b.learn_counter, f"{what}: learn counter")
-    _same(a.env.obs_cur, b.env.obs_cur, f"{what}: obs_cur")
-    _same(a.env.cnt_cur, b.env.cnt_cur, f"{what}: cnt_cur")
-    for n in ENV_ARRAYS:
-        _same(getattr(a.env.batch, n), getattr(b.env.batch, n), f"{what}: {n}")
-    assert a.env.total_timesteps == b.env.total_timesteps
-    sa, sb = a.env.episode_stats(), b.env.episode_stats()
-    for k in ("robot_episodes", "env_episodes", "success", "collision", "timeout"):
-        assert sa[k] == sb[k], (what, k, sa[k], sb[k])
-    assert abs(sa["mean_return"] - sb["mean_return"]) <= 1e-12 * max(1.0, abs(sb["mean_return"]))
+LIMIT = 3   # the episode limit, set before the first step: every env ends inside a window of 5
+BUFFER = 37 * 5 * 40
 
 
 def test_collect_window_matches_rollouts():
     """Two windows of 5 against 10 rollout() calls: compared after each window, so the second window starts from
     reset envs and a part-filled replay whose deferred priorities are entering the tree."""
     from distributional_rl_decision_and_control_amd.fused_rainbow import RainbowPack
-    ref, tr = _trainer(), _trainer()
+    ref, tr = (wc.trainer("Rainbow", LIMIT, E, buffer_size=BUFFER) for _ in range(2))
     pack = tr.fused_rb.window_pack
     assert isinstance(pack, RainbowPack) and pack.noisy and pack.image is tr.fused_rb.img
     assert pack.noisy_pack is tr.fused_rb.pack, "the training-mode pack allocates no second image"
@@ -69,9 +43,9 @@ def test_collect_window_matches_rollouts():
         assert 0 < pushed <= K * E * tr.R
         assert tr.per.pushed == (w + 1) * K * E * tr.R
         assert int(tr.env.counter.item()) == (w + 1) * K
-        _compare(tr, ref, f"window {w}")
+        wc.compare_trainers(tr, ref, f"window {w}")
         # the last step's actions are what rollout() left in ref.actions: (index, 0.0)
-        _same(rec.actions[-1], ref.actions, f"window {w}: last actions")
+        wc.same(rec.actions[-1], ref.actions, f"window {w}: last actions")
         a0 = rec.actions[..., 0]
         assert bool(((a0 >= 0) & (a0 < 25) & (a0 == a0.round())).all())
         assert bool((rec.actions[..., 1] == 0.0).all())
@@ -80,26 +54,20 @@ def test_collect_window_matches_rollouts():
         head = (int(tr.per.state[0].item()) - E * tr.R) % tr.per.capacity
         last = tr.per.rows[head:head + E * tr.R]
         acted = rec.obj_cnt[-1] >= 0
-        _same(last[acted, 40].double(), rec.actions[-1][acted, 0], f"window {w}: the replay's action column")
+        wc.same(last[acted, 40].double(), rec.actions[-1][acted, 0], f"window {w}: the replay's action column")
     assert resets >= 2 * E, "every env restarts inside both windows"
     assert ref.env.episode_stats()["env_episodes"] == resets
     assert tr.replay_size_host() >= tr.learning_starts, "the tree holds complete windows: learn() can draw"
-    la, lb = tr.learn(), ref.learn()   # the update draws from identical trees
-    torch.cuda.synchronize()
-    for x, y in zip(la, lb):
-        if torch.is_tensor(x):
-            _same(x, y, "loss / gradient norm after the windows")
-        else:
-            assert x == y
-    _same(tr.fused_rb.loss, ref.fused_rb.loss, "per-sample loss")
+    wc.same_learn(tr, ref, "loss / gradient norm after the windows")   # the update draws from identical trees
+    wc.same(tr.fused_rb.loss, ref.fused_rb.loss, "per-sample loss")
     assert bool(torch.isfinite(tr.fused_rb.loss).all())
     for n in PER_ARRAYS:
-        _same(getattr(tr.per, n), getattr(ref.per, n), f"after learn: per.{n} (the priorities)")
-    _same(tr.per_idx, ref.per_idx, "the drawn leaves")
+        wc.same(getattr(tr.per, n), getattr(ref.per, n), f"after learn: per.{n} (the priorities)")
+    wc.same(tr.per_idx, ref.per_idx, "the drawn leaves")
 
 
 def test_the_four_still_refuse_rainbow():
-    tr = _trainer()
+    tr = wc.trainer("Rainbow", LIMIT, E, buffer_size=BUFFER)
     cfgs = []
     for refused in (lambda: tr.collect(K), tr.policy_pack, tr.greedy_episodes, lambda: tr.evaluate(cfgs)):
         with pytest.raises(NotImplementedError):

@@ -17,168 +17,38 @@ penalty, which makes a second parameter group of two envs.
 Tolerances as in tests/test_device_eval_gpu.py: integers and flags exact; f64 sums 1e-12 relative (pow and summation
 order over at most 64 terms of 2.3e-16 each), the return relative to max(1, sum |term|). The weights are a seeded
 SAC_Policy's actor."""
-import copy
-import functools
-import json
-import math
-import os
-
 import numpy as np
 import pytest
 import torch
 
+import device_eval_cases as dev
+import window_cases as wc
+from device_eval_cases import CHUNK, GAMMA, LIMIT, PSEED, SEED
+
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "eval60_ref.npz")
-PICK = (0, 10, 20, 30, 40, 55)   # 3, 4, 5 robots without buoys; 5 robots with 2, 3 and 4 buoys
-GAMMA = 0.99
-LIMIT, CHUNK, SEED, PSEED = 22, 5, 17, 900
-
-
-@functools.lru_cache(maxsize=None)
-def _all_configs():
-    return json.loads(str(np.load(GOLDEN)["trained/configs"]))
-
-
-def _configs(second_group=True):
-    out = [copy.deepcopy(_all_configs()[i]) for i in PICK]
-    assert [c["env"]["num_robots"] for c in out] == [3, 4, 5, 5, 5, 5]
-    assert [len(c["env"]["obstacles"]["r"]) for c in out] == [0, 0, 0, 2, 3, 4]
-    if second_group:   # another env-level parameter: a DeviceEnvBatch of their own
-        for i in (2, 3):
-            c = copy.deepcopy(out[i])
-            c["env"]["timestep_penalty"] = 2.0 * c["env"]["timestep_penalty"] - 0.25
-            out.append(c)
-    return out
-
-
-@functools.lru_cache(maxsize=None)
-def _net():
-    from distributional_rl_decision_and_control_amd.policy.SAC_model import SAC_Policy
-    from distributional_rl_decision_and_control_amd.vec_trainer import DEFAULT_NET
-    return SAC_Policy(**DEFAULT_NET, value_ranges_of_action=[[-1.0, 1.0], [-1.0, 1.0]], device="cuda", seed=100)
-
-
-@functools.lru_cache(maxsize=None)
-def _pack(operands):
-    from distributional_rl_decision_and_control_amd.fused_sac import SacActorPack
-    return SacActorPack(_net().actor, operands)
-
-
-def _close(got, ref, scale=None, what=""):
-    got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
-    scale = np.abs(ref) if scale is None else np.asarray(scale, dtype=np.float64)
-    err = np.abs(got - ref) / np.maximum(scale, 1e-300)
-    print(f"{what}: max relative error {err.max():.2e}")
-    assert (np.abs(got - ref) <= 1e-12 * scale).all(), (what, got, ref)
-
-
-def _same_results(a, b, what):
-    assert a["lengths"] == b["lengths"] and a["successes"] == b["successes"], what
-    for name in ("rewards", "times", "energies"):
-        assert np.array(a[name]).tobytes() == np.array(b[name]).tobytes(), (what, name)
-    for name in ("robot_rewards", "robot_times", "robot_energies", "robot_outcomes"):
-        assert all(x.tobytes() == y.tobytes() for x, y in zip(a[name], b[name])), (what, name)
+CASE = wc.CASES["sac"]
 
 
 # ------------------------------------------------------------------ closed loop against the composed loop
-def _bookkeep(st, n_robots, R, reward, info, tl, tr, dt, N, pc, stepping, limit):
-    """trainer.py:286-303 for one step of every env in `stepping` (numpy, in place)."""
-    from distributional_rl_decision_and_control_amd import _abi
-    for e in np.nonzero(stepping)[0]:
-        if st["ended"][e]:
-            continue
-        collided = False
-        for i in range(n_robots[e]):
-            r = e * R + i
-            if st["deact"][r]:
-                continue
-            term = GAMMA ** int(st["length"][e]) * reward[r]
-            st["ret"][r] += term
-            st["abs"][r] += abs(term)
-            st["time"][r] += dt[r] * N[r]
-            st["energy"][r] += pc[r] * np.abs(tl[r]) * dt[r] * N[r] + pc[r] * np.abs(tr[r]) * dt[r] * N[r]
-            if info[r] in (_abi.INFO_COLLISION, _abi.INFO_REACH_GOAL):
-                st["deact"][r] = 1
-                st["outcome"][r] = 2 if info[r] == _abi.INFO_COLLISION else 1
-                collided |= info[r] == _abi.INFO_COLLISION
-        end = st["length"][e] >= limit or collided or bool(st["deact"][e * R:e * R + n_robots[e]].all())
-        st["length"][e] += 1
-        st["ended"][e] = end
-
-
-def _composed(ev, g, pack, limit, chunk, seed, policy_seed, deterministic):
-    """Group g's evaluation as single launches on the evaluator's own batch (after ev.observe): greedy-schedule
-    sac_act + the step at the Philox keys run() uses for the group, an env leaving at a window's start once the
-    bookkeeping ended it and inside a window once the step's env_done held it. Also returns every action taken."""
-    from distributional_rl_decision_and_control_amd import _abi
-    from distributional_rl_decision_and_control_amd.fused_sac import sac_act
-    grp = ev.groups[g]
-    b = grp.batch
-    E, R = b.n_envs, b.max_robots
-    NT = E * R
-    n_robots = b.n_robots.cpu().numpy()
-    dt, N, pc = (t.cpu().numpy() for t in (grp.dt, grp.N, grp.pc))
-    st = dict(length=np.zeros(E, np.int64), ended=np.zeros(E, bool), deact=np.zeros(NT, np.uint8),
-              outcome=np.zeros(NT, np.uint8), ret=np.zeros(NT), time=np.zeros(NT), energy=np.zeros(NT),
-              abs=np.zeros(NT))
-    act64 = torch.zeros((NT, 2), dtype=torch.float64, device="cuda")
-    eps_out = torch.zeros((NT, 2), dtype=torch.float32, device="cuda")
-    eps_in = torch.zeros_like(eps_out) if deterministic else None
-    step = torch.zeros(1, dtype=torch.int64, device="cuda")
-    mask = None
-    taken = []
-    for t in range(limit + 1):
-        if t % chunk == 0:
-            mask = torch.from_numpy((~st["ended"]).astype(np.uint8)).cuda()
-        step.fill_(t)
-        sac_act(pack, b.obs, act64, eps_out, step, 1.0, 1.0, 1.0, 0.0, 0.0, policy_seed + g, eps_in=eps_in)
-        taken.append(act64.cpu().numpy().copy())
-        b.step(act64, trainer_deactivate=True, seed=seed + g, counter=t, fast_noise=True, env_mask=mask)
-        rs = b.rs.cpu().numpy()
-        _bookkeep(st, n_robots, R, b.reward.cpu().numpy(), b.info.cpu().numpy(), rs[_abi.F_TL], rs[_abi.F_TR], dt, N,
-                  pc, mask.cpu().numpy() != 0, limit)
-        mask = mask * (b.env_done == 0).to(torch.uint8)
-    return st, np.stack(taken)
-
-
 @pytest.mark.parametrize("deterministic", [False, True], ids=["sampled", "deterministic"])
 @pytest.mark.parametrize("operands", ["bf16", "f32"])
 def test_closed_loop_matches_single_launches(operands, deterministic):
     from distributional_rl_decision_and_control_amd.policy.device_eval import DeviceEvaluator
-    pack = _pack(operands)
-    ev = DeviceEvaluator(_configs(), chunk=CHUNK, gamma=GAMMA)
+    pack = wc.pack(CASE, operands)
+    ev = DeviceEvaluator(dev.configs(True), chunk=CHUNK, gamma=GAMMA)
     assert [grp.members for grp in ev.groups] == [[0, 1, 2, 3, 4, 5], [6, 7]]
-    kw = dict(seed=SEED, episode_limit=LIMIT, policy_seed=PSEED, deterministic=deterministic)
-    got = ev.run(pack, **kw)
-    assert ev.windows <= math.ceil((LIMIT + 1) / CHUNK) and ev.steps <= LIMIT + 1
-    again = ev.run(pack, **kw)          # restored by copy: the same bits
-    nosync = ev.run(pack, sync=False, **kw)
-    assert ev.windows == math.ceil((LIMIT + 1) / CHUNK) and ev.steps == LIMIT + 1
-    _same_results(again, got, "second run")
-    _same_results(nosync, got, "sync=False")
+    got = dev.run_thrice(ev, pack, LIMIT, CHUNK, seed=SEED, policy_seed=PSEED, deterministic=deterministic)
     print(operands, "lengths", got["lengths"], "outcomes", [o.tolist() for o in got["robot_outcomes"]])
     assert max(got["lengths"]) > CHUNK, "some episode must run past the first window"
     ev.observe(seed=SEED)
     first = []
-    for g, grp in enumerate(ev.groups):
-        st, taken = _composed(ev, g, pack, LIMIT, CHUNK, SEED, PSEED, deterministic)
+    for g in range(len(ev.groups)):
+        st, taken = dev.composed(ev, g, CASE, pack, LIMIT, CHUNK, SEED, PSEED, deterministic=deterministic)
         first.append(taken[0])
-        R = grp.batch.max_robots
-        assert st["ended"].all()
-        assert np.isfinite(taken).all() and (np.abs(taken) <= 1.0).all() and len(np.unique(taken[0])) > taken[0].size // 4
-        for le, c in enumerate(grp.members):
-            sl = slice(le * R, le * R + ev.n_robots[c])
-            assert got["lengths"][c] == int(st["length"][le])
-            assert got["robot_outcomes"][c].tolist() == st["outcome"][sl].tolist()
-            assert got["successes"][c] == bool((st["outcome"][sl] == 1).all())
-            _close(got["robot_times"][c], st["time"][sl], what=f"config {c} times")
-            _close(got["robot_energies"][c], st["energy"][sl], what=f"config {c} energies")
-            _close(got["robot_rewards"][c], st["ret"][sl], scale=np.maximum(1.0, st["abs"][sl]),
-                   what=f"config {c} returns")
-            assert got["rewards"][c] == np.mean(got["robot_rewards"][c])
-            assert got["times"][c] == np.mean(got["robot_times"][c])
-            assert got["energies"][c] == np.mean(got["robot_energies"][c])
+        assert np.isfinite(taken).all() and (np.abs(taken) <= 1.0).all()
+        assert len(np.unique(taken[0])) > taken[0].size // 4
+        dev.check_group(ev, got, g, st)
     # configs 6 and 7 start where 2 and 3 start, at batch-local rows 0..9 of their group: under one seed their first
     # actions would repeat rows 0..9 of group 0's draws. They are drawn under policy_seed + 1 (and act on another
     # observation noise, seed + 1), so no row agrees; without noise in the action, rows may.
@@ -189,32 +59,25 @@ def test_closed_loop_matches_single_launches(operands, deterministic):
 
 
 def test_policy_seed_and_groups(monkeypatch):
-    from distributional_rl_decision_and_control_amd.device_env import DeviceEnvBatch
     from distributional_rl_decision_and_control_amd.fused_sac import sac_act
     from distributional_rl_decision_and_control_amd.policy.device_eval import DeviceEvaluator
-    pack = _pack("bf16")
-    ev = DeviceEvaluator(_configs(), chunk=CHUNK, gamma=GAMMA)
-    seen = []
-    inner = DeviceEnvBatch.policy_rollout
-
-    def spy(self, *a, **kw):
-        seen.append((next(g for g, grp in enumerate(ev.groups) if grp.batch is self), kw["policy_seed"],
-                     kw["deterministic"]))
-        return inner(self, *a, **kw)
-    monkeypatch.setattr(DeviceEnvBatch, "policy_rollout", spy)
+    pack = wc.pack(CASE, "bf16")
+    ev = DeviceEvaluator(dev.configs(True), chunk=CHUNK, gamma=GAMMA)
+    seen = dev.spy_on_rollouts(monkeypatch, ev, "deterministic")
     kw = dict(seed=SEED, episode_limit=LIMIT)
     a = ev.run(pack, policy_seed=PSEED, **kw)
     assert seen and {s[0] for s in seen} == {0, 1}
     assert all(s[1] == PSEED + s[0] and s[2] is False for s in seen), "group g runs under policy_seed + g"
-    _same_results(ev.run(pack, policy_seed=PSEED, **kw), a, "the same policy_seed")
+    dev.same_results(ev.run(pack, policy_seed=PSEED, **kw), a, "the same policy_seed")
     other = ev.run(pack, policy_seed=PSEED + 50, **kw)
     assert other["rewards"] != a["rewards"], "another policy_seed is another sampled evaluation"
     seen.clear()
     d0 = ev.run(pack, policy_seed=PSEED, deterministic=True, **kw)
     assert seen and all(s[2] is True for s in seen)
-    _same_results(ev.run(pack, policy_seed=PSEED + 50, deterministic=True, **kw), d0, "deterministic: no draw is used")
+    dev.same_results(ev.run(pack, policy_seed=PSEED + 50, deterministic=True, **kw), d0,
+                     "deterministic: no draw is used")
     assert d0["rewards"] != a["rewards"], "the mean action is another evaluation than the sampled one"
-    _same_results(ev.run(pack, deterministic=True, **kw), d0, "policy_seed defaults to 0; unused when deterministic")
+    dev.same_results(ev.run(pack, deterministic=True, **kw), d0, "policy_seed defaults to 0; unused when deterministic")
     # two seeds that differ by one (two groups) share no draw: the eps of every row differs
     x = ev.groups[0].batch.obs
     n = x.shape[0]
@@ -226,22 +89,15 @@ def test_policy_seed_and_groups(monkeypatch):
 
 
 def test_deterministic_is_the_sampled_actors_own():
-    from distributional_rl_decision_and_control_amd.fused_dqn import DqnPack
-    from distributional_rl_decision_and_control_amd.fused_mlp import MlpPack
-    from distributional_rl_decision_and_control_amd.policy.AC_IQN_model import AC_IQN_Policy
-    from distributional_rl_decision_and_control_amd.policy.DQN_model import DQN_Policy
     from distributional_rl_decision_and_control_amd.policy.device_eval import DeviceEvaluator
-    from distributional_rl_decision_and_control_amd.vec_trainer import DEFAULT_NET
-    ev = DeviceEvaluator(_configs(False)[:1], chunk=5, gamma=GAMMA)
-    pol = AC_IQN_Policy(**DEFAULT_NET, value_ranges_of_action=[[-1, 1], [-1, 1]], device="cuda", seed=100)
-    actor = MlpPack(pol.actor, "actor")
+    ev = DeviceEvaluator(dev.configs(False)[:1], chunk=5, gamma=GAMMA)
+    actor = wc.pack(wc.CASES["actor"])
     with pytest.raises(ValueError, match="deterministic"):
         ev.run(actor, deterministic=True)
-    dqn = DqnPack(DQN_Policy(**DEFAULT_NET, action_size=25, device="cuda", seed=100).to("cuda"), "bf16")
     with pytest.raises(ValueError, match="deterministic"):
-        ev.run(dqn, deterministic=True)
+        ev.run(wc.pack(wc.CASES["dqn"], "bf16"), deterministic=True)
     # for the Actor's pack nothing changes: the greedy schedule uses no draw, whatever the seed
-    _same_results(ev.run(actor, episode_limit=LIMIT, policy_seed=5), ev.run(actor, episode_limit=LIMIT), "Actor")
+    dev.same_results(ev.run(actor, episode_limit=LIMIT, policy_seed=5), ev.run(actor, episode_limit=LIMIT), "Actor")
 
 
 # ------------------------------------------------------------------ VecTrainer
@@ -249,7 +105,7 @@ def test_vec_trainer_window_pack_and_device_evaluator():
     from distributional_rl_decision_and_control_amd.fused_sac import SacActorPack
     from distributional_rl_decision_and_control_amd.policy.device_eval import DeviceEvaluator
     from distributional_rl_decision_and_control_amd.vec_trainer import VecTrainer
-    cfgs = _configs()
+    cfgs = dev.configs(True)
     tr = VecTrainer(agent_type="SAC", n_envs=37, batch_size=64, buffer_size=4096, graphs=False)
     st = tr.fused_sac
     assert st.window_pack is st.actor and st.policy_pack is None and st.actor_pack is None
@@ -286,9 +142,9 @@ def test_vec_trainer_window_pack_and_device_evaluator():
     assert now["rewards"] != got["rewards"], "the updated actor is another policy"
     fresh = SacActorPack(tr.local.actor, st.operands)
     ref = DeviceEvaluator(cfgs, chunk=CHUNK, gamma=tr.gamma).run(fresh, episode_limit=LIMIT, seed=4, policy_seed=PSEED)
-    _same_results(now, ref, "the current image set against a fresh pack of tr.local.actor")
+    dev.same_results(now, ref, "the current image set against a fresh pack of tr.local.actor")
     for kw in (dict(), dict(deterministic=True)):
-        _same_results(ev.run(st.window_pack, episode_limit=LIMIT, seed=4, **kw),
+        dev.same_results(ev.run(st.window_pack, episode_limit=LIMIT, seed=4, **kw),
                       DeviceEvaluator(cfgs, chunk=CHUNK, gamma=tr.gamma).run(fresh, episode_limit=LIMIT, seed=4, **kw),
                       f"current image set {kw}")
     with pytest.raises(NotImplementedError):

@@ -6,48 +6,12 @@ import ctypes as C
 
 import pytest
 
-P = 0x1000   # a made-up, 16-byte aligned address
-NAMES = ("asvrl_sac_rollout", "asvrl_sac_rollout_ar")
-IMAGES = ("enc_frag", "b_enc", "w1_frag", "w2_frag", "b1", "b2", "wout", "bout")
+import rollout_abi_cases
+from rollout_abi_cases import P
 
-
-def _args(**over):
-    """Arguments that pass every check of both calls up to the launch (nothing is launched: every test overrides
-    one of them into a refusal). Overrides are obj__field=value; w__<image> sets a trunk image, sw__<name> the
-    head's weight or bias."""
-    from distributional_rl_decision_and_control_amd import _abi
-    from distributional_rl_decision_and_control_amd.device_env import reset_cfg
-    a = dict(params=_abi.params_from(), state=_abi.AsvEnvState(), ctl=_abi.AsvStepCtl(), out=_abi.AsvStepOut(),
-             ro=_abi.AsvRollout(), pi=_abi.AsvSacPolicy(), ar=_abi.AsvAutoReset())
-    st = a["state"]
-    st.n_envs, st.max_robots, st.max_obs, st.max_cores = 4, 5, 4, 2
-    for n in ("rs", "rflags", "n_robots", "n_obs", "n_cores", "ep_ts", "obstacles", "cores"):
-        setattr(st, n, P)
-    ctl = a["ctl"]
-    ctl.is_continuous, ctl.do_dynamics, ctl.trainer_deactivate, ctl.noise_mode = 1, 1, 1, 2
-    for n in ("obs", "obj_cnt", "reward", "done", "info", "env_done"):
-        setattr(a["out"], n, P)
-    a["ro"].n_steps = 3
-    pi = a["pi"]
-    pi.obs_in = P
-    for n in IMAGES:
-        setattr(pi.w.trunk, n, P)
-    pi.w.head, pi.w.bhead = P, P
-    a["ar"].cfg = reset_cfg(5, 4, 2)
-    for k, v in over.items():
-        obj, field = k.split("__")
-        setattr(a["pi"].w.trunk if obj == "w" else (a["pi"].w if obj == "sw" else a[obj]), field, v)
-    return a
-
-
-def _call(L, name, a, null=()):
-    order = ["params", "state", "ctl", "out", "ro", "pi"] + (["ar"] if name.endswith("_ar") else [])
-    return getattr(L, name)(*[None if k in null else C.byref(a[k]) for k in order], None, None)
-
-
-def _refused(L, name, text, null=(), **over):
-    assert _call(L, name, _args(**over), null) != 0, (name, text)
-    assert L.asvrl_last_error().decode() == f"{name}: {text}"
+RO = rollout_abi_cases.Rollout("sac")
+NAMES, IMAGES = RO.names, RO.images
+_refused = RO.refused
 
 
 @pytest.mark.parametrize("ops", ["bf16", "f32"])
@@ -121,26 +85,10 @@ def test_the_actor_call_is_unchanged(ops):
     """asvrl_policy_rollout keeps its struct, its checks and their texts: the SAC dispatch is a call of its own."""
     from distributional_rl_decision_and_control_amd import _abi
     L = _abi.lib(ops)
-
-    def call(pol, **over):
-        a = _args(**over)
-        return L.asvrl_policy_rollout(C.byref(a["params"]), C.byref(a["state"]), C.byref(a["ctl"]), C.byref(a["out"]),
-                                      C.byref(a["ro"]), None if pol is None else C.byref(pol), None, None)
-
-    def policy(**over):
-        pol = _abi.AsvPolicy()
-        pol.obs_in = P
-        for n in IMAGES:
-            setattr(pol.w, n, P)
-        for k, v in over.items():
-            setattr(pol.w if k in IMAGES else pol, k, v)
-        return pol
-
-    for pol, over, text in ((None, {}, "null policy"), (policy(obs_in=None), {}, "null obs_in"),
-                            (policy(), dict(ctl__is_continuous=0),
-                             "is_continuous must be 1 (the Actor is the continuous agent)"),
-                            (policy(wout=None), {}, "null actor image"),
-                            (policy(), dict(ro__actions=P), "ro->actions must be null (the policy supplies the actions)"),
-                            (policy(obs_in=P + 4), {}, "observation rows must be 16-byte aligned")):
-        assert call(pol, **over) != 0, text
-        assert L.asvrl_last_error().decode() == f"asvrl_policy_rollout: {text}"
+    actor, name = rollout_abi_cases.Rollout("actor"), "asvrl_policy_rollout"
+    actor.refused(L, name, "null policy", null=("pi",))
+    actor.refused(L, name, "null obs_in", pi__obs_in=None)
+    actor.refused(L, name, "is_continuous must be 1 (the Actor is the continuous agent)", ctl__is_continuous=0)
+    actor.refused(L, name, "null actor image", w__wout=None)
+    actor.refused(L, name, "ro->actions must be null (the policy supplies the actions)", ro__actions=P)
+    actor.refused(L, name, "observation rows must be 16-byte aligned", pi__obs_in=P + 4)
