@@ -222,6 +222,19 @@ class AsvEvalMetrics(C.Structure):
                                    "alive", "deact", "outcome", "ret", "time", "energy")]
 
 
+HISTORY_ROW_TILE, HISTORY_STEP_TILE = 32, 16   # asvrl_eval_history_pack's tile: robot rows x history entries
+TRAJ_DIM, HISTORY_OBS_DIM = 13, 32
+# the 13 trajectory values (wamv.py:191-193) as planes of rs: ..., left_pos, right_pos, left_thrust, right_thrust
+TRAJ_FIELDS = (F_X, F_Y, F_THETA, F_VR0, F_VR1, F_VR2, F_V0, F_V1, F_V2, F_LP, F_RP, F_TL, F_TR)
+HISTORY_ARRAYS = ("info", "length", "n_robots", "counts", "offsets", "rs0", "rs", "actions", "obs0", "obs", "cnt0",
+                  "obj_cnt", "traj", "act", "obs_out", "cnt_out")
+
+
+class AsvEvalHistory(C.Structure):
+    _fields_ = [("n_steps", _I32), ("n_envs", _I32), ("max_robots", _I32), ("act_steps", _I32)] + \
+               [(n, _VP) for n in HISTORY_ARRAYS] + [("traj_rows", _I64), ("act_rows", _I64), ("obs_rows", _I64)]
+
+
 class AsvNoiseStreams(C.Structure):
     _fields_ = [("n_envs", _I32), ("max_robots", _I32), ("max_obs", _I32), ("_pad0", _I32)] + \
                [(n, _VP) for n in ("n_robots", "n_obs", "rflags", "env_mask", "robot_params", "key", "pos", "has_gauss",
@@ -492,6 +505,10 @@ EXPORTS = [
                                            _VP, _VP, _VP, _I64, _VP]),
     ("asvrl_eval_metrics", C.c_int, [C.POINTER(AsvEvalMetrics), _VP]),
     ("asvrl_eval_metrics_struct_size", _I64, []),
+    ("asvrl_eval_history_count", C.c_int, [C.POINTER(AsvEvalHistory), _VP]),
+    ("asvrl_eval_history_pack", C.c_int, [C.POINTER(AsvEvalHistory), _VP]),
+    ("asvrl_eval_history_struct_size", _I64, []),
+    ("asvrl_eval_history_step_tile", _I32, []),
     ("asvrl_noise_streams", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvNoiseStreams), _VP]),
     ("asvrl_noise_streams_host", C.c_int, [C.POINTER(AsvParams), C.POINTER(AsvNoiseStreams), _VP]),
     ("asvrl_noise_streams_struct_size", _I64, []),

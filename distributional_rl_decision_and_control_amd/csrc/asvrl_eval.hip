@@ -1,5 +1,6 @@
 // asvrl_eval.hip -- the evaluation bookkeeping of Trainer.evaluation (trainer.py:286-303) over the records of
-// one hold_done rollout window: asvrl_eval_metrics.
+// one hold_done rollout window: asvrl_eval_metrics; and, further down, its per-robot histories (trainer.py:347-365)
+// cut out of episode-long records: asvrl_eval_history_count, asvrl_eval_history_pack.
 //
 // The rollout kernels end an episode by the training rule (every robot deactivated, or the step limit). The
 // evaluation rule also ends it at the first collision of any robot, and it accumulates, per robot that is not yet
@@ -93,12 +94,226 @@ __global__ __launch_bounds__(256) void eval_metrics_kernel(const AsvEvalMetrics 
   }
 }
 
+// ------------------------------------------------------------------ episode histories
+// asvrl_eval_history_count / asvrl_eval_history_pack: the observation, action and trajectory histories of
+// Trainer.evaluation (trainer.py:347-365) cut out of episode-long records.
+//
+// count: one lane per robot row, as above; a wave reads consecutive bytes of one info row per step.
+//
+// pack: a masked transpose. The records are contiguous across robot rows for a fixed (step, field); a robot's history
+// is contiguous across (step, field). A block of 256 threads takes kRows = 32 robot rows by kSteps = 16 history
+// entries and moves each of the three transposed arrays through one LDS tile, the tile re-used between them:
+//   trajectory  tile[16 * 13][33] f64. In: lane = row, 8 (entry, field) planes per pass, so a half-wave reads 32
+//               consecutive doubles; ds_write_b64 (bank (a/4) % 32, groups of 16 consecutive lanes) sees 16
+//               consecutive doubles = 32 banks. Out: a wave per robot row, lane = (entry, field) index p, consecutive
+//               doubles in HBM; ds_read_b64 (bank (a/4) % 64, groups of 32 lanes) reads tile[p][row] at dword
+//               2 * (33 p + row): 33 is odd, so 32 consecutive p land on the 32 even bank pairs once each.
+//   actions     tile[16][66] f64, the (row, component) pairs of one step contiguous. In: a wave per step reads 64
+//               consecutive doubles. Out: a half-wave per robot row, lane = (step, component); dword
+//               2 * (66 s + 2 row + c) = 4 s + 2 c + const mod 64: 32 lanes, 32 bank pairs.
+//   counts      tile[16][34] i32 (the i8 widened). In: lane = row, ds_write_b32 on consecutive dwords. Out: 16 lanes
+//               per robot row, lane = entry: ds_read_b32 (bank (a/4) % 32) at dword 34 s + row: a half-wave holds two
+//               rows, 2 s + row and 2 s + row + 1, 32 banks.
+// The observation rows need no transpose: the packed row of a (step, robot) is 160 contiguous bytes of which the
+// first 128 are kept, and a robot's consecutive entries are consecutive 128-byte rows of the output. Eight lanes
+// move one row as float4, consecutive lane groups take consecutive entries of one robot.
+// Per row the three counts bound every read and write; a tile with no entry below any of its rows' counts leaves
+// after reading the counts.
+constexpr int kHistRows = ASVRL_HISTORY_ROW_TILE, kHistSteps = ASVRL_HISTORY_STEP_TILE;
+constexpr int kTrajDim = ASVRL_TRAJ_DIM, kHistObs = ASVRL_HISTORY_OBS_DIM;
+constexpr int kTrajLd = kHistRows + 1, kActLd = 2 * kHistRows + 2, kCntLd = kHistRows + 2;
+static_assert(kHistRows == 32 && kHistSteps == 16, "the lane maps below are written for a 32 x 16 tile");
+
+__global__ __launch_bounds__(256) void eval_history_count_kernel(const AsvEvalHistory h) {
+  const int R = h.max_robots, T = h.n_steps;
+  const size_t NT = static_cast<size_t>(h.n_envs) * R;
+  const size_t row = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (row >= NT) return;
+  const int e = static_cast<int>(row / R), j = static_cast<int>(row - static_cast<size_t>(e) * R);
+  int n_traj = 0, n_act = 0, n_obs = 0;
+  if (j < h.n_robots[e]) {
+    const int L = min(max(h.length[e], 0), T);
+    n_act = L;
+    for (int s = 0; s < L; ++s) {
+      const uint8_t info = h.info[static_cast<size_t>(s) * NT + row];
+      if (info == ASVRL_INFO_COLLISION || info == ASVRL_INFO_REACH_GOAL) {
+        n_act = s + 1;
+        break;
+      }
+    }
+    n_traj = n_act + 1;
+    n_obs = L + 1;
+  }
+  h.counts[row] = n_traj;
+  h.counts[NT + row] = n_act;
+  h.counts[2 * NT + row] = n_obs;
+}
+
+__global__ __launch_bounds__(256) void eval_history_pack_kernel(const AsvEvalHistory h) {
+  __shared__ double tile[kHistSteps * kTrajDim * kTrajLd];
+  __shared__ int s_n[3][kHistRows];
+  __shared__ long long s_off[3][kHistRows];
+  const int T = h.n_steps;
+  const size_t NT = static_cast<size_t>(h.n_envs) * h.max_robots;
+  const int t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;
+  const size_t row0 = static_cast<size_t>(blockIdx.x) * kHistRows;
+  const int k0 = blockIdx.y * kHistSteps;   // the tile's first history entry
+
+  // the rows' counts, clamped to what the records hold and to the outputs' capacity
+  int any = 0;
+  if (t < 3 * kHistRows) {
+    const int q = t / kHistRows, r = t - q * kHistRows;
+    int n = 0;
+    long long off = 0;
+    if (row0 + r < NT) {
+      n = h.counts[q * NT + row0 + r];
+      off = h.offsets[q * NT + row0 + r];
+      const long long cap = q == 0 ? h.traj_rows : (q == 1 ? h.act_rows : h.obs_rows);
+      n = min(n, q == 1 ? min(T, h.act_steps) : T + 1);
+      if (off < 0 || off > cap) n = 0;
+      n = static_cast<int>(min(static_cast<long long>(n), cap - off));
+      n = max(n, 0);
+    }
+    s_n[q][r] = n;
+    s_off[q][r] = off;
+    any = n > k0;
+  }
+  if (__syncthreads_or(any) == 0) return;
+
+  // ---- trajectory: entry k of a row is rs0 (k = 0) or rs[k - 1], 13 of the 17 planes in wamv.py:191-193 order
+  {
+    const int r = t & (kHistRows - 1);
+    const int lim = s_n[0][r] - k0;   // entries of this row inside the tile
+    for (int p = t / kHistRows; p < kHistSteps * kTrajDim; p += 256 / kHistRows) {
+      const int ks = p / kTrajDim, c = p - ks * kTrajDim;
+      if (ks < lim) {
+        const int f = c < ASVRL_F_TL ? c : (c < ASVRL_F_TL + 2 ? c + 2 : c - 2);   // ..., LP, RP, TL, TR
+        const int k = k0 + ks;
+        const double* src = k == 0 ? h.rs0 : h.rs + static_cast<size_t>(k - 1) * ASVRL_NUM_FIELDS * NT;
+        tile[p * kTrajLd + r] = src[static_cast<size_t>(f) * NT + row0 + r];
+      }
+    }
+    __syncthreads();
+    for (int rr = wave; rr < kHistRows; rr += 256 / kWave) {
+      const int n = min(s_n[0][rr] - k0, kHistSteps) * kTrajDim;
+      double* dst = h.traj + (s_off[0][rr] + k0) * kTrajDim;
+      for (int p = lane; p < n; p += kWave) dst[p] = tile[p * kTrajLd + rr];
+    }
+    __syncthreads();
+  }
+
+  // ---- actions: entry k is actions[k]
+  {
+    for (int ks = wave; ks < kHistSteps; ks += 256 / kWave) {
+      const int r = lane >> 1;
+      if (ks < s_n[1][r] - k0)
+        tile[ks * kActLd + lane] = h.actions[(static_cast<size_t>(k0 + ks) * NT + row0) * 2 + lane];
+    }
+    __syncthreads();
+    const int half = t >> 5, p = t & 31;   // (step, component) of one row per half-wave
+    for (int rr = half; rr < kHistRows; rr += 256 / 32) {
+      const int n = min(s_n[1][rr] - k0, kHistSteps) * 2;
+      if (p < n) h.act[(s_off[1][rr] + k0) * 2 + p] = tile[(p >> 1) * kActLd + 2 * rr + (p & 1)];
+    }
+    __syncthreads();
+  }
+
+  // ---- object counts: entry k is cnt0 (k = 0) or obj_cnt[k - 1]
+  {
+    int* ctile = reinterpret_cast<int*>(tile);
+    const int r = t & (kHistRows - 1);
+    for (int ks = t / kHistRows; ks < kHistSteps; ks += 256 / kHistRows) {
+      if (ks < s_n[2][r] - k0) {
+        const int k = k0 + ks;
+        ctile[ks * kCntLd + r] = k == 0 ? h.cnt0[row0 + r] : h.obj_cnt[static_cast<size_t>(k - 1) * NT + row0 + r];
+      }
+    }
+    __syncthreads();
+    const int ks = t & (kHistSteps - 1);
+    for (int rr = t / kHistSteps; rr < kHistRows; rr += 256 / kHistSteps)
+      if (ks < s_n[2][rr] - k0) h.cnt_out[s_off[2][rr] + k0 + ks] = static_cast<int8_t>(ctile[ks * kCntLd + rr]);
+  }
+
+  // ---- observations: 8 lanes per (row, entry), 16 bytes each
+  {
+    const int sub = t & 7;
+    for (int pair = t >> 3; pair < kHistRows * kHistSteps; pair += 256 / 8) {
+      const int rr = pair / kHistSteps, ks = pair - rr * kHistSteps;
+      if (ks < s_n[2][rr] - k0) {
+        const int k = k0 + ks;
+        const float* src = k == 0 ? h.obs0 : h.obs + static_cast<size_t>(k - 1) * NT * ASVRL_OBS_DIM;
+        const float4 v = reinterpret_cast<const float4*>(src + (row0 + rr) * ASVRL_OBS_DIM)[sub];
+        reinterpret_cast<float4*>(h.obs_out + (s_off[2][rr] + k) * kHistObs)[sub] = v;
+      }
+    }
+  }
+}
+
 }  // namespace
 }  // namespace asvrl
 
 using namespace asvrl;
 
 extern "C" int64_t asvrl_eval_metrics_struct_size(void) { return sizeof(AsvEvalMetrics); }
+
+extern "C" int64_t asvrl_eval_history_struct_size(void) { return sizeof(AsvEvalHistory); }
+
+extern "C" int32_t asvrl_eval_history_step_tile(void) { return kHistSteps; }
+
+static int eval_history_check(const AsvEvalHistory* h, const std::string& who) {
+  ASVRL_REQUIRE(h != nullptr, who + ": null struct");
+  ASVRL_REQUIRE(h->n_steps >= 1, who + ": n_steps must be >= 1");
+  ASVRL_REQUIRE(h->n_envs >= 1, who + ": n_envs must be >= 1");
+  ASVRL_REQUIRE(h->max_robots >= 1 && h->max_robots <= 32, who + ": max_robots must be in 1..32");
+  return 0;
+}
+
+#define ASVRL_HIST_ARRAY(name) ASVRL_REQUIRE(h->name != nullptr, who + ": null array " #name)
+
+extern "C" int asvrl_eval_history_count(const AsvEvalHistory* h, void* stream) {
+  const std::string who = "asvrl_eval_history_count";
+  if (eval_history_check(h, who)) return 1;
+  ASVRL_HIST_ARRAY(info);
+  ASVRL_HIST_ARRAY(length);
+  ASVRL_HIST_ARRAY(n_robots);
+  ASVRL_HIST_ARRAY(counts);
+  const long long NT = static_cast<long long>(h->n_envs) * h->max_robots;
+  const int blocks = static_cast<int>((NT + 255) / 256);
+  hipLaunchKernelGGL(eval_history_count_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), *h);
+  return check_launch("asvrl_eval_history_count");
+}
+
+extern "C" int asvrl_eval_history_pack(const AsvEvalHistory* h, void* stream) {
+  const std::string who = "asvrl_eval_history_pack";
+  if (eval_history_check(h, who)) return 1;
+  ASVRL_REQUIRE(h->act_steps >= 1, who + ": act_steps must be >= 1");
+  ASVRL_REQUIRE(h->traj_rows >= 0 && h->act_rows >= 0 && h->obs_rows >= 0,
+                who + ": traj_rows, act_rows and obs_rows must be >= 0");
+  ASVRL_HIST_ARRAY(counts);
+  ASVRL_HIST_ARRAY(offsets);
+  ASVRL_HIST_ARRAY(rs0);
+  ASVRL_HIST_ARRAY(rs);
+  ASVRL_HIST_ARRAY(actions);
+  ASVRL_HIST_ARRAY(obs0);
+  ASVRL_HIST_ARRAY(obs);
+  ASVRL_HIST_ARRAY(cnt0);
+  ASVRL_HIST_ARRAY(obj_cnt);
+  ASVRL_REQUIRE(h->traj != nullptr || h->traj_rows == 0, who + ": null array traj");
+  ASVRL_REQUIRE(h->act != nullptr || h->act_rows == 0, who + ": null array act");
+  ASVRL_REQUIRE(h->obs_out != nullptr || h->obs_rows == 0, who + ": null array obs_out");
+  ASVRL_REQUIRE(h->cnt_out != nullptr || h->obs_rows == 0, who + ": null array cnt_out");
+  const auto aligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+  ASVRL_REQUIRE(aligned(h->obs0) && aligned(h->obs) && aligned(h->obs_out),
+                who + ": obs0, obs and obs_out must be 16-byte aligned");
+  const long long NT = static_cast<long long>(h->n_envs) * h->max_robots;
+  const int bx = static_cast<int>((NT + kHistRows - 1) / kHistRows);
+  const int by = (h->n_steps + 1 + kHistSteps - 1) / kHistSteps;
+  ASVRL_REQUIRE(by <= 65535, who + ": n_steps is too large for one launch");
+  hipLaunchKernelGGL(eval_history_pack_kernel, dim3(bx, by), dim3(256), 0, as_stream(stream), *h);
+  return check_launch("asvrl_eval_history_pack");
+}
+
+#undef ASVRL_HIST_ARRAY
 
 extern "C" int asvrl_eval_metrics(const AsvEvalMetrics* m, void* stream) {
   const std::string who = "asvrl_eval_metrics";

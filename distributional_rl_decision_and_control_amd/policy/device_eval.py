@@ -27,7 +27,17 @@ step long, because which robots draw depends on the deactivations of the step be
 the reference, Trainer.evaluation and evaluate_configs produce for the same configs and actions
 (tests/test_eval60_reference_noise_gpu.py). In both modes SAC's action noise is Philox + Box-Muller on (row, step,
 policy_seed + group), not torch's generator, and IQN's quantile fractions and the exploration draw are Philox too.
-Observation, action and trajectory histories are not kept.
+
+Observation, action and trajectory histories (trainer.py:347-365; what visualize_eval_episode.py plays back) are kept
+on request, run(histories=True): every group then records its windows into episode-long buffers of
+T = episode_limit + 1 steps (the window at t0 of length k takes the slices [t0:t0 + k] as its keep= tensors: no copy
+and no launch per window), 322 bytes per robot-step -- reward 8, info 1, rs 136, actions 16, obs 160, obj_cnt 1 --
+which is 97 MB for the 300 robot rows of the shipped schedule at the limit of 1000, allocated once and reused. At the
+end of the run asvrl_eval_history_count cuts them by the evaluation's rules (an env's records stop at its evaluation
+length L, a robot's actions and trajectory at its own collision or goal), and one asvrl_eval_history_pack launch per
+group writes four packed arrays in which every robot's history is contiguous (EvalHistory); history_lists turns them
+into the reference's nested lists. Observation values are the packed f32 rows the policy was fed, not the f64 the host
+paths keep. Without histories nothing of this is allocated or launched.
 """
 import ctypes as C
 
@@ -78,6 +88,131 @@ def new_metrics_state(E, R, device):
                 ret=torch.zeros(NT, **f64), time=torch.zeros(NT, **f64), energy=torch.zeros(NT, **f64))
 
 
+HISTORY_RECORDS = ("reward", "info", "rs", "actions", "obs", "obj_cnt")   # the episode-long records of histories=True
+HISTORY_BYTES = 8 + 1 + 8 * _abi.NUM_FIELDS + 16 + 4 * _abi.OBS_DIM + 1   # per robot-step: 322
+
+
+def _history_struct(T, E, R, act_steps=1):
+    h = _abi.AsvEvalHistory()
+    h.n_steps, h.n_envs, h.max_robots, h.act_steps = int(T), int(E), int(R), int(act_steps)
+    return h
+
+
+def _set(h, name, t, shape, dtype):
+    assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape), name
+    setattr(h, name, t.data_ptr() if t.numel() else None)
+
+
+def history_count(L, T, E, R, info, length, n_robots, counts=None, stream=None):
+    """asvrl_eval_history_count of library L: info [T, NT] u8 (episode-long), length [E] i32 (the evaluation's
+    lengths), n_robots [E] i32. Returns counts [3, NT] i32: per robot row its trajectory rows (n_act + 1), actions
+    (n_act) and observations (L + 1); zeros for an absent slot."""
+    NT = E * R
+    if counts is None:
+        counts = torch.zeros((3, NT), dtype=torch.int32, device=info.device)
+    h = _history_struct(T, E, R)
+    _set(h, "info", info, (T, NT), torch.uint8)
+    _set(h, "length", length, (E,), torch.int32)
+    _set(h, "n_robots", n_robots, (E,), torch.int32)
+    _set(h, "counts", counts, (3, NT), torch.int32)
+    _abi.check(L.asvrl_eval_history_count(C.byref(h), _abi.stream_ptr(stream)), "asvrl_eval_history_count", L)
+    return counts
+
+
+def history_offsets(counts):
+    """The exclusive scans of the three count planes, [3, NT] i64: where every robot row's history starts."""
+    return (torch.cumsum(counts, dim=1) - counts).contiguous()
+
+
+def history_pack(L, T, E, R, counts, offsets, src, out, stream=None):
+    """asvrl_eval_history_pack of library L. src: rs0 [17, NT] f64, rs [T, 17, NT] f64, actions [Ta, NT, 2] f64,
+    obs0 [NT, 40] f32, obs [T, NT, 40] f32, cnt0 [NT] i8, obj_cnt [T, NT] i8; out: traj [n, 13] f64, act [n, 2] f64,
+    obs [n, 32] f32, cnt [n] i8 with at least the sums of the count planes as their n (a smaller n drops what does
+    not fit, it is never written past)."""
+    NT = E * R
+    Ta = int(src["actions"].shape[0])
+    h = _history_struct(T, E, R, Ta)
+    _set(h, "counts", counts, (3, NT), torch.int32)
+    _set(h, "offsets", offsets, (3, NT), torch.int64)
+    _set(h, "rs0", src["rs0"], (_abi.NUM_FIELDS, NT), torch.float64)
+    _set(h, "rs", src["rs"], (T, _abi.NUM_FIELDS, NT), torch.float64)
+    _set(h, "actions", src["actions"], (Ta, NT, 2), torch.float64)
+    _set(h, "obs0", src["obs0"], (NT, _abi.OBS_DIM), torch.float32)
+    _set(h, "obs", src["obs"], (T, NT, _abi.OBS_DIM), torch.float32)
+    _set(h, "cnt0", src["cnt0"], (NT,), torch.int8)
+    _set(h, "obj_cnt", src["obj_cnt"], (T, NT), torch.int8)
+    h.traj_rows, h.act_rows, h.obs_rows = int(out["traj"].shape[0]), int(out["act"].shape[0]), int(out["obs"].shape[0])
+    _set(h, "traj", out["traj"], (h.traj_rows, _abi.TRAJ_DIM), torch.float64)
+    _set(h, "act", out["act"], (h.act_rows, 2), torch.float64)
+    _set(h, "obs_out", out["obs"], (h.obs_rows, _abi.HISTORY_OBS_DIM), torch.float32)
+    _set(h, "cnt_out", out["cnt"], (h.obs_rows,), torch.int8)
+    _abi.check(L.asvrl_eval_history_pack(C.byref(h), _abi.stream_ptr(stream)), "asvrl_eval_history_pack", L)
+
+
+class EvalHistory:
+    """The histories of one evaluation as four packed host arrays -- traj [sum(n_act + 1), 13] f64, act
+    [sum n_act, 2] f64, obs [sum(L + 1), 32] f32 and cnt [sum(L + 1)] i8 -- in which the history of every robot is
+    contiguous (robots in batch order: group by group, config by config; time fastest), and slices[c][i], the
+    (trajectory, action, observation) slices of config c's robot i into them. Everything the accessors return is a
+    view of those arrays, except a discrete policy's int64 action indices."""
+
+    def __init__(self, traj, act, obs, cnt, slices, continuous):
+        self.traj, self.act, self.obs, self.cnt = traj, act, obs, cnt
+        self.slices = slices
+        self.continuous = bool(continuous)
+
+    def trajectory(self, c, i):
+        """[n_act + 1, 13] f64: the reset row and the row after every step the robot acted in (wamv.py:191-193)."""
+        return self.traj[self.slices[c][i][0]]
+
+    def action(self, c, i):
+        """[n_act, 2] f64, the pairs the env was given; of a discrete policy [n_act] int64, the action indices."""
+        a = self.act[self.slices[c][i][1]]
+        return a if self.continuous else a[:, 0].astype(np.int64)
+
+    def observation(self, c, i):
+        """(self [L + 1, 7], objects [L + 1, 5, 5], count [L + 1]): the reset observation and the one after every
+        step of the episode; count < 0 is the reference's [None, None], else the first `count` objects hold."""
+        sl = self.slices[c][i][2]
+        o = self.obs[sl]
+        return o[:, :_abi.SELF_DIM], o[:, _abi.SELF_DIM:].reshape(-1, _abi.MAX_OBJ, _abi.OBJ_DIM), self.cnt[sl]
+
+    def _nested(self, get):
+        return [[get(c, i) for i in range(len(robots))] for c, robots in enumerate(self.slices)]
+
+    @property
+    def trajectories(self):
+        return self._nested(self.trajectory)
+
+    @property
+    def actions(self):
+        return self._nested(self.action)
+
+    @property
+    def observations(self):
+        return self._nested(self.observation)
+
+
+def history_lists(result):
+    """Fill observations / actions / trajectories of a run(histories=True) result with the reference's nested Python
+    lists (trainer.py:347-365): per config and robot the trajectory rows as lists of 13 floats, the actions as
+    [left, right] float pairs or, of a discrete policy, ints, and the observations as [self, objects] with self 7
+    floats and objects one list of 5 floats per perceived object, or [None, None]. Costs host time the arrays do not,
+    so it is a call of its own. Returns result."""
+    h = result.get("history")
+    if h is None:
+        raise ValueError("history_lists: the result has no histories (run(..., histories=True))")
+    for c, robots in enumerate(h.slices):
+        obs_c, act_c, traj_c = [], [], []
+        for i in range(len(robots)):
+            traj_c.append(h.trajectory(c, i).tolist())
+            act_c.append(h.action(c, i).tolist())
+            s, o, n = (a.tolist() for a in h.observation(c, i))
+            obs_c.append([[None, None] if k < 0 else [s[q], o[q][:k]] for q, k in enumerate(n)])
+        result["observations"][c], result["actions"][c], result["trajectories"][c] = obs_c, act_c, traj_c
+    return result
+
+
 def _check_perception(who, perception, *noises):
     if perception not in PERCEPTIONS:
         raise ValueError(f"{who}: perception must be one of {PERCEPTIONS}, not {perception!r}")
@@ -123,6 +258,7 @@ class _Group:
         self.state = new_metrics_state(E, R, device)
         self.step = torch.zeros(1, dtype=torch.int64, device=device)
         self._rec = {}
+        self._hist = {}
         self._streams = None
 
     def streams(self):
@@ -157,6 +293,31 @@ class _Group:
                    for n in RECORDS}
             rec["steps_run"] = torch.zeros(b.n_envs, dtype=torch.int32, device=b.device)
             self._rec[K] = rec
+        return rec
+
+    def history(self, T):
+        """The episode-long records of run(histories=True), allocated once per T = episode_limit + 1 and reused by
+        later runs: HISTORY_RECORDS as [T, ...] at the records' pre-fill, steps_run, the observation pass's rows
+        (obs0, cnt0; rs0 is initial["rs"]) and the counts of asvrl_eval_history_count. Rows at or behind an env's
+        evaluation end keep whatever an earlier window or run left there: nothing reads them."""
+        H = self._hist.get(T)
+        if H is None:
+            b = self.batch
+            specs = b._record_specs()
+            specs["actions"] = ((b.n_envs * b.max_robots, 2), torch.float64, 0)
+            H = {n: torch.full((T,) + specs[n][0], specs[n][2], dtype=specs[n][1], device=b.device)
+                 for n in HISTORY_RECORDS}
+            H["steps_run"] = torch.zeros(b.n_envs, dtype=torch.int32, device=b.device)
+            H["obs0"], H["cnt0"] = torch.zeros_like(b.obs), torch.zeros_like(b.obj_cnt)
+            H["counts"] = torch.zeros((3, b.n_envs * b.max_robots), dtype=torch.int32, device=b.device)
+            self._hist[T] = H
+        return H
+
+    @staticmethod
+    def window(H, t0, k, names):
+        """The window at t0 of length k as keep= tensors: the slices [t0:t0 + k] of the episode-long records."""
+        rec = {n: H[n][t0:t0 + k] for n in names}
+        rec["steps_run"] = H["steps_run"]
         return rec
 
 
@@ -236,7 +397,7 @@ class DeviceEvaluator:
 
     @torch.no_grad()
     def run(self, pack=None, *, actions=None, noise=None, obs_noise=None, seed=0, episode_limit=1000, sync=True,
-            is_continuous=None, policy_seed=0, deterministic=False, cvar=1.0, perception="philox"):
+            is_continuous=None, policy_seed=0, deterministic=False, cvar=1.0, perception="philox", histories=False):
         """One evaluation of every config. pack: the Actor's MlpPack or DQN's DqnPack, greedy in closed-loop
         windows, or SAC's SacActorPack, which samples its action as act_sac does in evaluation too (group g draws
         under policy_seed + g: rows are batch-local, so two groups share no draws) or, with deterministic=True (a
@@ -261,7 +422,13 @@ class DeviceEvaluator:
         noise= or obs_noise= with it, and any other value of perception, is a ValueError. policy_seed, IQN's tau
         draws, SAC's action noise and the exploration draw stay Philox in both modes. The result then also carries
         draws_n, draws_sum and draws_sq: per config, an array per robot of the count, sum and sum of squares of its
-        step draws in draw order (the observation pass's are not counted); in the Philox mode the three are None."""
+        step draws in draw order (the observation pass's are not counted); in the Philox mode the three are None.
+        histories: True keeps the episode's records (the module docstring: 322 bytes per robot-step over
+        episode_limit + 1 steps, allocated once) and adds "history", an EvalHistory: the packed trajectory, action,
+        observation and object-count arrays and every robot's slices of them; the action history is the `actions`
+        record of the windows or, teacher-forced, the caller's table, read as is_continuous says. observations /
+        actions / trajectories stay empty per robot until history_lists(result) fills them with the reference's
+        lists. False (the default) allocates and launches nothing for them."""
         if (pack is None) == (actions is None):
             raise ValueError("run takes the Actor's pack or an action table, not both")
         if pack is not None and not pack.is_policy:
@@ -281,13 +448,20 @@ class DeviceEvaluator:
             total = min(total, T)
         L = pack.L if pack is not None else _abi.lib()
         self.observe(obs_noise, seed, perception)
+        hist = names = None
+        if histories:   # the episode-long records, and what stands in front of step 0
+            hist = [grp.history(episode_limit + 1) for grp in self.groups]
+            names = HISTORY_RECORDS if pack is not None else tuple(n for n in HISTORY_RECORDS if n != "actions")
+            for grp, H in zip(self.groups, hist):
+                H["obs0"].copy_(grp.batch.obs)
+                H["cnt0"].copy_(grp.batch.obj_cnt)
         numpy_noise = perception == "numpy"
         t0 = self.windows = 0
         while t0 < total:
             k = 1 if numpy_noise else min(self.chunk, total - t0)
             for g, grp in enumerate(self.groups):
                 b, st = grp.batch, grp.state
-                rec = grp.records(k)
+                rec = grp.window(hist[g], t0, k, names) if histories else grp.records(k)
                 if numpy_noise:   # this step's rows from the streams of the robots still active
                     noise[g] = grp.streams().fill(b, env_mask=st["alive"])[None]
                 if pack is not None:
@@ -311,15 +485,59 @@ class DeviceEvaluator:
             if sync and not any(bool(grp.state["alive"].any().item()) for grp in self.groups):
                 break   # one host wait per window
         self.steps = t0
-        return self._result(check_ended=pack is None and total < episode_limit + 1, draws=numpy_noise)
+        if histories:   # the records, the action source per group and how to read it
+            hist = dict(L=L, T=episode_limit + 1, records=hist,
+                        actions=[H["actions"] for H in hist] if pack is not None else actions,
+                        continuous=pack.continuous if pack is not None else is_continuous)
+        return self._result(check_ended=pack is None and total < episode_limit + 1, draws=numpy_noise, hist=hist)
 
-    def _result(self, check_ended=False, draws=False):
+    def _history(self, hist, counts):
+        """The EvalHistory of a run: counts the host image of every group's count planes ([3, NT] each), read in
+        _result's one copy. Allocates the four packed outputs for all groups together, packs every group into its
+        part with one launch and brings each array over in one copy."""
+        counts = [c.astype(np.int64) for c in counts]
+        base = np.zeros((len(counts) + 1, 3), np.int64)
+        for g, c in enumerate(counts):
+            base[g + 1] = base[g] + c.sum(axis=1)
+        n_traj, n_act, n_obs = (int(v) for v in base[-1])
+        dev = self.device
+        out = dict(traj=torch.empty((n_traj, _abi.TRAJ_DIM), dtype=torch.float64, device=dev),
+                   act=torch.empty((n_act, 2), dtype=torch.float64, device=dev),
+                   obs=torch.empty((n_obs, _abi.HISTORY_OBS_DIM), dtype=torch.float32, device=dev),
+                   cnt=torch.empty(n_obs, dtype=torch.int8, device=dev))
+        slices = [None] * len(self.envs)
+        for g, grp in enumerate(self.groups):
+            b, H = grp.batch, hist["records"][g]
+            lo, hi = base[g], base[g + 1]
+            part = dict(traj=out["traj"][lo[0]:hi[0]], act=out["act"][lo[1]:hi[1]], obs=out["obs"][lo[2]:hi[2]],
+                        cnt=out["cnt"][lo[2]:hi[2]])
+            src = dict(rs0=grp.initial["rs"], rs=H["rs"], actions=hist["actions"][g], obs0=H["obs0"], obs=H["obs"],
+                       cnt0=H["cnt0"], obj_cnt=H["obj_cnt"])
+            history_pack(hist["L"], hist["T"], b.n_envs, b.max_robots, H["counts"], H["offsets"], src, part)
+            c = counts[g]
+            start = np.cumsum(c, axis=1) - c + lo[:, None]
+            R = b.max_robots
+            for le, cfg in enumerate(grp.members):
+                rows = range(le * R, le * R + self.n_robots[cfg])
+                slices[cfg] = [tuple(slice(int(start[q, r]), int(start[q, r] + c[q, r])) for q in range(3))
+                               for r in rows]
+        host = {n: t.cpu().numpy() for n, t in out.items()}
+        return EvalHistory(host["traj"], host["act"], host["obs"], host["cnt"], slices, hist["continuous"])
+
+    def _result(self, check_ended=False, draws=False, hist=None):
         # one copy: every group's lengths, ended flags, outcomes and sums in one f64 tensor
         parts = []
         for grp in self.groups:
             st = grp.state
             parts += [st["length"].double(), st["ended"].double(), st["outcome"].double(), st["ret"], st["time"],
                       st["energy"]]
+        if hist is not None:   # behind them every group's history counts; their scans stay on the device
+            for grp, H in zip(self.groups, hist["records"]):
+                b = grp.batch
+                history_count(hist["L"], hist["T"], b.n_envs, b.max_robots, H["info"], grp.state["length"],
+                              b.n_robots, counts=H["counts"])
+                H["offsets"] = history_offsets(H["counts"])
+                parts.append(H["counts"].double().reshape(-1))
         flat = torch.cat(parts).cpu().numpy()
         n = len(self.envs)
         out = dict(observations=[None] * n, actions=[None] * n, trajectories=[None] * n, rewards=[None] * n,
@@ -357,4 +575,11 @@ class DeviceEvaluator:
                 out["lengths"][c] = int(length[le])
                 for name in ("observations", "actions", "trajectories", "relations"):
                     out[name][c] = [[] for _ in range(k)]
+        if hist is not None:
+            counts = []
+            for grp in self.groups:
+                NT = grp.batch.n_envs * grp.batch.max_robots
+                counts.append(flat[at:at + 3 * NT].reshape(3, NT))
+                at += 3 * NT
+            out["history"] = self._history(hist, counts)
         return out

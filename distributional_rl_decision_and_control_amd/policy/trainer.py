@@ -15,7 +15,9 @@ files keep the reference's cadence and format; the trained networks are copied i
 With "device_eval": true in that dict (AC-IQN, DDPG, DQN, IQN and Rainbow) the evaluations run on the device with the
 batched trainer's own actor, Q network, quantile network or, for Rainbow, the mu-only (eval-mode) images of its online
 network (evaluation(batched="device"), policy/device_eval.py). "device_eval": {"perception": "numpy"} does the same
-with the perception noise drawn from every robot's own RandomState stream, as the other evaluation paths draw it.
+with the perception noise drawn from every robot's own RandomState stream, as the other evaluation paths draw it, and
+"device_eval": {"histories": true} also keeps every robot's observation, action and trajectory history, so
+evaluations.npz replays in the reference's visualize_eval_episode.py like the file of the other evaluation paths.
 """
 import json
 import os
@@ -175,13 +177,17 @@ class Trainer:
         # (DQN), quantile network (IQN) or eval-mode Rainbow network (evaluation(batched="device")) instead of copying the
         # networks out and stepping the Python eval envs. A dict in its place switches it on with options:
         # {"perception": "numpy"} draws the perception noise from the robots' own RandomState streams, as the other
-        # two evaluation paths do (DeviceEvaluator.run's perception)
+        # two evaluation paths do (DeviceEvaluator.run's perception); {"histories": true} keeps the observation, action
+        # and trajectory histories, so eval_observations / eval_actions / eval_trajectories and evaluations.npz have
+        # the reference's content (DeviceEvaluator.run's histories, device_eval.history_lists)
         opts = kw.pop("device_eval", False)
         if isinstance(opts, dict):
-            if set(opts) - {"perception"}:
-                raise ValueError(f"device_eval: unknown option(s) {sorted(set(opts) - {'perception'})}; it takes "
-                                 "\"perception\"")
+            if set(opts) - {"perception", "histories"}:
+                raise ValueError(f"device_eval: unknown option(s) {sorted(set(opts) - {'perception', 'histories'})}; "
+                                 "it takes \"perception\" and \"histories\"")
             self._device_eval_kw = dict(opts)
+            if "histories" in opts:
+                self._device_eval_kw["histories"] = bool(opts["histories"])
             opts = True
         else:
             self._device_eval_kw = {}
@@ -340,6 +346,9 @@ class Trainer:
             # Rainbow's eval_pack is Rainbow_Policy.eval(): the mu-only images, packed on this read
             res = tr.device_evaluator(self.eval_config, template_env=self.eval_env).run(
                 tr.learner.eval_pack, **getattr(self, "_device_eval_kw", {}))
+            if "history" in res:   # "device_eval": {"histories": true}: the reference's nested lists
+                from .device_eval import history_lists
+                history_lists(res)
             obs_d, act_d, traj_d = res["observations"], res["actions"], res["trajectories"]
             rew_d, succ_d, time_d, en_d, rel_d = (res["rewards"], res["successes"], res["times"], res["energies"],
                                                   res["relations"])

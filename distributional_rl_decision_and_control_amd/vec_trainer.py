@@ -241,7 +241,9 @@ class VecTrainer:
         (MarineNavEnv3.episode_data) are loaded into env batches once and cached; every call restores them, runs the
         current local actor greedily in closed-loop windows of `chunk` steps and reduces the windows to the
         reference's per-config rewards / successes / times / energies / lengths on the device. kw: run()'s seed,
-        episode_limit, sync and perception ("numpy": the robots' own RandomState streams, as the other paths draw). The actor's packed images are the learner's own, so no copy into a drop-in agent is
+        episode_limit, sync, perception ("numpy": the robots' own RandomState streams, as the other paths draw) and
+        histories (True: the result's "history" holds every robot's observation, action and trajectory history as
+        packed arrays; device_eval.history_lists turns them into the reference's lists). The actor's packed images are the learner's own, so no copy into a drop-in agent is
         needed; the training env, the replay and the step counter are not touched. AC-IQN and DDPG only."""
         if self.learner.actor_pack is None:
             raise NotImplementedError("evaluate runs the AC-IQN / DDPG actor; IQN, Rainbow and DQN act inside their "

@@ -1192,6 +1192,60 @@ int asvrl_eval_metrics(const AsvEvalMetrics* m, void* stream);
 /* sizeof(AsvEvalMetrics) as compiled. */
 int64_t asvrl_eval_metrics_struct_size(void);
 
+/* The episode histories of Trainer.evaluation (trainer.py:347-365; env.py:262-269, 348-351) cut out of episode-long
+ * rollout records: the records of every window of an evaluation kept time-major over T steps (row s of each array is
+ * step s of the episode), and length[e] = L the evaluation's own length after the run (AsvEvalMetrics.length).
+ *
+ * asvrl_eval_history_count: for robot row e * max_robots + j with j < n_robots[e], d = the first step s < min(L, T)
+ * with info ASVRL_INFO_COLLISION or ASVRL_INFO_REACH_GOAL, n_act = d + 1 when there is one and L otherwise;
+ * counts[0][row] = n_act + 1 (trajectory rows), counts[1][row] = n_act (actions), counts[2][row] = L + 1
+ * (observations). A slot beyond n_robots[e] gets three zeros. No info row at or behind L is read.
+ *
+ * asvrl_eval_history_pack: with offsets the exclusive scans of the three count planes, in one launch
+ *   traj   [offsets[0][row] + k][13]  k = 0: rs0, k > 0: rs[k - 1]; the 13 values in wamv.py:191-193 order (x, y, theta,
+ *                                      velocity_r, velocity, left_pos, right_pos, left_thrust, right_thrust)
+ *   act    [offsets[1][row] + k][2]   actions[k]
+ *   obs_out[offsets[2][row] + k][32]  k = 0: obs0, k > 0: obs[k - 1]; the first 32 floats of the packed row
+ *   cnt_out[offsets[2][row] + k]      k = 0: cnt0, k > 0: obj_cnt[k - 1]
+ * for k below the row's count: every robot's history contiguous, robots in batch order, time fastest. A block takes
+ * ASVRL_HISTORY_ROW_TILE rows by ASVRL_HISTORY_STEP_TILE steps; the f64 planes and the counts go through an LDS tile
+ * (read along rows, written along a robot's run), the observation rows are copied 128 bytes at a time. Nothing at
+ * or behind a row's count is read; a destination index at or past its *_rows capacity is not written. No atomics. */
+#define ASVRL_HISTORY_ROW_TILE 32
+#define ASVRL_HISTORY_STEP_TILE 16
+#define ASVRL_TRAJ_DIM 13          /* wamv.py:191-193 */
+#define ASVRL_HISTORY_OBS_DIM 32   /* self 7 | objects 5 x 5 of the packed row */
+
+typedef struct AsvEvalHistory {
+  int32_t n_steps;      /* T >= 1: rows of info, rs, obs and obj_cnt */
+  int32_t n_envs;       /* E >= 1 */
+  int32_t max_robots;   /* 1..32; NT = n_envs * max_robots */
+  int32_t act_steps;    /* >= 1: rows of actions (an action table may be shorter or longer than T) */
+  const uint8_t* info;       /* [T][NT] (count) */
+  const int32_t* length;     /* [E] (count) */
+  const int32_t* n_robots;   /* [E] (count) */
+  int32_t*       counts;     /* [3][NT] written by count, read by pack */
+  const int64_t* offsets;    /* [3][NT] exclusive scans of counts (pack) */
+  const double*  rs0;        /* [ASVRL_NUM_FIELDS][NT] the state in front of step 0 */
+  const double*  rs;         /* [T][ASVRL_NUM_FIELDS][NT] */
+  const double*  actions;    /* [act_steps][NT][2] */
+  const float*   obs0;       /* [NT][ASVRL_OBS_DIM] the observation pass's rows (16-byte aligned) */
+  const float*   obs;        /* [T][NT][ASVRL_OBS_DIM] (16-byte aligned) */
+  const int8_t*  cnt0;       /* [NT] */
+  const int8_t*  obj_cnt;    /* [T][NT] */
+  double* traj;              /* [traj_rows][13] */
+  double* act;               /* [act_rows][2]; may be NULL when act_rows == 0 */
+  float*  obs_out;           /* [obs_rows][32] (16-byte aligned) */
+  int8_t* cnt_out;           /* [obs_rows] */
+  int64_t traj_rows, act_rows, obs_rows;   /* the sums of the three count planes */
+} AsvEvalHistory;
+
+int asvrl_eval_history_count(const AsvEvalHistory* h, void* stream);
+int asvrl_eval_history_pack(const AsvEvalHistory* h, void* stream);
+/* sizeof(AsvEvalHistory) as compiled, and ASVRL_HISTORY_STEP_TILE. */
+int64_t asvrl_eval_history_struct_size(void);
+int32_t asvrl_eval_history_step_tile(void);
+
 /* ---------------------------------------------------------------- the reference's perception-noise streams */
 
 /* One env step's perception noise drawn from every robot's own numpy.random.RandomState stream (wamv.py:5-40,

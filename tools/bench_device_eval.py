@@ -16,6 +16,11 @@ another stream, so nothing is asserted on them. One process, no retries; run it 
 --agent DQN: the same procedure with a seeded Agent(agent_type="DQN") (no trained DQN network is shipped) and its
 DqnPack in the closed-loop windows; the default output is profiles/device_eval_dqn.json (its golden_* fields stay
 the trained AC-IQN network's, for the record only).
+
+--histories: no host evaluation; the device evaluation without histories, with them as packed arrays
+(run(histories=True)) and with device_eval.history_lists on top, alternating; then the asvrl_eval_history_pack launch
+alone with its achieved bytes per second, against the same packing by torch (permute and boolean mask), whose outputs
+are first compared with the kernel's byte for byte. The default output is profiles/eval_histories.json.
 """
 import argparse
 import json
@@ -33,6 +38,105 @@ SCHEDULE = {"num_episodes": [10] * 6, "num_robots": [3, 4, 5, 5, 5, 5], "num_cor
             "num_obstacles": [0, 0, 0, 2, 3, 4], "min_start_goal_dis": [30.0, 35.0, 40.0, 40.0, 40.0, 40.0]}
 
 
+HBM_BYTES_PER_S = 8.0e12   # MI355X HBM3E peak, for the pack launch's share
+
+
+def torch_pack(grp, H, actions, counts, steps):
+    """The packing of asvrl_eval_history_pack by the obvious torch route: put the row in front of step 0 on top of
+    the records' first `steps` rows, permute to robot-major and select with a boolean mask of the counts."""
+    from distributional_rl_decision_and_control_amd import _abi
+    k = torch.arange(steps + 1, device=counts.device)[None, :]
+    n_traj, n_act, n_obs = (counts[q].long()[:, None] for q in range(3))
+    fields = torch.tensor(_abi.TRAJ_FIELDS, device=counts.device)
+    rs = torch.cat([grp.initial["rs"][None], H["rs"][:steps]])[:, fields]             # [steps + 1, 13, NT]
+    obs = torch.cat([H["obs0"][None], H["obs"][:steps]])[:, :, :_abi.HISTORY_OBS_DIM]   # [steps + 1, NT, 32]
+    cnt = torch.cat([H["cnt0"][None], H["obj_cnt"][:steps]])
+    return dict(traj=rs.permute(2, 0, 1)[k < n_traj], act=actions[:steps].permute(1, 0, 2)[k[:, :steps] < n_act],
+                obs=obs.permute(1, 0, 2)[k < n_obs], cnt=cnt.permute(1, 0)[k < n_obs])
+
+
+def histories(a, ev, pack, clock, z):
+    """--histories: the per-evaluation time without histories, with them as packed arrays and with history_lists on
+    top (alternating, after a warm-up round of each); then the pack launch alone on the last run's records (device
+    events around --kernel-launches launches, and a host clock around one launch and a synchronise) against
+    torch_pack on the same records (a host clock: its mask selection waits for the device itself), compared byte
+    for byte first."""
+    from distributional_rl_decision_and_control_amd.policy import device_eval as de
+    runs = {"off": lambda: ev.run(pack, seed=1),
+            "arrays": lambda: ev.run(pack, seed=1, histories=True),
+            "lists": lambda: de.history_lists(ev.run(pack, seed=1, histories=True))}
+    times = {k: [] for k in runs}
+    last = {}
+    for rep in range(a.reps + 1):   # the first round is the warm-up (it also allocates the episode-long records)
+        for name, fn in runs.items():
+            s, last[name] = clock(fn)
+            if rep > 0:
+                times[name].append(s)
+    assert len(ev.groups) == 1 and not any(last["off"][n][0][0] for n in ("observations", "actions", "trajectories"))
+    assert all(last["off"][n] == last["arrays"][n] for n in ("lengths", "successes", "rewards", "times", "energies")), \
+        "histories changed the metrics"
+    h = last["arrays"]["history"]
+    grp = ev.groups[0]
+    b = grp.batch
+    T = 1001
+    H = grp.history(T)
+    counts, offsets = H["counts"], H["offsets"]
+    totals = [int(v) for v in counts.sum(dim=1).cpu()]
+    assert totals == [len(h.traj), len(h.act), len(h.obs)]
+    out = dict(traj=torch.empty((totals[0], 13), dtype=torch.float64, device="cuda"),
+               act=torch.empty((totals[1], 2), dtype=torch.float64, device="cuda"),
+               obs=torch.empty((totals[2], 32), dtype=torch.float32, device="cuda"),
+               cnt=torch.empty(totals[2], dtype=torch.int8, device="cuda"))
+    src = dict(rs0=grp.initial["rs"], rs=H["rs"], actions=H["actions"], obs0=H["obs0"], obs=H["obs"], cnt0=H["cnt0"],
+               obj_cnt=H["obj_cnt"])
+
+    def launch():
+        de.history_pack(pack.L, T, b.n_envs, b.max_robots, counts, offsets, src, out)
+    steps = max(last["arrays"]["lengths"])
+    ref = torch_pack(grp, H, H["actions"], counts, steps)
+    launch()
+    torch.cuda.synchronize()
+    for n in out:
+        assert torch.equal(out[n], ref[n]), f"torch route and kernel differ in {n}"
+        assert out[n].cpu().numpy().tobytes() == getattr(h, n).tobytes(), n
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(a.kernel_launches):
+        launch()
+    e1.record()
+    torch.cuda.synchronize()
+    pack_us = 1e3 * e0.elapsed_time(e1) / a.kernel_launches
+    pack_host, torch_host = [], []
+    for _ in range(max(a.reps, 5)):
+        pack_host.append(1e6 * clock(launch)[0])
+        torch_host.append(1e6 * clock(lambda: torch_pack(grp, H, H["actions"], counts, steps))[0])
+    payload = totals[0] * 13 * 8 + totals[1] * 16 + totals[2] * (32 * 4 + 1)   # bytes read = bytes written
+    med = lambda v: sorted(v)[len(v) // 2]   # noqa: E731
+    res = {"agent": a.agent, "configs": len(ev.envs), "chunk": a.chunk, "reps": a.reps, "robot_rows": b.n_envs * b.max_robots,
+           "record_steps": T, "record_bytes": de.HISTORY_BYTES * T * b.n_envs * b.max_robots,
+           "env_steps": int(sum(last["arrays"]["lengths"])), "longest_episode": steps,
+           "history_rows": dict(zip(("traj", "act", "obs"), totals)),
+           "off_s": times["off"], "arrays_s": times["arrays"], "lists_s": times["lists"],
+           "off_s_median": med(times["off"]), "arrays_s_median": med(times["arrays"]),
+           "lists_s_median": med(times["lists"]),
+           "off_spread_s": max(times["off"]) - min(times["off"]),
+           "arrays_spread_s": max(times["arrays"]) - min(times["arrays"]),
+           "lists_spread_s": max(times["lists"]) - min(times["lists"]),
+           "pack_launches": a.kernel_launches, "pack_us": pack_us, "pack_payload_bytes": 2 * payload,
+           "pack_bytes_per_s": 2 * payload / (pack_us * 1e-6),
+           "pack_share_of_hbm_peak": 2 * payload / (pack_us * 1e-6) / HBM_BYTES_PER_S,
+           "pack_host_us": pack_host, "pack_host_us_median": med(pack_host),
+           "torch_route_host_us": torch_host, "torch_route_host_us_median": med(torch_host),
+           "golden_success_rate": float(np.mean(z["trained/successes"])),
+           "device_success_rate": float(np.mean(last["arrays"]["successes"]))}
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
@@ -40,9 +144,14 @@ def main():
     ap.add_argument("--kernel-launches", type=int, default=200)
     ap.add_argument("--agent", default="AC-IQN", choices=("AC-IQN", "DQN"))
     ap.add_argument("--out", default=None)
+    ap.add_argument("--histories", action="store_true",
+                    help="time the device evaluation without histories, with them as arrays and with history_lists, "
+                         "the pack launch alone and the same packing by torch (no host evaluation)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "device_eval_dqn.json" if a.agent == "DQN" else "device_eval.json")
+        name = "eval_histories.json" if a.histories else ("device_eval_dqn.json" if a.agent == "DQN"
+                                                          else "device_eval.json")
+        a.out = os.path.join(ROOT, "profiles", name)
     assert torch.cuda.is_available(), "this benchmark needs the GPU"
     from distributional_rl_decision_and_control_amd import _abi
     from distributional_rl_decision_and_control_amd.agent import Agent
@@ -71,6 +180,8 @@ def main():
         return time.perf_counter() - t0, out
 
     load_s, ev = clock(lambda: DeviceEvaluator(configs, template_env=tr.eval_env, chunk=a.chunk, gamma=agent.GAMMA))
+    if a.histories:
+        return histories(a, ev, pack, clock, z)
     runs = {"host": lambda: evaluate_configs(agent, configs, template_env=tr.eval_env),
             "device_sync": lambda: ev.run(pack, seed=1),
             "device_nosync": lambda: ev.run(pack, seed=1, sync=False)}
