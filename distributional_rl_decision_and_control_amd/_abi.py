@@ -156,6 +156,15 @@ class AsvIqnPolicy(C.Structure):
                [("actions", _VP), ("cvar", C.c_float), ("_pad0", _I32)]
 
 
+# the per-row risk level of asvrl_iqn_act_risk / asvrl_iqn_rollout_risk: AsvIqnRisk.mode
+IQN_RISK_ROWS, IQN_RISK_ADAPTIVE = 1, 2
+
+
+class AsvIqnRisk(C.Structure):
+    _fields_ = [("mode", _I32), ("near", C.c_float), ("margin", C.c_float), ("floor", C.c_float),
+                ("cvar_rows", _VP), ("cvar_out", _VP)]
+
+
 MAX_SUM_SEGS = 24
 
 
@@ -395,6 +404,10 @@ def _rollout_exports():
     for name, policy in ROLLOUTS.values():
         yield name, C.c_int, head + [C.POINTER(policy)] + tail
         yield name + "_ar", C.c_int, head + [C.POINTER(policy), C.POINTER(AsvAutoReset)] + tail
+    # IQN's windows under a per-row risk level: the IQN calls with the AsvIqnRisk behind the policy
+    risk = [C.POINTER(AsvIqnPolicy), C.POINTER(AsvIqnRisk)]
+    yield "asvrl_iqn_rollout_risk", C.c_int, head + risk + tail
+    yield "asvrl_iqn_rollout_risk_ar", C.c_int, head + risk + [C.POINTER(AsvAutoReset)] + tail
 
 
 EXPORTS = [
@@ -542,6 +555,9 @@ EXPORTS = [
     ("asvrl_iqn_act_ex", C.c_int, [C.POINTER(AsvCriticWeights), C.POINTER(AsvIqnHead), C.POINTER(AsvIqnIO),
                                    C.POINTER(AsvIqnActEx), _VP]),
     ("asvrl_iqn_act_ex_struct_size", _I64, []),
+    ("asvrl_iqn_act_risk", C.c_int, [C.POINTER(AsvCriticWeights), C.POINTER(AsvIqnHead), C.POINTER(AsvIqnIO),
+                                     C.POINTER(AsvIqnActEx), C.POINTER(AsvIqnRisk), _VP]),
+    ("asvrl_iqn_risk_struct_size", _I64, []),
     ("asvrl_iqn_policy_struct_size", _I64, []),
     ("asvrl_rainbow_net_act_ex", C.c_int, [C.POINTER(AsvRainbowImg), C.POINTER(AsvRainbowNetIO),
                                            C.POINTER(AsvRainbowActEx), _VP]),

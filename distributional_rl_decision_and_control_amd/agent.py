@@ -241,6 +241,25 @@ class Agent:
             action = random.choice(np.arange(self.action_size))
         return action, quantiles.cpu().data.numpy(), taus.cpu().data.numpy()
 
+    def adjust_cvar(self, state, near=10.0, margin=2.8, floor=0.1):
+        """The risk level from the closest object (agent.py:342-358, commented out there): 1 without objects or at
+        d = |p0| - r0 - margin >= near, else d / near -- with a floor, which the reference's rule lacks (its level
+        goes negative inside the margin). Host numpy f64 on the (self, objects) state; fused_iqn.AdaptiveCvar is the
+        same rule in f32 on packed rows, inside the act kernel."""
+        assert len(state) == 2, "The number of elements in state must be 2!"
+        _, objects = state
+        if len(objects) == 0:
+            return 1.0
+        closest = np.asarray(objects[0], dtype=np.float64)
+        d = float(np.linalg.norm(closest[:2]) - closest[4] - margin)
+        return 1.0 if d >= near else max(d / near, float(floor))
+
+    def act_adaptive_iqn(self, state, eps=0.0, use_eval=True, taus=None):
+        """act_iqn at the level adjust_cvar picks for this state (agent.py:331-340): (action, quantiles, taus, cvar)."""
+        cvar = self.adjust_cvar(state)
+        action, quantiles, taus = self.act_iqn(state, eps, cvar, use_eval=use_eval, taus=taus)
+        return action, quantiles, taus, cvar
+
     def act_rainbow(self, state, eps=0.0, use_eval=True):
         s = self._batch1(state)
         self.policy_local.eval() if use_eval else self.policy_local.train()

@@ -33,6 +33,19 @@ int launch_partial_sum(const float* partial, int groups, int nw, int nb, float* 
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// What asvrl_iqn_act_risk and the two _risk windows refuse in an AsvIqnRisk (nullptr: nothing). have_obs: the act
+// pass gets observation rows (the adaptive rule reads them; precomputed features carry none).
+inline const char* iqn_risk_problem(const AsvIqnRisk* r, bool have_obs) {
+  if (r == nullptr) return "null risk";
+  if (r->mode == ASVRL_IQN_RISK_ROWS) return r->cvar_rows != nullptr ? nullptr : "the rows mode needs risk->cvar_rows";
+  if (r->mode != ASVRL_IQN_RISK_ADAPTIVE) return "risk->mode must be ASVRL_IQN_RISK_ROWS or ASVRL_IQN_RISK_ADAPTIVE";
+  if (!have_obs) return "the adaptive mode needs io->obs (the rule reads the observation row)";
+  if (!(r->near > 0.f && r->near <= 3.4e38f)) return "risk->near must be > 0";
+  if (!(r->margin >= -3.4e38f && r->margin <= 3.4e38f)) return "risk->margin must be finite";
+  if (!(r->floor > 0.f && r->floor <= 1.f)) return "risk->floor must be in (0, 1]";
+  return nullptr;
+}
+
 // compute units of the current device (cached; 256 on MI355X when the query fails)
 inline int cu_count() {
   static int n = 0;

@@ -31,6 +31,7 @@
 //              (agent.py:455-468); the output layer's gradient leaves as a one-hot bf16
 //              [R][32] matrix so its weight gradient is one more 32 x 128 MFMA reduction
 //   IQN_ACT    act_iqn (agent.py:227-256): mean over K = 32 taus per state, argmax, epsilon-greedy
+//   IQN_ACT_RISK IQN_ACT_EX with the factor per state (asvrl_iqn_act_risk): AsvIqnRisk's rows or its adaptive rule
 //   IQN_ACT_EX the same pass as the rollout windows launch it (asvrl_iqn_act_ex): taus * cvar, step + step_add,
 //              the (index, 0.0) pair and its masked record row, the action values
 #include "asvrl_common.h"
@@ -165,10 +166,11 @@ template <int NT> struct CriticWaves { static constexpr int n = NT == 32 ? 8 : 4
 template <int MODE, int NT> struct ModeWaves { static constexpr int n = CriticWaves<NT>::n; };
 template <> struct ModeWaves<MODE_IQN_ACT, 32> { static constexpr int n = ASVRL_IQN_ACT_WAVES; };
 template <> struct ModeWaves<MODE_IQN_ACT_EX, 32> { static constexpr int n = ASVRL_IQN_ACT_WAVES; };
+template <> struct ModeWaves<MODE_IQN_ACT_RISK, 32> { static constexpr int n = ASVRL_IQN_ACT_WAVES; };
 
-// one workgroup of critic_kernel (ex: IQN_ACT_EX's additions, null in every other mode)
+// one workgroup of critic_kernel (ex: IQN_ACT_EX's additions, null in every other mode; risk: IQN_ACT_RISK's)
 template <int MODE, int NT>
-__device__ __forceinline__ void critic_block(const CriticArgs& a, const AsvIqnActEx* ex) {
+__device__ __forceinline__ void critic_block(const CriticArgs& a, const AsvIqnActEx* ex, const AsvIqnRisk* risk = nullptr) {
   constexpr int W = ModeWaves<MODE, NT>::n, S = 32 / NT;
   __shared__ typename LdsOf<MODE>::T L;
   using FT = typename FOf<MODE>::T;
@@ -209,7 +211,7 @@ __device__ __forceinline__ void critic_block(const CriticArgs& a, const AsvIqnAc
   const bool wout = MODE == MODE_TRAIN && a.acts.wout_part != nullptr;
   float* wsum = wout ? Ws + (threadIdx.x >> 6) * (kH + 1) : nullptr;
   if (tile < tiles) {
-    critic_tile<MODE, NT>(a, L, tile, lane, Fw, Gw, wsum, nullptr, ex);
+    critic_tile<MODE, NT>(a, L, tile, lane, Fw, Gw, wsum, nullptr, ex, risk);
   } else if (wout) {
     for (int i = lane; i < kH + 1; i += 64) wsum[i] = 0.f;
   }
@@ -233,6 +235,12 @@ __global__ __launch_bounds__((ModeWaves<MODE, NT>::n) * 64) void critic_kernel(C
 // asvrl_iqn_act_ex: IQN_ACT's workgroup (16 waves, one state's 32 taus per wave) with the window's additions
 __global__ __launch_bounds__((ModeWaves<MODE_IQN_ACT_EX, 32>::n) * 64) void iqn_act_ex_kernel(CriticArgs a, AsvIqnActEx x) {
   critic_block<MODE_IQN_ACT_EX, 32>(a, &x);
+}
+
+// asvrl_iqn_act_risk: the same workgroup with the CVaR factor per state
+__global__ __launch_bounds__((ModeWaves<MODE_IQN_ACT_RISK, 32>::n) * 64) void iqn_act_risk_kernel(CriticArgs a, AsvIqnActEx x,
+                                                                                                  AsvIqnRisk r) {
+  critic_block<MODE_IQN_ACT_RISK, 32>(a, &x, &r);
 }
 
 int train_b_grid(int tiles) { return (tiles + 7) / 8; }
@@ -488,5 +496,29 @@ extern "C" int asvrl_iqn_act_ex(const AsvCriticWeights* w, const AsvIqnHead* hea
 }
 
 extern "C" int64_t asvrl_iqn_act_ex_struct_size(void) { return sizeof(AsvIqnActEx); }
+
+extern "C" int asvrl_iqn_act_risk(const AsvCriticWeights* w, const AsvIqnHead* head, const AsvIqnIO* io,
+                                  const AsvIqnActEx* ex, const AsvIqnRisk* risk, void* stream) {
+  if (int rc = iqn_validate(w, head, io)) return rc;
+  ASVRL_REQUIRE(ex != nullptr, "asvrl_iqn_act_risk: null ex");
+  if (const char* what = iqn_risk_problem(risk, io->obs != nullptr)) {
+    set_error(std::string("asvrl_iqn_act_risk: ") + what);
+    return 1;
+  }
+  ASVRL_REQUIRE(io->N == 32, "asvrl_iqn_act_risk: K = 32 quantile samples per state");
+  ASVRL_REQUIRE((io->act_out || ex->act_pair || ex->rec_row) && (!io->act_out || io->ld_act >= 1) &&
+                    io->eps_total > 0.0 && io->eps_fraction > 0.0,
+                "asvrl_iqn_act_risk: needs act_out with ld_act (or act_pair / rec_row) and the epsilon schedule");
+  ASVRL_REQUIRE(ex->cvar == 1.f, "asvrl_iqn_act_risk: ex->cvar must be 1 (the level comes from risk)");
+  ASVRL_REQUIRE(ex->robots_per_env >= 1, "asvrl_iqn_act_risk: robots_per_env must be >= 1");
+  ASVRL_REQUIRE(!ex->qmean_out || ex->ld_q >= head->n_actions, "asvrl_iqn_act_risk: ld_q must cover n_actions");
+  if (io->B == 0) return 0;
+  const CriticArgs a = iqn_args(w, head, io);
+  constexpr int W = ModeWaves<MODE_IQN_ACT_RISK, 32>::n;
+  hipLaunchKernelGGL(iqn_act_risk_kernel, dim3((a.B + W - 1) / W), dim3(W * 64), 0, as_stream(stream), a, *ex, *risk);
+  return check_launch("asvrl_iqn_act_risk");
+}
+
+extern "C" int64_t asvrl_iqn_risk_struct_size(void) { return sizeof(AsvIqnRisk); }
 
 extern "C" int32_t asvrl_critic_wout_groups(int32_t B, int32_t N) { return wout_groups(B, N); }

@@ -13,10 +13,13 @@ namespace ctile {
 
 constexpr int kC = 256, kH = 128, kNcos = 64;
 enum { MODE_FWD = 0, MODE_TRAIN = 1, MODE_ACTOR = 2, MODE_IQN_MAX = 3, MODE_IQN_TRAIN = 4, MODE_IQN_ACT = 5,
-       MODE_IQN_ACT_EX = 6 };
+       MODE_IQN_ACT_EX = 6, MODE_IQN_ACT_RISK = 7 };
 // IQN_ACT_EX: the window form of IQN_ACT (asvrl_iqn_act_ex): the same tile with AsvIqnActEx's CVaR factor, step
 // offset, action pair / record row and action values; an instantiation of its own, so IQN_ACT's code stays put
-template <int MODE> constexpr bool kAct = MODE == MODE_IQN_ACT || MODE == MODE_IQN_ACT_EX;
+// IQN_ACT_RISK: IQN_ACT_EX with the factor per state (asvrl_iqn_act_risk: AsvIqnRisk's rows, or its rule on the
+// state's observation row); again an instantiation of its own, so the two above compile to what they did
+template <int MODE> constexpr bool kActEx = MODE == MODE_IQN_ACT_EX || MODE == MODE_IQN_ACT_RISK;
+template <int MODE> constexpr bool kAct = MODE == MODE_IQN_ACT || kActEx<MODE>;
 constexpr int kMaxA = ASVRL_IQN_MAX_ACTIONS;
 template <int MODE> constexpr bool kIqn = MODE >= MODE_IQN_MAX;
 template <int MODE> constexpr bool kTrainMode = MODE == MODE_TRAIN || MODE == MODE_IQN_TRAIN;
@@ -103,6 +106,7 @@ template <> struct LdsOf<MODE_IQN_MAX> { using T = CriticLdsIqn; };
 template <> struct LdsOf<MODE_IQN_TRAIN> { using T = CriticLdsIqn; };
 template <> struct LdsOf<MODE_IQN_ACT> { using T = CriticLdsIqn; };
 template <> struct LdsOf<MODE_IQN_ACT_EX> { using T = CriticLdsIqn; };
+template <> struct LdsOf<MODE_IQN_ACT_RISK> { using T = CriticLdsIqn; };
 // the staged F rows: f32 copies of the operand-rounded values (no per-use conversion) in the AC-IQN
 // modes; operand-typed in the IQN modes, whose larger LDS image leaves no room for them
 template <int MODE> struct FOf { using T = float; };
@@ -110,6 +114,7 @@ template <> struct FOf<MODE_IQN_MAX> { using T = elem_t; };
 template <> struct FOf<MODE_IQN_TRAIN> { using T = elem_t; };
 template <> struct FOf<MODE_IQN_ACT> { using T = elem_t; };
 template <> struct FOf<MODE_IQN_ACT_EX> { using T = elem_t; };
+template <> struct FOf<MODE_IQN_ACT_RISK> { using T = elem_t; };
 static_assert(sizeof(CriticLdsIqn) <= 160 * 1024, "IQN LDS image exceeds the CU's 160 KB");
 
 // The wave's feature rows in LDS for its 32 / NT samples: F (bf16 [S][256]) = observation_processor
@@ -198,14 +203,36 @@ __device__ __forceinline__ float act_tau(const CriticArgs& a, int grow, const As
   return static_cast<float>(u.x >> 8) * (1.0f / 16777216.0f);
 }
 
+// IQN_ACT_RISK: the risk level of state b (one 32-tau tile, so one wave: b is wave-uniform). Every lane evaluates it
+// on the same addresses -- uniform loads and a handful of VALU instructions, no cross-lane traffic -- and the
+// first lane's copy is made the wave's (readfirstlane), so the level lives in a scalar register through the tile.
+// Rows: risk->cvar_rows[b]. Adaptive: AsvIqnRisk's rule on the observation row (object 0 = the nearest: columns
+// 7, 8 its position, 11 its radius, 32 its mask), f32.
+__device__ __forceinline__ float iqn_risk_level(const CriticArgs& a, const AsvIqnRisk* risk, int b) {
+  const int bu = __builtin_amdgcn_readfirstlane(b);
+  float cv;
+  if (risk->mode == ASVRL_IQN_RISK_ROWS) {
+    cv = risk->cvar_rows[bu];
+  } else {
+    const float* x = a.obs + static_cast<int64_t>(bu) * a.ld_obs;
+    const float px = x[kSelfIn], py = x[kSelfIn + 1], rad = x[kSelfIn + 4], mk = x[kObsMask];
+    const float d = sqrtf(px * px + py * py) - rad - risk->margin;
+    cv = (mk < 0.5f || d >= risk->near) ? 1.0f : fmaxf(d / risk->near, risk->floor);
+  }
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, cv)));
+}
+
 // act_iqn's selection (agent.py:240-250) for the state of this tile (its 32 rows = the K = 32
 // quantile samples): argmax_a of sum_n Q (= K * mean, same argmax; np.argmax's first maximum),
 // then greedy iff random() > eps, else a uniform action.
 // ex (IQN_ACT_EX): also the action values quantiles.mean(dim=1) (the same sums times 1/32, from the lanes that
 // hold them) into ex->qmean_out, the pair (index, 0.0) into ex->act_pair and, for a tile whose env steps
 // (ex->env_mask, one byte per ex->robots_per_env tiles), into ex->rec_row: policy_actions_kernel's copy.
+// risk (IQN_ACT_RISK): the record row's second element is the state's level cv (widened exactly; the env step's
+// pair keeps 0.0), and cv goes to risk->cvar_out.
 __device__ __forceinline__ void iqn_act_select(const CriticArgs& a, const CriticLdsIqn& L, const f32x16& ao,
-                                               int tile, int lane, const AsvIqnActEx* ex = nullptr) {
+                                               int tile, int lane, const AsvIqnActEx* ex = nullptr,
+                                               const AsvIqnRisk* risk = nullptr, float cv = 0.f) {
   const int h = lane >> 5, A = a.hd.n_actions;
   float best = -__builtin_inff();
   int bi = kMaxA;
@@ -248,8 +275,9 @@ __device__ __forceinline__ void iqn_act_select(const CriticArgs& a, const Critic
   }
   if (ex->rec_row != nullptr && (ex->env_mask == nullptr || ex->env_mask[tile / ex->robots_per_env] != 0)) {
     ex->rec_row[o] = static_cast<double>(act);
-    ex->rec_row[o + 1] = 0.0;
+    ex->rec_row[o + 1] = risk != nullptr ? static_cast<double>(cv) : 0.0;
   }
+  if (risk != nullptr && risk->cvar_out != nullptr) risk->cvar_out[tile] = cv;
 }
 
 // acc[mb] += W(mb, ks) B(ks) over ks < KS for MB feature blocks, the weight fragments W (staged in LDS)
@@ -285,7 +313,7 @@ __device__ __forceinline__ void mfma_wrows(f32x16 (&acc)[MB], WF wf, BF bf) {
 template <int MODE, int NT, class LT, class FT>
 __device__ __forceinline__ void critic_tile(const CriticArgs& a, const LT& L, int tile, int lane, const FT* Fl,
                                             const float* Gl, float* wsum = nullptr, const float* tau_tile = nullptr,
-                                            const AsvIqnActEx* ex = nullptr) {
+                                            const AsvIqnActEx* ex = nullptr, const AsvIqnRisk* risk = nullptr) {
   constexpr bool IQN = kIqn<MODE>;
   constexpr bool TRAINM = kTrainMode<MODE>;
   const int r = lane & 31, h = lane >> 5;
@@ -296,6 +324,11 @@ __device__ __forceinline__ void critic_tile(const CriticArgs& a, const LT& L, in
   else if (tau_tile != nullptr) tau = tau_tile[r];   // the tile's taus staged by the caller (LDS)
   else tau = a.taus[grow];
   if constexpr (MODE == MODE_IQN_ACT_EX) tau = tau * ex->cvar;   // calc_cos's taus * cvar (IQN_model.py:68); * 1.0f is exact
+  float cv = 0.f;   // IQN_ACT_RISK: the state's own factor, once per state (NT = 32: the tile is the state)
+  if constexpr (MODE == MODE_IQN_ACT_RISK) {
+    cv = iqn_risk_level(a, risk, b);
+    tau = tau * cv;
+  }
   const FT* Fb = Fl + (b - tile * 32 / NT) * kC;                       // F[b], the wave's LDS row
   const float* Gb = IQN ? nullptr : Gl + (b - tile * 32 / NT) * kH;     // G[b]
   const frag8* WC = kFwdOnly<MODE> ? wimg(L.wc, a.w.wc_frag) : reinterpret_cast<const frag8*>(a.w.wc_frag);
@@ -440,7 +473,8 @@ __device__ __forceinline__ void critic_tile(const CriticArgs& a, const LT& L, in
     for (int ks = 0; ks < kH / 16; ++ks) ao = mfma(L.wo_img[ks * 64 + lane], h2pk[ks], ao);
     const int A = a.hd.n_actions;   // register g of half h holds action feat(0, g, h)
     if constexpr (kAct<MODE>) {
-      iqn_act_select(a, L, ao, tile, lane, ex);
+      if constexpr (MODE == MODE_IQN_ACT_RISK) iqn_act_select(a, L, ao, tile, lane, ex, risk, cv);
+      else iqn_act_select(a, L, ao, tile, lane, ex);
       return;
     }
     if constexpr (MODE == MODE_IQN_MAX) {

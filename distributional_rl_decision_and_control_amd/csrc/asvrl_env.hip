@@ -2073,7 +2073,7 @@ template <> struct PolicyTraits<AsvSacPolicy> : PolicyDefaults {
 // 150 KB image and 16 waves do not fit beside the env's carve. act_iqn with K = 32 taus per state, drawn in the kernel.
 template <> struct PolicyTraits<AsvIqnPolicy> : PolicyDefaults {
   static constexpr bool kWindow = false, kActRecords = true;
-  static int checks(const char* who, const AsvStepCtl* ctl, const AsvIqnPolicy* pi) {
+  static int images(const char* who, const AsvStepCtl* ctl, const AsvIqnPolicy* pi) {
     ENV_REQUIRE(!ctl->is_continuous, "is_continuous must be 0 (IQN's actions are indices)");
     const AsvCriticWeights& w = pi->w;
     ENV_REQUIRE(w.wc_frag && w.w1_frag && w.w2_frag && w.bc && w.b1 && w.b2 && w.self_w && w.self_b && w.obj_w && w.obj_b,
@@ -2081,24 +2081,60 @@ template <> struct PolicyTraits<AsvIqnPolicy> : PolicyDefaults {
     ENV_REQUIRE(pi->head.wo_frag != nullptr, "null pi->head.wo_frag");
     ENV_REQUIRE(pi->head.bo != nullptr, "null pi->head.bo");
     ENV_REQUIRE(pi->head.n_actions >= 1 && pi->head.n_actions <= ASVRL_IQN_MAX_ACTIONS, "pi->head.n_actions must be in 1..32");
+    return 0;
+  }
+  static int checks(const char* who, const AsvStepCtl* ctl, const AsvIqnPolicy* pi) {
+    if (int rc = images(who, ctl, pi)) return rc;
     ENV_REQUIRE(pi->cvar > 0.f && pi->cvar <= 1.f, "pi->cvar must be in (0, 1]");
     return 0;
   }
-  static int act(const AsvIqnPolicy* pi, const ActStep& s, void* stream) {
+  static AsvIqnIO act_io(const AsvIqnPolicy* pi, const ActStep& s) {
     AsvIqnIO io{};
     io.obs = s.x;
     io.ld_obs = ASVRL_OBS_DIM;
     io.B = static_cast<int32_t>(s.n);
     io.N = 32;
     act_schedule(io, pi, s.step);
+    return io;
+  }
+  static AsvIqnActEx act_ex(const ActStep& s, float cvar) {
     AsvIqnActEx ex{};
-    ex.cvar = pi->cvar;
+    ex.cvar = cvar;
     ex.robots_per_env = s.robots_per_env;
     ex.step_add = s.step_add;
     ex.act_pair = s.act;
     ex.rec_row = s.rec_row;
     ex.env_mask = s.env_mask;
+    return ex;
+  }
+  static int act(const AsvIqnPolicy* pi, const ActStep& s, void* stream) {
+    const AsvIqnIO io = act_io(pi, s);
+    const AsvIqnActEx ex = act_ex(s, pi->cvar);
     return asvrl_iqn_act_ex(&pi->w, &pi->head, &io, &ex, stream);
+  }
+};
+
+// IQN_Policy under a per-robot risk level (asvrl_iqn_rollout_risk): the policy struct with the call's AsvIqnRisk
+// beside it; every step's act launch is asvrl_iqn_act_risk (rows: the levels per robot slot, the same at every step;
+// adaptive: from the row the robot acts on). The window always acts on observation rows.
+struct IqnRiskPolicy : AsvIqnPolicy {
+  const AsvIqnRisk* risk;
+};
+template <> struct PolicyTraits<IqnRiskPolicy> : PolicyDefaults {
+  using Iqn = PolicyTraits<AsvIqnPolicy>;
+  static constexpr bool kWindow = false, kActRecords = true;
+  static int checks(const char* who, const AsvStepCtl* ctl, const IqnRiskPolicy* pi) {
+    if (int rc = Iqn::images(who, ctl, pi)) return rc;
+    if (const char* what = iqn_risk_problem(pi->risk, true)) return env_fail(who, what);
+    ENV_REQUIRE(pi->cvar == 1.f, "pi->cvar must be 1 (the level comes from risk)");
+    return 0;
+  }
+  static int act(const IqnRiskPolicy* pi, const ActStep& s, void* stream) {
+    const AsvIqnIO io = Iqn::act_io(pi, s);
+    const AsvIqnActEx ex = Iqn::act_ex(s, 1.f);
+    AsvIqnRisk risk = *pi->risk;
+    risk.cvar_out = nullptr;
+    return asvrl_iqn_act_risk(&pi->w, &pi->head, &io, &ex, &risk, stream);
   }
 };
 
@@ -2572,6 +2608,31 @@ extern "C" int asvrl_iqn_rollout_ar(const AsvParams* params, const AsvEnvState* 
 }
 
 extern "C" int64_t asvrl_iqn_policy_struct_size(void) { return sizeof(AsvIqnPolicy); }
+
+// the policy of a _risk call: *pi with the risk beside it (a null pi stays null: env_checks names it)
+static const IqnRiskPolicy* risk_policy(IqnRiskPolicy& p, const AsvIqnPolicy* pi, const AsvIqnRisk* risk) {
+  if (pi == nullptr) return nullptr;
+  static_cast<AsvIqnPolicy&>(p) = *pi;
+  p.risk = risk;
+  return &p;
+}
+
+extern "C" int asvrl_iqn_rollout_risk(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                                      const AsvStepOut* out, const AsvRollout* ro, const AsvIqnPolicy* pi,
+                                      const AsvIqnRisk* risk, const AsvEnvLaunch* launch, void* stream) {
+  IqnRiskPolicy p{};
+  return rollout_call<false>("asvrl_iqn_rollout_risk", params, state, ctl, out, ro, risk_policy(p, pi, risk), nullptr,
+                             launch, stream);
+}
+
+extern "C" int asvrl_iqn_rollout_risk_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                                         const AsvStepOut* out, const AsvRollout* ro, const AsvIqnPolicy* pi,
+                                         const AsvIqnRisk* risk, const AsvAutoReset* ar, const AsvEnvLaunch* launch,
+                                         void* stream) {
+  IqnRiskPolicy p{};
+  return rollout_call<true>("asvrl_iqn_rollout_risk_ar", params, state, ctl, out, ro, risk_policy(p, pi, risk), ar,
+                            launch, stream);
+}
 
 extern "C" int asvrl_rainbow_rollout(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
                                      const AsvStepOut* out, const AsvRollout* ro, const AsvRainbowPolicy* pi,

@@ -276,7 +276,9 @@ class DeviceEnvBatch:
         may be the tensor the step writes) and round t > 0 on the observation of round t - 1. pack: an MlpPack of kind
         "actor", a DqnPack, SacActorPack, IqnPack or RainbowPack -- anything with the window-policy surface MlpPack
         describes; each class says what its rounds are and which of cvar / deterministic it takes (a ValueError for
-        the others, and for cvar outside (0, 1]). The call is pack.rollout of pack.L (its _ar form under auto_reset),
+        the others, and for cvar outside (0, 1]; for an IqnPack cvar may also be an f32 tensor [E*R] on this device or
+        a fused_iqn.AdaptiveCvar, and "actions" then holds (index, level used) -- a record for evaluation, not for
+        a replay push). The call is pack.rollout of pack.L (its _ar form under auto_reset),
         so an f32 pack runs the f32-operand build. eps: (steps_per_count, total, fraction, initial, final) of the
         linear epsilon schedule (the default is greedy); step_dev: i64 device step counter (None: 0), only read. keep,
         noise, hold_done and the remaining arguments are rollout()'s; keep also takes "actions": f64 [K, E*R, 2], the
@@ -286,7 +288,7 @@ class DeviceEnvBatch:
         "obs_prev" records the rows it acted on at every step (obs_in comes from this call's own)."""
         K, NT = int(K), self.n_envs * self.max_robots
         assert pack.is_policy
-        cvar = policy_options("policy_rollout", pack, cvar, deterministic)
+        cvar = policy_options("policy_rollout", pack, cvar, deterministic, rows=NT, device=self.device)
         assert obs_in.dtype == torch.float32 and obs_in.is_contiguous() and tuple(obs_in.shape) == (NT, OBS_DIM)
         if step_dev is not None:
             assert step_dev.dtype == torch.int64 and step_dev.numel() >= 1
@@ -300,6 +302,9 @@ class DeviceEnvBatch:
         pi.obs_in = obs_in.data_ptr()
         _abi.fill_schedule(pi, step_dev, eps, policy_seed)
         pi.actions = b.rec["actions"].data_ptr() if "actions" in b.rec else None
+        risk = getattr(pi, "risk", None)   # IqnPack under a per-robot level: its _risk call, the AsvIqnRisk behind pi
+        if risk is not None:
+            return self._rollout_call(b, pack.L, pack.rollout_risk, [C.byref(pi), C.byref(risk)], stream)
         return self._rollout_call(b, pack.L, pack.rollout, [C.byref(pi)], stream)
 
     def reset(self, cfg, env_mask=None, seed=0, counter=0, counter_dev=None, stream=None):
@@ -334,10 +339,27 @@ class DeviceEnvBatch:
         _abi.check(rc, "asvrl_env_reset_observe")
 
 
-def policy_options(who, pack, cvar, deterministic):
+def policy_options(who, pack, cvar, deterministic, rows=None, device=None):
     """The refusals of the per-policy options every front end of the closed-loop windows shares (`who`: its name):
     cvar must lie in (0, 1] and differ from 1 only for a pack that takes it, deterministic needs one that takes it.
-    pack may be None (DeviceEvaluator.run's action table). Returns cvar as a float."""
+    pack may be None (DeviceEvaluator.run's action table). Returns cvar as a float.
+    A level decided per robot -- an f32 tensor of `rows` values on `device` (one per robot slot, each in (0, 1]:
+    checked on the host, one synchronisation) or a fused_iqn.AdaptiveCvar -- is returned as it is, for a pack that
+    takes cvar only."""
+    from .fused_iqn import is_risk, risk_struct
+    if is_risk(cvar):
+        if not getattr(pack, "takes_cvar", False):
+            raise ValueError(f"{who}: cvar is the risk distortion of IQN's quantile fractions (an IqnPack); "
+                             "the other policies have no quantiles to distort")
+        if deterministic and not getattr(pack, "takes_deterministic", False):
+            raise ValueError(f"{who}: deterministic=True is the sampled actor's mean action (a SacActorPack); "
+                             "the Actor and DQN_Policy have no sample to switch off")
+        if torch.is_tensor(cvar):
+            if rows is None:
+                raise ValueError(f"{who}: a per-row cvar is not offered here (the rows are regrouped per batch); "
+                                 "pass a float or an AdaptiveCvar")
+            risk_struct(cvar, rows, device, who=who)   # dtype, length, device and range
+        return cvar
     cvar = float(cvar)
     if not 0.0 < cvar <= 1.0:
         raise ValueError(f"{who}: cvar must be in (0, 1]")

@@ -36,6 +36,8 @@ DeviceEnvBatch.policy_rollout(..., cvar=1.0), DeviceEvaluator.run(..., policy_se
 Arithmetic: bf16 MFMA operands with f32 accumulation, f32 master weights / Adam.
 """
 import ctypes as C
+import dataclasses
+import math
 
 import torch
 
@@ -61,6 +63,69 @@ FUSED_TRAIN = True
 TARGET_IN_FUSED = False
 
 
+@dataclasses.dataclass(frozen=True)
+class AdaptiveCvar:
+    """The risk level chosen per robot and per act from what the robot sees (the reference's adjust_cvar,
+    agent.py:326-343, with a floor): on the packed observation row (self 7 | objects 5 x 5 (px, py, vx, vy, r),
+    nearest first | mask 5), 1 when mask[0] is 0 (no object); otherwise d = sqrt(px0^2 + py0^2) - r0 - margin and the
+    level is 1 for d >= near, else max(d / near, floor). f32 arithmetic, inside the act kernel. near and margin default
+    to the reference's constants; floor keeps the level in (0, 1] (the reference's d / 10 is unclamped and can go
+    negative), 0.1 by default."""
+    near: float = 10.0
+    margin: float = 2.8
+    floor: float = 0.1
+
+    def __post_init__(self):
+        for name in ("near", "margin", "floor"):
+            object.__setattr__(self, name, float(getattr(self, name)))
+        if not (math.isfinite(self.near) and self.near > 0.0):
+            raise ValueError("AdaptiveCvar: near must be > 0")
+        if not math.isfinite(self.margin):
+            raise ValueError("AdaptiveCvar: margin must be finite")
+        if not 0.0 < self.floor <= 1.0:
+            raise ValueError("AdaptiveCvar: floor must be in (0, 1]")
+
+    def levels(self, obs_rows):
+        """The rule in torch f32 on packed observation rows [..., >= 37]: the level of every row."""
+        x = obs_rows.to(torch.float32)
+        px, py, r, m0 = x[..., 7], x[..., 8], x[..., 11], x[..., 32]
+        d = torch.sqrt(px * px + py * py) - r - x.new_tensor(self.margin)
+        lev = torch.clamp(d / x.new_tensor(self.near), min=self.floor)
+        one = torch.ones_like(lev)
+        return torch.where((m0 < 0.5) | (d >= x.new_tensor(self.near)), one, lev)
+
+    def as_dict(self):
+        return dataclasses.asdict(self)
+
+
+def risk_struct(cvar, rows, device, cvar_out=None, check=True, who="iqn_act"):
+    """The AsvIqnRisk of a risk level that is not a float: an f32 device tensor [rows] of levels in (0, 1] (checked on
+    the host unless check is False: one sync) or an AdaptiveCvar. Returns (struct, what it must keep alive)."""
+    rk = _abi.AsvIqnRisk()
+    if isinstance(cvar, AdaptiveCvar):
+        rk.mode, rk.near, rk.margin, rk.floor = _abi.IQN_RISK_ADAPTIVE, cvar.near, cvar.margin, cvar.floor
+    else:
+        if cvar.dtype != torch.float32 or cvar.dim() != 1 or not cvar.is_contiguous():
+            raise ValueError(f"{who}: a per-row cvar must be a contiguous f32 tensor of one value per row")
+        if cvar.shape[0] != rows:
+            raise ValueError(f"{who}: a per-row cvar needs {rows} values, one per row; got {cvar.shape[0]}")
+        dev = torch.device(device)
+        if cvar.device.type != dev.type or (dev.index is not None and cvar.device.index != dev.index):
+            raise ValueError(f"{who}: a per-row cvar must be on {device}")
+        if check and rows and not bool(((cvar > 0) & (cvar <= 1)).all().item()):
+            raise ValueError(f"{who}: cvar must be in (0, 1]")
+        rk.mode, rk.cvar_rows = _abi.IQN_RISK_ROWS, cvar.data_ptr()
+    if cvar_out is not None:
+        assert cvar_out.dtype == torch.float32 and cvar_out.is_contiguous() and cvar_out.numel() >= rows
+        rk.cvar_out = cvar_out.data_ptr()
+    return rk, (cvar, cvar_out)
+
+
+def is_risk(cvar):
+    """A risk level that is decided per row: a tensor or an AdaptiveCvar (not a float)."""
+    return isinstance(cvar, AdaptiveCvar) or torch.is_tensor(cvar)
+
+
 def supported(net, B, N):
     return (default_net(net) and net.n == 64 and 1 <= net.action_size <= _abi.IQN_MAX_ACTIONS and N in (8, 16, 32)
             and (B * N) % 32 == 0)
@@ -75,8 +140,12 @@ class IqnPack(CriticPack):
     step, *eps, policy_seed, obs=obs, cvar=cvar) -- K = 32 taus per state drawn in the kernel on (global row, step,
     policy_seed) -- and step(act64, is_continuous=False, ...); "actions" holds (action index, 0.0). The act stays a
     launch of its own per step (it is not fused into the env kernel), all enqueued by the one call. cvar in (0, 1]
-    (this pack only): act_iqn's risk distortion, every tau times cvar."""
+    (this pack only): act_iqn's risk distortion, every tau times cvar. cvar may also be an f32 device tensor [NT] (one
+    level per robot slot, constant over the window) or an AdaptiveCvar (the level from the row the robot acts on, at
+    every step): the rounds are then iqn_act(..., cvar=that) and the call is rollout_risk (asvrl_iqn_rollout_risk),
+    which the windows pick from the policy struct's `risk`; "actions" then holds (action index, level used)."""
     rollout, policy_struct = _abi.ROLLOUTS["iqn"]
+    rollout_risk = "asvrl_iqn_rollout_risk"
     continuous = False
     takes_cvar, takes_deterministic = True, False
     is_policy = True
@@ -93,6 +162,11 @@ class IqnPack(CriticPack):
 
     def policy(self, cvar=1.0, deterministic=False):
         pi = self.policy_struct()
+        if is_risk(cvar):   # validated by policy_options; the struct rides on pi (a Python attribute, not a member)
+            pi.w, pi.head, pi.cvar = self.struct, self.head, 1.0
+            pi.risk, pi.risk_keep = risk_struct(cvar, cvar.shape[0] if torch.is_tensor(cvar) else 0,
+                                                self.head_img.device, check=False, who="policy")
+            return pi
         pi.w, pi.head, pi.cvar = self.struct, self.head, float(cvar)
         return pi
 
@@ -198,15 +272,29 @@ def iqn_train_fused(pack, net, taus, N, q_next, actions, rewards, dones, gamma, 
 
 def iqn_act(pack, F, actions64, step_dev, steps_per_count, total, fraction, initial, final, seed, taus=None,
             stream=None, obs=None, cvar=1.0, step_add=0, q_out=None, actions_rec=None, env_mask=None,
-            robots_per_env=1):
+            robots_per_env=1, cvar_out=None, check_cvar=True):
     """act_iqn for every row of F (or of the observation rows `obs`) into actions64[:, 0] (f64 action index).
     The window form (asvrl_iqn_act_ex, taken only when one of these is set): cvar in (0, 1] multiplies every tau,
     drawn or given (act_iqn's risk distortion, IQN_model.py:68); step_add is added to the step counter's value;
     q_out (f32 [rows, >= A]) receives the action values quantiles.mean(dim=1); actions_rec (f64 [rows, 2]) receives
-    (index, 0.0) for the rows of envs with env_mask != 0 (u8, one per robots_per_env rows; None: every row)."""
+    (index, 0.0) for the rows of envs with env_mask != 0 (u8, one per robots_per_env rows; None: every row).
+    cvar may also be decided per row (asvrl_iqn_act_risk): an f32 device tensor [rows], row b's 32 taus times cvar[b]
+    (its range is checked on the host, which is one synchronisation; check_cvar=False skips it, for graph capture),
+    or an AdaptiveCvar, the level computed in the kernel from observation row b (needs obs). actions_rec then
+    receives (index, level used) and cvar_out (f32 [rows]) the level of every row. A ValueError for a level outside
+    (0, 1], a tensor of another dtype, length or device, and an AdaptiveCvar without obs."""
     io = _io(F, K_ACT, obs=obs, taus=taus, act_out=actions64, ld_act=actions64.stride(0))
     _abi.fill_schedule(io, step_dev, (steps_per_count, total, fraction, initial, final), seed)
-    if float(cvar) == 1.0 and int(step_add) == 0 and q_out is None and actions_rec is None and env_mask is None:
+    risk = None
+    if is_risk(cvar):
+        if isinstance(cvar, AdaptiveCvar) and obs is None:
+            raise ValueError("iqn_act: an AdaptiveCvar reads the observation rows (obs=); features alone carry none")
+        risk, _keep = risk_struct(cvar, io.B, actions64.device, cvar_out, check_cvar)
+        cvar = 1.0
+    elif cvar_out is not None:
+        raise ValueError("iqn_act: cvar_out is the per-row level of a tensor or AdaptiveCvar cvar")
+    if (risk is None and float(cvar) == 1.0 and int(step_add) == 0 and q_out is None and actions_rec is None
+            and env_mask is None):
         _abi.check(pack.L.asvrl_iqn_act(C.byref(pack.struct), C.byref(pack.head), C.byref(io),
                                         _abi.stream_ptr(stream)), "asvrl_iqn_act", pack.L)
         return
@@ -224,6 +312,10 @@ def iqn_act(pack, F, actions64, step_dev, steps_per_count, total, fraction, init
         assert env_mask.dtype == torch.uint8 and env_mask.is_contiguous()
         assert env_mask.numel() * int(robots_per_env) >= io.B
         ex.env_mask = env_mask.data_ptr()
+    if risk is not None:
+        _abi.check(pack.L.asvrl_iqn_act_risk(C.byref(pack.struct), C.byref(pack.head), C.byref(io), C.byref(ex),
+                                             C.byref(risk), _abi.stream_ptr(stream)), "asvrl_iqn_act_risk", pack.L)
+        return
     _abi.check(pack.L.asvrl_iqn_act_ex(C.byref(pack.struct), C.byref(pack.head), C.byref(io), C.byref(ex),
                                        _abi.stream_ptr(stream)), "asvrl_iqn_act_ex", pack.L)
 

@@ -156,10 +156,11 @@ class EvalHistory:
     (trajectory, action, observation) slices of config c's robot i into them. Everything the accessors return is a
     view of those arrays, except a discrete policy's int64 action indices."""
 
-    def __init__(self, traj, act, obs, cnt, slices, continuous):
+    def __init__(self, traj, act, obs, cnt, slices, continuous, levels=False):
         self.traj, self.act, self.obs, self.cnt = traj, act, obs, cnt
         self.slices = slices
         self.continuous = bool(continuous)
+        self.levels = bool(levels)   # the run's risk level was decided per robot (an AdaptiveCvar)
 
     def trajectory(self, c, i):
         """[n_act + 1, 13] f64: the reset row and the row after every step the robot acted in (wamv.py:191-193)."""
@@ -169,6 +170,15 @@ class EvalHistory:
         """[n_act, 2] f64, the pairs the env was given; of a discrete policy [n_act] int64, the action indices."""
         a = self.act[self.slices[c][i][1]]
         return a if self.continuous else a[:, 0].astype(np.int64)
+
+    def cvar(self, c, i):
+        """[n_act] f64: the risk level the robot acted on at every act of a run under an AdaptiveCvar (the second
+        column of its packed action pairs, the f32 level widened exactly). A ValueError after a run at a float
+        level, whose pairs carry 0.0 there."""
+        if not self.levels:
+            raise ValueError("EvalHistory.cvar: the run had one float risk level (its result's \"cvar\"); the level "
+                             "per act is recorded under run(..., cvar=AdaptiveCvar())")
+        return self.act[self.slices[c][i][1]][:, 1]
 
     def observation(self, c, i):
         """(self [L + 1, 7], objects [L + 1, 5, 5], count [L + 1]): the reset observation and the one after every
@@ -403,7 +413,10 @@ class DeviceEvaluator:
         under policy_seed + g: rows are batch-local, so two groups share no draws) or, with deterministic=True (a
         ValueError for any other pack), takes its mean action, or IQN's IqnPack, greedy over the mean of K = 32
         quantile samples whose fractions are drawn per act (group g under policy_seed + g, as for SAC) and, with
-        cvar in (0, 1] (a ValueError for any other pack and outside the range), distorted as act_iqn(cvar=) does, or
+        cvar in (0, 1] (a ValueError for any other pack and outside the range), distorted as act_iqn(cvar=) does -- or
+        with cvar a fused_iqn.AdaptiveCvar, at the level the rule gives every robot at every act from the row it acts
+        on (with histories, EvalHistory.cvar(c, i); a per-row tensor is not offered: the rows are regrouped per
+        config batch); the result's "cvar" is the float or the rule's three parameters --, or
         Rainbow's RainbowPack, greedy on the images of its last refresh() (FusedRainbow.eval_pack: mu only, as the
         reference's policy_local.eval(); group g under policy_seed + g as well, though at epsilon 0 nothing is drawn); or actions: a [T, NT, 2] f64 table per group (a tensor when there is one group, else a list)
         applied open loop, with noise ([T, NT, O + R, 5] f64 per group) or the Philox stream. is_continuous: what
@@ -436,7 +449,7 @@ class DeviceEvaluator:
         if pack is not None and is_continuous is not None and bool(is_continuous) != pack.continuous:
             raise ValueError("run: is_continuous=%s does not match the pack (a DqnPack, IqnPack or RainbowPack picks "
                              "discrete actions, the Actor continuous ones)" % bool(is_continuous))
-        cvar = policy_options("run", pack, cvar, deterministic)
+        cvar = policy_options("run", pack, cvar, deterministic)   # a float or an AdaptiveCvar (no per-row tensor)
         _check_perception("run", perception, noise, obs_noise)
         is_continuous = True if is_continuous is None else bool(is_continuous)
         episode_limit = int(episode_limit)
@@ -488,8 +501,11 @@ class DeviceEvaluator:
         if histories:   # the records, the action source per group and how to read it
             hist = dict(L=L, T=episode_limit + 1, records=hist,
                         actions=[H["actions"] for H in hist] if pack is not None else actions,
-                        continuous=pack.continuous if pack is not None else is_continuous)
-        return self._result(check_ended=pack is None and total < episode_limit + 1, draws=numpy_noise, hist=hist)
+                        continuous=pack.continuous if pack is not None else is_continuous,
+                        levels=not isinstance(cvar, float))
+        out = self._result(check_ended=pack is None and total < episode_limit + 1, draws=numpy_noise, hist=hist)
+        out["cvar"] = cvar if isinstance(cvar, float) else cvar.as_dict()
+        return out
 
     def _history(self, hist, counts):
         """The EvalHistory of a run: counts the host image of every group's count planes ([3, NT] each), read in
@@ -522,7 +538,8 @@ class DeviceEvaluator:
                 slices[cfg] = [tuple(slice(int(start[q, r]), int(start[q, r] + c[q, r])) for q in range(3))
                                for r in rows]
         host = {n: t.cpu().numpy() for n, t in out.items()}
-        return EvalHistory(host["traj"], host["act"], host["obs"], host["cnt"], slices, hist["continuous"])
+        return EvalHistory(host["traj"], host["act"], host["obs"], host["cnt"], slices, hist["continuous"],
+                           hist["levels"])
 
     def _result(self, check_ended=False, draws=False, hist=None):
         # one copy: every group's lengths, ended flags, outcomes and sums in one f64 tensor

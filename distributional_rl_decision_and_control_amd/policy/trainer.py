@@ -16,6 +16,8 @@ With "device_eval": true in that dict (AC-IQN, DDPG, DQN, IQN and Rainbow) the e
 batched trainer's own actor, Q network, quantile network or, for Rainbow, the mu-only (eval-mode) images of its online
 network (evaluation(batched="device"), policy/device_eval.py). "device_eval": {"perception": "numpy"} does the same
 with the perception noise drawn from every robot's own RandomState stream, as the other evaluation paths draw it, and
+"device_eval": {"cvar": 0.25 | "adaptive" | {"near": .., "margin": .., "floor": ..}} (IQN only) evaluates at that risk
+level, the last two at the level fused_iqn.AdaptiveCvar gives every robot at every act, and
 "device_eval": {"histories": true} also keeps every robot's observation, action and trajectory history, so
 evaluations.npz replays in the reference's visualize_eval_episode.py like the file of the other evaluation paths.
 """
@@ -23,6 +25,22 @@ import json
 import os
 
 import numpy as np
+
+
+def _eval_cvar(v):
+    """The "cvar" of the "device_eval" dict as DeviceEvaluator.run takes it: a number, "adaptive" (the default
+    fused_iqn.AdaptiveCvar) or {"near": .., "margin": .., "floor": ..} (any subset)."""
+    from ..fused_iqn import AdaptiveCvar
+    if v == "adaptive":
+        return AdaptiveCvar()
+    if isinstance(v, dict):
+        if set(v) - {"near", "margin", "floor"}:
+            raise ValueError(f"device_eval: unknown option(s) {sorted(set(v) - {'near', 'margin', 'floor'})} in "
+                             "\"cvar\"; it takes \"near\", \"margin\" and \"floor\"")
+        return AdaptiveCvar(**v)
+    if isinstance(v, (int, float)) and not isinstance(v, bool):
+        return float(v)
+    raise ValueError("device_eval: \"cvar\" must be a number, \"adaptive\" or {\"near\", \"margin\", \"floor\"}")
 
 
 class Trainer:
@@ -182,10 +200,15 @@ class Trainer:
         # the reference's content (DeviceEvaluator.run's histories, device_eval.history_lists)
         opts = kw.pop("device_eval", False)
         if isinstance(opts, dict):
-            if set(opts) - {"perception", "histories"}:
-                raise ValueError(f"device_eval: unknown option(s) {sorted(set(opts) - {'perception', 'histories'})}; "
-                                 "it takes \"perception\" and \"histories\"")
+            known = {"perception", "histories", "cvar"}
+            if set(opts) - known:
+                raise ValueError(f"device_eval: unknown option(s) {sorted(set(opts) - known)}; "
+                                 "it takes \"perception\", \"histories\" and \"cvar\"")
             self._device_eval_kw = dict(opts)
+            if "cvar" in opts:   # IQN's risk level: a number, "adaptive" or the rule's parameters
+                if agent.agent_type != "IQN":
+                    raise ValueError(f"device_eval: \"cvar\" is IQN's risk level; {agent.agent_type} has none")
+                self._device_eval_kw["cvar"] = _eval_cvar(opts["cvar"])
             if "histories" in opts:
                 self._device_eval_kw["histories"] = bool(opts["histories"])
             opts = True

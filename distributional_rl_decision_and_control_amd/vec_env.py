@@ -133,7 +133,8 @@ class VecMarineNavEnv:
         default is greedy). The contract is otherwise rollout()'s. Returns the kept per-step records (keep also takes
         "actions"). auto_reset, count: as rollout()'s (the policy acts on a reset env's reset observation at the next
         step). pack.continuous must match how this env was built; deterministic and cvar are the pack's own options
-        (see the pack classes)."""
+        (see the pack classes; for an IqnPack cvar may be a float, an f32 tensor of one level per robot slot or a
+        fused_iqn.AdaptiveCvar, and "actions" then records (index, level used))."""
         if not pack.continuous:
             if self.is_continuous:
                 raise ValueError("policy_rollout: a DqnPack, IqnPack or RainbowPack picks discrete actions, this env "

@@ -511,6 +511,29 @@ int asvrl_iqn_act_ex(const AsvCriticWeights* w, const AsvIqnHead* head, const As
 /* sizeof(AsvIqnActEx) as compiled. */
 int64_t asvrl_iqn_act_ex_struct_size(void);
 
+/* A risk level per row instead of AsvIqnActEx's one scalar (new entry points only: the ABI version stays 29). Row b's 32
+ * quantile fractions, drawn or given, are multiplied by level[b] before the cosine embedding. */
+#define ASVRL_IQN_RISK_ROWS 1      /* level[b] = cvar_rows[b] */
+#define ASVRL_IQN_RISK_ADAPTIVE 2  /* level[b] from io->obs row b (self 7 | objects 5 x 5 (px, py, vx, vy, r), nearest
+                                      first | mask 5), in f32: 1 if mask[0] < 0.5 (no object); otherwise
+                                      d = sqrt(px0^2 + py0^2) - r0 - margin, and 1 if d >= near, else max(d / near, floor)
+                                      (the rule agent.py:342-358 keeps commented out, with a floor) */
+typedef struct AsvIqnRisk {
+  int32_t mode;            /* ASVRL_IQN_RISK_ROWS or ASVRL_IQN_RISK_ADAPTIVE */
+  float near;              /* adaptive: > 0 (the reference's 10) */
+  float margin;            /* adaptive: finite (the reference's 2.8) */
+  float floor;             /* adaptive: in (0, 1]; the reference's rule has none */
+  const float* cvar_rows;  /* rows: [B], each in (0, 1] (not checked: device memory) */
+  float* cvar_out;         /* optional [B]: the level every row used */
+} AsvIqnRisk;
+/* asvrl_iqn_act_ex with the factor taken from risk: ex->cvar must be 1. ex->act_pair still receives (index, 0.0), the
+ * pair the env step takes; ex->rec_row receives (index, level used), the f32 level widened exactly. The adaptive
+ * mode needs io->obs (precomputed features carry no observation row). */
+int asvrl_iqn_act_risk(const AsvCriticWeights* w, const AsvIqnHead* head, const AsvIqnIO* io, const AsvIqnActEx* ex,
+                       const AsvIqnRisk* risk, void* stream);
+/* sizeof(AsvIqnRisk) as compiled. */
+int64_t asvrl_iqn_risk_struct_size(void);
+
 /* ---------------------------------------------------------------- replay (replay_buffer.py) */
 
 /* ReplayBuffer.add (replay_buffer.py:22-24) for every robot that acted in the last step
@@ -1634,6 +1657,18 @@ int asvrl_iqn_rollout_ar(const AsvParams* params, const AsvEnvState* state, cons
                          const AsvAutoReset* ar, const AsvEnvLaunch* launch /* NULL: automatic */, void* stream);
 /* sizeof(AsvIqnPolicy) as compiled. */
 int64_t asvrl_iqn_policy_struct_size(void);
+
+/* The two IQN windows under a per-robot risk level: every step's act launch is asvrl_iqn_act_risk. risk->cvar_rows is
+ * per robot slot [NT] and constant over the window; the adaptive level is computed at every step from the row the
+ * robot acts on. pi->cvar must be 1; risk->cvar_out is not used. pi->actions records (action index, level used); the
+ * env step still takes (index, 0.0). */
+int asvrl_iqn_rollout_risk(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                           const AsvStepOut* last, const AsvRollout* ro, const AsvIqnPolicy* pi,
+                           const AsvIqnRisk* risk, const AsvEnvLaunch* launch /* NULL: automatic */, void* stream);
+int asvrl_iqn_rollout_risk_ar(const AsvParams* params, const AsvEnvState* state, const AsvStepCtl* ctl,
+                              const AsvStepOut* last, const AsvRollout* ro, const AsvIqnPolicy* pi,
+                              const AsvIqnRisk* risk, const AsvAutoReset* ar,
+                              const AsvEnvLaunch* launch /* NULL: automatic */, void* stream);
 
 /* ---------------------------------------------------------------- closed-loop rollout windows for Rainbow
  * New entry points only: the ABI version stays 29. */

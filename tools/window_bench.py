@@ -9,7 +9,8 @@ window: the protocol follows from the pack. Where the act runs inside the env ke
 launch for K steps) both variants are captured as HIP graphs (a: one fused call; b: the 2 K launches) and timed with
 device events around each replay: --calls timed replays after --warmup make one measurement. Where the window is K
 launches enqueued by one C call (iqn, rainbow) both variants run eagerly, device events around each call; the rounds
-are also timed with the four copies a step that give the window's outputs, and the window with no record kept. Either
+are also timed with the four copies a step that give the window's outputs, and the window with no record kept; for IQN also the window
+at cvar = 0.25 and under fused_iqn.AdaptiveCvar (window_cvar025, window_adaptive). Either
 way every call starts from the same restored state (the restore is outside the timed span), the variants alternate,
 --reps measurements give the median and the spread (max - min), and the final state of the two variants is compared
 bit for bit. Shapes: --shapes "E:R:O,..."; window lengths: --steps "K,...". The Actor's fused per-step time is also
@@ -19,7 +20,7 @@ the windows of DeviceEvaluator.run against per-step sac_act + step + asvrl_eval_
 one host wait per window / per step; alternated, --reps each.
 eval (iqn, rainbow): tools/bench_device_eval.py's protocol (one warm-up, --reps alternating repetitions, a host clock
 ending in a device synchronise) of policy/batched_eval.evaluate_configs against DeviceEvaluator.run (Rainbow: both the
-eval-mode, mu only, network).
+eval-mode, mu only, network; IQN: also at cvar = 0.25 and under AdaptiveCvar, device_cvar025 and device_adaptive).
 graph (iqn, rainbow): one capture attempt of a K-step window with caller-supplied records, replayed once against the
 eager call; a refusal by the runtime is recorded as its message, nothing is worked around. Runs last.
 
@@ -139,9 +140,9 @@ def window_bench(a, pack, act):
         act64 = torch.zeros((E * R, 2), dtype=torch.float64, device="cuda")
         steps = STEP0 + torch.arange(max(Ks + [8]), dtype=torch.int64, device="cuda")   # round t's step counter
 
-        def window(K, rec):
+        def window(K, rec, **options):
             b.policy_rollout(pack, K, b.obs, keep=rec, step_dev=steps[:1], eps=EPS, policy_seed=POLICY_SEED, seed=1,
-                             counter=10, fast_noise=True, launch=a.launch)
+                             counter=10, fast_noise=True, launch=a.launch, **options)
 
         def rounds(K, rec=None):
             """rec: the rounds with the window's outputs, four copies a step into the same records"""
@@ -200,6 +201,11 @@ def window_bench(a, pack, act):
                 # (the bare window keeps no per-step record: the record launch still counts the steps)
                 variants = {"window": w, "rounds_recording": lambda: rounds(K, rec),
                             "window_bare": lambda: window(K, bare), "rounds": r}
+                if pack.takes_cvar:   # IQN: the scalar risk level and the per-robot adaptive one, in the same session
+                    from distributional_rl_decision_and_control_amd.fused_iqn import AdaptiveCvar
+                    variants["window_cvar025"] = lambda: window(K, rec, cvar=0.25)
+                    variants["window_adaptive"] = lambda: window(K, rec, cvar=AdaptiveCvar())
+                    variants["rounds"] = variants.pop("rounds")   # the rounds stay the last call of a repetition
             us = {n: [] for n in variants}
             for _ in range(a.reps):
                 for n, fn in variants.items():
@@ -321,7 +327,9 @@ def eval_against_host(a, agent, pack):
             "device_sync": lambda: ev.run(pack, seed=1),
             "device_nosync": lambda: ev.run(pack, seed=1, sync=False)}
     if pack.takes_cvar:
+        from distributional_rl_decision_and_control_amd.fused_iqn import AdaptiveCvar
         runs["device_cvar025"] = lambda: ev.run(pack, seed=1, cvar=0.25)
+        runs["device_adaptive"] = lambda: ev.run(pack, seed=1, cvar=AdaptiveCvar())
     times = {k: [] for k in runs}
     last, windows = {}, {}
     for rep in range(a.reps + 1):   # the first round is the warm-up
