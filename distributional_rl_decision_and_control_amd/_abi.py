@@ -165,6 +165,29 @@ class AsvIqnRisk(C.Structure):
                 ("cvar_rows", _VP), ("cvar_out", _VP)]
 
 
+# asvrl_iqn_dist: the readout of the quantile samples behind recorded IQN decisions
+class AsvIqnDist(C.Structure):
+    _fields_ = [("rows_per_step", _I32), ("cvar", C.c_float), ("step0", _I64), ("level_rows", _VP), ("actions", _VP),
+                ("z_out", _VP), ("tau_out", _VP), ("all_out", _VP), ("ld_a", _I64), ("greedy_out", _VP),
+                ("qmean_out", _VP), ("ld_q", _I64)]
+
+
+# asvrl_dist_prepare: the critic's fractions and the f32 action pairs in front of asvrl_critic_forward
+class AsvDistPrepare(C.Structure):
+    _fields_ = [("rows", _I32), ("rows_per_step", _I32), ("step0", _I64), ("seed", _U64), ("taus_out", _VP),
+                ("actions", _VP), ("act_out", _VP)]
+
+
+DIST_SAMPLES = 32   # quantile samples per decision (K of act_iqn)
+DIST_STATS_ARRAYS = ("z", "tau", "reward", "n_act", "n_robots", "g_plane", "g0", "pred0", "pit", "pinball", "bias",
+                     "steps")
+
+
+class AsvEvalDistStats(C.Structure):
+    _fields_ = [("n_steps", _I32), ("n_envs", _I32), ("max_robots", _I32), ("block", _I32), ("gamma", _D)] + \
+               [(n, _VP) for n in DIST_STATS_ARRAYS]
+
+
 MAX_SUM_SEGS = 24
 
 
@@ -559,6 +582,13 @@ EXPORTS = [
                                      C.POINTER(AsvIqnActEx), C.POINTER(AsvIqnRisk), _VP]),
     ("asvrl_iqn_risk_struct_size", _I64, []),
     ("asvrl_iqn_policy_struct_size", _I64, []),
+    ("asvrl_iqn_dist", C.c_int, [C.POINTER(AsvCriticWeights), C.POINTER(AsvIqnHead), C.POINTER(AsvIqnIO),
+                                 C.POINTER(AsvIqnDist), _VP]),
+    ("asvrl_iqn_dist_struct_size", _I64, []),
+    ("asvrl_dist_prepare", C.c_int, [C.POINTER(AsvDistPrepare), _VP]),
+    ("asvrl_dist_prepare_struct_size", _I64, []),
+    ("asvrl_eval_dist_stats", C.c_int, [C.POINTER(AsvEvalDistStats), _VP]),
+    ("asvrl_eval_dist_stats_struct_size", _I64, []),
     ("asvrl_rainbow_net_act_ex", C.c_int, [C.POINTER(AsvRainbowImg), C.POINTER(AsvRainbowNetIO),
                                            C.POINTER(AsvRainbowActEx), _VP]),
     ("asvrl_rainbow_act_ex_struct_size", _I64, []),

@@ -32,6 +32,8 @@
 //              [R][32] matrix so its weight gradient is one more 32 x 128 MFMA reduction
 //   IQN_ACT    act_iqn (agent.py:227-256): mean over K = 32 taus per state, argmax, epsilon-greedy
 //   IQN_ACT_RISK IQN_ACT_EX with the factor per state (asvrl_iqn_act_risk): AsvIqnRisk's rows or its adaptive rule
+//   IQN_DIST   IQN_ACT_EX's pass with the selection replaced by a readout (asvrl_iqn_dist): the 32 quantile samples of
+//              the recorded or greedy action, their fractions, every action's values, the arg-max, the action values
 //   IQN_ACT_EX the same pass as the rollout windows launch it (asvrl_iqn_act_ex): taus * cvar, step + step_add,
 //              the (index, 0.0) pair and its masked record row, the action values
 #include "asvrl_common.h"
@@ -167,10 +169,13 @@ template <int MODE, int NT> struct ModeWaves { static constexpr int n = CriticWa
 template <> struct ModeWaves<MODE_IQN_ACT, 32> { static constexpr int n = ASVRL_IQN_ACT_WAVES; };
 template <> struct ModeWaves<MODE_IQN_ACT_EX, 32> { static constexpr int n = ASVRL_IQN_ACT_WAVES; };
 template <> struct ModeWaves<MODE_IQN_ACT_RISK, 32> { static constexpr int n = ASVRL_IQN_ACT_WAVES; };
+template <> struct ModeWaves<MODE_IQN_DIST, 32> { static constexpr int n = ASVRL_IQN_ACT_WAVES; };
 
-// one workgroup of critic_kernel (ex: IQN_ACT_EX's additions, null in every other mode; risk: IQN_ACT_RISK's)
+// one workgroup of critic_kernel (ex: IQN_ACT_EX's additions, null in every other mode; risk: IQN_ACT_RISK's;
+// dist: IQN_DIST's)
 template <int MODE, int NT>
-__device__ __forceinline__ void critic_block(const CriticArgs& a, const AsvIqnActEx* ex, const AsvIqnRisk* risk = nullptr) {
+__device__ __forceinline__ void critic_block(const CriticArgs& a, const AsvIqnActEx* ex, const AsvIqnRisk* risk = nullptr,
+                                             const AsvIqnDist* dist = nullptr) {
   constexpr int W = ModeWaves<MODE, NT>::n, S = 32 / NT;
   __shared__ typename LdsOf<MODE>::T L;
   using FT = typename FOf<MODE>::T;
@@ -211,7 +216,7 @@ __device__ __forceinline__ void critic_block(const CriticArgs& a, const AsvIqnAc
   const bool wout = MODE == MODE_TRAIN && a.acts.wout_part != nullptr;
   float* wsum = wout ? Ws + (threadIdx.x >> 6) * (kH + 1) : nullptr;
   if (tile < tiles) {
-    critic_tile<MODE, NT>(a, L, tile, lane, Fw, Gw, wsum, nullptr, ex, risk);
+    critic_tile<MODE, NT>(a, L, tile, lane, Fw, Gw, wsum, nullptr, ex, risk, dist);
   } else if (wout) {
     for (int i = lane; i < kH + 1; i += 64) wsum[i] = 0.f;
   }
@@ -241,6 +246,25 @@ __global__ __launch_bounds__((ModeWaves<MODE_IQN_ACT_EX, 32>::n) * 64) void iqn_
 __global__ __launch_bounds__((ModeWaves<MODE_IQN_ACT_RISK, 32>::n) * 64) void iqn_act_risk_kernel(CriticArgs a, AsvIqnActEx x,
                                                                                                   AsvIqnRisk r) {
   critic_block<MODE_IQN_ACT_RISK, 32>(a, &x, &r);
+}
+
+// asvrl_iqn_dist: the same workgroup again, the selection replaced by the readout of the quantile samples
+__global__ __launch_bounds__((ModeWaves<MODE_IQN_DIST, 32>::n) * 64) void iqn_dist_kernel(CriticArgs a, AsvIqnDist d) {
+  critic_block<MODE_IQN_DIST, 32>(a, nullptr, nullptr, &d);
+}
+
+// asvrl_dist_prepare: one thread per (row, sample): the critic's fraction of that sample, and from the row's first two
+// threads the f32 copy of its recorded action pair
+__global__ __launch_bounds__(256) void dist_prepare_kernel(AsvDistPrepare p) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= static_cast<int64_t>(p.rows) * 32) return;
+  const int m = static_cast<int>(i >> 5), j = static_cast<int>(i & 31);
+  if (p.taus_out != nullptr) {
+    const int n = m % p.rows_per_step;
+    const uint64_t t = static_cast<uint64_t>(p.step0 + m / p.rows_per_step);
+    p.taus_out[i] = tau_draw(p.seed, static_cast<uint32_t>(n * 32 + j), t, kTauStreamCritic);
+  }
+  if (p.act_out != nullptr && j < 2) p.act_out[2 * static_cast<int64_t>(m) + j] = static_cast<float>(p.actions[2 * static_cast<int64_t>(m) + j]);
 }
 
 int train_b_grid(int tiles) { return (tiles + 7) / 8; }
@@ -520,5 +544,42 @@ extern "C" int asvrl_iqn_act_risk(const AsvCriticWeights* w, const AsvIqnHead* h
 }
 
 extern "C" int64_t asvrl_iqn_risk_struct_size(void) { return sizeof(AsvIqnRisk); }
+
+extern "C" int asvrl_iqn_dist(const AsvCriticWeights* w, const AsvIqnHead* head, const AsvIqnIO* io,
+                              const AsvIqnDist* dist, void* stream) {
+  ASVRL_REQUIRE(w && head && io && dist, "asvrl_iqn_dist: null argument");
+  ASVRL_REQUIRE(io->N == 32, "asvrl_iqn_dist: K = 32 quantile samples per state (N must be 32)");
+  if (int rc = iqn_validate(w, head, io)) return rc;
+  ASVRL_REQUIRE(dist->rows_per_step >= 1, "asvrl_iqn_dist: rows_per_step must be >= 1");
+  ASVRL_REQUIRE(dist->cvar > 0.f && dist->cvar <= 1.f, "asvrl_iqn_dist: cvar must be in (0, 1]");
+  ASVRL_REQUIRE(dist->level_rows == nullptr || dist->cvar == 1.f,
+                "asvrl_iqn_dist: cvar must be 1 with level_rows (one level, the scalar or the rows')");
+  ASVRL_REQUIRE(dist->step0 >= 0, "asvrl_iqn_dist: step0 must be >= 0");
+  ASVRL_REQUIRE(!dist->all_out || dist->ld_a >= head->n_actions, "asvrl_iqn_dist: ld_a must cover n_actions");
+  ASVRL_REQUIRE(!dist->qmean_out || dist->ld_q >= head->n_actions, "asvrl_iqn_dist: ld_q must cover n_actions");
+  if (io->B == 0) return 0;
+  const CriticArgs a = iqn_args(w, head, io);
+  constexpr int W = ModeWaves<MODE_IQN_DIST, 32>::n;
+  hipLaunchKernelGGL(iqn_dist_kernel, dim3((a.B + W - 1) / W), dim3(W * 64), 0, as_stream(stream), a, *dist);
+  return check_launch("asvrl_iqn_dist");
+}
+
+extern "C" int64_t asvrl_iqn_dist_struct_size(void) { return sizeof(AsvIqnDist); }
+
+extern "C" int asvrl_dist_prepare(const AsvDistPrepare* p, void* stream) {
+  ASVRL_REQUIRE(p != nullptr, "asvrl_dist_prepare: null struct");
+  ASVRL_REQUIRE(p->rows >= 0, "asvrl_dist_prepare: rows must be >= 0");
+  ASVRL_REQUIRE(p->rows_per_step >= 1, "asvrl_dist_prepare: rows_per_step must be >= 1");
+  ASVRL_REQUIRE(p->step0 >= 0, "asvrl_dist_prepare: step0 must be >= 0");
+  ASVRL_REQUIRE(p->taus_out || p->act_out, "asvrl_dist_prepare: needs taus_out or act_out");
+  ASVRL_REQUIRE(!p->act_out || p->actions, "asvrl_dist_prepare: act_out needs actions");
+  if (p->rows == 0) return 0;
+  const int64_t n = static_cast<int64_t>(p->rows) * 32;
+  hipLaunchKernelGGL(dist_prepare_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, as_stream(stream),
+                     *p);
+  return check_launch("asvrl_dist_prepare");
+}
+
+extern "C" int64_t asvrl_dist_prepare_struct_size(void) { return sizeof(AsvDistPrepare); }
 
 extern "C" int32_t asvrl_critic_wout_groups(int32_t B, int32_t N) { return wout_groups(B, N); }

@@ -13,13 +13,16 @@ namespace ctile {
 
 constexpr int kC = 256, kH = 128, kNcos = 64;
 enum { MODE_FWD = 0, MODE_TRAIN = 1, MODE_ACTOR = 2, MODE_IQN_MAX = 3, MODE_IQN_TRAIN = 4, MODE_IQN_ACT = 5,
-       MODE_IQN_ACT_EX = 6, MODE_IQN_ACT_RISK = 7 };
+       MODE_IQN_ACT_EX = 6, MODE_IQN_ACT_RISK = 7, MODE_IQN_DIST = 8 };
 // IQN_ACT_EX: the window form of IQN_ACT (asvrl_iqn_act_ex): the same tile with AsvIqnActEx's CVaR factor, step
 // offset, action pair / record row and action values; an instantiation of its own, so IQN_ACT's code stays put
 // IQN_ACT_RISK: IQN_ACT_EX with the factor per state (asvrl_iqn_act_risk: AsvIqnRisk's rows, or its rule on the
 // state's observation row); again an instantiation of its own, so the two above compile to what they did
 template <int MODE> constexpr bool kActEx = MODE == MODE_IQN_ACT_EX || MODE == MODE_IQN_ACT_RISK;
-template <int MODE> constexpr bool kAct = MODE == MODE_IQN_ACT || kActEx<MODE>;
+// IQN_DIST: the readout of the quantile samples behind recorded decisions (asvrl_iqn_dist): IQN_ACT_EX's tile up to
+// the output block -- the same passes, the same MFMA order, so the same action values -- and then iqn_dist_write in
+// place of the selection; a third instantiation of its own
+template <int MODE> constexpr bool kAct = MODE == MODE_IQN_ACT || kActEx<MODE> || MODE == MODE_IQN_DIST;
 constexpr int kMaxA = ASVRL_IQN_MAX_ACTIONS;
 template <int MODE> constexpr bool kIqn = MODE >= MODE_IQN_MAX;
 template <int MODE> constexpr bool kTrainMode = MODE == MODE_TRAIN || MODE == MODE_IQN_TRAIN;
@@ -107,6 +110,7 @@ template <> struct LdsOf<MODE_IQN_TRAIN> { using T = CriticLdsIqn; };
 template <> struct LdsOf<MODE_IQN_ACT> { using T = CriticLdsIqn; };
 template <> struct LdsOf<MODE_IQN_ACT_EX> { using T = CriticLdsIqn; };
 template <> struct LdsOf<MODE_IQN_ACT_RISK> { using T = CriticLdsIqn; };
+template <> struct LdsOf<MODE_IQN_DIST> { using T = CriticLdsIqn; };
 // the staged F rows: f32 copies of the operand-rounded values (no per-use conversion) in the AC-IQN
 // modes; operand-typed in the IQN modes, whose larger LDS image leaves no room for them
 template <int MODE> struct FOf { using T = float; };
@@ -115,6 +119,7 @@ template <> struct FOf<MODE_IQN_TRAIN> { using T = elem_t; };
 template <> struct FOf<MODE_IQN_ACT> { using T = elem_t; };
 template <> struct FOf<MODE_IQN_ACT_EX> { using T = elem_t; };
 template <> struct FOf<MODE_IQN_ACT_RISK> { using T = elem_t; };
+template <> struct FOf<MODE_IQN_DIST> { using T = elem_t; };
 static_assert(sizeof(CriticLdsIqn) <= 160 * 1024, "IQN LDS image exceeds the CU's 160 KB");
 
 // The wave's feature rows in LDS for its 32 / NT samples: F (bf16 [S][256]) = observation_processor
@@ -195,12 +200,30 @@ __device__ __forceinline__ uint64_t act_step(const CriticArgs& a, const AsvIqnAc
 
 // act_iqn's quantile fractions when the caller passes none: uniform [0, 1) per row (calc_cos's
 // torch.rand, IQN_model.py:63), Philox on (row, step)
-__device__ __forceinline__ float act_tau(const CriticArgs& a, int grow, const AsvIqnActEx* ex = nullptr) {
-  const uint64_t step = act_step(a, ex);
-  const U4 u = philox4x32_10(U4{static_cast<uint32_t>(grow), static_cast<uint32_t>(step),
-                                static_cast<uint32_t>(step >> 32), 0x1A7u},
-                             static_cast<uint32_t>(a.seed), static_cast<uint32_t>(a.seed >> 32));
+constexpr uint32_t kTauStreamAct = 0x1A7u, kTauStreamCritic = 0x1A9u;   // act_iqn's fractions; asvrl_dist_prepare's
+__device__ __forceinline__ float tau_draw(uint64_t seed, uint32_t row, uint64_t step, uint32_t stream) {
+  const U4 u = philox4x32_10(U4{row, static_cast<uint32_t>(step), static_cast<uint32_t>(step >> 32), stream},
+                             static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32));
   return static_cast<float>(u.x >> 8) * (1.0f / 16777216.0f);
+}
+__device__ __forceinline__ float act_tau(const CriticArgs& a, int grow, const AsvIqnActEx* ex = nullptr) {
+  return tau_draw(a.seed, static_cast<uint32_t>(grow), act_step(a, ex), kTauStreamAct);
+}
+
+// IQN_DIST: row m = tile of the [steps][rows_per_step] layout is robot slot n at step t. Its fraction of sample r:
+// given, or the draw the act launch over rows_per_step rows made at step t (act_tau's key with grow = n * 32 + r);
+// then times the level, the scalar or the row's (the f32 product of IQN_ACT_EX / IQN_ACT_RISK).
+__device__ __forceinline__ float iqn_dist_tau(const CriticArgs& a, const AsvIqnDist* d, int tile, int r) {
+  float tau;
+  if (a.taus != nullptr) {
+    tau = a.taus[static_cast<int64_t>(tile) * 32 + r];
+  } else {
+    const int n = tile % d->rows_per_step;
+    const uint64_t t = static_cast<uint64_t>(d->step0 + tile / d->rows_per_step);
+    tau = tau_draw(a.seed, static_cast<uint32_t>(n * 32 + r), t, kTauStreamAct);
+  }
+  const float cv = d->level_rows != nullptr ? d->level_rows[__builtin_amdgcn_readfirstlane(tile)] : d->cvar;
+  return tau * cv;
 }
 
 // IQN_ACT_RISK: the risk level of state b (one 32-tau tile, so one wave: b is wave-uniform). Every lane evaluates it
@@ -280,6 +303,52 @@ __device__ __forceinline__ void iqn_act_select(const CriticArgs& a, const Critic
   if (risk != nullptr && risk->cvar_out != nullptr) risk->cvar_out[tile] = cv;
 }
 
+// IQN_DIST's epilogue for the state of this tile. ao: register g of lane (r, h) is Q(tau_r, action feat(0, g, h))
+// before the bias. The sums over the 32 taus, their first maximum and the action values are iqn_act_select's,
+// instruction for instruction. The selected action is the recorded one (d->actions, device data: an index outside
+// 0..A-1 selects nothing and the row's z_out is NaN; no address is formed from it) or that maximum.
+__device__ __forceinline__ void iqn_dist_write(const CriticArgs& a, const CriticLdsIqn& L, const f32x16& ao, int tile,
+                                               int lane, float tau, const AsvIqnDist* d) {
+  const int r = lane & 31, h = lane >> 5, A = a.hd.n_actions;
+  const int64_t row = static_cast<int64_t>(tile) * 32 + r;
+  if (d->tau_out != nullptr && h == 0) d->tau_out[row] = tau;
+  float best = -__builtin_inff();
+  int bi = kMaxA;
+#pragma unroll
+  for (int g = 0; g < 16; ++g) {
+    const int m = feat(0, g, h);
+    float v = m < A ? ao[g] + L.bo_a[m] : 0.f;
+    if (d->all_out != nullptr && m < A) d->all_out[row * d->ld_a + m] = v;
+    v = seg_sum<32>(v);   // lanes 31 / 63: the sum over the state's 32 taus
+    if (d->qmean_out != nullptr && r == 31 && m < A)
+      d->qmean_out[static_cast<int64_t>(tile) * d->ld_q + m] = v * (1.0f / 32.0f);
+    if (m < A && v > best) {
+      best = v;
+      bi = m;
+    }
+  }
+  const float ob = __shfl_xor(best, 32, 64);
+  const int oi = __shfl_xor(bi, 32, 64);
+  if (ob > best || (ob == best && oi < bi)) bi = oi;
+  const int greedy = __builtin_amdgcn_readlane(bi, 31);   // lane 31 holds the state's arg-max (kMaxA: none, all NaN)
+  if (d->greedy_out != nullptr && lane == 0) d->greedy_out[tile] = greedy;
+  if (d->z_out == nullptr) return;
+  int sel = greedy;
+  if (d->actions != nullptr) {
+    const double av = d->actions[2 * static_cast<int64_t>(tile)];
+    sel = (av >= 0.0 && av < static_cast<double>(A)) ? static_cast<int>(av) : -1;
+  }
+  if (sel < 0 || sel >= A) {
+    if (h == 0) d->z_out[row] = __uint_as_float(0x7FC00000u);   // NaN (by its bits: one includer builds without NaNs)
+    return;
+  }
+#pragma unroll
+  for (int g = 0; g < 16; ++g) {
+    const int m = feat(0, g, h);
+    if (m == sel) d->z_out[row] = ao[g] + L.bo_a[m];   // one half holds the action: all_out's value of it
+  }
+}
+
 // acc[mb] += W(mb, ks) B(ks) over ks < KS for MB feature blocks, the weight fragments W (staged in LDS)
 // of k-step ks + 1 read while k-step ks's MFMAs issue, one scheduling fence per k-step: otherwise each
 // MFMA waits on its own fragment read (A/B knob; same MFMA order, bit-identical). Not for IQN_ACT, whose
@@ -313,14 +382,16 @@ __device__ __forceinline__ void mfma_wrows(f32x16 (&acc)[MB], WF wf, BF bf) {
 template <int MODE, int NT, class LT, class FT>
 __device__ __forceinline__ void critic_tile(const CriticArgs& a, const LT& L, int tile, int lane, const FT* Fl,
                                             const float* Gl, float* wsum = nullptr, const float* tau_tile = nullptr,
-                                            const AsvIqnActEx* ex = nullptr, const AsvIqnRisk* risk = nullptr) {
+                                            const AsvIqnActEx* ex = nullptr, const AsvIqnRisk* risk = nullptr,
+                                            const AsvIqnDist* dist = nullptr) {
   constexpr bool IQN = kIqn<MODE>;
   constexpr bool TRAINM = kTrainMode<MODE>;
   const int r = lane & 31, h = lane >> 5;
   const int grow = tile * 32 + r;
   const int b = grow / NT;
   float tau;
-  if (kAct<MODE> && a.taus == nullptr) tau = act_tau(a, grow, ex);
+  if constexpr (MODE == MODE_IQN_DIST) tau = iqn_dist_tau(a, dist, tile, r);
+  else if (kAct<MODE> && a.taus == nullptr) tau = act_tau(a, grow, ex);
   else if (tau_tile != nullptr) tau = tau_tile[r];   // the tile's taus staged by the caller (LDS)
   else tau = a.taus[grow];
   if constexpr (MODE == MODE_IQN_ACT_EX) tau = tau * ex->cvar;   // calc_cos's taus * cvar (IQN_model.py:68); * 1.0f is exact
@@ -472,7 +543,10 @@ __device__ __forceinline__ void critic_tile(const CriticArgs& a, const LT& L, in
 #pragma unroll
     for (int ks = 0; ks < kH / 16; ++ks) ao = mfma(L.wo_img[ks * 64 + lane], h2pk[ks], ao);
     const int A = a.hd.n_actions;   // register g of half h holds action feat(0, g, h)
-    if constexpr (kAct<MODE>) {
+    if constexpr (MODE == MODE_IQN_DIST) {
+      iqn_dist_write(a, L, ao, tile, lane, tau, dist);
+      return;
+    } else if constexpr (kAct<MODE>) {
       if constexpr (MODE == MODE_IQN_ACT_RISK) iqn_act_select(a, L, ao, tile, lane, ex, risk, cv);
       else iqn_act_select(a, L, ao, tile, lane, ex);
       return;

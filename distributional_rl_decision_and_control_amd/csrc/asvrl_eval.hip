@@ -1,6 +1,7 @@
 // asvrl_eval.hip -- the evaluation bookkeeping of Trainer.evaluation (trainer.py:286-303) over the records of
 // one hold_done rollout window: asvrl_eval_metrics; and, further down, its per-robot histories (trainer.py:347-365)
-// cut out of episode-long records: asvrl_eval_history_count, asvrl_eval_history_pack.
+// cut out of episode-long records: asvrl_eval_history_count, asvrl_eval_history_pack; and, at the end, the return-to-go and
+// calibration of recorded return distributions: asvrl_eval_dist_stats.
 //
 // The rollout kernels end an episode by the training rule (every robot deactivated, or the step limit). The
 // evaluation rule also ends it at the first collision of any robot, and it accumulates, per robot that is not yet
@@ -249,10 +250,132 @@ __global__ __launch_bounds__(256) void eval_history_pack_kernel(const AsvEvalHis
   }
 }
 
+// ------------------------------------------------------------------ return distributions
+// asvrl_eval_dist_stats: the return-to-go of every robot and how the recorded quantile samples sit around it (the
+// formulas stand at AsvEvalDistStats). Two launches:
+//
+// scan:  one lane per robot row, as the count kernel. G_t = reward[t] + gamma * G_{t+1} backwards from t = A - 1, one
+//        dependent f64 multiply-add pair per step (uncontracted), G written to g_plane; a wave reads consecutive
+//        doubles of one reward row per step. g0 and steps leave here.
+// stats: one wave per robot row, lane = (step parity, sample): the two halves take the steps 2 i and 2 i + 1, which
+//        depend on nothing but g_plane, so the loads of a pair are independent of every sum. Per step the three sums
+//        over the 32 samples -- the count of z <= G, the pinball terms, z itself -- are the xor butterfly 16, 8, 4, 2,
+//        1 inside the half, in f64 (every lane of the half ends with the same bits; the count is a ballot). Over the
+//        steps each sum runs in lane 0 in the order t = 0, 1, 2, ...: step 2 i, then step 2 i + 1 (read from lane
+//        32). The PIT bin u is counted by lane u (33 lanes, integers). No LDS, no atomics, no barrier; a robot's wave
+//        does not know the block it sits in, so the block size changes nothing.
+constexpr int kDistS = ASVRL_DIST_SAMPLES, kPitBins = kDistS + 1;
+static_assert(2 * kDistS == kWave, "the stats kernel puts two steps of 32 samples in a wave");
+
+__device__ __forceinline__ bool dist_row_exists(const AsvEvalDistStats& s, size_t row) {
+  const int e = static_cast<int>(row / s.max_robots);
+  return static_cast<int>(row - static_cast<size_t>(e) * s.max_robots) < s.n_robots[e];
+}
+
+__global__ __launch_bounds__(1024) void eval_dist_scan_kernel(const AsvEvalDistStats s) {
+  const size_t NT = static_cast<size_t>(s.n_envs) * s.max_robots;
+  const size_t row = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (row >= NT || !dist_row_exists(s, row)) return;
+  const int A = min(max(s.n_act[row], 0), s.n_steps);
+  double G = 0.0;
+  for (int t = A - 1; t >= 0; --t) {
+    const size_t at = static_cast<size_t>(t) * NT + row;
+    G = s.reward[at] + s.gamma * G;
+    s.g_plane[at] = G;
+  }
+  s.g0[row] = G;
+  s.steps[row] = A;
+}
+
+__device__ __forceinline__ double half_butterfly(double v) {   // the sum over the lane's 32-lane half, in every lane
+#pragma unroll
+  for (int m = kDistS / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
+  return v;
+}
+
+__global__ __launch_bounds__(1024) void eval_dist_stats_kernel(const AsvEvalDistStats s) {
+  const size_t NT = static_cast<size_t>(s.n_envs) * s.max_robots;
+  const int lane = threadIdx.x & (kWave - 1), j = lane & (kDistS - 1), h = lane / kDistS;
+  const size_t row = static_cast<size_t>(blockIdx.x) * (blockDim.x / kWave) + threadIdx.x / kWave;   // wave-uniform
+  if (row >= NT || !dist_row_exists(s, row)) return;
+  const int A = min(max(s.n_act[row], 0), s.n_steps);
+  double pin = 0.0, bias = 0.0, pred0 = 0.0;   // lane 0's are the robot's
+  int bin = 0;                                  // lane u: steps with u samples at or below the return
+  for (int t0 = 0; t0 < A; t0 += 2) {
+    const int t = t0 + h;
+    const bool on = t < A;   // the odd half of the last pair of an odd A
+    double G = 0.0, z = 0.0, tau = 0.0;
+    if (on) {
+      const size_t at = static_cast<size_t>(t) * NT + row;
+      G = s.g_plane[at];
+      z = static_cast<double>(s.z[at * kDistS + j]);
+      tau = static_cast<double>(s.tau[at * kDistS + j]);
+    }
+    const unsigned long long le = __ballot(on && z <= G);
+    const int u0 = __popcll(le & 0xFFFFFFFFull), u1 = __popcll(le >> kDistS);
+    const double d = G - z;
+    const double p = half_butterfly(d * (tau - (d < 0.0 ? 1.0 : 0.0)));
+    const double m = half_butterfly(z) * (1.0 / kDistS);
+    const double b = m - G;
+    const double p1 = __shfl(p, kDistS, kWave), b1 = __shfl(b, kDistS, kWave);
+    const bool two = t0 + 1 < A;   // wave-uniform
+    if (t0 == 0) pred0 = m;
+    pin += p;
+    bias += b;
+    if (two) {
+      pin += p1;
+      bias += b1;
+    }
+    bin += (lane == u0 ? 1 : 0) + (two && lane == u1 ? 1 : 0);
+  }
+  if (lane < kPitBins) s.pit[row * kPitBins + lane] = bin;
+  if (lane == 0) {
+    s.pinball[row] = pin;
+    s.bias[row] = bias;
+    s.pred0[row] = pred0;
+  }
+}
+
 }  // namespace
 }  // namespace asvrl
 
 using namespace asvrl;
+
+extern "C" int64_t asvrl_eval_dist_stats_struct_size(void) { return sizeof(AsvEvalDistStats); }
+
+extern "C" int asvrl_eval_dist_stats(const AsvEvalDistStats* s, void* stream) {
+  const std::string who = "asvrl_eval_dist_stats";
+  ASVRL_REQUIRE(s != nullptr, who + ": null struct");
+  ASVRL_REQUIRE(s->n_steps >= 1, who + ": n_steps must be >= 1");
+  ASVRL_REQUIRE(s->n_envs >= 1, who + ": n_envs must be >= 1");
+  ASVRL_REQUIRE(s->max_robots >= 1 && s->max_robots <= 32, who + ": max_robots must be in 1..32");
+  ASVRL_REQUIRE(s->block == 0 || (s->block >= kWave && s->block <= 1024 && s->block % kWave == 0),
+                who + ": block must be 0 or a multiple of 64 up to 1024");
+  ASVRL_REQUIRE(s->gamma == s->gamma && s->gamma >= 0.0 && s->gamma <= 1.0, who + ": gamma must be in [0, 1]");
+#define ASVRL_DIST_ARRAY(name) ASVRL_REQUIRE(s->name != nullptr, who + ": null array " #name)
+  ASVRL_DIST_ARRAY(z);
+  ASVRL_DIST_ARRAY(tau);
+  ASVRL_DIST_ARRAY(reward);
+  ASVRL_DIST_ARRAY(n_act);
+  ASVRL_DIST_ARRAY(n_robots);
+  ASVRL_DIST_ARRAY(g_plane);
+  ASVRL_DIST_ARRAY(g0);
+  ASVRL_DIST_ARRAY(pred0);
+  ASVRL_DIST_ARRAY(pit);
+  ASVRL_DIST_ARRAY(pinball);
+  ASVRL_DIST_ARRAY(bias);
+  ASVRL_DIST_ARRAY(steps);
+#undef ASVRL_DIST_ARRAY
+  const int block = s->block == 0 ? 256 : s->block;
+  const long long NT = static_cast<long long>(s->n_envs) * s->max_robots;
+  hipLaunchKernelGGL(eval_dist_scan_kernel, dim3(static_cast<unsigned>((NT + block - 1) / block)), dim3(block), 0,
+                     as_stream(stream), *s);
+  if (int rc = check_launch("asvrl_eval_dist_stats (scan)")) return rc;
+  const int wpb = block / kWave;
+  hipLaunchKernelGGL(eval_dist_stats_kernel, dim3(static_cast<unsigned>((NT + wpb - 1) / wpb)), dim3(block), 0,
+                     as_stream(stream), *s);
+  return check_launch("asvrl_eval_dist_stats");
+}
 
 extern "C" int64_t asvrl_eval_metrics_struct_size(void) { return sizeof(AsvEvalMetrics); }
 

@@ -11,6 +11,7 @@ cos embedding, both hidden layers, the output layer, the quantile-Huber loss and
 backward -- in two kernel launches per critic pass, the state/action encoders and the actor
 on torch, and the trunk's weight gradients as split-K bf16 GEMMs over the saved activations.
 """
+import collections
 import contextlib
 import ctypes as C
 
@@ -134,6 +135,57 @@ def critic_forward(pack, F, G, taus, N, q=None, stream=None, obs=None, act=None)
     _abi.check(pack.L.asvrl_critic_forward(C.byref(pack.struct), C.byref(io), _abi.stream_ptr(stream)),
                "asvrl_critic_forward", pack.L)
     return q.view(B, N)
+
+
+CriticDistribution = collections.namedtuple("CriticDistribution", "z taus")
+
+
+def dist_prepare(L, rows, rows_per_step, step0, seed, taus_out=None, actions64=None, act_out=None, stream=None):
+    """asvrl_dist_prepare of library L: the critic's Philox fractions of `rows` rows laid out [steps][rows_per_step]
+    (key (slot * 32 + sample, step0 + step, seed), a stream of its own) into taus_out [rows, 32] f32, and the f32 copy
+    of the f64 pairs actions64 [rows, 2] into act_out. One launch, nothing drawn by torch, no synchronisation."""
+    p = _abi.AsvDistPrepare()
+    p.rows, p.rows_per_step, p.step0, p.seed = int(rows), int(rows_per_step), int(step0), int(seed) & (2 ** 64 - 1)
+    p.taus_out, p.actions, p.act_out = _p(taus_out), _p(actions64), _p(act_out)
+    _abi.check(L.asvrl_dist_prepare(C.byref(p), _abi.stream_ptr(stream)), "asvrl_dist_prepare", L)
+
+
+def critic_dist(pack, obs, actions64, *, rows_per_step, step0=0, seed=0, taus=None, z_out=None, tau_out=None,
+                stream=None, act32=None):
+    """The AC-IQN critic's return distribution at recorded actions: Z(s_m, a_m, tau_mj), j < 32, for the observation
+    rows obs [M, >= 37] f32 and the f64 action pairs actions64 [M, 2] (the windows' record: the actor's f32 output
+    widened, so its f32 copy is exact). The fractions are `taus` [M, 32] or drawn by asvrl_dist_prepare (rows laid out
+    [steps][rows_per_step], key (slot * 32 + sample, step0 + step, seed); not the policy's stream and not torch's);
+    the forward is asvrl_critic_forward with N = 32 on the rows and the f32 pairs. act32: scratch [M, 2] f32 for that
+    copy (allocated when None). Returns CriticDistribution(z [M, 32], taus [M, 32]): z_out / tau_out or new tensors;
+    with `taus` given and no tau_out, taus itself."""
+    if obs.dtype != torch.float32 or obs.dim() != 2 or obs.stride(-1) != 1 or obs.shape[1] < 37:
+        raise ValueError("critic_dist: obs must be f32 rows [M, >= 37] with unit column stride")
+    M, dev = obs.shape[0], obs.device
+    if int(rows_per_step) < 1:
+        raise ValueError("critic_dist: rows_per_step must be >= 1")
+    if int(step0) < 0:
+        raise ValueError("critic_dist: step0 must be >= 0")
+    if actions64.dtype != torch.float64 or tuple(actions64.shape) != (M, 2) or not actions64.is_contiguous():
+        raise ValueError(f"critic_dist: actions64 must be a contiguous f64 tensor ({M}, 2)")
+    for name, t in (("taus", taus), ("z_out", z_out), ("tau_out", tau_out)):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (M, 32) or not t.is_contiguous()):
+            raise ValueError(f"critic_dist: {name} must be a contiguous f32 tensor ({M}, 32)")
+    f = dict(dtype=torch.float32, device=dev)
+    z = z_out if z_out is not None else torch.empty((M, 32), **f)
+    act32 = act32 if act32 is not None else torch.empty((M, 2), **f)
+    if M == 0:   # nothing to launch (an empty tensor has no address to hand over)
+        return CriticDistribution(z, tau_out if tau_out is not None else (taus if taus is not None else z.clone()))
+    if taus is None:
+        tu = tau_out if tau_out is not None else torch.empty((M, 32), **f)
+        dist_prepare(pack.L, M, rows_per_step, step0, seed, tu, actions64, act32, stream)
+    else:
+        tu = taus
+        dist_prepare(pack.L, M, rows_per_step, step0, seed, None, actions64, act32, stream)
+        if tau_out is not None:
+            tu = tau_out.copy_(taus)
+    critic_forward(pack, None, None, tu.view(-1), 32, q=z.view(-1), stream=stream, obs=obs, act=act32)
+    return CriticDistribution(z, tu)
 
 
 class TrainBuffers:

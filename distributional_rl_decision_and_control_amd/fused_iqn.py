@@ -35,6 +35,7 @@ DeviceEnvBatch.policy_rollout(..., cvar=1.0), DeviceEvaluator.run(..., policy_se
 
 Arithmetic: bf16 MFMA operands with f32 accumulation, f32 master weights / Adam.
 """
+import collections
 import ctypes as C
 import dataclasses
 import math
@@ -318,6 +319,88 @@ def iqn_act(pack, F, actions64, step_dev, steps_per_count, total, fraction, init
         return
     _abi.check(pack.L.asvrl_iqn_act_ex(C.byref(pack.struct), C.byref(pack.head), C.byref(io), C.byref(ex),
                                        _abi.stream_ptr(stream)), "asvrl_iqn_act_ex", pack.L)
+
+
+IqnDistribution = collections.namedtuple("IqnDistribution", "z taus all greedy q")
+
+
+def iqn_dist(pack, obs, *, rows_per_step=None, step0=0, seed=0, cvar=1.0, levels=None, taus=None, actions=None,
+             z_out=None, tau_out=None, all_out=None, greedy_out=None, q_out=None, stream=None):
+    """The quantile samples behind act_iqn's decisions on the observation rows `obs` [M, >= 37] f32 (asvrl_iqn_dist:
+    the act pass's tile, so its action values bit for bit; nothing is drawn for exploration and no action is written).
+    The rows are [steps][rows_per_step] (default: one step of M rows): row m is robot slot m % rows_per_step at step
+    step0 + m // rows_per_step, and its 32 fractions are `taus` [M, 32] or the Philox draws of the act launch over
+    rows_per_step rows at that step under `seed` (iqn_act(..., step_add=t) with a null or zero step counter). Every
+    fraction is multiplied by cvar in (0, 1], or by the row's entry of levels (f32 [M], each in (0, 1], not checked:
+    no synchronisation; cvar must then be 1. The device evaluation passes the recorded levels of every slot, acted
+    or not: a slot that did not act carries 0.0 or a stale value, which only scales that row's fractions, and the row
+    is never read). actions (f64 [M, 2], the windows' record): the selected action is column
+    0, otherwise the first arg-max of the 32-sample sums; an index outside 0..A-1 gives a NaN row of z.
+    Returns IqnDistribution(z [M, 32] the selected action's quantile values in sample order, taus [M, 32] the
+    fractions used, all [M, 32, A] every action's values (what act_iqn returns as quantiles), greedy [M] i32 the
+    arg-max, q [M, A] the action values); each is the tensor given (all_out / q_out may have a wider last stride) or
+    allocated here."""
+    if obs.dtype != torch.float32 or obs.dim() != 2 or obs.stride(-1) != 1 or obs.shape[1] < 37:
+        raise ValueError("iqn_dist: obs must be f32 rows [M, >= 37] with unit column stride")
+    M, A, dev = obs.shape[0], pack.head.n_actions, obs.device
+    rows_per_step = max(M, 1) if rows_per_step is None else int(rows_per_step)
+    if rows_per_step < 1:
+        raise ValueError("iqn_dist: rows_per_step must be >= 1")
+    if int(step0) < 0:
+        raise ValueError("iqn_dist: step0 must be >= 0")
+    if not 0.0 < float(cvar) <= 1.0:
+        raise ValueError("iqn_dist: cvar must be in (0, 1]")
+    if levels is not None and float(cvar) != 1.0:
+        raise ValueError("iqn_dist: one level, cvar or levels, not both")
+
+    def given(t, name, dtype, shape):
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"iqn_dist: {name} must be a contiguous {dtype} tensor {shape} on {dev}")
+        return t
+
+    def out2(t, name, dtype, lead):   # outputs whose last dimension may be padded: [lead..., >= A]
+        if t is None:
+            return torch.empty(lead + (A,), dtype=dtype, device=dev)
+        if (t.dtype != dtype or tuple(t.shape[:-1]) != lead or t.shape[-1] < A or t.device != dev
+                or not t.is_contiguous()):
+            raise ValueError(f"iqn_dist: {name} must be a contiguous {dtype} tensor {lead + ('>= %d' % A,)} on {dev}")
+        return t
+    f32 = torch.float32
+    z = torch.empty((M, K_ACT), dtype=f32, device=dev) if z_out is None else given(z_out, "z_out", f32, (M, K_ACT))
+    tu = torch.empty((M, K_ACT), dtype=f32, device=dev) if tau_out is None else given(tau_out, "tau_out", f32,
+                                                                                       (M, K_ACT))
+    gr = torch.empty(M, dtype=torch.int32, device=dev) if greedy_out is None else given(greedy_out, "greedy_out",
+                                                                                        torch.int32, (M,))
+    al = out2(all_out, "all_out", f32, (M, K_ACT))
+    qm = out2(q_out, "q_out", f32, (M,))
+    if taus is not None:
+        given(taus, "taus", f32, (M, K_ACT))
+    if levels is not None:
+        given(levels, "levels", f32, (M,))
+    if actions is not None:
+        given(actions, "actions", torch.float64, (M, 2))
+    if M:   # no rows: nothing to launch (an empty tensor has no address to hand over)
+        iqn_dist_launch(pack, obs, rows_per_step, step0, seed, cvar, levels, taus, actions, z, tu, al, gr, qm, stream)
+    return IqnDistribution(z, tu, al, gr, qm)
+
+
+def iqn_dist_launch(pack, obs, rows_per_step, step0, seed, cvar, levels, taus, actions, z, tau, all_, greedy, q,
+                    stream=None):
+    """asvrl_iqn_dist on checked tensors (iqn_dist's, or the evaluator's planes); an output that is None is not
+    written, so a caller that wants the samples alone moves no [M, 32, A] block."""
+    io = _io(None, K_ACT, obs=obs, taus=taus)
+    io.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    d = _abi.AsvIqnDist()
+    d.rows_per_step, d.cvar, d.step0 = int(rows_per_step), float(cvar), int(step0)
+    for name, t in (("level_rows", levels), ("actions", actions), ("z_out", z), ("tau_out", tau),
+                    ("greedy_out", greedy)):
+        setattr(d, name, t.data_ptr() if t is not None else None)
+    if all_ is not None:
+        d.all_out, d.ld_a = all_.data_ptr(), all_.shape[-1]
+    if q is not None:
+        d.qmean_out, d.ld_q = q.data_ptr(), q.shape[-1]
+    _abi.check(pack.L.asvrl_iqn_dist(C.byref(pack.struct), C.byref(pack.head), C.byref(io), C.byref(d),
+                                     _abi.stream_ptr(stream)), "asvrl_iqn_dist", pack.L)
 
 
 class FusedIQNState:

@@ -223,6 +223,123 @@ def history_lists(result):
     return result
 
 
+# ------------------------------------------------------------------ return distributions
+DIST_OUTPUTS = (("g0", torch.float64, ()), ("pred0", torch.float64, ()), ("pinball", torch.float64, ()),
+                ("bias", torch.float64, ()), ("steps", torch.int32, ()), ("pit", torch.int32, (_abi.DIST_SAMPLES + 1,)))
+
+
+def new_dist_outputs(NT, device):
+    """The per-robot outputs of asvrl_eval_dist_stats at their pre-fill (zeros; absent slots keep it)."""
+    return {n: torch.zeros((NT,) + tail, dtype=dt, device=device) for n, dt, tail in DIST_OUTPUTS}
+
+
+def eval_dist_stats(L, T, E, R, z, tau, reward, n_act, n_robots, gamma, out, G, block=0, stream=None):
+    """asvrl_eval_dist_stats of library L for one group: z, tau [T, NT, 32] f32 (the quantile samples and fractions
+    behind the decision of robot row n at step t), reward [T, NT] f64, n_act [NT] i32 (plane 1 of history_count's
+    counts), n_robots [E] i32; out: new_dist_outputs' tensors, G [T, NT] f64 the return-to-go plane (rows at or behind
+    a robot's n_act are not written). block: threads per block of the two launches (0: 256); the results do not
+    depend on it. Two launches, no atomics: the same bits from run to run."""
+    NT = E * R
+    s = _abi.AsvEvalDistStats()
+    s.n_steps, s.n_envs, s.max_robots, s.block, s.gamma = int(T), int(E), int(R), int(block), float(gamma)
+    S = _abi.DIST_SAMPLES
+    shapes = dict(z=((T, NT, S), torch.float32), tau=((T, NT, S), torch.float32), reward=((T, NT), torch.float64),
+                  n_act=((NT,), torch.int32), n_robots=((E,), torch.int32), g_plane=((T, NT), torch.float64))
+    given = dict(z=z, tau=tau, reward=reward, n_act=n_act, n_robots=n_robots, g_plane=G)
+    for n, dt, tail in DIST_OUTPUTS:
+        shapes[n], given[n] = ((NT,) + tail, dt), out[n]
+    for name, (shape, dtype) in shapes.items():
+        t = given[name]
+        assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape, name
+        setattr(s, name, t.data_ptr())
+    _abi.check(L.asvrl_eval_dist_stats(C.byref(s), _abi.stream_ptr(stream)), "asvrl_eval_dist_stats", L)
+    return out, G
+
+
+class EvalDistribution:
+    """What run(distribution=...) adds as result["distribution"]: per config c and robot i, as arrays indexed [c][i],
+    g0 (the discounted return the robot collected from step 0: robot_rewards by a backward scan), pred0 (the mean of
+    the 32 quantile samples at its first decision), pit ([33]: how often u of the 32 samples lay at or below the
+    return-to-go, over its decisions), pinball (the quantile loss summed over its decisions and samples), bias (the
+    sum over its decisions of sample mean - return-to-go), steps (its decisions) and truncated (its outcome is 0: the
+    episode ended at the limit or by another robot's collision while it was running, so its returns are cut short).
+    mismatches (an IqnPack only, else None): acted robot-steps whose recomputed greedy action differs from the
+    recorded one. The samples themselves stay on the device, in planes the evaluator reuses at its next run with a
+    distribution: quantiles / taus / returns_to_go copy a robot's rows on demand."""
+    ARRAYS = ("g0", "pred0", "pit", "pinball", "bias", "steps", "truncated")
+
+    def __init__(self, arrays, where, planes, mismatches, kind):
+        for name in self.ARRAYS:
+            setattr(self, name, arrays[name])
+        self._where, self._planes = where, planes
+        self.mismatches, self.kind = mismatches, kind
+
+    def _rows(self, name, c, i):
+        g, row0 = self._where[c]
+        return self._planes[g][name][:int(self.steps[c][i]), row0 + i].cpu().numpy()
+
+    def quantiles(self, c, i):
+        """[steps, 32] f32: the quantile values of the action robot i of config c took, in sample order."""
+        return self._rows("z", c, i)
+
+    def taus(self, c, i):
+        """[steps, 32] f32: their fractions (after the risk level)."""
+        return self._rows("tau", c, i)
+
+    def returns_to_go(self, c, i):
+        """[steps] f64: G_t, the discounted return from step t on."""
+        return self._rows("G", c, i)
+
+    def summary(self, terminated_only=True):
+        """Calibration per config and overall (host numpy over the per-robot arrays): "pit" the normalised PIT
+        histogram [33] (uniform for a calibrated distribution up to the samples' own spread), "pinball" the quantile
+        loss per sample, "bias" the mean of sample mean - return-to-go per decision, "pred0_minus_g0" the mean over
+        robots of pred0 - g0, "robots" and "steps" what entered. terminated_only drops the truncated robots. Values
+        with nothing behind them are NaN. Returns {"configs": {name: array over configs}, "overall": {name: value}}."""
+        S = _abi.DIST_SAMPLES
+
+        def reduce(sel):
+            steps = sum(int(self.steps[c][m].sum()) for c, m in sel)
+            robots = sum(int((self.steps[c][m] > 0).sum()) for c, m in sel)
+            pit = sum((self.pit[c][m].sum(axis=0) for c, m in sel), np.zeros(S + 1))
+            pin = sum(float(self.pinball[c][m].sum()) for c, m in sel)
+            bias = sum(float(self.bias[c][m].sum()) for c, m in sel)
+            gap = sum(float((self.pred0[c][m] - self.g0[c][m])[self.steps[c][m] > 0].sum()) for c, m in sel)
+            nan = float("nan")
+            return dict(pit=pit / steps if steps else np.full(S + 1, nan), pinball=pin / (steps * S) if steps else nan,
+                        bias=bias / steps if steps else nan, pred0_minus_g0=gap / robots if robots else nan,
+                        robots=robots, steps=steps)
+        masks = [(~t if terminated_only else np.ones_like(t)) for t in self.truncated]
+        per = [reduce([(c, m)]) for c, m in enumerate(masks)]
+        return dict(configs={k: np.array([p[k] for p in per]) for k in per[0]}, overall=reduce(list(enumerate(masks))),
+                    terminated_only=bool(terminated_only))
+
+
+def distribution_source(who, pack, distribution):
+    """The refusals of run(distribution=...): None -> None; else ("iqn", pack) for an IqnPack with True, or
+    ("critic", CriticPack) for the Actor's pack with the AC-IQN critic's CriticPack."""
+    from ..fused_critic import CriticPack
+    from ..fused_iqn import IqnPack
+    from ..fused_mlp import MlpPack
+    if distribution is None or distribution is False:
+        return None
+    if pack is None:
+        raise ValueError(f"{who}: distribution reads the quantiles of the policy that acted; an action table has none")
+    if isinstance(pack, IqnPack):
+        if distribution is not True:
+            raise ValueError(f"{who}: an IqnPack's distribution is its own (distribution=True)")
+        return "iqn", pack
+    if type(pack) is MlpPack and getattr(pack, "kind", None) == "actor":   # not DQN's or SAC's packs, its subclasses
+        if type(distribution) is CriticPack and distribution.struct.ae_w:
+            if distribution.L is not pack.L:
+                raise ValueError(f"{who}: the critic's pack and the actor's are of different operand builds")
+            return "critic", distribution
+        raise ValueError(f"{who}: with the Actor's pack, distribution must be the AC-IQN critic's CriticPack (a "
+                         "trainer's fused2.local_trunk); DDPG's critic has no return distribution")
+    raise ValueError(f"{who}: distribution is offered for an IqnPack (True) and for AC-IQN's Actor with its critic's "
+                     f"CriticPack, not for a {type(pack).__name__} (Rainbow's C51 atoms are not read out yet)")
+
+
 def _check_perception(who, perception, *noises):
     if perception not in PERCEPTIONS:
         raise ValueError(f"{who}: perception must be one of {PERCEPTIONS}, not {perception!r}")
@@ -269,6 +386,7 @@ class _Group:
         self.step = torch.zeros(1, dtype=torch.int64, device=device)
         self._rec = {}
         self._hist = {}
+        self._dist = {}
         self._streams = None
 
     def streams(self):
@@ -322,6 +440,23 @@ class _Group:
             H["counts"] = torch.zeros((3, b.n_envs * b.max_robots), dtype=torch.int32, device=b.device)
             self._hist[T] = H
         return H
+
+    def distribution(self, T, kind):
+        """The planes of run(distribution=...), allocated once per T and reused: z, tau [T, NT, 32] f32 and G [T, NT]
+        f64, the per-robot outputs of asvrl_eval_dist_stats, and what the readout of `kind` needs beside them."""
+        D = self._dist.get(T)
+        if D is None:
+            b = self.batch
+            NT, dev = b.n_envs * b.max_robots, b.device
+            D = dict(z=torch.zeros((T, NT, _abi.DIST_SAMPLES), dtype=torch.float32, device=dev),
+                     tau=torch.zeros((T, NT, _abi.DIST_SAMPLES), dtype=torch.float32, device=dev),
+                     G=torch.zeros((T, NT), dtype=torch.float64, device=dev), out=new_dist_outputs(NT, dev))
+            self._dist[T] = D
+        if kind == "iqn" and "greedy" not in D:
+            D["greedy"] = torch.zeros(D["G"].shape, dtype=torch.int32, device=D["G"].device)
+        if kind == "critic" and "act32" not in D:
+            D["act32"] = torch.zeros(D["G"].shape + (2,), dtype=torch.float32, device=D["G"].device)
+        return D
 
     @staticmethod
     def window(H, t0, k, names):
@@ -407,7 +542,8 @@ class DeviceEvaluator:
 
     @torch.no_grad()
     def run(self, pack=None, *, actions=None, noise=None, obs_noise=None, seed=0, episode_limit=1000, sync=True,
-            is_continuous=None, policy_seed=0, deterministic=False, cvar=1.0, perception="philox", histories=False):
+            is_continuous=None, policy_seed=0, deterministic=False, cvar=1.0, perception="philox", histories=False,
+            distribution=None):
         """One evaluation of every config. pack: the Actor's MlpPack or DQN's DqnPack, greedy in closed-loop
         windows, or SAC's SacActorPack, which samples its action as act_sac does in evaluation too (group g draws
         under policy_seed + g: rows are batch-local, so two groups share no draws) or, with deterministic=True (a
@@ -441,7 +577,16 @@ class DeviceEvaluator:
         observation and object-count arrays and every robot's slices of them; the action history is the `actions`
         record of the windows or, teacher-forced, the caller's table, read as is_continuous says. observations /
         actions / trajectories stay empty per robot until history_lists(result) fills them with the reference's
-        lists. False (the default) allocates and launches nothing for them."""
+        lists. False (the default) allocates and launches nothing for them.
+        distribution: None (the default: nothing allocated, launched or added), True with an IqnPack, or the AC-IQN
+        critic's CriticPack (a trainer's fused2.local_trunk) with its Actor's pack; a ValueError for anything else
+        (distribution_source). Keeps the episode-long records of histories=True (packed into "history" only if that is
+        set too) and, after the last window, reads out per group the 32 quantile samples behind every recorded
+        decision -- IQN: fused_iqn.iqn_dist on the rows the robots acted on, at the recorded action, under the act
+        launches' own Philox keys (policy_seed + g, step t) and the run's cvar, or under an AdaptiveCvar the level
+        recorded with every action; AC-IQN: fused_critic.critic_dist at the recorded thrust pair, its fractions a
+        Philox stream of their own -- and reduces them against the return each robot then collected
+        (asvrl_eval_dist_stats). Adds "distribution", an EvalDistribution."""
         if (pack is None) == (actions is None):
             raise ValueError("run takes the Actor's pack or an action table, not both")
         if pack is not None and not pack.is_policy:
@@ -450,6 +595,8 @@ class DeviceEvaluator:
             raise ValueError("run: is_continuous=%s does not match the pack (a DqnPack, IqnPack or RainbowPack picks "
                              "discrete actions, the Actor continuous ones)" % bool(is_continuous))
         cvar = policy_options("run", pack, cvar, deterministic)   # a float or an AdaptiveCvar (no per-row tensor)
+        dist = distribution_source("run", pack, distribution)
+        record = bool(histories) or dist is not None   # the episode-long records
         _check_perception("run", perception, noise, obs_noise)
         is_continuous = True if is_continuous is None else bool(is_continuous)
         episode_limit = int(episode_limit)
@@ -462,7 +609,7 @@ class DeviceEvaluator:
         L = pack.L if pack is not None else _abi.lib()
         self.observe(obs_noise, seed, perception)
         hist = names = None
-        if histories:   # the episode-long records, and what stands in front of step 0
+        if record:   # the episode-long records, and what stands in front of step 0
             hist = [grp.history(episode_limit + 1) for grp in self.groups]
             names = HISTORY_RECORDS if pack is not None else tuple(n for n in HISTORY_RECORDS if n != "actions")
             for grp, H in zip(self.groups, hist):
@@ -474,7 +621,7 @@ class DeviceEvaluator:
             k = 1 if numpy_noise else min(self.chunk, total - t0)
             for g, grp in enumerate(self.groups):
                 b, st = grp.batch, grp.state
-                rec = grp.window(hist[g], t0, k, names) if histories else grp.records(k)
+                rec = grp.window(hist[g], t0, k, names) if record else grp.records(k)
                 if numpy_noise:   # this step's rows from the streams of the robots still active
                     noise[g] = grp.streams().fill(b, env_mask=st["alive"])[None]
                 if pack is not None:
@@ -498,12 +645,15 @@ class DeviceEvaluator:
             if sync and not any(bool(grp.state["alive"].any().item()) for grp in self.groups):
                 break   # one host wait per window
         self.steps = t0
-        if histories:   # the records, the action source per group and how to read it
+        if record:   # the records, the action source per group and how to read it
             hist = dict(L=L, T=episode_limit + 1, records=hist,
                         actions=[H["actions"] for H in hist] if pack is not None else actions,
                         continuous=pack.continuous if pack is not None else is_continuous,
-                        levels=not isinstance(cvar, float))
-        out = self._result(check_ended=pack is None and total < episode_limit + 1, draws=numpy_noise, hist=hist)
+                        levels=not isinstance(cvar, float), pack=bool(histories))
+        if dist is not None:
+            dist = dict(kind=dist[0], pack=dist[1], seed=int(policy_seed), cvar=cvar)
+        out = self._result(check_ended=pack is None and total < episode_limit + 1, draws=numpy_noise, hist=hist,
+                           dist=dist)
         out["cvar"] = cvar if isinstance(cvar, float) else cvar.as_dict()
         return out
 
@@ -541,7 +691,38 @@ class DeviceEvaluator:
         return EvalHistory(host["traj"], host["act"], host["obs"], host["cnt"], slices, hist["continuous"],
                            hist["levels"])
 
-    def _result(self, check_ended=False, draws=False, hist=None):
+    def _distribution_pass(self, g, hist, dist):
+        """Group g's readout and reduction behind the last window (the count launch has run): the quantile samples of
+        the steps that ran -- obs0 and the recorded action of step 0, then obs[0 : steps - 1] and the actions of the
+        steps 1 .. steps - 1 -- into the group's planes, then asvrl_eval_dist_stats. Returns the planes."""
+        from ..fused_critic import critic_dist
+        from ..fused_iqn import iqn_dist_launch
+        grp, H = self.groups[g], hist["records"][g]
+        b = grp.batch
+        NT, T, S = b.n_envs * b.max_robots, hist["T"], _abi.DIST_SAMPLES
+        D = grp.distribution(T, dist["kind"])
+        act = H["actions"]
+        for t0, t1, obs in ((0, 1, H["obs0"]), (1, self.steps, H["obs"][:max(self.steps - 1, 0)])):
+            if t1 <= t0:
+                continue
+            M = (t1 - t0) * NT
+            rows, a64 = obs.reshape(M, _abi.OBS_DIM), act[t0:t1].reshape(M, 2)
+            z, tau = D["z"][t0:t1].view(M, S), D["tau"][t0:t1].view(M, S)
+            if dist["kind"] == "iqn":
+                per_robot = not isinstance(dist["cvar"], float)   # the level recorded with every action
+                levels = a64[:, 1].to(torch.float32).contiguous() if per_robot else None
+                iqn_dist_launch(dist["pack"], rows, NT, t0, dist["seed"] + g, 1.0 if per_robot else dist["cvar"], levels,
+                                None, a64, z, tau, None, D["greedy"][t0:t1].view(M), None)
+            else:
+                critic_dist(dist["pack"], rows, a64, rows_per_step=NT, step0=t0, seed=dist["seed"] + g, z_out=z,
+                            tau_out=tau, act32=D["act32"][t0:t1].view(M, 2))
+        for t in D["out"].values():
+            t.zero_()
+        eval_dist_stats(hist["L"], T, b.n_envs, b.max_robots, D["z"], D["tau"], H["reward"], H["counts"][1],
+                        b.n_robots, self.gamma, D["out"], D["G"])
+        return D
+
+    def _result(self, check_ended=False, draws=False, hist=None, dist=None):
         # one copy: every group's lengths, ended flags, outcomes and sums in one f64 tensor
         parts = []
         for grp in self.groups:
@@ -555,6 +736,16 @@ class DeviceEvaluator:
                               b.n_robots, counts=H["counts"])
                 H["offsets"] = history_offsets(H["counts"])
                 parts.append(H["counts"].double().reshape(-1))
+        planes = []
+        if dist is not None:   # behind those every group's per-robot distribution outputs (and IQN's mismatch count)
+            for g, (grp, H) in enumerate(zip(self.groups, hist["records"])):
+                D = self._distribution_pass(g, hist, dist)
+                planes.append(D)
+                parts += [D["out"][n].double().reshape(-1) for n, _, _ in DIST_OUTPUTS]
+                if dist["kind"] == "iqn":
+                    k = self.steps
+                    acted = torch.arange(k, device=self.device)[:, None] < H["counts"][1][None, :]
+                    parts.append(((D["greedy"][:k].double() != H["actions"][:k, :, 0]) & acted).sum().double()[None])
         flat = torch.cat(parts).cpu().numpy()
         n = len(self.envs)
         out = dict(observations=[None] * n, actions=[None] * n, trajectories=[None] * n, rewards=[None] * n,
@@ -598,5 +789,28 @@ class DeviceEvaluator:
                 NT = grp.batch.n_envs * grp.batch.max_robots
                 counts.append(flat[at:at + 3 * NT].reshape(3, NT))
                 at += 3 * NT
-            out["history"] = self._history(hist, counts)
+            if hist["pack"]:
+                out["history"] = self._history(hist, counts)
+        if dist is not None:
+            arrays = {name: [None] * n for name in EvalDistribution.ARRAYS}
+            where, mismatches = [None] * n, 0
+            for g, grp in enumerate(self.groups):
+                R = grp.batch.max_robots
+                NT = grp.batch.n_envs * R
+                got = {}
+                for name, dt, tail in DIST_OUTPUTS:
+                    w = NT * int(np.prod(tail, dtype=np.int64))
+                    got[name] = flat[at:at + w].reshape((NT,) + tail)
+                    at += w
+                if dist["kind"] == "iqn":
+                    mismatches += int(flat[at])
+                    at += 1
+                for le, c in enumerate(grp.members):
+                    sl = slice(le * R, le * R + self.n_robots[c])
+                    where[c] = (g, le * R)
+                    for name, dt, _ in DIST_OUTPUTS:
+                        arrays[name][c] = got[name][sl].astype(np.int32 if dt == torch.int32 else np.float64)
+                    arrays["truncated"][c] = out["robot_outcomes"][c] == 0
+            out["distribution"] = EvalDistribution(arrays, where, planes, mismatches if dist["kind"] == "iqn" else None,
+                                                   dist["kind"])
         return out

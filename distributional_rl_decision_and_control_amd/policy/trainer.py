@@ -18,6 +18,8 @@ network (evaluation(batched="device"), policy/device_eval.py). "device_eval": {"
 with the perception noise drawn from every robot's own RandomState stream, as the other evaluation paths draw it, and
 "device_eval": {"cvar": 0.25 | "adaptive" | {"near": .., "margin": .., "floor": ..}} (IQN only) evaluates at that risk
 level, the last two at the level fused_iqn.AdaptiveCvar gives every robot at every act, and
+"device_eval": {"distribution": true} (IQN and AC-IQN) also reads out the return distribution behind every decision and
+keeps each evaluation's calibration summary in Trainer.eval_distributions (eval_distributions.npz).
 "device_eval": {"histories": true} also keeps every robot's observation, action and trajectory history, so
 evaluations.npz replays in the reference's visualize_eval_episode.py like the file of the other evaluation paths.
 """
@@ -200,11 +202,18 @@ class Trainer:
         # the reference's content (DeviceEvaluator.run's histories, device_eval.history_lists)
         opts = kw.pop("device_eval", False)
         if isinstance(opts, dict):
-            known = {"perception", "histories", "cvar"}
+            known = {"perception", "histories", "cvar", "distribution"}
             if set(opts) - known:
                 raise ValueError(f"device_eval: unknown option(s) {sorted(set(opts) - known)}; "
-                                 "it takes \"perception\", \"histories\" and \"cvar\"")
+                                 "it takes \"perception\", \"histories\", \"cvar\" and \"distribution\"")
             self._device_eval_kw = dict(opts)
+            # {"distribution": true}: every evaluation also reads out the return distribution behind each decision
+            # and its calibration (DeviceEvaluator.run's distribution; IQN's own quantiles, AC-IQN's local critic):
+            # eval_distributions keeps each evaluation's summary(), save_evaluation writes eval_distributions.npz
+            self._device_eval_dist = bool(self._device_eval_kw.pop("distribution", False))
+            if self._device_eval_dist and agent.agent_type not in ("IQN", "AC-IQN"):
+                raise ValueError(f"device_eval: \"distribution\" reads IQN's or the AC-IQN critic's quantiles; "
+                                 f"{agent.agent_type} has no return distribution to read")
             if "cvar" in opts:   # IQN's risk level: a number, "adaptive" or the rule's parameters
                 if agent.agent_type != "IQN":
                     raise ValueError(f"device_eval: \"cvar\" is IQN's risk level; {agent.agent_type} has none")
@@ -213,7 +222,7 @@ class Trainer:
                 self._device_eval_kw["histories"] = bool(opts["histories"])
             opts = True
         else:
-            self._device_eval_kw = {}
+            self._device_eval_kw, self._device_eval_dist = {}, False
         device_eval = bool(opts) and agent.agent_type in ("AC-IQN", "DQN", "DDPG", "IQN", "Rainbow")
         kw.setdefault("graphs", True)
         for key, sk in (("num_robots", "num_robots"), ("num_obs", "num_obstacles"), ("num_cores", "num_cores")):
@@ -367,8 +376,15 @@ class Trainer:
             print(f"Evaluating episodes 0-{len(self.eval_config) - 1} (on the device)")
             # the batched trainer's own local images on device-resident eval configs (policy/device_eval.py);
             # Rainbow's eval_pack is Rainbow_Policy.eval(): the mu-only images, packed on this read
-            res = tr.device_evaluator(self.eval_config, template_env=self.eval_env).run(
-                tr.learner.eval_pack, **getattr(self, "_device_eval_kw", {}))
+            run_kw = dict(getattr(self, "_device_eval_kw", {}))
+            if getattr(self, "_device_eval_dist", False):   # IQN's own quantiles, or the AC-IQN local critic's
+                run_kw["distribution"] = True if tr.fused2 is None else tr.fused2.local_trunk
+            res = tr.device_evaluator(self.eval_config, template_env=self.eval_env).run(tr.learner.eval_pack, **run_kw)
+            if "distribution" in res:
+                if not hasattr(self, "eval_distributions"):
+                    self.eval_distributions = []
+                self.eval_distributions.append(dict(timestep=self.current_timestep,
+                                                    **res["distribution"].summary()))
             if "history" in res:   # "device_eval": {"histories": true}: the reference's nested lists
                 from .device_eval import history_lists
                 history_lists(res)
@@ -423,3 +439,11 @@ class Trainer:
                       times=self.eval_times, energies=self.eval_energies, relations=self.eval_relations)
         arrays = {k: np.array(v, dtype=object) for k, v in fields.items()}  # trainer.py:397-410 format
         np.savez(os.path.join(eval_log_path, "evaluations.npz"), **arrays)
+        dists = getattr(self, "eval_distributions", None)
+        if dists:   # "device_eval": {"distribution": true}: a file of its own, evaluations.npz keeps the reference's keys
+            names = ("pit", "pinball", "bias", "pred0_minus_g0", "robots", "steps")
+            out = dict(timesteps=np.array([d["timestep"] for d in dists]))
+            for k in names:
+                out[k] = np.array([d["configs"][k] for d in dists])
+                out["overall_" + k] = np.array([d["overall"][k] for d in dists])
+            np.savez(os.path.join(eval_log_path, "eval_distributions.npz"), **out)

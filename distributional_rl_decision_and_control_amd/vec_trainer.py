@@ -243,12 +243,20 @@ class VecTrainer:
         reference's per-config rewards / successes / times / energies / lengths on the device. kw: run()'s seed,
         episode_limit, sync, perception ("numpy": the robots' own RandomState streams, as the other paths draw) and
         histories (True: the result's "history" holds every robot's observation, action and trajectory history as
-        packed arrays; device_eval.history_lists turns them into the reference's lists). The actor's packed images are the learner's own, so no copy into a drop-in agent is
+        packed arrays; device_eval.history_lists turns them into the reference's lists) and distribution (True: the
+        result's "distribution", an EvalDistribution, holds the local critic's 32 quantile samples at every recorded
+        decision reduced against the return each robot then collected; AC-IQN only, a ValueError for DDPG. An IQN
+        trainer's route is device_evaluator(cfgs).run(fused_iqn.window_pack, distribution=True)). The actor's packed images are the learner's own, so no copy into a drop-in agent is
         needed; the training env, the replay and the step counter are not touched. AC-IQN and DDPG only."""
         if self.learner.actor_pack is None:
             raise NotImplementedError("evaluate runs the AC-IQN / DDPG actor; IQN, Rainbow and DQN act inside their "
                                       "own kernels (device_evaluator(...).run(policy_pack()) for DQN, "
                                       "run(fused_iqn.window_pack) for IQN, run(fused_rb.eval_pack) for Rainbow)")
+        if kw.get("distribution") is True:   # the critic whose quantiles are read out at the recorded actions
+            if self.fused2 is None:
+                raise ValueError(f"evaluate: distribution=True reads the AC-IQN critic's return distribution; "
+                                 f"{self.agent_type}'s critic has none")
+            kw["distribution"] = self.fused2.local_trunk
         return self.device_evaluator(configs, chunk, template_env).run(self.learner.actor_pack, **kw)
 
     def policy_pack(self):

@@ -534,6 +534,52 @@ int asvrl_iqn_act_risk(const AsvCriticWeights* w, const AsvIqnHead* head, const 
 /* sizeof(AsvIqnRisk) as compiled. */
 int64_t asvrl_iqn_risk_struct_size(void);
 
+/* The quantile samples behind act_iqn's decisions (act_iqn's (action, quantiles, taus), agent.py:227-256), read out
+ * after the fact (new entry points only: the ABI version stays 29). The pass is asvrl_iqn_act_ex's tile -- the same
+ * workgroup, the same MFMA order -- so the action values it recomputes are the bits the act launch chose from; it
+ * draws no exploration and writes no action. io: obs (or F), ld_obs, B = M rows, N = 32, taus ([M][32] or NULL =
+ * drawn) and seed; io->step_dev is not read. The rows are laid out [steps][rows_per_step]: row m is robot slot
+ * n = m % rows_per_step at step t = step0 + m / rows_per_step, and a drawn fraction is act_tau's Philox draw on
+ * (n * 32 + sample, t, seed): what the window's act launch over rows_per_step rows drew at step t. */
+typedef struct AsvIqnDist {
+  int32_t rows_per_step;   /* >= 1 */
+  float cvar;              /* in (0, 1]: every fraction times cvar; must be 1 with level_rows */
+  int64_t step0;
+  const float* level_rows; /* optional [M], each in (0, 1] (device memory: not checked): row m's fractions times it.
+                              A value outside the range only scales that row's fractions -- no address depends on it;
+                              the device evaluation relies on that for the rows of slots that did not act */
+  const double* actions;   /* optional [M][2]: the selected action is column 0 (the windows' actions record); NULL:
+                              the recomputed arg-max. An index outside 0..A-1 gives a NaN z_out row */
+  float* z_out;            /* optional [M][32]: the selected action's quantile values in sample order */
+  float* tau_out;          /* optional [M][32]: the fractions used, after the level */
+  float* all_out;          /* optional [M][32][ld_a]: every action's values, columns >= n_actions not written */
+  int64_t ld_a;            /* >= n_actions with all_out */
+  int32_t* greedy_out;     /* optional [M]: the first arg-max of the 32-sample sums, whatever actions says */
+  float* qmean_out;        /* optional [M][ld_q]: the action values, as AsvIqnActEx.qmean_out */
+  int64_t ld_q;            /* >= n_actions with qmean_out */
+} AsvIqnDist;
+int asvrl_iqn_dist(const AsvCriticWeights* w, const AsvIqnHead* head, const AsvIqnIO* io, const AsvIqnDist* dist,
+                   void* stream);
+/* sizeof(AsvIqnDist) as compiled. */
+int64_t asvrl_iqn_dist_struct_size(void);
+
+/* What stands in front of asvrl_critic_forward (N = 32, obs and act) when the AC-IQN critic's quantiles are read
+ * out at recorded actions: the fractions and the f32 copy of the f64 action pairs, in one launch. Row m is robot
+ * slot n = m % rows_per_step at step t = step0 + m / rows_per_step; taus_out[m][j] is the Philox draw on
+ * (n * 32 + j, t, seed) of a stream of its own (not act_tau's), uniform [0, 1). */
+typedef struct AsvDistPrepare {
+  int32_t rows;            /* M >= 0 */
+  int32_t rows_per_step;   /* >= 1 */
+  int64_t step0;
+  uint64_t seed;
+  float* taus_out;         /* optional [M][32] */
+  const double* actions;   /* optional [M][2] f64, with act_out */
+  float* act_out;          /* optional [M][2]: (float) of the pair; exact for an actor's f32 output widened */
+} AsvDistPrepare;
+int asvrl_dist_prepare(const AsvDistPrepare* p, void* stream);
+/* sizeof(AsvDistPrepare) as compiled. */
+int64_t asvrl_dist_prepare_struct_size(void);
+
 /* ---------------------------------------------------------------- replay (replay_buffer.py) */
 
 /* ReplayBuffer.add (replay_buffer.py:22-24) for every robot that acted in the last step
@@ -1268,6 +1314,41 @@ int asvrl_eval_history_pack(const AsvEvalHistory* h, void* stream);
 /* sizeof(AsvEvalHistory) as compiled, and ASVRL_HISTORY_STEP_TILE. */
 int64_t asvrl_eval_history_struct_size(void);
 int32_t asvrl_eval_history_step_tile(void);
+
+/* Return-to-go and calibration of recorded return distributions, for one group of n_envs * max_robots = NT robot
+ * rows over episode-long records of n_steps = T steps (new entry point only: the ABI version stays 29). z and tau
+ * [T][NT][32] f32 are the 32 quantile samples and their fractions behind the decision robot row n took at step t;
+ * reward [T][NT] f64; n_act [NT] i32 (plane 1 of asvrl_eval_history_count's counts, clamped to 0..T here): robot n
+ * acted at steps 0..A-1, A = n_act[n]. Per robot row that exists (n % max_robots < n_robots[n / max_robots]; the
+ * others' outputs are not written), all in f64:
+ *   G_A = 0, G_t = reward[t][n] + gamma * G_{t+1} for t = A-1 .. 0       (g_plane[t][n], rows t >= A not written)
+ *   u_t = #{ j : z[t][n][j] <= G_t } in 0..32,  pit[n][u_t] += 1                                   (pit [NT][33])
+ *   pinball[n] = sum_t sum_j rho(tau[t][n][j], G_t - z[t][n][j]),  rho(tau, d) = d * (tau - (d < 0 ? 1 : 0))
+ *   bias[n] = sum_t (mean_t - G_t),  mean_t = (1/32) sum_j z[t][n][j];  pred0[n] = mean_0 (0 when A = 0)
+ *   g0[n] = G_0 (0 when A = 0),  steps[n] = A
+ * The sums over j are a fixed butterfly over the 32 lanes of a step and the sums over t run t = 0, 1, ... in
+ * order, in one lane: no atomics, the same bits from run to run and for every block size. */
+typedef struct AsvEvalDistStats {
+  int32_t n_steps, n_envs, max_robots;
+  int32_t block;           /* threads per block of both launches: 0 = 256, else a multiple of 64 up to 1024 */
+  double gamma;
+  const float* z;
+  const float* tau;
+  const double* reward;
+  const int32_t* n_act;
+  const int32_t* n_robots; /* [n_envs] */
+  double* g_plane;         /* [T][NT]: scratch of the call and, to the caller, the return-to-go plane */
+  double* g0;              /* [NT] */
+  double* pred0;           /* [NT] */
+  int32_t* pit;            /* [NT][33] */
+  double* pinball;         /* [NT] */
+  double* bias;            /* [NT] */
+  int32_t* steps;          /* [NT] */
+} AsvEvalDistStats;
+#define ASVRL_DIST_SAMPLES 32
+int asvrl_eval_dist_stats(const AsvEvalDistStats* s, void* stream);
+/* sizeof(AsvEvalDistStats) as compiled. */
+int64_t asvrl_eval_dist_stats_struct_size(void);
 
 /* ---------------------------------------------------------------- the reference's perception-noise streams */
 

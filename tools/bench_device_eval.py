@@ -21,9 +21,19 @@ the trained AC-IQN network's, for the record only).
 (run(histories=True)) and with device_eval.history_lists on top, alternating; then the asvrl_eval_history_pack launch
 alone with its achieved bytes per second, against the same packing by torch (permute and boolean mask), whose outputs
 are first compared with the kernel's byte for byte. The default output is profiles/eval_histories.json.
+
+--distribution (--agent AC-IQN or IQN; IQN is a seeded network, none is shipped): no host evaluation; the device
+evaluation without it, with histories=True and with distribution= (the AC-IQN critic's CriticPack, or True for the
+IqnPack), alternating; then the post-pass alone on the last run's records -- the readout launches and
+asvrl_eval_dist_stats -- between device events, with the bytes they move. The result is added to
+profiles/eval_distribution.json under the agent's name (--label), one entry per process. The parent commit's seconds
+belong in the same file from the same session: --plain times the evaluation with no option only, and with
+--package-root <a built checkout of the parent> it runs the parent's package (--label "AC-IQN parent"); --plain
+without it gives this commit's repeated plain runs as a separate process, for the run-to-run spread.
 """
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -137,17 +147,132 @@ def histories(a, ev, pack, clock, z):
             f.write(line + "\n")
 
 
+def distribution(a, ev, pack, source, clock):
+    """--distribution: the per-evaluation time without it, with histories=True and with distribution=source
+    (alternating, after a warm-up round of each); then, on the last run's records, the readout launches
+    (asvrl_iqn_dist, or asvrl_dist_prepare + asvrl_critic_forward) and the two launches of asvrl_eval_dist_stats, each
+    between device events over --kernel-launches repetitions, with the bytes they move."""
+    from distributional_rl_decision_and_control_amd import _abi
+    from distributional_rl_decision_and_control_amd.policy import device_eval as de
+    runs = {"off": lambda: ev.run(pack, seed=1),
+            "histories": lambda: ev.run(pack, seed=1, histories=True),
+            "distribution": lambda: ev.run(pack, seed=1, distribution=source)}
+    times = {k: [] for k in runs}
+    last = {}
+    for rep in range(a.reps + 1):   # the first round is the warm-up (it also allocates the records and the planes)
+        for name, fn in runs.items():
+            sec, last[name] = clock(fn)
+            if rep > 0:
+                times[name].append(sec)
+    assert len(ev.groups) == 1
+    assert all(last["off"][n] == last["distribution"][n] for n in ("lengths", "successes", "rewards", "times",
+                                                                   "energies")), "distribution changed the metrics"
+    d = last["distribution"]["distribution"]
+    grp = ev.groups[0]
+    b, T = grp.batch, 1001
+    NT = b.n_envs * b.max_robots
+    H, D = grp.history(T), grp.distribution(T, d.kind)
+    hist = dict(L=pack.L, T=T, records=[H])
+    dist = dict(kind=d.kind, pack=pack if d.kind == "iqn" else source, seed=0, cvar=1.0)
+    steps = ev.steps
+    acted = int(sum(int(x.sum()) for x in d.steps))
+
+    def stats():
+        de.eval_dist_stats(pack.L, T, b.n_envs, b.max_robots, D["z"], D["tau"], H["reward"], H["counts"][1],
+                           b.n_robots, ev.gamma, D["out"], D["G"])
+
+    def whole():   # the readout launches and the stats launches, as run() enqueues them
+        ev._distribution_pass(0, hist, dist)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    us = {}
+    for name, fn in (("stats", stats), ("pass", whole)):
+        fn()
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(a.kernel_launches):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        us[name] = 1e3 * e0.elapsed_time(e1) / a.kernel_launches
+    rows = steps * NT   # the readout covers every slot of the steps that ran
+    readout_bytes = rows * (4 * _abi.OBS_DIM + 16 + 2 * 4 * _abi.DIST_SAMPLES + (4 if d.kind == "iqn" else 8 + 4 * 32))
+    stats_bytes = acted * (2 * 4 * _abi.DIST_SAMPLES + 8 + 2 * 8) + NT * (4 * 8 + 4 * 34)
+    med = lambda v: sorted(v)[len(v) // 2]   # noqa: E731
+    summ = d.summary()["overall"]
+    res = {"agent": a.agent, "kind": d.kind, "configs": len(ev.envs), "chunk": a.chunk, "reps": a.reps,
+           "robot_rows": NT, "steps_run": steps, "acted_robot_steps": acted,
+           "plane_bytes": T * NT * (2 * 4 * _abi.DIST_SAMPLES + 8),
+           "off_s": times["off"], "histories_s": times["histories"], "distribution_s": times["distribution"],
+           "off_s_median": med(times["off"]), "histories_s_median": med(times["histories"]),
+           "distribution_s_median": med(times["distribution"]),
+           "off_spread_s": max(times["off"]) - min(times["off"]),
+           "launches": a.kernel_launches, "stats_us": us["stats"], "readout_us": us["pass"] - us["stats"],
+           "pass_us": us["pass"], "readout_bytes": readout_bytes, "stats_bytes": stats_bytes,
+           "mismatches": d.mismatches, "pinball_per_sample": summ["pinball"], "mean_bias": summ["bias"],
+           "pred0_minus_g0": summ["pred0_minus_g0"], "terminated_robots": summ["robots"]}
+    print(json.dumps(res))
+    merge_out(a.out, a.label or a.agent, res)
+
+
+def merge_out(path, label, res):
+    """profiles/eval_distribution.json is one object of results by label ("AC-IQN", "IQN", "AC-IQN parent", ...):
+    the runs of one session are separate processes, and each adds its own entry."""
+    if not path:
+        return
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    doc = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            doc = json.load(f)
+    doc[label] = {k: (None if isinstance(v, float) and not math.isfinite(v) else v) for k, v in res.items()}
+    with open(path, "w") as f:
+        json.dump(doc, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
+def plain(a, ev, pack, clock):
+    """--plain: the evaluation with no option, a warm-up and --reps repetitions; with --package-root it runs the
+    package of another checkout (the parent commit's, built), which is how the parent's seconds get into the same
+    file in the same session (--label "AC-IQN parent")."""
+    times = []
+    for rep in range(a.reps + 1):
+        sec, last = clock(lambda: ev.run(pack, seed=1))
+        if rep > 0:
+            times.append(sec)
+    res = {"agent": a.agent, "package": "another checkout (--package-root)" if a.package_root else "this checkout", "reps": a.reps, "chunk": a.chunk,
+           "off_s": times, "off_s_median": sorted(times)[len(times) // 2], "off_spread_s": max(times) - min(times),
+           "env_steps": int(sum(last["lengths"]))}
+    print(json.dumps(res))
+    merge_out(a.out, a.label or a.agent + " plain", res)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--chunk", type=int, default=64)
     ap.add_argument("--kernel-launches", type=int, default=200)
-    ap.add_argument("--agent", default="AC-IQN", choices=("AC-IQN", "DQN"))
+    ap.add_argument("--agent", default="AC-IQN", choices=("AC-IQN", "DQN", "IQN"))
     ap.add_argument("--out", default=None)
     ap.add_argument("--histories", action="store_true",
                     help="time the device evaluation without histories, with them as arrays and with history_lists, "
                          "the pack launch alone and the same packing by torch (no host evaluation)")
+    ap.add_argument("--distribution", action="store_true",
+                    help="time the device evaluation without, with histories and with the return distributions "
+                         "(AC-IQN: the critic's; IQN: its own), and the readout and stats launches alone")
+    ap.add_argument("--plain", action="store_true",
+                    help="time the evaluation with no option only and add it to profiles/eval_distribution.json")
+    ap.add_argument("--package-root", default=None,
+                    help="with --plain: import the package from this checkout (the parent commit's, built) instead")
+    ap.add_argument("--label", default=None, help="the entry's key in profiles/eval_distribution.json")
     a = ap.parse_args()
+    if a.agent == "IQN" and not (a.distribution or a.plain):
+        ap.error("--agent IQN goes with --distribution or --plain")
+    if a.package_root:
+        if not a.plain:
+            ap.error("--package-root goes with --plain")
+        sys.path.insert(0, os.path.abspath(a.package_root))
+    if a.out is None and (a.distribution or a.plain):
+        a.out = os.path.join(ROOT, "profiles", "eval_distribution.json")
     if a.out is None:
         name = "eval_histories.json" if a.histories else ("device_eval_dqn.json" if a.agent == "DQN"
                                                           else "device_eval.json")
@@ -170,7 +295,11 @@ def main():
         agent.policy_local.actor.load_state_dict({k[len("trained/net/"):]: torch.from_numpy(z[k]) for k in z.files
                                                   if k.startswith("trained/net/")})
     tr = Trainer(MarineNavEnv3(seed=1), MarineNavEnv3(seed=253, is_eval_env=True), SCHEDULE, agent)
-    pack = DqnPack(agent.policy_local) if a.agent == "DQN" else MlpPack(agent.policy_local.actor, "actor")
+    if a.agent == "IQN":
+        from distributional_rl_decision_and_control_amd.fused_iqn import IqnPack
+        pack = IqnPack(agent.policy_local)
+    else:
+        pack = DqnPack(agent.policy_local) if a.agent == "DQN" else MlpPack(agent.policy_local.actor, "actor")
 
     def clock(fn):
         torch.cuda.synchronize()
@@ -182,6 +311,13 @@ def main():
     load_s, ev = clock(lambda: DeviceEvaluator(configs, template_env=tr.eval_env, chunk=a.chunk, gamma=agent.GAMMA))
     if a.histories:
         return histories(a, ev, pack, clock, z)
+    if a.plain:
+        return plain(a, ev, pack, clock)
+    if a.distribution:
+        if a.agent == "DQN":
+            ap.error("--distribution reads IQN's or the AC-IQN critic's quantiles")
+        from distributional_rl_decision_and_control_amd.fused_critic import CriticPack
+        return distribution(a, ev, pack, True if a.agent == "IQN" else CriticPack(agent.policy_local.critic), clock)
     runs = {"host": lambda: evaluate_configs(agent, configs, template_env=tr.eval_env),
             "device_sync": lambda: ev.run(pack, seed=1),
             "device_nosync": lambda: ev.run(pack, seed=1, sync=False)}
